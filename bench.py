@@ -32,10 +32,18 @@ Also on the JSON line:
     roofline_projection   the signature projection against its 8(d) HBM bytes, with the digest's traffic and the ratio, and
                           (gather_view) against the L2 -> L1 line rate its first tier is really bound by.
     cpu_baseline  the CPU oracle's literal findSimilarPairs4 (oracle/, kind "port": the reference itself cannot
-                  be built in this image) on the first cells of the same signatures, one thread, ~15-20 s.
-Before timing AND after the last timed step, the GPU result is checked against the oracle bit for bit: the signatures of
+                  be built in this image) on the first cells of the same signatures, one thread, ~15-20 s (--full).
+
+A plain run (the command above) does what its headline needs and no more: inputs, the first (untimed) pass, W warmup steps,
+K timed steps, the line.  --full adds everything else, as before: the golden digests, the parity gates, the rocm-smi device
+state around the timed steps, the CPU baselines, the per-stage diagnostic pass of several ranks and the `extra` block
+(configs[1], [3], [4], the rows form as rank r of P, non-integer counts, the facade, the clustered regimes).  With --full,
+before timing AND after the last timed step, the GPU result is checked against the oracle bit for bit: the signatures of
 64 cells and >= 10^4 SimilarPairs rows x all columns at 1M cells (the whole result for configs[1]), the
 oracle's rows spread over the host's threads -- a run whose check fails prints no number.
+
+--dump-outputs DIR writes what the last timed step handed its caller, for a fixed seeded sample of 64-row blocks of the rows
+rank 0 owns (dump_outputs()): the inputs depend on the arguments alone, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -150,7 +158,18 @@ def parse_args():
     p.add_argument("--no-check", action="store_true",
                    help="diagnostic runs only (EM2_MATRIX_DIAG makes results wrong on purpose): skip the parity gates; "
                         "the line says so and is not a measurement")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="everything beside the headline (fsp4): golden digests and parity gates against the oracle, device "
+                        "state, CPU baselines, per-stage diagnostics of several ranks and the extra configurations")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write a fixed seeded sample of the last step's signatures and SimilarPairs "
+                        "(fsp4) to DIR/<name>.npy, float32 / float64, 64 MB at most")
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.workload != "fsp4":
+        p.error("--dump-outputs: the fsp4 workload only")
+    return args
 
 
 class Watchdog:
@@ -304,6 +323,46 @@ def parity_gate(pipe, oracle, synthetic, sig_host, toc, data, vectors_host, chec
             raise SystemExit("PARITY FAILURE: SimilarPairs rows %d..%d differ from the oracle" % (begin, end))
         rows_checked += end - begin
     return sample, rows_checked
+
+
+DUMP_SEED = 20240531
+DUMP_BLOCKS = 256                # 64-row blocks: 16 384 rows at most
+DUMP_BUDGET = 60 << 20           # bytes, below the 64 MB allowed
+
+
+def dump_outputs(directory, pipe):
+    """--dump-outputs: what the timed path hands its caller after its last step -- the signatures and the SimilarPairs rows
+    (cell, similarity, used) -- for a fixed sample of whole 64-row blocks of the rows this rank owns (numpy's default_rng
+    with DUMP_SEED picks the blocks; as many as fit in DUMP_BUDGET, DUMP_BLOCKS at most), as .npy files under `directory`:
+        rows.npy              float64 [S]       the global cell id of every sampled row
+        signatures.npy        float64 [S, 2W]   the signature's 32-bit words, low word of each 64-bit word first
+        pairs_cell.npy        float64 [S, k]    SimilarPairs cell ids (every slot, as the gates compare them)
+        pairs_similarity.npy  float32 [S, k]    SimilarPairs similarities
+        pairs_used.npy        float64 [S]       stored pairs per row
+    Returns {name: shape}."""
+    blocks = [(b, min(end, b + 64)) for begin, end in pipe.owned_ranges() for b in range(begin, end, 64)]
+    per_row = pipe.k * (8 + 4) + 2 * pipe.words * 8 + 8 + 8
+    count = max(1, min(len(blocks), DUMP_BLOCKS, DUMP_BUDGET // (64 * per_row)))
+    picked = np.sort(np.random.default_rng(DUMP_SEED).choice(len(blocks), size=count, replace=False)) if blocks else []
+    rows, words, cells, sims, used = [], [], [], [], []
+    for index in picked:
+        begin, end = blocks[index]
+        pairs, u = pipe.results_for(begin, end)
+        rows.append(np.arange(begin, end, dtype=np.float64))
+        words.append(pipe.full_sig[begin:end].cpu().numpy().view(np.uint32).astype(np.float64))
+        cells.append(pairs["cell"].astype(np.float64))
+        sims.append(np.ascontiguousarray(pairs["similarity"], dtype=np.float32))
+        used.append(u.astype(np.float64))
+    k, width = pipe.k, 2 * pipe.words
+    out = {"rows": np.concatenate(rows) if rows else np.zeros(0),
+           "signatures": np.concatenate(words) if words else np.zeros((0, width)),
+           "pairs_cell": np.concatenate(cells) if cells else np.zeros((0, k)),
+           "pairs_similarity": np.concatenate(sims) if sims else np.zeros((0, k), dtype=np.float32),
+           "pairs_used": np.concatenate(used) if used else np.zeros(0)}
+    os.makedirs(directory, exist_ok=True)
+    for name, array in out.items():
+        np.save(os.path.join(directory, name + ".npy"), array)
+    return {name: list(array.shape) for name, array in out.items()}
 
 
 def rows_form_block(args, capi, pipe, oracle, sig_host, torch, threads, shards=((2, 1), (4, 1), (8, 3)), repeats=3, oracle_rows=1024):
@@ -1052,8 +1111,10 @@ def main():
     # ---- synthetic inputs, resident in HBM ----
     vectors_host = capi.lsh_generate_vectors(G, L, args.seed)            # Lsh::generateLshVectors (host, once)
     vectors = torch.from_numpy(vectors_host).to(device)
-    import oracle_binding
-    oracle = oracle_binding.load_oracle()
+    oracle = None
+    if args.full:
+        import oracle_binding
+        oracle = oracle_binding.load_oracle()
     inputs = {}
 
     prepare_ms = []
@@ -1086,13 +1147,13 @@ def main():
     gate_threads = args.check_threads or max(1, min(64, usable_cpus() // world))
 
     def run_leg(pipe, label, golden_cases):
-        """One measurement by the contract: correctness gate (an untimed pass against the CPU oracle), W warmup steps, exactly K
-        timed steps between barrier + synchronize on both sides, MAX over the ranks, the gate again on the LAST timed step's
-        result.  Every stage runs under the watchdog."""
+        """One measurement by the contract: an untimed first pass (with --full: the correctness gate against the CPU oracle on
+        it), W warmup steps, exactly K timed steps between barrier + synchronize on both sides, MAX over the ranks (with --full:
+        the gate again on the LAST timed step's result).  Every stage runs under the watchdog."""
         toc, data = inputs["toc"], inputs["data"]
         check = {"golden_cases": 0, "signature_cells": 0, "fsp4_rows": 0}
         watchdog.arm(label + ": first pass and parity gate", 900)
-        if rank == 0 and not args.no_check and golden_cases:
+        if rank == 0 and args.full and not args.no_check and golden_cases:
             # the committed golden digests (tests/golden/, produced by the oracle) against this build's GPU path
             from golden.make_golden import digest, make_signatures, regression_cases
             with open(os.path.join(ROOT, "tests", "golden", "oracle_regression.json")) as f:
@@ -1104,8 +1165,8 @@ def main():
                 check["golden_cases"] += 1
         pipe.step()
         torch.cuda.synchronize()
-        sig_host = pipe.full_sig[:C].cpu().numpy().view(np.uint64)
-        if not args.no_check:
+        sig_host = pipe.full_sig[:C].cpu().numpy().view(np.uint64) if args.full else None
+        if args.full and not args.no_check:
             check["signature_cells"], check["fsp4_rows"] = parity_gate(pipe, oracle, synthetic, sig_host, toc, data, vectors_host,
                                                                        rows_per_gate, gate_threads)
         # ---- warmup + timed steps ----
@@ -1119,7 +1180,7 @@ def main():
         torch.cuda.synchronize()
         pipe.scan_events = []
         proj_events = []
-        state_before = device_state(local_rank) if rank == 0 else None
+        state_before = device_state(local_rank) if rank == 0 and args.full else None
         t0 = time.perf_counter()
         for _ in range(args.steps):
             e0 = torch.cuda.Event(enable_timing=True)
@@ -1135,13 +1196,15 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
-        state_after = device_state(local_rank) if rank == 0 else None
+        state_after = device_state(local_rank) if rank == 0 and args.full else None
         pipe.check()                 # the scan's inter-wave hand-offs all completed (raises otherwise)
         # The hand-off, speculation and inbox paths of the scan depend on timing, so the result of the LAST timed step is
         # put through the same gate again: same signatures as before, sampled rows bit-identical to the oracle.
         watchdog.arm(label + ": parity gate after the timed steps", 900)
         if args.no_check:
             check["skipped"] = "--no-check: diagnostic run, NOT a measurement"
+        elif not args.full:
+            check["skipped"] = "plain run: the golden digests and the parity gates against the oracle run with --full"
         else:
             sig_after = pipe.full_sig[:C].cpu().numpy().view(np.uint64)
             if not np.array_equal(sig_after, sig_host):
@@ -1383,9 +1446,10 @@ def main():
     else:
         rows_leg = run_leg(make_pipe(False), "row shards", True)
         rows_result = assemble(rows_leg)
-        rows_result["stages_ms_max_over_ranks"] = {"form": "row-shards", "backend": dist.get_backend(),
-                                                   "note": "diagnostic pass with a synchronisation after every stage; not the measurement",
-                                                   **stage_times(rows_leg["pipe"], "row shards")}
+        if args.full:
+            rows_result["stages_ms_max_over_ranks"] = {"form": "row-shards", "backend": dist.get_backend(),
+                                                       "note": "diagnostic pass with a synchronisation after every stage; not the measurement",
+                                                       **stage_times(rows_leg["pipe"], "row shards")}
         result = rows_result
         symmetric_pipe = make_pipe(True)
         if symmetric_pipe.sharded:
@@ -1403,11 +1467,13 @@ def main():
                     rows_result["sharded_symmetric_leg"] = {"status": "fell back to row shards by agreement of the ranks"}
                 else:
                     result = assemble(sym_leg)
-                    result["stages_ms_max_over_ranks"] = {"form": result["config"]["scan"], "backend": dist.get_backend(),
-                                                          "note": "diagnostic pass with a synchronisation after every stage; not the measurement",
-                                                          **stage_times(sym_leg["pipe"], "sharded symmetric")}
+                    if args.full:
+                        result["stages_ms_max_over_ranks"] = {"form": result["config"]["scan"], "backend": dist.get_backend(),
+                                                              "note": "diagnostic pass with a synchronisation after every stage; not the measurement",
+                                                              **stage_times(sym_leg["pipe"], "sharded symmetric")}
                     result["row_shard_leg"] = {key: rows_result[key] for key in ("value", "unit", "ms_per_step", "steps", "warmup", "parity_check",
-                                                                                   "phases_ms_rank0", "stages_ms_max_over_ranks")}
+                                                                                   "phases_ms_rank0", "stages_ms_max_over_ranks")
+                                               if key in rows_result}
                     result["row_shard_leg"]["scan"] = "row-shards"
                     result["row_shard_leg"]["note"] = ("the same job with north_star's partitioning, measured first by the same contract: every "
                                                        "rank scans its contiguous rows against all columns (each unordered pair evaluated twice "
@@ -1426,8 +1492,10 @@ def main():
             watchdog.exit_code = 1
         leg = rows_leg if result is rows_result else sym_leg
     pipe, sig_host = leg["pipe"], leg["sig_host"]
+    if rank == 0 and args.dump_outputs:
+        result["dumped_outputs"] = dump_outputs(args.dump_outputs, pipe)
 
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         m = min(args.cpu_baseline_cells, C)
         t1 = time.perf_counter()
         oracle.find_similar_pairs4(sig_host[:m], L, k, thr)
@@ -1460,7 +1528,7 @@ def main():
     elif rank == 0:
         result["cpu_baseline"] = None
 
-    if rank == 0 and world == 1 and not args.no_extra and (C, G) == (1000000, 30000):
+    if rank == 0 and world == 1 and args.full and not args.no_extra and (C, G) == (1000000, 30000):
         # BASELINE configs[1] (100k cells x 20k genes, 1% nnz, 1024 bit, 1 GPU): a second, small measurement on the same
         # line -- never the headline.  Same pipeline, same gates (sampled rows against the oracle before and after).
         result["extra"] = {}

@@ -23,7 +23,7 @@ def run_two_ranks(extra_env, cells, port, ranks=2, extra_args=(), timeout=600):
     env.update(extra_env)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "1",
-           "--warmup", "0", "--cells", str(cells), "--genes", "3000", "--no-cpu-baseline", "--check-rows", "96"] + list(extra_args)
+           "--warmup", "0", "--cells", str(cells), "--genes", "3000", "--full", "--no-cpu-baseline", "--check-rows", "96"] + list(extra_args)
     done = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
     assert done.returncode == 0, done.stdout[-3000:] + done.stderr[-3000:]
     lines = [line for line in done.stdout.splitlines() if line.startswith("{")]
@@ -80,7 +80,7 @@ def test_plain_command_starts_its_own_ranks():
     env.update({"EM2_BENCH_SHARE_DEVICE": "1", "EM2_BENCH_BACKEND": "gloo", "EM2_BLOCKS_PER_CU": "1", "HSA_ENABLE_IPC_MODE_LEGACY": "0",
                 "EM2_SHARDED_MIN_CELLS": "1000"})
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--cells", "30000", "--genes", "3000",
-           "--no-cpu-baseline", "--check-rows", "96"]
+           "--full", "--no-cpu-baseline", "--check-rows", "96"]
     done = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert done.returncode == 0, done.stdout[-3000:] + done.stderr[-3000:]
     lines = [line for line in done.stdout.splitlines() if line.startswith("{")]

@@ -3,7 +3,7 @@
 #   tools/ab_convoy.sh [rounds]
 cd "$(dirname "$0")/.."
 run() {
-  EM2_MATRIX_CONVOY=$1 python bench.py --steps 5 --warmup 2 --no-extra --no-cpu-baseline --check-rows 1024 $2 2>/dev/null | tail -1 | python3 -c "
+  EM2_MATRIX_CONVOY=$1 python bench.py --steps 5 --warmup 2 --full --no-extra --no-cpu-baseline --check-rows 1024 $2 2>/dev/null | tail -1 | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read()); r = d['roofline']
 print('convoy $1 $2: step %.1f  kernel %.2f ms  clock %.3f GHz  frac %.3f  scan %.1f' % (d['ms_per_step'], r['kernel_ms'], r.get('clock_ghz') or 0, r['frac'], d['phases_ms_rank0']['scan']))"

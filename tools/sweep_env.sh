@@ -3,7 +3,7 @@
 #   tools/sweep_env.sh "EM2_MATRIX_RING=0" "EM2_MATRIX_RING=1 EM2_RING_SEGMENT_COLUMNS=4096" ...
 cd "$(dirname "$0")/.."
 for setting in "$@"; do
-  env $setting python bench.py --steps 4 --warmup 2 --no-extra --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "
+  env $setting python bench.py --steps 4 --warmup 2 --full --no-extra --no-cpu-baseline 2>/dev/null | tail -1 | python3 -c "
 import json, sys
 try:
     d = json.loads(sys.stdin.read()); r = d['roofline']
