@@ -51,6 +51,14 @@ SYMBOLS = {
     "em2_dev_find_similar_pairs4": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_uint32, _c.c_uint32,
                                                _c.c_uint32, _c.c_double, _c.c_void_p, _c.c_void_p, _c.c_void_p,
                                                _c.c_size_t, _c.c_void_p]),
+    "em2_find_similar_pairs6": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_uint32, _c.c_double, _c.c_uint32,
+                                           _c.c_uint32, _c.c_uint32, _c.c_int32, _c.c_void_p, _c.c_void_p]),
+    "em2_dev_find_similar_pairs6": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_uint32, _c.c_uint32, _c.c_uint32,
+                                               _c.c_double, _c.c_uint32, _c.c_uint32, _c.c_uint32, _c.c_int32,
+                                               _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "em2_matrix_find_similar_pairs6": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_char_p, _c.c_char_p,
+                                                  _c.c_size_t, _c.c_double, _c.c_size_t, _c.c_size_t, _c.c_size_t,
+                                                  _c.c_int]),
     "em2_find_similar_pairs7": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_uint32, _c.c_double, _c.c_void_p,
                                            _c.c_uint32, _c.c_uint32, _c.c_uint32, _c.c_void_p, _c.c_void_p]),
     "em2_dev_find_similar_pairs7": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_uint32, _c.c_uint32, _c.c_uint32,
@@ -376,6 +384,18 @@ def analyze_lsh(toc, data, gene_count, signatures, lsh_count, global_cell_ids, s
     return out
 
 
+def find_similar_pairs6(signatures, lsh_count, k, similarity_threshold, permutation_count, search_count,
+                        permuted_bit_count=64, seed=231):
+    """findSimilarPairs6 (the Charikar permutation search) on host signatures -> (pairs [cells, k], usedCount)."""
+    signatures = np.ascontiguousarray(signatures, dtype=np.uint64)
+    cell_count = signatures.shape[0]
+    pairs = np.zeros((cell_count, k), dtype=PAIR_DTYPE)
+    used = np.zeros(cell_count, dtype=np.uint32)
+    check(load().em2_find_similar_pairs6(_ptr(signatures), cell_count, lsh_count, k, similarity_threshold, permutation_count,
+                                         search_count, permuted_bit_count, seed, _ptr(pairs), _ptr(used)))
+    return pairs, used
+
+
 def find_similar_pairs7(signatures, lsh_count, k, similarity_threshold, lsh_slice_lengths, max_check, log2_bucket_count):
     signatures = np.ascontiguousarray(signatures, dtype=np.uint64)
     lengths = np.ascontiguousarray(lsh_slice_lengths, dtype=np.int32)
@@ -537,3 +557,10 @@ def dev_vector_aux_bytes(gene_count, lsh_count):
 
 def dev_prepare_vectors(vectors_ptr, gene_count, lsh_count, aux_ptr, stream):
     check(load().em2_dev_prepare_vectors(vectors_ptr, gene_count, lsh_count, aux_ptr, stream))
+
+
+def dev_find_similar_pairs6(sig_ptr, cell_count, row_begin, row_end, lsh_count, k, similarity_threshold, permutation_count,
+                            search_count, permuted_bit_count, seed, pairs_ptr, used_ptr, stream):
+    check(load().em2_dev_find_similar_pairs6(sig_ptr, cell_count, row_begin, row_end, lsh_count, k, similarity_threshold,
+                                             permutation_count, search_count, permuted_bit_count, seed, pairs_ptr, used_ptr,
+                                             stream))

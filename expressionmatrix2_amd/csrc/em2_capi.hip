@@ -737,6 +737,52 @@ int em2_dev_find_similar_pairs5(const uint64_t* d_signatures, uint32_t cellCount
 }
 
 
+// The argument checks of findSimilarPairs6 (src/ExpressionMatrixLsh.cpp:885-893 and the kernels' limits).  Run before
+// any device call, so that they also answer on a machine without a GPU.
+static int prepareFsp6(const char* who, uint32_t cellCount, uint32_t lshCount, uint32_t permutationCount, uint32_t searchCount,
+                       uint32_t permutedBitCount)
+{
+    if (lshCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": lshCount must be positive");
+    if (permutedBitCount > lshCount) {
+        return fail(EM2_ERROR_RUNTIME, "Argument permutationStoreBitCount " + std::to_string(permutedBitCount) +
+                                           " exceeds number of signature bits " + std::to_string(lshCount));
+    }
+    // the reference computes ((0-1) >> 6) + 1 = 2^58 words here (:920) and dies allocating them
+    if (permutedBitCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": permutedBitCount must be positive");
+    if (permutationCount > em2::fsp6MaxPermutations()) {
+        return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": permutationCount above " + std::to_string(em2::fsp6MaxPermutations()) +
+                                               " is not supported");
+    }
+    if (permutedBitCount > em2::fsp6MaxPermutedBits()) {
+        return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": permutedBitCount above " + std::to_string(em2::fsp6MaxPermutedBits()) +
+                                               " is not supported");
+    }
+    if (em2::fsp6EffectiveSearch(cellCount, permutationCount, searchCount) > em2::fsp6MaxSearch()) {
+        return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": more than " + std::to_string(em2::fsp6MaxSearch()) +
+                                               " candidates per cell (min(searchCount, permutationCount*(cellCount-1))) is not supported");
+    }
+    return EM2_OK;
+}
+
+int em2_dev_find_similar_pairs6(const uint64_t* d_signatures, uint32_t cellCount, uint32_t rowBegin, uint32_t rowEnd,
+                                uint32_t lshCount, uint32_t k, double similarityThreshold, uint32_t permutationCount,
+                                uint32_t searchCount, uint32_t permutedBitCount, int32_t seed,
+                                em2_pair* d_pairs, uint32_t* d_usedCount, void* stream)
+{
+    const int prc = prepareFsp6("em2_dev_find_similar_pairs6", cellCount, lshCount, permutationCount, searchCount, permutedBitCount);
+    if (prc != EM2_OK) return prc;
+    if (rowBegin > rowEnd || rowEnd > cellCount) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dev_find_similar_pairs6: bad row range");
+    if (rowBegin == rowEnd) return EM2_OK;
+    if (!d_signatures || !d_usedCount || (!d_pairs && k)) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dev_find_similar_pairs6: null pointer");
+    em2::DeviceTables tables;
+    const int rc = getDeviceTables(lshCount, similarityThreshold, tables);
+    if (rc != EM2_OK) return rc;
+    EM2_HIP(em2::runFsp6(d_signatures, cellCount, rowBegin, rowEnd, lshCount, k, permutationCount, searchCount, permutedBitCount,
+                         seed, tables, reinterpret_cast<em2::PairOut*>(d_pairs), d_usedCount, static_cast<hipStream_t>(stream)));
+    return EM2_OK;
+}
+
+
 // The argument checks of findSimilarPairs7 in the reference's order (src/ExpressionMatrixLsh.cpp:548-561) and
 // Lsh::computeMismatchCountThresholdFromSimilarityThreshold (src/Lsh.hpp:86-95).
 static int prepareFsp7(const char* who, uint32_t lshCount, double similarityThreshold, const int32_t* sliceLengths,
@@ -817,6 +863,31 @@ int em2_find_similar_pairs7(const uint64_t* signatures, uint32_t cellCount, uint
     EM2_HIP(hipMemcpy(dSig.p, signatures, size_t(cellCount) * words * sizeof(uint64_t), hipMemcpyHostToDevice));
     const int rc = em2_dev_find_similar_pairs7(dSig.as<uint64_t>(), cellCount, 0, cellCount, lshCount, k, similarityThreshold,
                                                sliceLengths, sliceLengthCount, maxCheck, log2BucketCount, dPairs.as<em2_pair>(),
+                                               dUsed.as<uint32_t>(), nullptr);
+    if (rc != EM2_OK) return rc;
+    if (k) EM2_HIP(hipMemcpy(pairs, dPairs.p, size_t(cellCount) * k * sizeof(em2_pair), hipMemcpyDeviceToHost));
+    EM2_HIP(hipMemcpy(usedCount, dUsed.p, size_t(cellCount) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return EM2_OK;
+}
+
+
+int em2_find_similar_pairs6(const uint64_t* signatures, uint32_t cellCount, uint32_t lshCount, uint32_t k,
+                            double similarityThreshold, uint32_t permutationCount, uint32_t searchCount,
+                            uint32_t permutedBitCount, int32_t seed, em2_pair* pairs, uint32_t* usedCount)
+{
+    const int prc = prepareFsp6("em2_find_similar_pairs6", cellCount, lshCount, permutationCount, searchCount, permutedBitCount);
+    if (prc != EM2_OK) return prc;
+    if (cellCount == 0) return EM2_OK;
+    if (!signatures || !usedCount || (!pairs && k)) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_find_similar_pairs6: null pointer");
+    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, "em2_find_similar_pairs6: no HIP device is visible (this library has no CPU path)");
+    const uint32_t words = wordCountOf(lshCount);
+    DeviceBuffer dSig, dPairs, dUsed;
+    EM2_HIP(dSig.allocate(size_t(cellCount) * words * sizeof(uint64_t)));
+    EM2_HIP(dPairs.allocate(size_t(cellCount) * k * sizeof(em2_pair)));
+    EM2_HIP(dUsed.allocate(size_t(cellCount) * sizeof(uint32_t)));
+    EM2_HIP(hipMemcpy(dSig.p, signatures, size_t(cellCount) * words * sizeof(uint64_t), hipMemcpyHostToDevice));
+    const int rc = em2_dev_find_similar_pairs6(dSig.as<uint64_t>(), cellCount, 0, cellCount, lshCount, k, similarityThreshold,
+                                               permutationCount, searchCount, permutedBitCount, seed, dPairs.as<em2_pair>(),
                                                dUsed.as<uint32_t>(), nullptr);
     if (rc != EM2_OK) return rc;
     if (k) EM2_HIP(hipMemcpy(pairs, dPairs.p, size_t(cellCount) * k * sizeof(em2_pair), hipMemcpyDeviceToHost));

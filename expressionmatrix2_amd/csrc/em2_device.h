@@ -154,6 +154,17 @@ hipError_t runFsp7(const uint64_t* d_sig, uint32_t cellCount, uint32_t rowBegin,
                    const int32_t* sliceLengths, uint32_t sliceLengthCount, uint32_t maxCheck, uint32_t log2BucketCount,
                    uint64_t mismatchThreshold, const DeviceTables& tables, PairOut* d_pairs, uint32_t* d_used, hipStream_t stream);
 
+// findSimilarPairs6 (src/ExpressionMatrixLsh.cpp:842-1145), results for the cells [rowBegin,rowEnd); the sorted tables
+// always cover all cells.  Allocates its own scratch and synchronises the stream.  The limits are those of the kernels'
+// LDS: permutationCount, fsp6EffectiveSearch() (searchCount capped by what the queue can hold) and permutedBitCount.
+uint32_t fsp6MaxPermutations();
+uint32_t fsp6MaxSearch();
+uint32_t fsp6MaxPermutedBits();
+uint64_t fsp6EffectiveSearch(uint32_t cellCount, uint32_t permutationCount, uint32_t searchCount);
+hipError_t runFsp6(const uint64_t* d_sig, uint32_t cellCount, uint32_t rowBegin, uint32_t rowEnd, uint32_t lshCount, uint32_t k,
+                   uint32_t permutationCount, uint32_t searchCount, uint32_t permutedBitCount, int32_t seed,
+                   const DeviceTables& tables, PairOut* d_pairs, uint32_t* d_used, hipStream_t stream);
+
 // CellGraph::CellGraph (src/CellGraph.cpp:33-117): edges of the k-NN graph in the reference's insertion order.
 hipError_t runCellGraphEdges(const PairOut* pairs, const uint32_t* usedCount, uint32_t spCellCount, uint32_t k,
                              const uint32_t* spCellSet, const uint32_t* graphCellSet, const uint32_t* graphSortedIds,

@@ -466,6 +466,40 @@ void Matrix::findSimilarPairs5(const std::string& geneSetName, const std::string
     writeSimilarPairs(directoryName_, similarPairsName, geneSetName, cellSetName, k, uint32_t(cellCount), pairs.data(), used.data());
 }
 
+void Matrix::findSimilarPairs6(const std::string& geneSetName, const std::string& cellSetName,
+                               const std::string& lshName, const std::string& similarPairsName, size_t k,
+                               double similarityThreshold, size_t permutationCount, size_t searchCount,
+                               size_t permutedBitCount, int seed) const
+{
+    // ExpressionMatrixLsh.cpp:859-893
+    const GeneSet& genes = geneSet(geneSetName);
+    if (genes.size() == 0) fail(EM2_ERROR_RUNTIME, "Gene set " + geneSetName + " is empty.");
+    const MappedFile& cells = cellSet(cellSetName);
+    const uint64_t cellCount = cells.objectCount();
+    if (cellCount == 0) fail(EM2_ERROR_RUNTIME, "Cell set " + cellSetName + " is empty.");
+    uint64_t lshCells = 0, lshCount = 0;
+    std::vector<uint64_t> signatures;
+    readLsh(directoryName_ + "/Lsh-" + lshName, lshCells, lshCount, signatures);
+    if (lshCells != cellCount) {
+        fail(EM2_ERROR_RUNTIME, "LSH object " + lshName + " has a number of cells inconsistent with cell set " + cellSetName);
+    }
+    if (permutedBitCount > lshCount) {
+        fail(EM2_ERROR_RUNTIME, "Argument permutationStoreBitCount " + std::to_string(permutedBitCount) +
+                                    " exceeds number of signature bits " + std::to_string(lshCount));
+    }
+    if (k > 0xffffffffULL) fail(EM2_ERROR_INVALID_ARGUMENT, "findSimilarPairs6: argument out of range");
+    // counts beyond 32 bits: a searchCount that large never binds (the queue empties first), a permutationCount that large
+    // is above the supported limit either way
+    const uint32_t permutations = uint32_t(std::min<size_t>(permutationCount, 0xffffffffULL));
+    const uint32_t search = uint32_t(std::min<size_t>(searchCount, 0xffffffffULL));
+    std::vector<em2_pair> pairs(size_t(cellCount) * k);
+    std::vector<uint32_t> used(cellCount);
+    const int rc = em2_find_similar_pairs6(signatures.data(), uint32_t(cellCount), uint32_t(lshCount), uint32_t(k), similarityThreshold,
+                                           permutations, search, uint32_t(permutedBitCount), int32_t(seed), pairs.data(), used.data());
+    if (rc != EM2_OK) fail(rc, em2_last_error());
+    writeSimilarPairs(directoryName_, similarPairsName, geneSetName, cellSetName, k, uint32_t(cellCount), pairs.data(), used.data());
+}
+
 void Matrix::findSimilarPairs7(const std::string& geneSetName, const std::string& cellSetName,
                                const std::string& lshName, const std::string& similarPairsName, size_t k,
                                double similarityThreshold, const std::vector<int32_t>& lshSliceLengths, uint32_t maxCheck,

@@ -97,6 +97,18 @@ int em2_matrix_find_similar_pairs5(em2_matrix* matrix, const char* geneSetName, 
     });
 }
 
+int em2_matrix_find_similar_pairs6(em2_matrix* matrix, const char* geneSetName, const char* cellSetName,
+                                   const char* lshName, const char* similarPairsName, size_t k,
+                                   double similarityThreshold, size_t permutationCount, size_t searchCount,
+                                   size_t permutedBitCount, int seed)
+{
+    if (!matrix || !geneSetName || !cellSetName || !lshName || !similarPairsName) return nullArgument("em2_matrix_find_similar_pairs6");
+    return guarded([&] {
+        matrix->impl->findSimilarPairs6(geneSetName, cellSetName, lshName, similarPairsName, k, similarityThreshold,
+                                        permutationCount, searchCount, permutedBitCount, seed);
+    });
+}
+
 int em2_matrix_find_similar_pairs7(em2_matrix* matrix, const char* geneSetName, const char* cellSetName,
                                    const char* lshName, const char* similarPairsName, size_t k,
                                    double similarityThreshold, const int32_t* lshSliceLengths, uint32_t sliceLengthCount,

@@ -103,6 +103,16 @@ class ExpressionMatrix:
                                                               _b(lshName), _b(similarPairsName), k,
                                                               similarityThreshold, lshSliceLength, bucketOverflow))
 
+    # ---- src/PythonModule.cpp:866-880 ("Prototype code, see the code for details. Use findSimilarPairs4 instead.") ----
+    def findSimilarPairs6(self, geneSetName="AllGenes", cellSetName="AllCells", lshName=_REQUIRED,
+                          similarPairsName=_REQUIRED, k=100, similarityThreshold=0.2, permutationCount=_REQUIRED,
+                          searchCount=_REQUIRED, permutedBitCount=64, seed=231):
+        if _REQUIRED in (lshName, similarPairsName, permutationCount, searchCount):
+            raise TypeError("findSimilarPairs6(): lshName, similarPairsName, permutationCount and searchCount are required")
+        capi.check(capi.load().em2_matrix_find_similar_pairs6(self._handle, _b(geneSetName), _b(cellSetName), _b(lshName),
+                                                              _b(similarPairsName), k, similarityThreshold, permutationCount,
+                                                              searchCount, permutedBitCount, seed))
+
     # ---- src/PythonModule.cpp:882-897 ("Prototype code. Use findSimilarPairs4 instead.") ----
     def findSimilarPairs7(self, geneSetName="AllGenes", cellSetName="AllCells", lshName=_REQUIRED,
                           similarPairsName=_REQUIRED, k=100, similarityThreshold=0.2, lshSliceLengths=_REQUIRED,

@@ -103,6 +103,21 @@ int em2_find_similar_pairs7(const uint64_t* signatures, uint32_t cellCount, uint
                             double similarityThreshold, const int32_t* sliceLengths, uint32_t sliceLengthCount,
                             uint32_t maxCheck, uint32_t log2BucketCount, em2_pair* pairs, uint32_t* usedCount);
 
+/* ExpressionMatrix::findSimilarPairs6 after its lookups (src/ExpressionMatrixLsh.cpp:880-1145, src/charikar.hpp): the
+ * Charikar permutation search.  permutationCount bit permutations are drawn from one std::mt19937 seeded with `seed`
+ * (iota + std::shuffle over all lshCount bits, first permutedBitCount kept); the cells are sorted by their permuted
+ * prefixes per permutation; per cell a priority queue of pointers into those sorted lists (ordered by common prefix
+ * length, ties as libstdc++'s heap leaves them) yields up to searchCount candidates; those with
+ * similarityTable[mismatch] > similarityThreshold are kept, sorted by (similarity desc, id asc), deduplicated and cut
+ * to k.  Layout of pairs/usedCount as em2_find_similar_pairs4.
+ * Errors: "Argument permutationStoreBitCount N exceeds number of signature bits L" (the reference's text);
+ * permutedBitCount 0 is EM2_ERROR_INVALID_ARGUMENT (the reference sizes 2^58 words there).  Limits
+ * (EM2_ERROR_UNSUPPORTED): permutationCount <= 64, permutedBitCount <= 65472, min(searchCount,
+ * permutationCount*(cellCount-1)) <= 8192. */
+int em2_find_similar_pairs6(const uint64_t* signatures, uint32_t cellCount, uint32_t lshCount, uint32_t k,
+                            double similarityThreshold, uint32_t permutationCount, uint32_t searchCount,
+                            uint32_t permutedBitCount, int32_t seed, em2_pair* pairs, uint32_t* usedCount);
+
 /* ExpressionMatrixSubset + Lsh + findSimilarPairs4 in one call on host buffers (SURVEY.md 8(a) row a1 on the device:
  * src/ExpressionMatrixSubset.cpp:9-42 followed by src/Lsh.cpp:118-224 and src/ExpressionMatrixLsh.cpp:200-285): the
  * global CSR (CellExpressionCounts toc/data, global gene ids) restricted to the cells cellIds[0..cellCount) (NULL =
@@ -215,6 +230,14 @@ int em2_dev_find_similar_pairs7(const uint64_t* d_signatures, uint32_t cellCount
                                 uint32_t lshCount, uint32_t k, double similarityThreshold, const int32_t* sliceLengths,
                                 uint32_t sliceLengthCount, uint32_t maxCheck, uint32_t log2BucketCount, em2_pair* d_pairs,
                                 uint32_t* d_usedCount, void* stream);
+
+/* findSimilarPairs6 on device-resident signatures for the cells [rowBegin,rowEnd) (the sorted permutation tables
+ * always cover all cells; rows shard over ranks like em2_dev_find_similar_pairs5).  Allocates its own scratch and
+ * synchronises the stream. */
+int em2_dev_find_similar_pairs6(const uint64_t* d_signatures, uint32_t cellCount, uint32_t rowBegin, uint32_t rowEnd,
+                                uint32_t lshCount, uint32_t k, double similarityThreshold, uint32_t permutationCount,
+                                uint32_t searchCount, uint32_t permutedBitCount, int32_t seed,
+                                em2_pair* d_pairs, uint32_t* d_usedCount, void* stream);
 
 /* ---- findSimilarPairs4 across GPUs with every unordered pair evaluated once (one process per GPU) ----
  * The 64-cell blocks of the problem are dealt round-robin to the ranks (block g: rank g % world).  Every rank holds
@@ -436,6 +459,13 @@ int em2_matrix_analyze_lsh(em2_matrix* matrix, const char* geneSetName, const ch
 int em2_matrix_find_similar_pairs5(em2_matrix* matrix, const char* geneSetName, const char* cellSetName,
                                    const char* lshName, const char* similarPairsName, size_t k,
                                    double similarityThreshold, size_t lshSliceLength, size_t bucketOverflow);
+
+/* ExpressionMatrix::findSimilarPairs6 (src/ExpressionMatrixLsh.cpp:842-1145; bound at src/PythonModule.cpp:866-880,
+ * defaults k=100, similarityThreshold=0.2, permutedBitCount=64, seed=231). */
+int em2_matrix_find_similar_pairs6(em2_matrix* matrix, const char* geneSetName, const char* cellSetName,
+                                   const char* lshName, const char* similarPairsName, size_t k,
+                                   double similarityThreshold, size_t permutationCount, size_t searchCount,
+                                   size_t permutedBitCount, int seed);
 
 /* ExpressionMatrix::findSimilarPairs7 (src/ExpressionMatrixLsh.cpp:507-703; bound at src/PythonModule.cpp:882-897). */
 int em2_matrix_find_similar_pairs7(em2_matrix* matrix, const char* geneSetName, const char* cellSetName,
