@@ -373,14 +373,9 @@ hipError_t runFsp6(const uint64_t* d_sig, uint32_t cellCount, uint32_t rowBegin,
         EM2_TRY6(keysIn.allocate(size_t(n) * sizeof(uint64_t)));
         EM2_TRY6(keysOut.allocate(size_t(n) * sizeof(uint64_t)));
         EM2_TRY6(idsIn.allocate(size_t(n) * sizeof(uint32_t)));
-        const uint32_t lastLive = permutedBitCount - 64u * (prefixWords - 1u);
         size_t tempBytes = 0;
-        for (uint32_t beginBit : {0u, 64u - lastLive}) {
-            size_t bytes = 0;
-            EM2_TRY6(rocprim::radix_sort_pairs(nullptr, bytes, keysIn.as<uint64_t>(), keysOut.as<uint64_t>(), idsIn.as<uint32_t>(),
-                                               cellIds.as<uint32_t>(), size_t(n), beginBit, 64u, stream));
-            tempBytes = std::max(tempBytes, bytes);
-        }
+        EM2_TRY6(rocprim::radix_sort_pairs(nullptr, tempBytes, keysIn.as<uint64_t>(), keysOut.as<uint64_t>(), idsIn.as<uint32_t>(),
+                                           cellIds.as<uint32_t>(), size_t(n), 0u, 64u, stream));
         EM2_TRY6(temp.allocate(tempBytes));
         for (uint32_t p = 0; p < permutationCount; ++p) {
             const uint64_t* words = permWords.as<uint64_t>() + size_t(p) * prefixWords * n;
@@ -391,10 +386,10 @@ hipError_t runFsp6(const uint64_t* d_sig, uint32_t cellCount, uint32_t rowBegin,
                 gatherWordKernel<<<gridFor6(n), 256, 0, stream>>>(words + size_t(w) * n, ids, n, keysIn.as<uint64_t>());
                 EM2_TRY6(hipGetLastError());
                 EM2_TRY6(hipMemcpyAsync(idsIn.p, ids, size_t(n) * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
-                // the bits after permutedBitCount are zero: the last word only needs its high bits sorted
-                const uint32_t live = w == prefixWords - 1u ? lastLive : 64u;
+                // All 64 bits, the last word's included (its bits after permutedBitCount are zero).  Sorting only that
+                // word's live high bits (begin_bit > 0) gave a wrong order from a few thousand cells on.
                 EM2_TRY6(rocprim::radix_sort_pairs(temp.p, tempBytes, keysIn.as<uint64_t>(), keysOut.as<uint64_t>(),
-                                                   idsIn.as<uint32_t>(), ids, size_t(n), 64u - live, 64u, stream));
+                                                   idsIn.as<uint32_t>(), ids, size_t(n), 0u, 64u, stream));
             }
             scatterKernel<<<gridFor6(n), 256, 0, stream>>>(words, ids, n, prefixWords, position.as<uint32_t>() + size_t(p) * n,
                                                             sortedPrefix.as<uint64_t>() + size_t(p) * n * prefixWords);

@@ -59,8 +59,10 @@ def pop_heap(heap):
     heap.pop()
 
 
-def find_similar_pairs6(sig, lsh_count, k, threshold, permutations, search_count):
+def find_similar_pairs6(sig, lsh_count, k, threshold, permutations, search_count, rows=None):
+    """-> (cell [r, k], similarity [r, k] float32, usedCount [r]) for every cell, or for `rows` only."""
     n = sig.shape[0]
+    rows = list(range(n)) if rows is None else [int(r) for r in rows]
     table = [math.cos(float(m) * math.pi / float(lsh_count)) for m in range(lsh_count + 1)]    # src/Lsh.cpp:229-249
     bits = np.unpackbits(sig.astype(">u8").view(np.uint8).reshape(n, -1), axis=1)
     words = [[int(x) for x in row] for row in sig]
@@ -87,10 +89,10 @@ def find_similar_pairs6(sig, lsh_count, k, threshold, permutations, search_count
         x = prefixes[p][cell] ^ prefixes[p][sorted_cells[p][index]]
         return width if x == 0 else width - x.bit_length()
 
-    cells = np.zeros((n, k), dtype=np.uint32)
-    sims = np.zeros((n, k), dtype=np.float32)
-    used = np.zeros(n, dtype=np.uint32)
-    for cell in range(n):
+    cells = np.zeros((len(rows), k), dtype=np.uint32)
+    sims = np.zeros((len(rows), k), dtype=np.float32)
+    used = np.zeros(len(rows), dtype=np.uint32)
+    for r, cell in enumerate(rows):
         heap = []
         for p in range(len(permutations)):
             i = position[p][cell]
@@ -113,10 +115,10 @@ def find_similar_pairs6(sig, lsh_count, k, threshold, permutations, search_count
             elif not forward and index > 0:
                 push_heap(heap, (common_prefix(p, cell, index - 1), p, index - 1, False))
         best = sorted(set(neighbours), key=lambda x: (-x[1], x[0]))[:k]
-        used[cell] = len(best)
+        used[r] = len(best)
         for j, (other, s) in enumerate(best):
-            cells[cell, j] = other
-            sims[cell, j] = s
+            cells[r, j] = other
+            sims[r, j] = s
     return cells, sims, used
 
 
@@ -146,3 +148,26 @@ def test_python_restatement_matches_cpp(restatement, n, L, k, thr, P, S, pbits, 
     assert np.array_equal(got[1].view(np.uint32), expect[1].view(np.uint32))
     if thr < 1.0 and n > 3:
         assert expect[2].sum() > 0
+
+
+@pytest.mark.parametrize("n,L,k,thr,P,S,pbits,seed,kind", [
+    (129, 128, 200, -0.5, 64, 8192, 64, 231, "clustered"),   # 64 x 128 pointers: the queues hold exactly 8192 pops
+    (129, 64, 150, 0.2, 64, 10**6, 1, 3, "identical"),       # the same, reached by the clamp; every prefix length equal
+    (300, 100, 20, -0.5, 64, 8192, 100, -9, "clustered"),    # searchCount 8192 stops the walk before the queues empty
+    (257, 192, 30, 0.0, 64, 4097, 129, 17, "clustered"),     # just past a power of two; a third word with one live bit
+])
+def test_python_restatement_matches_cpp_at_the_search_limit(restatement, n, L, k, thr, P, S, pbits, seed, kind):
+    """The GPU kernels' limits (64 permutations, 8192 candidates per cell) on a few rows of each shape: both restatements
+    agree there too, so the C++ one can stand in for the reference at the sizes the GPU limit tests use."""
+    if kind == "identical":
+        sig = np.tile(synth.random_signatures(1, L, seed=5), (n, 1))
+    else:
+        sig = synth.clustered_signatures(n, L, cluster_count=2, flip=0.02, seed=n + L)
+    rows = np.array([0, 1, 2, 63, 64, n // 2, n - 2, n - 1], dtype=np.uint32)
+    permutations = restatement.permutations(L, P, pbits, seed)
+    expect = find_similar_pairs6(sig, L, k, thr, permutations, S, rows=rows)
+    got = restatement.find_similar_pairs6(sig, L, k, thr, P, S, pbits, seed, rows=rows)
+    assert np.array_equal(got[2], expect[2])
+    assert np.array_equal(got[0], expect[0])
+    assert np.array_equal(got[1].view(np.uint32), expect[1].view(np.uint32))
+    assert expect[2].min() > 0

@@ -136,3 +136,256 @@ def test_fsp6_scale_sampled_rows(restatement):
     cell, sim, used = restatement.find_similar_pairs6(sig, L, k, thr, P, S, pbits, seed, rows=rows)
     assert_same(pairs[rows], gused[rows], cell, sim, used)
     assert used.sum() > 0
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The kernels' limits: full candidate lists (8192 keys, 64 KiB of LDS in the select kernel), several row chunks, 64
+# permutations (64 KiB of walk heap), 64 prefix words, block and wave edges, a threshold exactly on a table value.
+# ---------------------------------------------------------------------------------------------------------------------
+
+MAX_SEARCH = 8192
+
+
+def effective_search(n, P, S):
+    return min(S, P * max(n - 1, 0))
+
+
+def chunk_rows(n, P, S):
+    """Rows per chunk of runFsp6: the candidate lists of a chunk take at most 1 GiB."""
+    return max(64, (1 << 30) // (effective_search(n, P, S) * 8))
+
+
+def dev_run(d_sig, n, begin, end, L, k, thr, P, S, pbits, seed):
+    """em2_dev_find_similar_pairs6 on rows [begin, end) -> (cell [rows, k], similarity bits [rows, k], usedCount)."""
+    import torch
+    rows = end - begin
+    d_pairs = torch.zeros((rows, k, 2), dtype=torch.int32, device="cuda")
+    d_used = torch.zeros(rows, dtype=torch.int32, device="cuda")
+    capi.dev_find_similar_pairs6(d_sig.data_ptr(), n, begin, end, L, k, thr, P, S, pbits, seed, d_pairs.data_ptr(),
+                                 d_used.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    p = d_pairs.cpu().numpy().view(np.uint32)
+    return p[:, :, 0], p[:, :, 1], d_used.cpu().numpy().view(np.uint32)
+
+
+def device_signatures(sig):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(sig).view(np.int64)).cuda()
+
+
+@pytest.mark.parametrize("n,L,k,thr,P,S,pbits,seed,kind", [
+    (129, 256, 20, -0.5, 64, 8192, 64, 231, "clustered"),      # 64 x 128 pops, all kept: span 8192; k below the 128 cells
+    (129, 256, 200, -0.5, 64, 8192, 64, 231, "clustered"),     # k above the distinct candidates: zero tail
+    (129, 128, 150, 0.2, 64, 10**6, 1, 3, "identical"),        # the clamp P * (n - 1) = 8192; every prefix length equal
+    (129, 192, 140, -0.9, 64, 10**6, 65, -5, "clustered"),     # the clamp with two prefix words
+    (300, 100, 30, -0.5, 64, 8192, 100, 9, "clustered"),       # searchCount stops the walk with pointers left
+    (129, 256, 130, -0.5, 64, 8191, 64, 231, "clustered"),     # just under the limit
+    (129, 256, 130, -0.5, 64, 4097, 64, 231, "clustered"),     # just past a power of two: span 8192 with 4095 pads
+    (129, 256, 130, -0.5, 64, 1025, 64, 231, "clustered"),     # span 2048
+    (1100, 512, 40, 0.1, 8, 1025, 64, 77, "clustered"),        # 1025 with fewer permutations and the threshold cutting
+])
+def test_fsp6_full_candidate_lists(restatement, n, L, k, thr, P, S, pbits, seed, kind):
+    if kind == "identical":
+        sig = np.tile(synth.random_signatures(1, L, seed=11), (n, 1))
+    else:
+        sig = synth.clustered_signatures(n, L, cluster_count=2, flip=0.02, seed=n + L + S)
+    assert effective_search(n, P, S) <= MAX_SEARCH
+    cell, sim, used = restatement.find_similar_pairs6(sig, L, k, thr, P, S, pbits, seed)
+    pairs, gused = capi.find_similar_pairs6(sig, L, k, thr, P, S, pbits, seed)
+    assert_same(pairs, gused, cell, sim, used)
+    assert used.min() > 0
+    if k > n - 1:
+        assert used.max() < k and np.all(pairs["cell"][:, -1] == 0)
+
+
+def chunk_rows_of_interest(n, chunk, count, seed):
+    """Both sides of every chunk edge, the first and last rows, and a hashed sample."""
+    edges = [0, 1, n - 2, n - 1]
+    for e in range(chunk, n, chunk):
+        edges += [e - 2, e - 1, e, e + 1]
+    sample = synth.hash_u64(seed, np.arange(count, dtype=np.uint64)) % np.uint64(n)
+    return np.union1d(np.array([e for e in edges if 0 <= e < n], dtype=np.uint32), sample.astype(np.uint32)).astype(np.uint32)
+
+
+def test_fsp6_several_row_chunks_and_shards(restatement):
+    """40 000 cells at 8192 candidates per cell: chunks of 16 384 rows, the third one ragged.  Rows on both sides of each
+    chunk edge against the restatement, then the same problem in row shards (not aligned to 64, crossing chunk edges of
+    the whole run and having chunk edges of their own) against the whole run, every row."""
+    n, L, k, thr, P, S, pbits, seed = 40000, 256, 30, -0.5, 4, 8192, 64, 231
+    assert chunk_rows(n, P, S) == 16384
+    sig = synth.clustered_signatures(n, L, cluster_count=16, flip=0.05, seed=4242)
+    pairs, gused = capi.find_similar_pairs6(sig, L, k, thr, P, S, pbits, seed)
+    rows = chunk_rows_of_interest(n, 16384, 120, 6)
+    assert {16383, 16384, 32767, 32768} <= set(rows.tolist())
+    cell, sim, used = restatement.find_similar_pairs6(sig, L, k, thr, P, S, pbits, seed, rows=rows)
+    assert_same(pairs[rows], gused[rows], cell, sim, used)
+    assert used.min() == k
+    d_sig = device_signatures(sig)
+    shards = [(0, 63), (63, 16449), (16449, 16450), (16450, n)]     # 1 + 2 + 1 + 2 chunks
+    parts = [dev_run(d_sig, n, b, e, L, k, thr, P, S, pbits, seed) for b, e in shards]
+    assert np.array_equal(np.concatenate([p[2] for p in parts]), gused)
+    assert np.array_equal(np.concatenate([p[0] for p in parts]), pairs["cell"])
+    assert np.array_equal(np.concatenate([p[1] for p in parts]), pairs["similarity"].view(np.uint32))
+
+
+def width_cases():
+    cases = []
+    for L in (1, 63, 65, 127, 129, 2048, 4095, 4096):
+        for pbits in sorted({1, 63, 64, 65, 128, L - 1, L}):
+            if 1 <= pbits <= L:
+                cases.append((L, pbits))
+    return cases
+
+
+@pytest.mark.parametrize("L,pbits", width_cases())
+def test_fsp6_widths_and_prefix_words(restatement, L, pbits):
+    """Signature widths around word edges and up to 64 words, prefixes of 1 .. 64 words (the permute grid's y, the LSD
+    passes, the last word's live bits, commonPrefix's word loop).  Low flip: long common prefixes."""
+    n, k, thr, P, S, seed = 150, 10, 0.5, 6, 80, 231 + L
+    sig = synth.clustered_signatures(n, L, cluster_count=3, flip=0.002 if L > 64 else 0.05, seed=L * 7 + pbits)
+    sig[n - 20:] = sig[n - 40:n - 20]                              # twenty pairs of identical cells
+    cell, sim, used = restatement.find_similar_pairs6(sig, L, k, thr, P, S, pbits, seed)
+    pairs, gused = capi.find_similar_pairs6(sig, L, k, thr, P, S, pbits, seed)
+    assert_same(pairs, gused, cell, sim, used)
+    assert used.sum() > 0
+
+
+def last_bit_signatures(restatement, n, L, P, pbits, seed):
+    """Cells that share every permuted bit but the last one: base copies, and under each permutation a cell with only
+    that permutation's last permuted bit set where the base has it clear.  The flipped cells have the lower ids, so
+    only the last bit puts them after the base copies."""
+    perms = restatement.permutations(L, P, pbits, seed)
+    base = synth.clustered_signatures(1, L, cluster_count=1, flip=0.0, seed=11)[0].copy()
+    last = [int(perms[p][pbits - 1]) for p in range(P)]
+    for b in last:
+        base[b >> 6] &= ~(np.uint64(1) << np.uint64(63 - (b & 63)))
+    sig = np.tile(base, (n, 1))
+    rng = np.random.default_rng(seed & 0xffff)
+    for i in range(n):
+        if i < 2 * P:
+            b = last[i % P]
+        elif i % 3 == 0:
+            continue
+        else:
+            b = int(rng.integers(L))
+        sig[i, b >> 6] ^= np.uint64(1) << np.uint64(63 - (b & 63))
+    return sig
+
+
+@pytest.mark.parametrize("L,pbits", [(4096, 4096), (4096, 4095), (4095, 4095), (129, 65), (128, 64), (64, 1)])
+def test_fsp6_last_permuted_bit_orders_the_sort(restatement, L, pbits):
+    """Only the last permuted bit orders these cells: a radix pass over the last prefix word that missed that bit would
+    leave them in id order."""
+    n, k, thr, P, S, seed = 48, 6, 0.2, 4, 6, 231
+    sig = last_bit_signatures(restatement, n, L, P, pbits, seed)
+    cell, sim, used = restatement.find_similar_pairs6(sig, L, k, thr, P, S, pbits, seed)
+    pairs, gused = capi.find_similar_pairs6(sig, L, k, thr, P, S, pbits, seed)
+    assert_same(pairs, gused, cell, sim, used)
+    assert used.min() > 0
+
+
+@pytest.mark.parametrize("n,L,pbits,P,S,flip", [
+    (20000, 64, 63, 1, 4097, 0.02),        # the fuzz case (seed 1): most cells share their prefix with hundreds of others
+    (5000, 128, 65, 2, 300, 0.02),         # a second word with one live bit
+    (5000, 256, 200, 3, 300, 0.1),         # 8 live bits in the fourth word
+])
+def test_fsp6_sort_of_a_partly_live_last_word_on_thousands_of_cells(restatement, n, L, pbits, P, S, flip):
+    """rocPRIM's radix sort over the last prefix word's live bits only (begin_bit > 0) put cells out of order from about
+    5 000 cells on; every earlier test had either fewer cells or whole prefix words."""
+    k, thr, seed = 100, 0.2, -366574767
+    sig = synth.clustered_signatures(n, L, cluster_count=1, flip=flip, seed=974555277)
+    pairs, gused = capi.find_similar_pairs6(sig, L, k, thr, P, S, pbits, seed)
+    rows = np.union1d(np.arange(0, n, n // 64), [n - 1]).astype(np.uint32)
+    cell, sim, used = restatement.find_similar_pairs6(sig, L, k, thr, P, S, pbits, seed, rows=rows)
+    assert_same(pairs[rows], gused[rows], cell, sim, used)
+    assert used.min() > 0
+
+
+@pytest.mark.parametrize("n", [63, 64, 65, 255, 256, 257])
+def test_fsp6_block_and_wave_edges(restatement, n):
+    L, k, thr, P, S, pbits, seed = 192, 12, 0.1, 8, 200, 65, 231
+    sig = synth.clustered_signatures(n, L, cluster_count=3, flip=0.05, seed=n)
+    cell, sim, used = restatement.find_similar_pairs6(sig, L, k, thr, P, S, pbits, seed)
+    pairs, gused = capi.find_similar_pairs6(sig, L, k, thr, P, S, pbits, seed)
+    assert_same(pairs, gused, cell, sim, used)
+    assert used.sum() > 0
+    d_sig = device_signatures(sig)
+    edges = [0] + [e for e in (63, 64, 65, 255, 256) if e < n] + [n]
+    parts = [dev_run(d_sig, n, b, e, L, k, thr, P, S, pbits, seed) for b, e in zip(edges[:-1], edges[1:])]
+    assert np.array_equal(np.concatenate([p[2] for p in parts]), used)
+    assert np.array_equal(np.concatenate([p[0] for p in parts]), cell)
+    assert np.array_equal(np.concatenate([p[1] for p in parts]), sim.view(np.uint32))
+
+
+def test_fsp6_threshold_on_a_table_value(restatement):
+    """similarityTable[m] > threshold: at the table value itself m is out, one double below it m is in."""
+    import oracle_binding
+    n, L, k, P, S, pbits, seed = 400, 256, 40, 8, 150, 64, 231
+    sig = synth.clustered_signatures(n, L, cluster_count=4, flip=0.1, seed=31)
+    cell, _, used = restatement.find_similar_pairs6(sig, L, k, -1.0, P, S, pbits, seed)
+    rows = np.repeat(np.arange(n), used)
+    other = cell[np.arange(k)[None, :] < used[:, None]]
+    m = np.array([sum(bin(int(a) ^ int(b)).count("1") for a, b in zip(sig[r], sig[o])) for r, o in zip(rows, other)])
+    values, counts = np.unique(m, return_counts=True)
+    m_hit = int(values[np.argmax(counts)])
+    t = float(oracle_binding.load_oracle().similarity_table(L)[m_hit])
+    hit = np.float32(t).view(np.uint32)
+    for thr, kept in ((np.nextafter(t, -np.inf), True), (t, False), (np.nextafter(t, np.inf), False)):
+        cell, sim, used = restatement.find_similar_pairs6(sig, L, k, float(thr), P, S, pbits, seed)
+        pairs, gused = capi.find_similar_pairs6(sig, L, k, float(thr), P, S, pbits, seed)
+        assert_same(pairs, gused, cell, sim, used)
+        stored = sim.view(np.uint32)[np.arange(k)[None, :] < used[:, None]]
+        assert (hit in stored) == kept
+
+
+def test_fsp6_just_past_the_limits_leaves_the_outputs(restatement):
+    """65 permutations, or 8193 candidates per cell: EM2_ERROR_UNSUPPORTED from the device entry, nothing written."""
+    import torch
+    n, L, k = 130, 128, 8
+    sig = synth.clustered_signatures(n, L, cluster_count=2, flip=0.02, seed=5)
+    d_sig = device_signatures(sig)
+    lib = capi.load()
+    for P, S in ((65, 100), (64, 8193), (64, 10**6)):
+        assert effective_search(n, P, S) > MAX_SEARCH or P > 64
+        d_pairs = torch.full((n, k, 2), 0x5a5a5a5a, dtype=torch.int32, device="cuda")
+        d_used = torch.full((n,), 0x3c3c3c3c, dtype=torch.int32, device="cuda")
+        rc = lib.em2_dev_find_similar_pairs6(d_sig.data_ptr(), n, 3, n, L, k, 0.2, P, S, 64, 231, d_pairs.data_ptr(),
+                                             d_used.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        assert rc == capi.EM2_ERROR_UNSUPPORTED
+        assert bool((d_pairs == 0x5a5a5a5a).all()) and bool((d_used == 0x3c3c3c3c).all())
+    # one below each limit is accepted: 64 permutations, 8192 candidates
+    cell, sim, used = restatement.find_similar_pairs6(sig[:129], L, k, 0.2, 64, 8192, 64, 231)
+    pairs, gused = capi.find_similar_pairs6(sig[:129], L, k, 0.2, 64, 8192, 64, 231)
+    assert_same(pairs, gused, cell, sim, used)
+
+
+def sweep_cases(count=50, seed=6006):
+    """A fixed list drawn once from a fixed seed: small n, everything else over the ranges the limit tests cover."""
+    rng = np.random.default_rng(seed)
+    cases = []
+    while len(cases) < count:
+        n = int(rng.choice([1, 2, 3, 63, 64, 65, 129, 129, 200, 255, 256, 257, 400]))
+        L = int(rng.choice([1, 63, 64, 65, 100, 127, 129, 256, 1024, 2048, 4095, 4096]))
+        P = int(rng.choice([1, 2, 5, 16, 33, 63, 64, 64]))
+        S = int(rng.choice([1, 10, 100, 1025, 4097, 8191, 8192, 10**6]))
+        if effective_search(n, P, S) > MAX_SEARCH or n * effective_search(n, P, S) * max(1, L // 512) > 8_000_000:
+            continue                                           # the restatement's time stays bounded
+        pbits = int(rng.choice([1, 63, 64, 65, 128, L - 1, L, int(rng.integers(1, L + 1))]))
+        if not 1 <= pbits <= L:
+            pbits = L
+        cases.append(dict(n=n, L=L, P=P, S=S, pbits=pbits, k=int(rng.choice([1, 5, 20, 100])),
+                          thr=float(rng.choice([-1.0, -0.2, 0.0, 0.2, 0.5, 0.9])), seed=int(rng.integers(-2**31, 2**31)),
+                          clusters=int(rng.choice([1, 2, 5])), flip=float(rng.choice([0.0, 0.005, 0.05, 0.2])),
+                          sig_seed=int(rng.integers(1 << 30))))
+    return cases
+
+
+@pytest.mark.parametrize("case", sweep_cases(), ids=lambda c: "n%(n)d-L%(L)d-P%(P)d-S%(S)d-b%(pbits)d" % c)
+def test_fsp6_seeded_sweep(restatement, case):
+    c = case
+    sig = synth.clustered_signatures(c["n"], c["L"], cluster_count=c["clusters"], flip=c["flip"], seed=c["sig_seed"])
+    args = (c["L"], c["k"], c["thr"], c["P"], c["S"], c["pbits"], c["seed"])
+    cell, sim, used = restatement.find_similar_pairs6(sig, *args)
+    pairs, gused = capi.find_similar_pairs6(sig, *args)
+    assert_same(pairs, gused, cell, sim, used)

@@ -2,7 +2,9 @@
 """Randomised parity sweep on a GPU box (not part of pytest): random shapes, thresholds, k and scan-form knobs, every
 result compared bit for bit with the CPU oracle.  SECONDS=300 python3 tools/fuzz_parity.py [seed]
 FUZZ_ONLY=fsp4 restricts the sweep to one path, FUZZ_WIDTHS=1100,1500,2048 to those signature widths, FUZZ_MODE=triangle
-to one scan form with the matrix cores on."""
+to one scan form with the matrix cores on.  The fsp6 leg compares with the C++ restatement (tests/fsp6_binding.py); shapes past
+its kernels' limits must answer EM2_ERROR_UNSUPPORTED and are counted apart (fsp6_unsupported), as are runs at the 8192
+clamp and runs over several row chunks."""
 import os
 import sys
 import time
@@ -12,6 +14,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import fsp6_binding  # noqa: E402
 import oracle_binding  # noqa: E402
 import synth  # noqa: E402
 from label_graphs import fast_graph  # noqa: E402
@@ -26,7 +29,9 @@ def main():
     rng = np.random.default_rng(seed)
     oracle = oracle_binding.load_oracle()
     deadline = time.time() + float(os.environ.get("SECONDS", "120"))
-    runs = {"fsp4": 0, "fsp5": 0, "fsp7": 0, "signatures": 0, "graph": 0, "labels": 0}
+    restatement6 = fsp6_binding.load()
+    runs = {"fsp4": 0, "fsp5": 0, "fsp6": 0, "fsp7": 0, "signatures": 0, "graph": 0, "labels": 0, "fsp6_unsupported": 0,
+            "fsp6_clamp8192": 0, "fsp6_chunks": 0}
     while time.time() < deadline:
         for key in KNOBS:
             os.environ.pop(key, None)
@@ -64,7 +69,7 @@ def main():
         flip = float(rng.choice([0.0, 0.02, 0.1, 0.3, 0.5]))
         sig_seed = int(rng.integers(1 << 30))
         sig = synth.clustered_signatures(n, L, cluster_count=clusters, flip=flip, seed=sig_seed)
-        what = rng.choice(["fsp4", "fsp4", "fsp4", "fsp5", "fsp7", "signatures", "graph"])
+        what = rng.choice(["fsp4", "fsp4", "fsp4", "fsp5", "fsp6", "fsp7", "signatures", "graph"])
         what = os.environ.get("FUZZ_ONLY", what)
         label = dict(n=n, L=L, k=k, thr=thr, clusters=clusters, flip=flip, sig_seed=sig_seed)
         if what == "fsp4":
@@ -95,6 +100,15 @@ def main():
             pairs, gused = capi.find_similar_pairs5(sig, L, k, thr, q, overflow)
             for key in knobs:
                 os.environ.pop(key, None)
+        elif what == "fsp6":
+            rows = fsp6_case(rng, restatement6, runs, label)
+            if rows is None:
+                continue
+            n, sig = label["n"], label.pop("sig")
+            args = (label["L"], k, thr, label["P"], label["S"], label["pbits"], label["seed"])
+            pairs, gused = capi.find_similar_pairs6(sig, *args)
+            cell, sim, used = restatement6.find_similar_pairs6(sig, *args, rows=rows)
+            pairs, gused = pairs[rows], gused[rows]
         elif what == "fsp7":
             lengths = sorted(set(int(x) for x in rng.choice([1, 2, 5, 8, 13, 16, 24, 33, 64], size=int(rng.integers(1, 4)))), reverse=True)
             max_check = int(rng.choice([0, 1, 7, 100, 100000]))
@@ -144,6 +158,54 @@ def main():
             raise SystemExit("PARITY FAILURE %s %r" % (what, label))
         runs[what] += 1
     print("fuzz ok", runs)
+
+
+def fsp6_case(rng, restatement, runs, label):
+    """Draws a findSimilarPairs6 case into `label` (n, L, P, S, pbits, seed and the signatures under "sig") and returns the
+    rows to compare, or None when the case lies past the kernels' limits and was answered EM2_ERROR_UNSUPPORTED as it
+    must be.  Large cases (several row chunks: more than 2^27 / effective-search rows) compare sampled rows that include
+    both sides of every chunk edge."""
+    big = rng.random() < 0.12
+    if big:
+        n = int(rng.choice([16385, 20000, 32769, 40000]))
+        L = int(rng.choice([64, 128, 256, 1024]))
+        P = int(rng.choice([1, 2, 4, 8]))
+        S = int(rng.choice([4097, 5000, 8192, 10 ** 6]))
+        pbits = int(rng.choice([1, 63, 64, 65, min(L, 128)]))
+    else:
+        n = int(rng.choice([1, 2, 3, 63, 64, 65, 129, 200, 257, 600, 1000, 2500]))
+        L = int(rng.choice([1, 63, 64, 65, 100, 127, 129, 256, 1024, 2048, 4095, 4096]))
+        P = int(rng.choice([1, 2, 5, 16, 33, 63, 64, 64, 65]))
+        S = int(rng.choice([1, 10, 100, 400, 1025, 4097, 8191, 8192, 8193, 10 ** 6]))
+        pbits = int(rng.choice([1, 63, 64, 65, 128, L - 1, L, int(rng.integers(1, L + 1))]))
+    pbits = pbits if 1 <= pbits <= L else L
+    seed = int(rng.integers(-2 ** 31, 2 ** 31))
+    clusters = int(rng.choice([1, 2, 5, 20]))
+    flip = float(rng.choice([0.0, 0.002, 0.02, 0.1, 0.3]))
+    sig_seed = int(rng.integers(1 << 30))
+    sig = synth.clustered_signatures(n, L, cluster_count=clusters, flip=flip, seed=sig_seed)
+    label.update(n=n, L=L, P=P, S=S, pbits=pbits, seed=seed, clusters=clusters, flip=flip, sig_seed=sig_seed)
+    effective = min(S, P * (n - 1))
+    if P > 64 or effective > 8192:
+        try:
+            capi.find_similar_pairs6(sig, L, 5, 0.2, P, S, pbits, seed)
+        except RuntimeError as e:
+            if "not supported" not in str(e):
+                raise SystemExit("PARITY FAILURE fsp6: %s %r" % (e, label))
+            runs["fsp6_unsupported"] += 1
+            return None
+        raise SystemExit("PARITY FAILURE fsp6: accepted past the limits %r" % label)
+    if S >= 8192 and effective == 8192:
+        runs["fsp6_clamp8192"] += 1
+    chunk = max(64, (1 << 30) // (max(effective, 1) * 8))
+    if n > chunk:
+        runs["fsp6_chunks"] += 1
+    label["sig"] = sig
+    if n * max(effective, 1) * max(1, L // 512) <= 4_000_000:
+        return np.arange(n, dtype=np.uint32)
+    edges = [0, n - 1] + [e + d for e in range(chunk, n, chunk) for d in (-2, -1, 0, 1)]
+    sample = rng.choice(n, size=min(n, 192), replace=False)
+    return np.union1d(np.array([e for e in edges if 0 <= e < n]), sample).astype(np.uint32)
 
 
 if __name__ == "__main__":
