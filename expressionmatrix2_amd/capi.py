@@ -51,6 +51,20 @@ SYMBOLS = {
     "em2_dev_find_similar_pairs4": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_uint32, _c.c_uint32,
                                                _c.c_uint32, _c.c_double, _c.c_void_p, _c.c_void_p, _c.c_void_p,
                                                _c.c_size_t, _c.c_void_p]),
+    "em2_find_similar_pairs0": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_uint32, _c.c_double,
+                                           _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "em2_dev_find_similar_pairs0_workspace": (_c.c_size_t, [_c.c_uint32, _c.c_uint32, _c.c_uint32, _c.c_uint32]),
+    "em2_dev_find_similar_pairs0": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_uint32, _c.c_uint32,
+                                               _c.c_uint32, _c.c_double, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                               _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "em2_matrix_find_similar_pairs0": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_char_p, _c.c_size_t,
+                                                  _c.c_double]),
+    "em2_analyze_similar_pairs": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_void_p, _c.c_void_p,
+                                             _c.c_uint32, _c.c_void_p, _c.c_double, _c.c_char_p, _c.c_char_p, _c.c_void_p,
+                                             _c.c_void_p, _c.c_void_p]),
+    "em2_matrix_analyze_similar_pairs": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_double, _c.c_char_p]),
+    "em2_matrix_compute_cell_similarity": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_uint32, _c.c_uint32, _c.c_void_p]),
+    "em2_matrix_compare_similar_pairs": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_char_p]),
     "em2_find_similar_pairs6": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_uint32, _c.c_double, _c.c_uint32,
                                            _c.c_uint32, _c.c_uint32, _c.c_int32, _c.c_void_p, _c.c_void_p]),
     "em2_dev_find_similar_pairs6": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_uint32, _c.c_uint32, _c.c_uint32,
@@ -384,6 +398,41 @@ def analyze_lsh(toc, data, gene_count, signatures, lsh_count, global_cell_ids, s
     return out
 
 
+def find_similar_pairs0(toc, data, gene_count, k=100, similarity_threshold=0.2):
+    """findSimilarPairs0 (exact, all pairs) on a subset's host CSR -> (pairs [cells, k], usedCount, lowestSimilarityIndex,
+    lowestSimilarity): the -Pairs content and the three CellInfo fields as SimilarPairs::add and sort leave them."""
+    toc = np.ascontiguousarray(toc, dtype=np.uint64)
+    data = np.ascontiguousarray(data, dtype=COUNT_DTYPE)
+    cell_count = len(toc) - 1
+    pairs = np.zeros((cell_count, k), dtype=PAIR_DTYPE)
+    used = np.zeros(cell_count, dtype=np.uint32)
+    lowest_index = np.zeros(cell_count, dtype=np.uint32)
+    lowest = np.zeros(cell_count, dtype=np.float32)
+    check(load().em2_find_similar_pairs0(_ptr(toc), _ptr(data), cell_count, gene_count, k, similarity_threshold, _ptr(pairs),
+                                         _ptr(used), _ptr(lowest_index), _ptr(lowest)))
+    return pairs, used, lowest_index, lowest
+
+
+def analyze_similar_pairs(toc, data, gene_count, pairs, used_count, global_cell_ids, csv_downsample, pairs_csv_path,
+                          statistics_csv_path):
+    """ExpressionMatrix::analyzeSimilarPairs on a subset's counts and a stored result (em2_analyze_similar_pairs) ->
+    dict(sum0, sum1, sum2); writes the two csv files."""
+    toc = np.ascontiguousarray(toc, dtype=np.uint64)
+    data = np.ascontiguousarray(data, dtype=COUNT_DTYPE)
+    pairs = np.ascontiguousarray(pairs, dtype=PAIR_DTYPE)
+    used_count = np.ascontiguousarray(used_count, dtype=np.uint32)
+    ids = np.ascontiguousarray(global_cell_ids, dtype=np.uint32)
+    n = len(toc) - 1
+    k = pairs.shape[1] if pairs.ndim == 2 else 0
+    if len(used_count) != n or len(ids) != n or (pairs.ndim == 2 and pairs.shape[0] != n):
+        raise ValueError("pairs, used_count and the cell ids must describe the cells of toc")
+    out = {"sum0": np.zeros(200, dtype=np.uint64), "sum1": np.zeros(200, dtype=np.float64), "sum2": np.zeros(200, dtype=np.float64)}
+    check(load().em2_analyze_similar_pairs(_ptr(toc), _ptr(data), n, gene_count, _ptr(pairs), _ptr(used_count), k, _ptr(ids),
+                                           csv_downsample, os.fsencode(pairs_csv_path), os.fsencode(statistics_csv_path),
+                                           _ptr(out["sum0"]), _ptr(out["sum1"]), _ptr(out["sum2"])))
+    return out
+
+
 def find_similar_pairs6(signatures, lsh_count, k, similarity_threshold, permutation_count, search_count,
                         permuted_bit_count=64, seed=231):
     """findSimilarPairs6 (the Charikar permutation search) on host signatures -> (pairs [cells, k], usedCount)."""
@@ -564,3 +613,14 @@ def dev_find_similar_pairs6(sig_ptr, cell_count, row_begin, row_end, lsh_count, 
     check(load().em2_dev_find_similar_pairs6(sig_ptr, cell_count, row_begin, row_end, lsh_count, k, similarity_threshold,
                                              permutation_count, search_count, permuted_bit_count, seed, pairs_ptr, used_ptr,
                                              stream))
+
+
+def dev_find_similar_pairs0_workspace(cell_count, row_count, gene_count, k):
+    return int(load().em2_dev_find_similar_pairs0_workspace(cell_count, row_count, gene_count, k))
+
+
+def dev_find_similar_pairs0(toc_ptr, data_ptr, cell_count, gene_count, row_begin, row_end, k, similarity_threshold, pairs_ptr,
+                            used_ptr, lowest_index_ptr, lowest_ptr, workspace_ptr, workspace_bytes, stream):
+    check(load().em2_dev_find_similar_pairs0(toc_ptr, data_ptr, cell_count, gene_count, row_begin, row_end, k,
+                                             similarity_threshold, pairs_ptr, used_ptr, lowest_index_ptr, lowest_ptr,
+                                             workspace_ptr, workspace_bytes, stream))

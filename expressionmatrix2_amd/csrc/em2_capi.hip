@@ -12,6 +12,7 @@
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
+#include <fstream>
 #include <functional>
 #include <thread>
 #include <cstdio>
@@ -1435,6 +1436,211 @@ int em2_analyze_lsh(const uint64_t* toc, const em2_count* data, uint32_t cellCou
     state = nullptr;
     if (!em2::analyzeLshEnd(finished, lshCount, statisticsCsvPath, sum0, sum1, sum2)) {
         return fail(EM2_ERROR_RUNTIME, std::string("em2_analyze_lsh: cannot write ") + (statisticsCsvPath ? statisticsCsvPath : ""));
+    }
+    return EM2_OK;
+}
+
+
+
+// ---- findSimilarPairs0 (em2_fsp0.hip) ----
+
+// The checks of findSimilarPairs0 that need no device.  CZI_ASSERT(similarityThreshold <= 1.)
+// (src/ExpressionMatrixFindSimilarPairs.cpp:26) comes first in the reference.
+static int prepareFsp0(const char* who, uint32_t cellCount, uint32_t geneCount, uint32_t k, double similarityThreshold)
+{
+    if (!(similarityThreshold <= 1.)) return fail(EM2_ERROR_RUNTIME, std::string(who) + ": Assertion failed: similarityThreshold <= 1.");
+    if (geneCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": geneCount must be positive");
+    if (!em2::fsp0Supported(cellCount, k)) {
+        return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": more than " + std::to_string(em2::fsp0MaxSlots()) +
+                                               " stored pairs per cell (min(k, cellCount-1)) is not supported");
+    }
+    return EM2_OK;
+}
+
+static int fsp0InputError(const char* who, uint32_t inputError)
+{
+    if (inputError & 1u) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": a local gene id is not below geneCount");
+    return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": the gene ids of a cell are not strictly ascending");
+}
+
+size_t em2_dev_find_similar_pairs0_workspace(uint32_t cellCount, uint32_t rowCount, uint32_t geneCount, uint32_t k)
+{
+    return em2::fsp0WorkspaceBytes(cellCount, rowCount, geneCount, k);
+}
+
+int em2_dev_find_similar_pairs0(const uint64_t* d_toc, const em2_count* d_data, uint32_t cellCount, uint32_t geneCount,
+                                uint32_t rowBegin, uint32_t rowEnd, uint32_t k, double similarityThreshold, em2_pair* d_pairs,
+                                uint32_t* d_usedCount, uint32_t* d_lowestSimilarityIndex, float* d_lowestSimilarity,
+                                void* d_workspace, size_t workspaceBytes, void* stream)
+{
+    const char* who = "em2_dev_find_similar_pairs0";
+    const int prc = prepareFsp0(who, cellCount, geneCount, k, similarityThreshold);
+    if (prc != EM2_OK) return prc;
+    if (rowBegin > rowEnd || rowEnd > cellCount) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": bad row range");
+    if (rowBegin == rowEnd) return EM2_OK;
+    if (!d_toc || !d_usedCount || !d_lowestSimilarityIndex || !d_lowestSimilarity || (!d_pairs && k) || !d_workspace) {
+        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+    }
+    if (workspaceBytes < em2::fsp0WorkspaceBytes(cellCount, rowEnd - rowBegin, geneCount, k)) {
+        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": workspace too small");
+    }
+    uint32_t inputError = 0;
+    EM2_HIP(em2::runFsp0(d_toc, reinterpret_cast<const em2::CountIn*>(d_data), cellCount, geneCount, rowBegin, rowEnd, k,
+                         similarityThreshold, reinterpret_cast<em2::PairOut*>(d_pairs), d_usedCount, d_lowestSimilarityIndex,
+                         d_lowestSimilarity, d_workspace, &inputError, static_cast<hipStream_t>(stream)));
+    if (inputError) return fsp0InputError(who, inputError);
+    return EM2_OK;
+}
+
+int em2_find_similar_pairs0(const uint64_t* toc, const em2_count* data, uint32_t cellCount, uint32_t geneCount, uint32_t k,
+                            double similarityThreshold, em2_pair* pairs, uint32_t* usedCount, uint32_t* lowestSimilarityIndex,
+                            float* lowestSimilarity)
+{
+    const char* who = "em2_find_similar_pairs0";
+    const int prc = prepareFsp0(who, cellCount, geneCount, k, similarityThreshold);
+    if (prc != EM2_OK) return prc;
+    if (cellCount == 0) return EM2_OK;
+    if (!toc || !usedCount || !lowestSimilarityIndex || !lowestSimilarity || (!pairs && k)) {
+        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+    }
+    for (uint32_t c = 0; c < cellCount; ++c) {
+        if (toc[c] > toc[c + 1]) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": toc is not ascending");
+    }
+    const uint64_t nnz = toc[cellCount] - toc[0];
+    if (nnz && !data) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null data");
+    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
+    // (the device checks the gene ids before any kernel indexes with them)
+    std::vector<uint64_t> tocFromZero;
+    const uint64_t first = toc[0];
+    if (first) {
+        tocFromZero.resize(size_t(cellCount) + 1);
+        for (uint32_t c = 0; c <= cellCount; ++c) tocFromZero[c] = toc[c] - first;
+    }
+    DeviceBuffer dToc, dData, dPairs, dUsed, dIndex, dLowest, dWorkspace;
+    const size_t workspaceBytes = em2::fsp0WorkspaceBytes(cellCount, cellCount, geneCount, k);
+    EM2_HIP(dToc.allocate((size_t(cellCount) + 1) * sizeof(uint64_t)));
+    EM2_HIP(dData.allocate(nnz * sizeof(em2_count)));
+    EM2_HIP(dPairs.allocate(size_t(cellCount) * k * sizeof(em2_pair)));
+    EM2_HIP(dUsed.allocate(size_t(cellCount) * sizeof(uint32_t)));
+    EM2_HIP(dIndex.allocate(size_t(cellCount) * sizeof(uint32_t)));
+    EM2_HIP(dLowest.allocate(size_t(cellCount) * sizeof(float)));
+    EM2_HIP(dWorkspace.allocate(workspaceBytes));
+    EM2_HIP(hipMemcpy(dToc.p, first ? tocFromZero.data() : toc, (size_t(cellCount) + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+    if (nnz) EM2_HIP(hipMemcpy(dData.p, data + first, nnz * sizeof(em2_count), hipMemcpyHostToDevice));
+    const int rc = em2_dev_find_similar_pairs0(dToc.as<uint64_t>(), dData.as<em2_count>(), cellCount, geneCount, 0, cellCount, k,
+                                               similarityThreshold, dPairs.as<em2_pair>(), dUsed.as<uint32_t>(), dIndex.as<uint32_t>(),
+                                               dLowest.as<float>(), dWorkspace.p, workspaceBytes, nullptr);
+    if (rc != EM2_OK) return rc;
+    if (k) EM2_HIP(hipMemcpy(pairs, dPairs.p, size_t(cellCount) * k * sizeof(em2_pair), hipMemcpyDeviceToHost));
+    EM2_HIP(hipMemcpy(usedCount, dUsed.p, size_t(cellCount) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    EM2_HIP(hipMemcpy(lowestSimilarityIndex, dIndex.p, size_t(cellCount) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    EM2_HIP(hipMemcpy(lowestSimilarity, dLowest.p, size_t(cellCount) * sizeof(float), hipMemcpyDeviceToHost));
+    return EM2_OK;
+}
+
+
+// ExpressionMatrix::analyzeSimilarPairs (src/ExpressionMatrixLsh.cpp:55-150) after its lookups: the exact similarity of every
+// stored pair on the device, chunk of rows by chunk of rows; bins, the seeded draw and the csv lines on the host in the
+// reference's order (cell 0 ascending, stored order).
+int em2_analyze_similar_pairs(const uint64_t* toc, const em2_count* data, uint32_t cellCount, uint32_t geneCount,
+                              const em2_pair* pairs, const uint32_t* usedCount, uint32_t k, const uint32_t* globalCellIds,
+                              double csvDownsample, const char* pairsCsvPath, const char* statisticsCsvPath,
+                              uint64_t* sum0, double* sum1, double* sum2)
+{
+    const char* who = "em2_analyze_similar_pairs";
+    if (geneCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": geneCount must be positive");
+    if (!toc || !usedCount || !globalCellIds || !pairsCsvPath || !statisticsCsvPath || (!pairs && k && cellCount)) {
+        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+    }
+    uint64_t stored = 0;
+    for (uint32_t c = 0; c < cellCount; ++c) {
+        if (toc[c] > toc[c + 1]) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": toc is not ascending");
+        if (usedCount[c] > k) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": a cell stores more than k pairs");
+        for (uint32_t t = 0; t < usedCount[c]; ++t) {
+            if (pairs[size_t(c) * k + t].cell >= cellCount) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": a stored pair names a cell that does not exist");
+        }
+        stored += usedCount[c];
+    }
+    const uint64_t nnz = cellCount ? toc[cellCount] : 0;
+    if (cellCount && toc[0] != 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": toc must start at 0");
+    if (nnz && !data) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null data");
+    if (stored && !haveDevice()) return fail(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
+
+    std::ofstream csvOut(pairsCsvPath);
+    if (!csvOut) return fail(EM2_ERROR_RUNTIME, std::string(who) + ": cannot open " + pairsCsvPath);
+    csvOut << "GlobalCellId0,GlobalCellId1,ExactSimilarity,StoredSimilarity\n";                         // :73
+    const size_t binCount = 200;                                                                         // :76-80
+    const double binWidth = 2. / double(binCount);
+    std::vector<uint64_t> s0(binCount, 0);
+    std::vector<double> s1(binCount, 0.), s2(binCount, 0.);
+    std::mt19937 randomSource(231);                                    // :84-90; boost::mt19937 has std::mt19937's parameters
+    const double factor = 1.0 / (double(0xffffffffu) + 1.0);          // boost::uniform_01 over a 32-bit engine: eng() * 2^-32
+
+    if (stored) {
+        // rows in chunks of at most 2^24 slots (128 MB of doubles), one row at least
+        const uint32_t chunkRows = std::max<uint32_t>(1u, uint32_t(std::min<uint64_t>(cellCount, (1ull << 24) / k)));
+        DeviceBuffer dToc, dData, dPairs, dUsed, dWorkspace, dExact;
+        EM2_HIP(dToc.allocate((size_t(cellCount) + 1) * sizeof(uint64_t)));
+        EM2_HIP(dData.allocate(nnz * sizeof(em2_count)));
+        EM2_HIP(dPairs.allocate(size_t(cellCount) * k * sizeof(em2_pair)));
+        EM2_HIP(dUsed.allocate(size_t(cellCount) * sizeof(uint32_t)));
+        EM2_HIP(dWorkspace.allocate(em2::storedPairsWorkspaceBytes(cellCount, chunkRows, geneCount)));
+        EM2_HIP(dExact.allocate(size_t(chunkRows) * k * sizeof(double)));
+        EM2_HIP(hipMemcpy(dToc.p, toc, (size_t(cellCount) + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+        if (nnz) EM2_HIP(hipMemcpy(dData.p, data, nnz * sizeof(em2_count), hipMemcpyHostToDevice));
+        EM2_HIP(hipMemcpy(dPairs.p, pairs, size_t(cellCount) * k * sizeof(em2_pair), hipMemcpyHostToDevice));
+        EM2_HIP(hipMemcpy(dUsed.p, usedCount, size_t(cellCount) * sizeof(uint32_t), hipMemcpyHostToDevice));
+        uint32_t inputError = 0;
+        EM2_HIP(em2::prepareStoredPairs(dToc.as<uint64_t>(), dData.as<em2::CountIn>(), cellCount, geneCount, dWorkspace.p, &inputError, nullptr));
+        if (inputError) return fsp0InputError(who, inputError);
+        std::vector<double> exact(size_t(chunkRows) * k);
+        for (uint32_t begin = 0; begin < cellCount; begin += chunkRows) {
+            const uint32_t end = uint32_t(std::min<uint64_t>(cellCount, uint64_t(begin) + chunkRows));
+            EM2_HIP(em2::launchStoredPairs(dToc.as<uint64_t>(), dData.as<em2::CountIn>(), cellCount, geneCount, begin, end,
+                                           dPairs.as<em2::PairOut>(), dUsed.as<uint32_t>(), k, dWorkspace.p, dExact.as<double>(), nullptr));
+            EM2_HIP(hipStreamSynchronize(nullptr));
+            EM2_HIP(hipMemcpy(exact.data(), dExact.p, size_t(end - begin) * k * sizeof(double), hipMemcpyDeviceToHost));
+            for (uint32_t localCellId0 = begin; localCellId0 < end; ++localCellId0) {                    // :95-125
+                for (uint32_t t = 0; t < usedCount[localCellId0]; ++t) {
+                    const em2_pair& p = pairs[size_t(localCellId0) * k + t];
+                    const float storedSimilarity = p.similarity;
+                    const double exactSimilarity = exact[size_t(localCellId0 - begin) * k + t];
+                    const double delta = storedSimilarity - exactSimilarity;
+                    const size_t bin = size_t(std::floor((exactSimilarity + 1.) / binWidth));
+                    if (!(bin < binCount)) {
+                        return fail(EM2_ERROR_RUNTIME, std::string(who) + ": Assertion failed: bin < binCount (a stored pair with exact "
+                                                       "similarity 1 or not finite; src/ExpressionMatrixLsh.cpp:111)");
+                    }
+                    ++s0[bin];
+                    s1[bin] += delta;
+                    s2[bin] += delta * delta;
+                    if (double(randomSource()) * factor < csvDownsample) {
+                        csvOut << globalCellIds[localCellId0] << ",";
+                        csvOut << globalCellIds[p.cell] << ",";
+                        csvOut << exactSimilarity << ",";
+                        csvOut << storedSimilarity << "\n";
+                    }
+                }
+            }
+        }
+    }
+    csvOut.close();
+    std::ofstream statsOut(statisticsCsvPath);                                                          // :133-148
+    if (!statsOut) return fail(EM2_ERROR_RUNTIME, std::string(who) + ": cannot open " + statisticsCsvPath);
+    statsOut << "Similarity,Bias,Rms\n";
+    for (size_t bin = 0; bin < binCount; bin++) {
+        if (s0[bin] < 2) continue;
+        const double similarity = (double(bin) + 0.5) * binWidth - 1.;
+        const double average = s1[bin] / double(s0[bin]);
+        const double sigma = std::sqrt(s2[bin] / double(s0[bin]));
+        statsOut << similarity << ",";
+        statsOut << average << ",";
+        statsOut << sigma << "\n";
+    }
+    for (size_t bin = 0; bin < binCount; bin++) {
+        if (sum0) sum0[bin] = s0[bin];
+        if (sum1) sum1[bin] = s1[bin];
+        if (sum2) sum2[bin] = s2[bin];
     }
     return EM2_OK;
 }

@@ -196,6 +196,25 @@ bool analyzeLshRows(AnalyzeLshState* s, const double* sums, uint32_t cellCount, 
                     double* exactOut, double* lshOut);
 bool analyzeLshEnd(AnalyzeLshState* s, uint32_t lshCount, const char* statisticsCsvPath, uint64_t* sum0, double* sum1, double* sum2);
 
+// em2_fsp0.hip: ExpressionMatrix::findSimilarPairs0 (src/ExpressionMatrixFindSimilarPairs.cpp:16-99) for the cells
+// [rowBegin,rowEnd) against all cells: exact similarities, SimilarPairs::add replayed per cell, the lists sorted.  The
+// slots of a cell live in LDS: min(k, cellCount - 1) <= fsp0MaxSlots().  workspace: fsp0WorkspaceBytes().  Synchronises
+// the stream.  *inputError != 0: a gene id not below geneCount (bit 0) or not ascending within a cell (bit 1).
+uint32_t fsp0MaxSlots();
+bool fsp0Supported(uint32_t cellCount, uint32_t k);
+size_t fsp0WorkspaceBytes(uint32_t cellCount, uint32_t rowCount, uint32_t geneCount, uint32_t k);
+hipError_t runFsp0(const uint64_t* toc, const CountIn* data, uint32_t cellCount, uint32_t geneCount, uint32_t rowBegin, uint32_t rowEnd,
+                   uint32_t k, double similarityThreshold, PairOut* outPairs, uint32_t* outUsed, uint32_t* outLowestIndex,
+                   float* outLowestSimilarity, void* workspace, uint32_t* inputError, hipStream_t stream);
+// The device half of ExpressionMatrix::analyzeSimilarPairs (src/ExpressionMatrixLsh.cpp:55-150): the exact similarity of
+// every stored pair of the rows, exact[(row - rowBegin) * k + t].  prepareStoredPairs fills the workspace once.
+size_t storedPairsWorkspaceBytes(uint32_t cellCount, uint32_t rowCount, uint32_t geneCount);
+hipError_t prepareStoredPairs(const uint64_t* toc, const CountIn* data, uint32_t cellCount, uint32_t geneCount, void* workspace,
+                              uint32_t* inputError, hipStream_t stream);
+hipError_t launchStoredPairs(const uint64_t* toc, const CountIn* data, uint32_t cellCount, uint32_t geneCount, uint32_t rowBegin,
+                             uint32_t rowEnd, const PairOut* pairs, const uint32_t* usedCount, uint32_t k, void* workspace,
+                             double* exact, hipStream_t stream);
+
 }  // namespace em2
 
 #endif

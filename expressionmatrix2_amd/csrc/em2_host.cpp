@@ -19,7 +19,9 @@ extern "C" int em2_internal_subset_find_similar_pairs4(const uint64_t* globalToc
 #include <algorithm>
 #include <cerrno>
 #include <cfloat>
+#include <cmath>
 #include <cstring>
+#include <fstream>
 #include <dirent.h>
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -527,6 +529,120 @@ void Matrix::findSimilarPairs7(const std::string& geneSetName, const std::string
     writeSimilarPairs(directoryName_, similarPairsName, geneSetName, cellSetName, k, uint32_t(cellCount), pairs.data(), used.data());
 }
 
+void Matrix::findSimilarPairs0(const std::string& geneSetName, const std::string& cellSetName, const std::string& similarPairsName,
+                               size_t k, double similarityThreshold) const
+{
+    // ExpressionMatrixFindSimilarPairs.cpp:26-46: the assertion, then the lookups in the order of lookupSubset
+    if (!(similarityThreshold <= 1.)) fail(EM2_ERROR_RUNTIME, "findSimilarPairs0: Assertion failed: similarityThreshold <= 1.");
+    uint32_t cellCount = 0, geneCount = 0;
+    std::vector<uint64_t> toc;
+    std::vector<em2_count> data;
+    subset(geneSetName, cellSetName, toc, data, geneCount, cellCount);                        // :53-54
+    if (k > 0xffffffffULL) fail(EM2_ERROR_INVALID_ARGUMENT, "findSimilarPairs0: k out of range");
+    // :49, :57-82: the pair loop, SimilarPairs::add and SimilarPairs::sort on the device, straight into the mapped -Pairs file
+    SimilarPairsWriter writer(directoryName_, similarPairsName, geneSetName, cellSetName, k, cellCount);
+    std::vector<uint32_t> used(cellCount), lowestIndex(cellCount);
+    std::vector<float> lowest(cellCount);
+    const int rc = em2_find_similar_pairs0(toc.data(), data.data(), cellCount, geneCount, uint32_t(k), similarityThreshold, writer.pairs(),
+                                           used.data(), lowestIndex.data(), lowest.data());
+    if (rc != EM2_OK) fail(rc, em2_last_error());
+    writer.finish(used.data(), lowestIndex.data(), lowest.data());
+}
+
+void Matrix::analyzeSimilarPairs(const std::string& similarPairsName, double csvDownsample, const std::string& outputDirectory) const
+{
+    // ExpressionMatrixLsh.cpp:60-69: the stored object names its gene set and cell set
+    SimilarPairsInfo info;
+    std::vector<em2_pair> pairs;
+    std::vector<uint32_t> used;
+    readSimilarPairs(directoryName_, similarPairsName, info, &pairs, &used);
+    if (info.k > 0xffffffffULL) fail(EM2_ERROR_INVALID_ARGUMENT, "analyzeSimilarPairs: k out of range");
+    uint32_t cellCount = 0, geneCount = 0;
+    std::vector<uint64_t> toc;
+    std::vector<em2_count> data;
+    subset(info.geneSetName, info.cellSetName, toc, data, geneCount, cellCount);
+    const uint32_t* cellIds = static_cast<const uint32_t*>(cellSet(info.cellSetName).data());
+    const std::string prefix = (outputDirectory.empty() ? std::string() : outputDirectory + "/") + similarPairsName;
+    const int rc = em2_analyze_similar_pairs(toc.data(), data.data(), cellCount, geneCount, pairs.data(), used.data(), uint32_t(info.k),
+                                             cellIds, csvDownsample, (prefix + "-analysis.csv").c_str(),
+                                             (prefix + "-analysis-statistics.csv").c_str(), nullptr, nullptr, nullptr);
+    if (rc != EM2_OK) fail(rc, em2_last_error());
+}
+
+double Matrix::computeCellSimilarity(const std::string& geneSetName, uint32_t cellId0, uint32_t cellId1) const
+{
+    const GeneSet& genes = geneSet(geneSetName);                                              // ExpressionMatrix.cpp:1461-1465
+    if (cellId0 >= cellCount() || cellId1 >= cellCount()) fail(EM2_ERROR_INVALID_ARGUMENT, "computeCellSimilarity: a cell id is not below the cell count");
+    const uint64_t* toc = static_cast<const uint64_t*>(toc_.data());
+    const em2_count* data = static_cast<const em2_count*>(data_.data());
+    const em2_count *begin0 = data + toc[cellId0], *end0 = data + toc[cellId0 + 1];
+    const em2_count *begin1 = data + toc[cellId1], *end1 = data + toc[cellId1 + 1];
+    const auto contains = [&genes](uint32_t globalGeneId) { return genes.localId(globalGeneId) != kInvalidId; };
+    double sum01 = 0.;                                                                        // :1480-1499
+    for (const em2_count *it0 = begin0, *it1 = begin1; it0 != end0 && it1 != end1;) {
+        if (it0->gene < it1->gene) ++it0;
+        else if (it1->gene < it0->gene) ++it1;
+        else {
+            if (contains(it0->gene)) sum01 += it0->count * it1->count;                       // a float product
+            ++it0;
+            ++it1;
+        }
+    }
+    double sum0 = 0., sum00 = 0., sum1 = 0., sum11 = 0.;                                      // :1504-1523
+    for (const em2_count* it = begin0; it != end0; ++it) {
+        if (contains(it->gene)) {
+            sum0 += it->count;
+            sum00 += it->count * it->count;
+        }
+    }
+    for (const em2_count* it = begin1; it != end1; ++it) {
+        if (contains(it->gene)) {
+            sum1 += it->count;
+            sum11 += it->count * it->count;
+        }
+    }
+    const double n = double(genes.size());                                                    // :1529-1535
+    const double numerator = n * sum01 - sum0 * sum1;
+    const double denominator = std::sqrt((n * sum00 - sum0 * sum0) * (n * sum11 - sum1 * sum1));
+    return numerator / denominator;
+}
+
+void Matrix::compareSimilarPairs(const std::string& similarPairsName0, const std::string& similarPairsName1,
+                                 const std::string& outputDirectory) const
+{
+    SimilarPairsInfo info0, info1;                                                            // ExpressionMatrixLsh.cpp:1204-1209
+    std::vector<em2_pair> pairs0, pairs1;
+    std::vector<uint32_t> used0, used1;
+    readSimilarPairs(directoryName_, similarPairsName0, info0, &pairs0, &used0);
+    readSimilarPairs(directoryName_, similarPairsName1, info1, &pairs1, &used1);
+    // (sets of equal content have equal hashes; both objects' hashes were just checked against the sets on disk)
+    if (info0.geneSetHash != info1.geneSetHash || geneSet(info0.geneSetName).size() != geneSet(info1.geneSetName).size()) {
+        fail(EM2_ERROR_RUNTIME, "compareSimilarPairs: Assertion failed: similarPairs0.getGeneSet() == similarPairs1.getGeneSet()");
+    }
+    if (info0.cellSetHash != info1.cellSetHash || info0.cellCount != info1.cellCount) {
+        fail(EM2_ERROR_RUNTIME, "compareSimilarPairs: Assertion failed: similarPairs0.getCellSet() == similarPairs1.getCellSet()");
+    }
+    const std::string path = (outputDirectory.empty() ? std::string() : outputDirectory + "/") + "CompareSimilarPairs.csv";
+    std::ofstream csvOut(path);                                                               // :1212-1237
+    if (!csvOut) fail(EM2_ERROR_IO, "Cannot open " + path);
+    csvOut << "CellId,Stored0,Stored1,Lowest0,Lowest1,\n";
+    for (uint32_t cellId = 0; cellId < uint32_t(info0.cellCount); cellId++) {
+        const uint32_t n0 = used0[cellId], n1 = used1[cellId];
+        // `n ? float : 1.` is a double (:1218-1219)
+        const double lowest0 = n0 ? double(pairs0[size_t(cellId) * info0.k + n0 - 1].similarity) : 1.;
+        const double lowest1 = n1 ? double(pairs1[size_t(cellId) * info1.k + n1 - 1].similarity) : 1.;
+        if (n0 == n1 && lowest0 == lowest1) continue;
+        csvOut << cellId << ",";
+        csvOut << n0 << ",";
+        csvOut << n1 << ",";
+        if (n0) csvOut << lowest0;
+        csvOut << ",";
+        if (n1) csvOut << lowest1;
+        csvOut << ",";
+        csvOut << "\n";
+    }
+}
+
 void Matrix::removeSimilarPairs(const std::string& similarPairsName) const
 {
     // ExpressionMatrixFindSimilarPairs.cpp:126-135: open (with all consistency checks), then remove.
@@ -601,13 +717,14 @@ SimilarPairsWriter::~SimilarPairsWriter()
 
 em2_pair* SimilarPairsWriter::pairs() { return static_cast<em2_pair*>(pairsFile_.data()); }
 
-void SimilarPairsWriter::finish(const uint32_t* usedCount)
+void SimilarPairsWriter::finish(const uint32_t* usedCount, const uint32_t* lowestSimilarityIndex, const float* lowestSimilarity)
 {
     CellInfoRecord* ci = static_cast<CellInfoRecord*>(cellInfoFile_.data());
     for (uint32_t c = 0; c < cellCount_; c++) {
         ci[c].usedCount = usedCount[c];                      // SimilarPairs::copy, :376
-        ci[c].lowestSimilarityIndex = 0xffffffffu;           // constructor values, never updated by copy (:36-40)
-        ci[c].lowestSimilarity = FLT_MAX;
+        // constructor values, never updated by copy (:36-40); SimilarPairs::add updates them (:185-188, :220-228)
+        ci[c].lowestSimilarityIndex = lowestSimilarityIndex ? lowestSimilarityIndex[c] : 0xffffffffu;
+        ci[c].lowestSimilarity = lowestSimilarity ? lowestSimilarity[c] : FLT_MAX;
     }
     // The three files replace an existing object in this order: the old -Info is removed first (a reader opens -Info
     // first, SimilarPairs.cpp:49-52: while the swap is in progress it finds no object instead of a -Pairs file under an -Info

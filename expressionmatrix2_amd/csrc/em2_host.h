@@ -105,6 +105,17 @@ public:
                            const std::string& similarPairsName, size_t k, double similarityThreshold,
                            const std::vector<int32_t>& lshSliceLengths, uint32_t maxCheck, size_t log2BucketCount) const;
     void removeSimilarPairs(const std::string& similarPairsName) const;
+    // ExpressionMatrix::findSimilarPairs0 (src/ExpressionMatrixFindSimilarPairs.cpp:16-99): exact, all pairs.
+    void findSimilarPairs0(const std::string& geneSetName, const std::string& cellSetName, const std::string& similarPairsName,
+                           size_t k, double similarityThreshold) const;
+    // ExpressionMatrix::analyzeSimilarPairs (src/ExpressionMatrixLsh.cpp:55-150): writes <name>-analysis.csv and
+    // <name>-analysis-statistics.csv into outputDirectory (the reference: the working directory, "").
+    void analyzeSimilarPairs(const std::string& similarPairsName, double csvDownsample, const std::string& outputDirectory) const;
+    // ExpressionMatrix::computeCellSimilarity (src/ExpressionMatrix.cpp:1456-1537): global cell ids, one pair, on the host.
+    double computeCellSimilarity(const std::string& geneSetName, uint32_t cellId0, uint32_t cellId1) const;
+    // ExpressionMatrix::compareSimilarPairs (src/ExpressionMatrixLsh.cpp:1199-1240): writes CompareSimilarPairs.csv.
+    void compareSimilarPairs(const std::string& similarPairsName0, const std::string& similarPairsName1,
+                             const std::string& outputDirectory) const;
     // ExpressionMatrix::analyzeLsh (src/ExpressionMatrixLsh.cpp:1244-1367): writes Lsh-analysis.csv and
     // LSH-analysis-statistics.csv into outputDirectory (the reference: the working directory, "").
     void analyzeLsh(const std::string& geneSetName, const std::string& cellSetName, size_t lshCount, unsigned int seed,
@@ -130,7 +141,9 @@ public:
                        const std::string& cellSetName, size_t k, uint32_t cellCount);
     ~SimilarPairsWriter();                    // not finished: the temporary files go away, an existing object stays
     em2_pair* pairs();
-    void finish(const uint32_t* usedCount);   // fills CellInfo, then renames the three files into place
+    // fills CellInfo, then renames the three files into place.  Without the two lowest* arrays CellInfo keeps the
+    // constructor's values, as after SimilarPairs::copy; with them it holds what SimilarPairs::add left (findSimilarPairs0).
+    void finish(const uint32_t* usedCount, const uint32_t* lowestSimilarityIndex = nullptr, const float* lowestSimilarity = nullptr);
 private:
     void removeStale() const;
     MappedFile infoFile_, pairsFile_, cellInfoFile_;

@@ -124,6 +124,34 @@ int em2_matrix_find_similar_pairs7(em2_matrix* matrix, const char* geneSetName, 
     });
 }
 
+int em2_matrix_find_similar_pairs0(em2_matrix* matrix, const char* geneSetName, const char* cellSetName,
+                                   const char* similarPairsName, size_t k, double similarityThreshold)
+{
+    if (!matrix || !geneSetName || !cellSetName || !similarPairsName) return nullArgument("em2_matrix_find_similar_pairs0");
+    return guarded([&] { matrix->impl->findSimilarPairs0(geneSetName, cellSetName, similarPairsName, k, similarityThreshold); });
+}
+
+int em2_matrix_analyze_similar_pairs(em2_matrix* matrix, const char* similarPairsName, double csvDownsample,
+                                     const char* outputDirectory)
+{
+    if (!matrix || !similarPairsName) return nullArgument("em2_matrix_analyze_similar_pairs");
+    return guarded([&] { matrix->impl->analyzeSimilarPairs(similarPairsName, csvDownsample, outputDirectory ? outputDirectory : ""); });
+}
+
+int em2_matrix_compute_cell_similarity(em2_matrix* matrix, const char* geneSetName, uint32_t cellId0, uint32_t cellId1,
+                                       double* similarity)
+{
+    if (!matrix || !geneSetName || !similarity) return nullArgument("em2_matrix_compute_cell_similarity");
+    return guarded([&] { *similarity = matrix->impl->computeCellSimilarity(geneSetName, cellId0, cellId1); });
+}
+
+int em2_matrix_compare_similar_pairs(em2_matrix* matrix, const char* similarPairsName0, const char* similarPairsName1,
+                                     const char* outputDirectory)
+{
+    if (!matrix || !similarPairsName0 || !similarPairsName1) return nullArgument("em2_matrix_compare_similar_pairs");
+    return guarded([&] { matrix->impl->compareSimilarPairs(similarPairsName0, similarPairsName1, outputDirectory ? outputDirectory : ""); });
+}
+
 int em2_matrix_remove_similar_pairs(em2_matrix* matrix, const char* similarPairsName)
 {
     if (!matrix || !similarPairsName) return nullArgument("em2_matrix_remove_similar_pairs");

@@ -70,6 +70,36 @@ class ExpressionMatrix:
                                                               _b(similarPairsName), k, similarityThreshold,
                                                               lshCount, seed))
 
+    # ---- src/PythonModule.cpp:776-801: the exact all-pairs search ("slow", the reference says; here it is a device scan) ----
+    def findSimilarPairs0(self, geneSetName="AllGenes", cellSetName="AllCells", similarPairsName=_REQUIRED, k=100,
+                          similarityThreshold=0.2):
+        if similarPairsName is _REQUIRED:
+            raise TypeError("findSimilarPairs0(): missing required argument 'similarPairsName'")
+        capi.check(capi.load().em2_matrix_find_similar_pairs0(self._handle, _b(geneSetName), _b(cellSetName),
+                                                              _b(similarPairsName), k, similarityThreshold))
+
+    # ---- src/PythonModule.cpp:755-771 ----
+    def computeCellSimilarity(self, geneSetName="AllGenes", cellId0=_REQUIRED, cellId1=_REQUIRED):
+        """The exact similarity of two cells (global ids) over the genes of a gene set."""
+        if cellId0 is _REQUIRED or cellId1 is _REQUIRED:
+            raise TypeError("computeCellSimilarity(): cellId0 and cellId1 are required")
+        similarity = ctypes.c_double(0.)
+        capi.check(capi.load().em2_matrix_compute_cell_similarity(self._handle, _b(geneSetName), cellId0, cellId1,
+                                                                  ctypes.byref(similarity)))
+        return similarity.value
+
+    # ---- src/PythonModule.cpp:921-925: bound without argument names or defaults ("Only intended to be used for testing") ----
+    def analyzeSimilarPairs(self, similarPairsName, csvDownsample):
+        """Writes <similarPairsName>-analysis.csv and <similarPairsName>-analysis-statistics.csv into the working
+        directory (src/ExpressionMatrixLsh.cpp:72, :133)."""
+        capi.check(capi.load().em2_matrix_analyze_similar_pairs(self._handle, _b(similarPairsName), csvDownsample, None))
+
+    # ---- src/PythonModule.cpp:935-939 ("Only intended to be used for testing") ----
+    def compareSimilarPairs(self, similarPairsName0, similarPairsName1):
+        """Writes CompareSimilarPairs.csv into the working directory (src/ExpressionMatrixLsh.cpp:1212)."""
+        capi.check(capi.load().em2_matrix_compare_similar_pairs(self._handle, _b(similarPairsName0), _b(similarPairsName1),
+                                                                None))
+
     # ---- src/PythonModule.cpp:945-953 ----
     def computeLshSignatures(self, geneSetName="AllGenes", cellSetName="AllCells", lshName=_REQUIRED, lshCount=1024,
                              seed=231):

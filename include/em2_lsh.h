@@ -118,6 +118,24 @@ int em2_find_similar_pairs6(const uint64_t* signatures, uint32_t cellCount, uint
                             double similarityThreshold, uint32_t permutationCount, uint32_t searchCount,
                             uint32_t permutedBitCount, int32_t seed, em2_pair* pairs, uint32_t* usedCount);
 
+/* ExpressionMatrix::findSimilarPairs0 after its lookups (src/ExpressionMatrixFindSimilarPairs.cpp:57-82): the exact
+ * all-pairs search on the CSR of an expression matrix subset (toc[0..cellCount], data; local gene ids below geneCount,
+ * strictly ascending within a cell).  Per pair ExpressionMatrixSubset::computeCellSimilarity
+ * (src/ExpressionMatrixSubset.cpp:47-58,83-133: float products, double sums in ascending gene order, the correlation
+ * coefficient with separate multiplications, IEEE square root and division); a pair with similarity > similarityThreshold
+ * (as doubles) is offered to both cells through SimilarPairs::add (src/SimilarPairs.cpp:170-232), each cell seeing its
+ * candidates in ascending id of the other cell; SimilarPairs::sort (:399-405) at the end.  pairs[cellCount][k] (unused
+ * slots zero) and usedCount as em2_find_similar_pairs4; lowestSimilarityIndex / lowestSimilarity [cellCount] are the
+ * CellInfo fields as add leaves them (the index names the slot before the sort; 0xffffffff / FLT_MAX for a cell
+ * that stored nothing).  Counts that are zero, infinite or NaN take part exactly as in the reference's loop; a similarity
+ * that is NaN passes no threshold.  Where the reference is undefined (a replacement while the index is 0xffffffff: k
+ * stored similarities of +inf or FLT_MAX, or k = 0 with +inf) the candidate is dropped.
+ * Errors: similarityThreshold > 1 is EM2_ERROR_RUNTIME (CZI_ASSERT, :26); min(k, cellCount-1) > 4096 is
+ * EM2_ERROR_UNSUPPORTED. */
+int em2_find_similar_pairs0(const uint64_t* toc, const em2_count* data, uint32_t cellCount, uint32_t geneCount, uint32_t k,
+                            double similarityThreshold, em2_pair* pairs, uint32_t* usedCount, uint32_t* lowestSimilarityIndex,
+                            float* lowestSimilarity);
+
 /* ExpressionMatrixSubset + Lsh + findSimilarPairs4 in one call on host buffers (SURVEY.md 8(a) row a1 on the device:
  * src/ExpressionMatrixSubset.cpp:9-42 followed by src/Lsh.cpp:118-224 and src/ExpressionMatrixLsh.cpp:200-285): the
  * global CSR (CellExpressionCounts toc/data, global gene ids) restricted to the cells cellIds[0..cellCount) (NULL =
@@ -238,6 +256,17 @@ int em2_dev_find_similar_pairs6(const uint64_t* d_signatures, uint32_t cellCount
                                 uint32_t lshCount, uint32_t k, double similarityThreshold, uint32_t permutationCount,
                                 uint32_t searchCount, uint32_t permutedBitCount, int32_t seed,
                                 em2_pair* d_pairs, uint32_t* d_usedCount, void* stream);
+
+/* em2_find_similar_pairs0 on a device-resident CSR for the cells [rowBegin,rowEnd) against all cells: d_pairs
+ * [(rowEnd-rowBegin)][k] and the three per-cell arrays [rowEnd-rowBegin], indexed by row - rowBegin (rows shard over
+ * ranks like em2_dev_find_similar_pairs5; every cell's result is independent of the others).  d_workspace holds
+ * em2_dev_find_similar_pairs0_workspace(cellCount, rowEnd-rowBegin, geneCount, k) bytes.  The gene ids are checked on
+ * the device before any kernel indexes with them.  Synchronises the stream. */
+size_t em2_dev_find_similar_pairs0_workspace(uint32_t cellCount, uint32_t rowCount, uint32_t geneCount, uint32_t k);
+int em2_dev_find_similar_pairs0(const uint64_t* d_toc, const em2_count* d_data, uint32_t cellCount, uint32_t geneCount,
+                                uint32_t rowBegin, uint32_t rowEnd, uint32_t k, double similarityThreshold, em2_pair* d_pairs,
+                                uint32_t* d_usedCount, uint32_t* d_lowestSimilarityIndex, float* d_lowestSimilarity,
+                                void* d_workspace, size_t workspaceBytes, void* stream);
 
 /* ---- findSimilarPairs4 across GPUs with every unordered pair evaluated once (one process per GPU) ----
  * The 64-cell blocks of the problem are dealt round-robin to the ranks (block g: rank g % world).  Every rank holds
@@ -402,6 +431,19 @@ int em2_analyze_lsh(const uint64_t* toc, const em2_count* data, uint32_t cellCou
                     double csvDownsample, const char* pairsCsvPath, const char* statisticsCsvPath,
                     uint64_t* sum0, double* sum1, double* sum2, double* exactSimilarity, double* lshSimilarity);
 
+
+/* ExpressionMatrix::analyzeSimilarPairs after its lookups (src/ExpressionMatrixLsh.cpp:71-148) on a subset's CSR (toc
+ * from 0) and the content of a stored SimilarPairs object (pairs[cellCount][k], usedCount[cellCount], local ids): the
+ * exact similarity of every stored pair on the device, then in the reference's order (cell 0 ascending, stored order)
+ * delta = stored - exact into 200 bins of exact similarity, one draw per pair of mt19937(231) / uniform_01 against
+ * csvDownsample, and the csv line (GlobalCellId0,GlobalCellId1,ExactSimilarity,StoredSimilarity) to pairsCsvPath;
+ * statisticsCsvPath gets Similarity,Bias,Rms for bins with at least 2 pairs.  sum0/sum1/sum2 [200] may be NULL.
+ * CZI_ASSERT(bin < binCount) (:111) is EM2_ERROR_RUNTIME. */
+int em2_analyze_similar_pairs(const uint64_t* toc, const em2_count* data, uint32_t cellCount, uint32_t geneCount,
+                              const em2_pair* pairs, const uint32_t* usedCount, uint32_t k, const uint32_t* globalCellIds,
+                              double csvDownsample, const char* pairsCsvPath, const char* statisticsCsvPath,
+                              uint64_t* sum0, double* sum1, double* sum2);
+
 /* CellGraph::labelPropagationClustering (src/CellGraph.cpp:443-612, ClusterTable src/CellGraph.hpp:50-121; reached
  * from ExpressionMatrix::createClusterGraph, src/ExpressionMatrix.cpp:2145-2149) over the graph em2_cell_graph_edges
  * built.  SURVEY.md 8(f) row 2.  vertexCellIds[v] is the cell id of vertex v, in add_vertex order with removed
@@ -472,6 +514,33 @@ int em2_matrix_find_similar_pairs7(em2_matrix* matrix, const char* geneSetName, 
                                    const char* lshName, const char* similarPairsName, size_t k,
                                    double similarityThreshold, const int32_t* lshSliceLengths, uint32_t sliceLengthCount,
                                    uint32_t maxCheck, size_t log2BucketCount);
+
+
+/* ExpressionMatrix::findSimilarPairs0 (src/ExpressionMatrixFindSimilarPairs.cpp:16-99; bound at
+ * src/PythonModule.cpp:776-801, defaults k=100, similarityThreshold=0.2).  Unlike the LSH methods it leaves
+ * lowestSimilarityIndex / lowestSimilarity in SimilarPairs-<name>-CellInfo.  Errors in the reference's order:
+ * similarityThreshold > 1 (EM2_ERROR_RUNTIME), "Gene set X does not exist." / "is empty.", "Cell set X does not exist." /
+ * "is empty.". */
+int em2_matrix_find_similar_pairs0(em2_matrix* matrix, const char* geneSetName, const char* cellSetName,
+                                   const char* similarPairsName, size_t k, double similarityThreshold);
+
+/* ExpressionMatrix::analyzeSimilarPairs (src/ExpressionMatrixLsh.cpp:55-150; bound at src/PythonModule.cpp:921-925):
+ * writes <similarPairsName>-analysis.csv and <similarPairsName>-analysis-statistics.csv into outputDirectory (NULL or
+ * "": the working directory, as the reference). */
+int em2_matrix_analyze_similar_pairs(em2_matrix* matrix, const char* similarPairsName, double csvDownsample,
+                                     const char* outputDirectory);
+
+/* ExpressionMatrix::computeCellSimilarity (src/ExpressionMatrix.cpp:1456-1537; bound at src/PythonModule.cpp:755-771):
+ * the exact similarity of two cells given by GLOBAL id over the genes of a gene set.  Host code, one pair. */
+int em2_matrix_compute_cell_similarity(em2_matrix* matrix, const char* geneSetName, uint32_t cellId0, uint32_t cellId1,
+                                       double* similarity);
+
+/* ExpressionMatrix::compareSimilarPairs (src/ExpressionMatrixLsh.cpp:1199-1240): CompareSimilarPairs.csv in
+ * outputDirectory (NULL or "": the working directory) with one line per cell whose stored count or last stored
+ * similarity differ.  EM2_ERROR_RUNTIME where the two objects' gene sets or cell sets differ (CZI_ASSERT, :1208-1209).
+ * Host code. */
+int em2_matrix_compare_similar_pairs(em2_matrix* matrix, const char* similarPairsName0, const char* similarPairsName1,
+                                     const char* outputDirectory);
 
 /* ExpressionMatrix::removeSimilarPairs (src/ExpressionMatrixFindSimilarPairs.cpp:126-135). */
 int em2_matrix_remove_similar_pairs(em2_matrix* matrix, const char* similarPairsName);
