@@ -95,6 +95,18 @@ SYMBOLS = {
     "em2_dev_cell_graph_label_propagation": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_void_p,
                                                         _c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_void_p,
                                                         _c.c_void_p]),
+    "em2_cluster_average_expression": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_void_p, _c.c_void_p,
+                                                  _c.c_uint32, _c.c_void_p]),
+    "em2_cluster_similarities": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_uint64,
+                                            _c.c_void_p]),
+    "em2_cluster_graph_create": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_void_p, _c.c_uint32,
+                                            _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint64, _c.c_uint64,
+                                            _c.c_double, _c.c_double, _c.POINTER(_c.c_void_p)]),
+    "em2_cluster_graph_sizes": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_uint32), _c.POINTER(_c.c_uint32),
+                                           _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
+    "em2_cluster_graph_get": (_c.c_int, [_c.c_void_p] * 9),
+    "em2_cluster_graph_facts": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint32]),
+    "em2_cluster_graph_free": (None, [_c.c_void_p]),
     "em2_analyze_lsh": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_void_p, _c.c_uint32, _c.c_void_p,
                                    _c.c_uint32, _c.c_double, _c.c_char_p, _c.c_char_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
                                    _c.c_void_p, _c.c_void_p]),
@@ -142,6 +154,7 @@ SYMBOLS = {
     "em2_similar_pairs_info": (_c.c_int, [_c.c_char_p, _c.c_char_p, _c.POINTER(_c.c_uint64),
                                           _c.POINTER(_c.c_uint64), _c.c_char_p, _c.c_char_p]),
     "em2_matrix_cell_set": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.POINTER(_c.c_uint32), _c.c_void_p]),
+    "em2_matrix_gene_set": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.POINTER(_c.c_uint32), _c.c_void_p]),
     "em2_cell_graph_edges": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_void_p,
                                         _c.c_void_p, _c.c_uint32, _c.c_double, _c.c_uint32, _c.c_void_p,
                                         _c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_uint64)]),
@@ -374,6 +387,82 @@ def cell_graph_label_propagation(vertex_cell_ids, edge_vertex0, edge_vertex1, ed
                                                   seed, stable_iteration_count_threshold, max_iteration_count,
                                                   _ptr(clusters), ctypes.byref(iterations)))
     return clusters, int(iterations.value)
+
+
+def cluster_average_expression(toc, data, gene_count, cluster_cells, cluster_offsets):
+    """ExpressionMatrix::computeAverageExpression, L2 (src/ExpressionMatrix.cpp:1179-1296), for the clusters
+    cluster_cells[cluster_offsets[c]:cluster_offsets[c + 1]] (rows of the CSR, in the order of the additions)
+    -> float64 [clusters, genes]."""
+    toc = np.ascontiguousarray(toc, dtype=np.uint64)
+    data = np.ascontiguousarray(data, dtype=COUNT_DTYPE)
+    cells = np.ascontiguousarray(cluster_cells, dtype=np.uint32)
+    offsets = np.ascontiguousarray(cluster_offsets, dtype=np.uint64)
+    clusters = len(offsets) - 1
+    if clusters < 0 or (clusters >= 0 and int(offsets[-1]) != len(cells)):
+        raise ValueError("cluster_offsets must have one entry per cluster plus one and end at len(cluster_cells)")
+    averages = np.zeros((clusters, gene_count), dtype=np.float64)
+    check(load().em2_cluster_average_expression(_ptr(toc), _ptr(data), len(toc) - 1, gene_count, _ptr(cells), _ptr(offsets),
+                                                clusters, _ptr(averages)))
+    return averages
+
+
+def cluster_similarities(averages, edge_cluster0, edge_cluster1):
+    """regressionCoefficient (src/regressionCoefficient.cpp:10-42) of the rows of averages named by every edge -> float64."""
+    averages = np.ascontiguousarray(averages, dtype=np.float64)
+    e0 = np.ascontiguousarray(edge_cluster0, dtype=np.uint32)
+    e1 = np.ascontiguousarray(edge_cluster1, dtype=np.uint32)
+    if averages.ndim != 2 or len(e0) != len(e1):
+        raise ValueError("averages must be [clusters, genes] and the edge arrays of one length")
+    similarity = np.zeros(len(e0), dtype=np.float64)
+    check(load().em2_cluster_similarities(_ptr(averages), averages.shape[0], averages.shape[1], _ptr(e0), _ptr(e1), len(e0),
+                                          _ptr(similarity)))
+    return similarity
+
+
+def cluster_graph_create(toc, data, gene_count, vertex_rows, edge_vertex0, edge_vertex1, labels, min_cluster_size=100, k=3,
+                         similarity_threshold=0.5, similarity_threshold_for_merge=0.9):
+    """ExpressionMatrix::createClusterGraph after the label propagation (src/ExpressionMatrix.cpp:2153-2181) -> dict:
+    clusterIds (per surviving vertex, in vertex order), cellOffsets / cells and unclusteredCells (cell-graph vertex
+    indices), averages [clusters, genes], edgeCluster0 / edgeCluster1 / edgeSimilarity (creation order), facts.
+    vertex_rows None: vertex v is row v of the CSR."""
+    toc = np.ascontiguousarray(toc, dtype=np.uint64)
+    data = np.ascontiguousarray(data, dtype=COUNT_DTYPE)
+    labels = np.ascontiguousarray(labels, dtype=np.uint32)
+    rows = None if vertex_rows is None else np.ascontiguousarray(vertex_rows, dtype=np.uint32)
+    v0 = np.ascontiguousarray(edge_vertex0, dtype=np.uint32)
+    v1 = np.ascontiguousarray(edge_vertex1, dtype=np.uint32)
+    if len(v0) != len(v1) or (rows is not None and len(rows) != len(labels)):
+        raise ValueError("one label (and row) per vertex and two vertices per edge are needed")
+    lib = load()
+    handle = ctypes.c_void_p(None)
+    check(lib.em2_cluster_graph_create(_ptr(toc), _ptr(data), len(toc) - 1, gene_count, None if rows is None else _ptr(rows),
+                                       len(labels), _ptr(v0), _ptr(v1), len(v0), _ptr(labels), min_cluster_size, k,
+                                       similarity_threshold, similarity_threshold_for_merge, ctypes.byref(handle)))
+    try:
+        clusters, genes = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        clustered, unclustered, edges = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        check(lib.em2_cluster_graph_sizes(handle, ctypes.byref(clusters), ctypes.byref(genes), ctypes.byref(clustered),
+                                          ctypes.byref(unclustered), ctypes.byref(edges)))
+        out = {
+            "clusterIds": np.zeros(clusters.value, dtype=np.uint32),
+            "cellOffsets": np.zeros(clusters.value + 1, dtype=np.uint64),
+            "cells": np.zeros(clustered.value, dtype=np.uint32),
+            "unclusteredCells": np.zeros(unclustered.value, dtype=np.uint32),
+            "averages": np.zeros((clusters.value, genes.value), dtype=np.float64),
+            "edgeCluster0": np.zeros(edges.value, dtype=np.uint32),
+            "edgeCluster1": np.zeros(edges.value, dtype=np.uint32),
+            "edgeSimilarity": np.zeros(edges.value, dtype=np.float64),
+        }
+        check(lib.em2_cluster_graph_get(handle, *[_ptr(out[key]) for key in (
+            "clusterIds", "cellOffsets", "cells", "unclusteredCells", "averages", "edgeCluster0", "edgeCluster1",
+            "edgeSimilarity")]))
+        facts = np.zeros(5, dtype=np.float64)
+        check(lib.em2_cluster_graph_facts(handle, _ptr(facts), len(facts)))
+        out["facts"] = {"seconds": facts[0], "averagesSeconds": facts[1], "similaritiesSeconds": facts[2],
+                        "initialClusterCount": int(facts[3]), "initialEdgeCount": int(facts[4])}
+    finally:
+        lib.em2_cluster_graph_free(handle)
+    return out
 
 
 def analyze_lsh(toc, data, gene_count, signatures, lsh_count, global_cell_ids, seed, csv_downsample, pairs_csv_path,

@@ -228,6 +228,16 @@ int em2_matrix_cell_set(em2_matrix* matrix, const char* cellSetName, uint32_t* c
     });
 }
 
+int em2_matrix_gene_set(em2_matrix* matrix, const char* geneSetName, uint32_t* count, uint32_t* globalIds)
+{
+    if (!matrix || !geneSetName || !count) return nullArgument("em2_matrix_gene_set");
+    return guarded([&] {
+        const em2::host::GeneSet& g = matrix->impl->geneSet(geneSetName);
+        *count = g.size();
+        if (globalIds && *count) std::memcpy(globalIds, g.genes(), size_t(*count) * sizeof(uint32_t));
+    });
+}
+
 int em2_lsh_write(const char* directoryName, const char* lshName, uint64_t cellCount, uint64_t lshCount,
                   const uint64_t* signatures)
 {

@@ -43,6 +43,7 @@ class ExpressionMatrix:
         self.directoryName = directoryName
         self._handle = ctypes.c_void_p(None)
         self._cellGraphs = {}          # ExpressionMatrix::cellGraphs (src/ExpressionMatrix.hpp): in memory only
+        self._clusterGraphs = {}       # ExpressionMatrix::clusterGraphs, likewise
         capi.check(capi.load().em2_matrix_open(_b(directoryName), ctypes.byref(self._handle)))
 
     def close(self):
@@ -223,7 +224,7 @@ class ExpressionMatrix:
         ExpressionMatrix::createClusterGraph (src/ExpressionMatrix.cpp:2145-2149; defaults from
         ClusterGraphCreationParameters, src/ClusterGraph.hpp:48-50).  The reference keeps the result in the
         clusterId of every graph vertex; here it is returned: (cellIds, clusterIds), one entry per vertex, clusters
-        numbered from 0 by decreasing size.  The rest of createClusterGraph (ClusterGraph) is outside SURVEY.md 8."""
+        numbered from 0 by decreasing size.  createClusterGraph runs this and the rest (ClusterGraph)."""
         g = self._cell_graph(graphName)
         v0, v1 = g["edgeVertices"]
         clusters, iterations = capi.cell_graph_label_propagation(g["vertexCellIds"], v0, v1, g["edgeSimilarity"], seed,
@@ -231,6 +232,84 @@ class ExpressionMatrix:
         g["clusterIds"] = clusters
         g["labelPropagationIterations"] = iterations
         return g["vertexCellIds"].copy(), clusters
+
+    # ---- src/PythonModule.cpp:1064-1119 ----
+    def createClusterGraph(self, cellGraphName=_REQUIRED, clusterGraphName=_REQUIRED, stableIterationCount=3,
+                           maxIterationCount=100, seed=231, minClusterSize=100, k=3, similarityThreshold=0.5,
+                           similarityThresholdForMerge=0.9):
+        """ExpressionMatrix::createClusterGraph (src/ExpressionMatrix.cpp:2087-2185): label propagation on the cell graph,
+        then the ClusterGraph -- merge of similar clusters, removal of small ones, average expression and similarities
+        (em2_cluster_graph_create, on the GPU), weak edges, k-NN, renumbering by decreasing size.  The gene set is that of
+        the cell graph's SimilarPairs object (:2129-2131).  The graph lives in memory, like the reference's."""
+        if cellGraphName is _REQUIRED or clusterGraphName is _REQUIRED:
+            raise TypeError("createClusterGraph(): cellGraphName and clusterGraphName are required")
+        _b(clusterGraphName)
+        if cellGraphName not in self._cellGraphs:
+            raise RuntimeError("Cell graph " + cellGraphName + " does not exist.")
+        g = self._cellGraphs[cellGraphName]
+        _, _, geneSetName, _ = files.similar_pairs_info(self.directoryName, g["similarPairsName"])
+        if clusterGraphName in self._clusterGraphs:
+            raise RuntimeError("Cluster graph " + clusterGraphName + " already exists.")
+        vertexCellIds, labels = self.labelPropagationClustering(cellGraphName, seed, stableIterationCount, maxIterationCount)
+        geneCount, toc, data = self._subset(geneSetName, g["cellSetName"])
+        graphCells = self._cell_set(g["cellSetName"])
+        order = np.argsort(graphCells, kind="stable")
+        vertexRows = order[np.searchsorted(graphCells, vertexCellIds, sorter=order)].astype(np.uint32)
+        v0, v1 = g["edgeVertices"]
+        result = capi.cluster_graph_create(toc, data, geneCount, vertexRows, v0, v1, labels, minClusterSize, k,
+                                           similarityThreshold, similarityThresholdForMerge)
+        self._clusterGraphs[clusterGraphName] = {
+            "geneSetName": geneSetName, "vertexCellIds": vertexCellIds, "result": result,
+            "position": {int(clusterId): i for i, clusterId in enumerate(result["clusterIds"].tolist())},
+        }
+
+    def _cluster_graph(self, clusterGraphName):
+        if clusterGraphName not in self._clusterGraphs:
+            raise RuntimeError("Cluster graph " + clusterGraphName + " does not exist.")
+        return self._clusterGraphs[clusterGraphName]
+
+    def _cluster(self, clusterGraphName, clusterId):
+        c = self._cluster_graph(clusterGraphName)
+        if clusterId not in c["position"]:
+            raise RuntimeError("Cluster " + str(clusterId) + " of cluster graph " + clusterGraphName + " does not exist.")
+        return c, c["position"][clusterId]
+
+    def getClusterGraphVertices(self, clusterGraphName):
+        """The cluster ids, in the order of ClusterGraph::vertexMap (src/ExpressionMatrix.cpp:2210-2227): ascending."""
+        return sorted(self._cluster_graph(clusterGraphName)["position"])
+
+    def getClusterGraphGenes(self, clusterGraphName):
+        """The global ids of the genes the cluster graph was built on (src/ExpressionMatrix.cpp:2232-2244)."""
+        c = self._cluster_graph(clusterGraphName)
+        lib = capi.load()
+        count = ctypes.c_uint32(0)
+        capi.check(lib.em2_matrix_gene_set(self._handle, _b(c["geneSetName"]), ctypes.byref(count), None))
+        ids = np.zeros(count.value, dtype=np.uint32)
+        capi.check(lib.em2_matrix_gene_set(self._handle, _b(c["geneSetName"]), ctypes.byref(count), capi._ptr(ids)))
+        return ids.tolist()
+
+    def getClusterCells(self, clusterGraphName, clusterId):
+        """The global cell ids of a cluster, in the order the reference stores them (src/ExpressionMatrix.cpp:2249-2272)."""
+        c, at = self._cluster(clusterGraphName, clusterId)
+        r = c["result"]
+        return c["vertexCellIds"][r["cells"][int(r["cellOffsets"][at]):int(r["cellOffsets"][at + 1])]].tolist()
+
+    def getClusterAverageExpression(self, clusterGraphName, clusterId):
+        """The L2-normalized average expression of a cluster, one value per gene of getClusterGraphGenes
+        (src/ExpressionMatrix.cpp:2279-2303)."""
+        c, at = self._cluster(clusterGraphName, clusterId)
+        return c["result"]["averages"][at].tolist()
+
+    def _cluster_graph_edges(self, clusterGraphName):
+        """[(clusterId0, clusterId1, similarity)] in the order the edges were created; the reference shows its edges
+        through Graphviz only (ClusterGraph::write), hence no public name.  unclusteredCells likewise:
+        _cluster_graph_unclustered_cells."""
+        r = self._cluster_graph(clusterGraphName)["result"]
+        return list(zip(r["edgeCluster0"].tolist(), r["edgeCluster1"].tolist(), r["edgeSimilarity"].tolist()))
+
+    def _cluster_graph_unclustered_cells(self, clusterGraphName):
+        c = self._cluster_graph(clusterGraphName)
+        return c["vertexCellIds"][c["result"]["unclusteredCells"]].tolist()
 
     def _cell_graph_information(self, graphName):
         """The CellGraphInformation fields stored beside the graph (src/ExpressionMatrix.cpp:1824-1839); the

@@ -466,6 +466,73 @@ int em2_dev_cell_graph_label_propagation(const uint32_t* vertexCellIds, uint32_t
                                      uint64_t maxIterationCount, uint32_t* clusterIds, uint64_t* iterationCount);
 
 /* ------------------------------------------------------------------------------------------------------
+ * The rest of ExpressionMatrix::createClusterGraph (src/ExpressionMatrix.cpp:2087-2185) after the label propagation:
+ * ClusterGraph (src/ClusterGraph.cpp:59-386).  csrc/em2_cluster_graph.hip.  Host buffers.
+ * ------------------------------------------------------------------------------------------------------ */
+
+/* ExpressionMatrix::computeAverageExpression with NormalizationMethod::L2 (src/ExpressionMatrix.cpp:1179-1245, and
+ * computeExpressionVector :1253-1296) for clusterCount lists of cells at once.  toc / data: the counts restricted to the gene
+ * set (what em2_matrix_subset produces: local gene ids strictly ascending within a cell, below geneCount).  Cluster c holds the
+ * cells (rows of the CSR) clusterCells[clusterOffsets[c] .. clusterOffsets[c+1]), clusterOffsets[0] = 0; their ORDER is the
+ * order of the reference's double additions and is kept.  averages[clusterCount][geneCount].  Per cell the norm is the double
+ * sum of the float products c*c in stored order, factor = float(1/sqrt(sum)), every count float(c*factor); per cluster and gene
+ * the double sum over the cells in list order, times 1/double(cell count); then sum += a*a over the genes ascending and
+ * a *= 1/sqrt(sum).  No operation is contracted.  An empty cluster, or cells without counts, give the reference's NaN / inf.
+ * Errors: EM2_ERROR_INVALID_ARGUMENT for gene ids out of range or not ascending and rows that do not exist; EM2_ERROR_HIP
+ * ("out of memory", with the sizes) when the table clusterCount * geneCount * 8 bytes and the sort of the listed cells' counts
+ * (24 bytes each) do not fit into the device's free memory. */
+int em2_cluster_average_expression(const uint64_t* toc, const em2_count* data, uint32_t cellCount, uint32_t geneCount,
+                                   const uint32_t* clusterCells, const uint64_t* clusterOffsets, uint32_t clusterCount,
+                                   double* averages);
+
+/* ClusterGraph::computeSimilarities (src/ClusterGraph.cpp:154-169): similarity[e] = regressionCoefficient
+ * (src/regressionCoefficient.cpp:10-42) of the rows edgeCluster0[e] and edgeCluster1[e] of averages[clusterCount][geneCount]:
+ * the five double sums over the genes ascending, every product rounded before its addition (sx and sxx once per cluster: the
+ * order, hence the bits, are those of the per-edge loop), then n*sxy - sx*sy over sqrt((n*sxx - sx*sx) * (n*syy - sy*sy)). */
+int em2_cluster_similarities(const double* averages, uint32_t clusterCount, uint32_t geneCount, const uint32_t* edgeCluster0,
+                             const uint32_t* edgeCluster1, uint64_t edgeCount, double* similarity);
+
+/* ExpressionMatrix::createClusterGraph from the ClusterGraph constructor on (src/ExpressionMatrix.cpp:2153-2181):
+ *   ClusterGraph::ClusterGraph (src/ClusterGraph.cpp:61-120)  a vertex per distinct label at its first occurrence in vertex
+ *       order, cells appended in vertex order, an edge per unordered pair of distinct clusters joined by a cell-graph edge;
+ *   mergeVertices (:174-270)   averages and similarities, connected components over edges with similarity >
+ *       similarityThresholdForMerge; the first vertex of a component survives, the others' cells are appended to it in vertex
+ *       order, their edges go with them (they are NOT transferred);
+ *   removeSmallVertices (:304-319)   fewer than minClusterSize cells: removed, cells appended to unclusteredCells;
+ *   averages and similarities again, removeWeakEdges (:324-336: similarity < similarityThreshold), makeKnn (:342-386: an edge
+ *       stays if it is among the k most similar of at least one of its vertices);
+ *   renumberClusters (:276-299)   std::sort of (vertex, uint32 size) in vertex order by size descending -- not stable; the
+ *       host's own std::sort runs on the same sequence.
+ * Inputs: the counts as for em2_cluster_average_expression with rowCount rows; vertexRows[v] = the row of cell-graph vertex v
+ * (NULL: row v); the cell graph's edges as vertex pairs in add_edge order; labels[v] = the clusterId of vertex v (what
+ * em2_cell_graph_label_propagation returned).  Label propagation itself is not run here.
+ * Two places the reference does not pin: edges of one vertex with exactly equal similarity are ordered by makeKnn's sort by
+ * their Boost descriptors (addresses) -- here the edge created later by the constructor ranks higher; and a NaN similarity
+ * (a cluster without variance or with an all-zero average) that is left when makeKnn starts makes that sort undefined --
+ * EM2_ERROR_RUNTIME.
+ * The result is an object: em2_cluster_graph_sizes, then em2_cluster_graph_get into arrays of those sizes (any may be NULL):
+ *   clusterIds[clusterCount]        the final cluster id of every surviving vertex, in vertex order
+ *   cellOffsets[clusterCount + 1], cells[clusteredCellCount]   ClusterGraphVertex::cells as cell-graph vertex indices
+ *   unclusteredCells[unclusteredCellCount]                     ClusterGraph::unclusteredCells, likewise
+ *   averages[clusterCount][geneCount]                          ClusterGraphVertex::averageGeneExpression
+ *   edgeCluster0 / edgeCluster1 / edgeSimilarity[edgeCount]    the surviving edges as final cluster ids (source, target as
+ *                                                              created), in the order of their creation
+ * em2_cluster_graph_facts (benchmarks): values[0] seconds of the call, [1] of both average computations, [2] of both
+ * similarity computations (the rest is host bookkeeping and the upload), [3] vertices and [4] edges before the merge. */
+typedef struct em2_cluster_graph em2_cluster_graph;
+int em2_cluster_graph_create(const uint64_t* toc, const em2_count* data, uint32_t rowCount, uint32_t geneCount,
+                             const uint32_t* vertexRows, uint32_t vertexCount, const uint32_t* edgeVertex0,
+                             const uint32_t* edgeVertex1, uint64_t edgeCount, const uint32_t* labels, uint64_t minClusterSize,
+                             uint64_t k, double similarityThreshold, double similarityThresholdForMerge, em2_cluster_graph** graph);
+int em2_cluster_graph_sizes(const em2_cluster_graph* graph, uint32_t* clusterCount, uint32_t* geneCount, uint64_t* clusteredCellCount,
+                            uint64_t* unclusteredCellCount, uint64_t* edgeCount);
+int em2_cluster_graph_get(const em2_cluster_graph* graph, uint32_t* clusterIds, uint64_t* cellOffsets, uint32_t* cells,
+                          uint32_t* unclusteredCells, double* averages, uint32_t* edgeCluster0, uint32_t* edgeCluster1,
+                          double* edgeSimilarity);
+int em2_cluster_graph_facts(const em2_cluster_graph* graph, double* values, uint32_t valueCount);
+void em2_cluster_graph_free(em2_cluster_graph* graph);
+
+/* ------------------------------------------------------------------------------------------------------
  * ExpressionMatrix-level entry points: the methods the reference binds to Python (src/PythonModule.cpp),
  * operating by NAME on a data directory in the reference's memory-mapped formats.  Results are files in
  * that directory (SimilarPairs-<name>-{Info,Pairs,CellInfo}, Lsh-<name>-{Info,Signatures}), byte-compatible
@@ -566,6 +633,10 @@ int em2_similar_pairs_info(const char* directoryName, const char* similarPairsNa
 
 /* A cell set of the data directory (CellSet-<name>, src/CellSets.hpp:15): pass ids == NULL to get the count. */
 int em2_matrix_cell_set(em2_matrix* matrix, const char* cellSetName, uint32_t* count, uint32_t* ids);
+
+/* The global gene ids of a gene set of the data directory (GeneSet-<name>-GlobalIds, src/GeneSet.hpp), ascending: local gene
+ * id i is globalIds[i].  Pass globalIds == NULL to get the count. */
+int em2_matrix_gene_set(em2_matrix* matrix, const char* geneSetName, uint32_t* count, uint32_t* globalIds);
 
 /* Lsh files Lsh-<name>-{Info,Signatures} (src/Lsh.hpp:136-141, src/Lsh.cpp:26-28,48-64,148). */
 int em2_lsh_write(const char* directoryName, const char* lshName, uint64_t cellCount, uint64_t lshCount,
