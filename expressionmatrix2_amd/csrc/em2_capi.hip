@@ -5,6 +5,8 @@
 #include "../../include/em2_lsh.h"
 
 #include "em2_device.h"
+#include "em2_hip_util.h"
+#include "em2_scratch.h"
 #include "em2_cluster_graph.h"
 #include "em2_tables.h"
 
@@ -45,9 +47,9 @@ int failHip(hipError_t e, const char* what)
         if (em2HipError_ != hipSuccess) return failHip(em2HipError_, #call); \
     } while (0)
 
-size_t alignUp(size_t x) { return (x + 255u) & ~size_t(255u); }
-
-uint32_t wordCountOf(uint32_t lshCount) { return (lshCount - 1u) / 64u + 1u; }
+using em2::alignUp;
+using em2::DeviceBuffer;
+using em2::wordCountOf;
 
 bool haveDevice()
 {
@@ -183,53 +185,34 @@ unsigned usableCpus()
     return n;
 }
 
-// RAII device allocation for the host-buffer entry points.
-struct DeviceBuffer {
-    void* p = nullptr;
-    size_t cachedBytes = 0;          // allocateCached: the block's size in the library's scratch cache
-    bool idle = false;               // the owner sets it when the device has finished with the block (a synchronous copy came back)
-    ~DeviceBuffer()
-    {
-        if (!p) return;
-        if (cachedBytes && idle) em2::scratchGive(p, cachedBytes);
-        else (void)hipFree(p);
-    }
-    hipError_t allocate(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-    // from the scratch cache of the process when it holds a block of that size (em2_fsp5.hip: capped, em2_dev_release_scratch()
-    // frees it), and back into it when the call completed
-    hipError_t allocateCached(size_t bytes)
-    {
-        bytes = bytes ? bytes : 1;
-        p = em2::scratchTake(bytes, &cachedBytes);
-        if (p) return hipSuccess;
-        cachedBytes = bytes;
-        const auto t0 = std::chrono::steady_clock::now();
-        const hipError_t e = hipMalloc(&p, bytes);
-        if (getenv("EM2_TIMING")) fprintf(stderr, "[em2 timing] hipMalloc of %zu bytes (not in the scratch cache): %.1f ms, %s\n", bytes,
-                                          std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), e == hipSuccess ? "ok" : "FAILED");
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            em2::fsp5ReleaseScratch();          // (memory held by the cache may be what is missing)
-            return hipMalloc(&p, bytes);
-        }
-        return e;
-    }
-    // (the caller knows the device has finished with the block)
-    void release()
-    {
-        if (!p) return;
-        if (cachedBytes) em2::scratchGive(p, cachedBytes);
-        else (void)hipFree(p);
-        p = nullptr;
-    }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-
 // a piece of a larger device block
 struct Piece {
     void* p = nullptr;
     template <class T> T* as() const { return static_cast<T*>(p); }
 };
+
+// What the host-buffer searches share behind their own argument checks: no cells (nothing to do), null pointers, the device;
+// then the signatures to the device, the device-level call -- run(d_signatures, d_pairs, d_usedCount), which leaves the stream
+// synchronised -- and the pairs (k > 0) and the used counts back.
+template <class Run>
+int hostFindSimilarPairs(const char* who, const uint64_t* signatures, uint32_t cellCount, uint32_t lshCount, uint32_t k,
+                         em2_pair* pairs, uint32_t* usedCount, Run run)
+{
+    if (cellCount == 0) return EM2_OK;
+    if (!signatures || !usedCount || (!pairs && k)) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
+    const uint32_t words = wordCountOf(lshCount);
+    DeviceBuffer dSig, dPairs, dUsed;
+    EM2_HIP(dSig.allocate(size_t(cellCount) * words * sizeof(uint64_t)));
+    EM2_HIP(dPairs.allocate(size_t(cellCount) * k * sizeof(em2_pair)));
+    EM2_HIP(dUsed.allocate(size_t(cellCount) * sizeof(uint32_t)));
+    EM2_HIP(hipMemcpy(dSig.p, signatures, size_t(cellCount) * words * sizeof(uint64_t), hipMemcpyHostToDevice));
+    const int rc = run(dSig.as<uint64_t>(), dPairs.as<em2_pair>(), dUsed.as<uint32_t>());
+    if (rc != EM2_OK) return rc;
+    if (k) EM2_HIP(hipMemcpy(pairs, dPairs.p, size_t(cellCount) * k * sizeof(em2_pair), hipMemcpyDeviceToHost));
+    EM2_HIP(hipMemcpy(usedCount, dUsed.p, size_t(cellCount) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return EM2_OK;
+}
 
 }  // namespace
 
@@ -570,7 +553,7 @@ int em2_dev_find_similar_pairs4_last_launch(double* values, uint32_t valueCount)
 }
 
 
-void em2_dev_release_scratch(void) { em2::fsp5ReleaseScratch(); }
+void em2_dev_release_scratch(void) { em2::releaseScratch(); }
 
 int em2_dev_find_similar_pairs5_last_launch(double* values, uint32_t valueCount)
 {
@@ -720,6 +703,22 @@ int em2_dev_find_similar_pairs4_status(const void* d_workspace, uint32_t rowCoun
 }
 
 
+// What em2_dev_find_similar_pairs5/6/7 check behind their own arguments, and the tables: the row range, an empty range
+// (nothing to do: EM2_OK with `empty` set), null pointers.
+static int prepareRows(const char* who, const uint64_t* d_signatures, uint32_t cellCount, uint32_t rowBegin, uint32_t rowEnd,
+                       uint32_t lshCount, uint32_t k, double similarityThreshold, const em2_pair* d_pairs,
+                       const uint32_t* d_usedCount, em2::DeviceTables& tables, bool& empty)
+{
+    empty = false;
+    if (rowBegin > rowEnd || rowEnd > cellCount) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": bad row range");
+    if (rowBegin == rowEnd) {
+        empty = true;
+        return EM2_OK;
+    }
+    if (!d_signatures || !d_usedCount || (!d_pairs && k)) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+    return getDeviceTables(lshCount, similarityThreshold, tables);
+}
+
 int em2_dev_find_similar_pairs5(const uint64_t* d_signatures, uint32_t cellCount, uint32_t rowBegin,
                                 uint32_t rowEnd, uint32_t lshCount, uint32_t k, double similarityThreshold,
                                 uint32_t lshSliceLength, uint64_t bucketOverflow, em2_pair* d_pairs,
@@ -727,12 +726,11 @@ int em2_dev_find_similar_pairs5(const uint64_t* d_signatures, uint32_t cellCount
 {
     if (lshCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dev_find_similar_pairs5: lshCount must be positive");
     if (lshSliceLength == 0 || lshSliceLength > 32) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dev_find_similar_pairs5: lshSliceLength must be in [1,32]");
-    if (rowBegin > rowEnd || rowEnd > cellCount) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dev_find_similar_pairs5: bad row range");
-    if (rowBegin == rowEnd) return EM2_OK;
-    if (!d_signatures || !d_usedCount || (!d_pairs && k)) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dev_find_similar_pairs5: null pointer");
     em2::DeviceTables tables;
-    const int rc = getDeviceTables(lshCount, similarityThreshold, tables);
-    if (rc != EM2_OK) return rc;
+    bool empty = false;
+    const int rc = prepareRows("em2_dev_find_similar_pairs5", d_signatures, cellCount, rowBegin, rowEnd, lshCount, k, similarityThreshold,
+                               d_pairs, d_usedCount, tables, empty);
+    if (rc != EM2_OK || empty) return rc;
     EM2_HIP(em2::runFsp5(d_signatures, cellCount, rowBegin, rowEnd, lshCount, k, lshSliceLength, bucketOverflow, tables,
                          reinterpret_cast<em2::PairOut*>(d_pairs), d_usedCount, static_cast<hipStream_t>(stream)));
     return EM2_OK;
@@ -773,12 +771,11 @@ int em2_dev_find_similar_pairs6(const uint64_t* d_signatures, uint32_t cellCount
 {
     const int prc = prepareFsp6("em2_dev_find_similar_pairs6", cellCount, lshCount, permutationCount, searchCount, permutedBitCount);
     if (prc != EM2_OK) return prc;
-    if (rowBegin > rowEnd || rowEnd > cellCount) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dev_find_similar_pairs6: bad row range");
-    if (rowBegin == rowEnd) return EM2_OK;
-    if (!d_signatures || !d_usedCount || (!d_pairs && k)) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dev_find_similar_pairs6: null pointer");
     em2::DeviceTables tables;
-    const int rc = getDeviceTables(lshCount, similarityThreshold, tables);
-    if (rc != EM2_OK) return rc;
+    bool empty = false;
+    const int rc = prepareRows("em2_dev_find_similar_pairs6", d_signatures, cellCount, rowBegin, rowEnd, lshCount, k, similarityThreshold,
+                               d_pairs, d_usedCount, tables, empty);
+    if (rc != EM2_OK || empty) return rc;
     EM2_HIP(em2::runFsp6(d_signatures, cellCount, rowBegin, rowEnd, lshCount, k, permutationCount, searchCount, permutedBitCount,
                          seed, tables, reinterpret_cast<em2::PairOut*>(d_pairs), d_usedCount, static_cast<hipStream_t>(stream)));
     return EM2_OK;
@@ -829,12 +826,11 @@ int em2_dev_find_similar_pairs7(const uint64_t* d_signatures, uint32_t cellCount
     const int prc = prepareFsp7("em2_dev_find_similar_pairs7", lshCount, similarityThreshold, sliceLengths, sliceLengthCount, k,
                                 log2BucketCount, mismatchThreshold);
     if (prc != EM2_OK) return prc;
-    if (rowBegin > rowEnd || rowEnd > cellCount) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dev_find_similar_pairs7: bad row range");
-    if (rowBegin == rowEnd) return EM2_OK;
-    if (!d_signatures || !d_usedCount || (!d_pairs && k)) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dev_find_similar_pairs7: null pointer");
     em2::DeviceTables tables;
-    const int rc = getDeviceTables(lshCount, similarityThreshold, tables);
-    if (rc != EM2_OK) return rc;
+    bool empty = false;
+    const int rc = prepareRows("em2_dev_find_similar_pairs7", d_signatures, cellCount, rowBegin, rowEnd, lshCount, k, similarityThreshold,
+                               d_pairs, d_usedCount, tables, empty);
+    if (rc != EM2_OK || empty) return rc;
     EM2_HIP(em2::runFsp7(d_signatures, cellCount, rowBegin, rowEnd, lshCount, k, sliceLengths, sliceLengthCount, maxCheck,
                          log2BucketCount, mismatchThreshold, tables, reinterpret_cast<em2::PairOut*>(d_pairs), d_usedCount,
                          static_cast<hipStream_t>(stream)));
@@ -854,22 +850,12 @@ int em2_find_similar_pairs7(const uint64_t* signatures, uint32_t cellCount, uint
     const int prc = prepareFsp7("em2_find_similar_pairs7", lshCount, similarityThreshold, sliceLengths, sliceLengthCount, k,
                                 log2BucketCount, mismatchThreshold);
     if (prc != EM2_OK) return prc;
-    if (cellCount == 0) return EM2_OK;
-    if (!signatures || !usedCount || (!pairs && k)) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_find_similar_pairs7: null pointer");
-    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, "em2_find_similar_pairs7: no HIP device is visible (this library has no CPU path)");
-    const uint32_t words = wordCountOf(lshCount);
-    DeviceBuffer dSig, dPairs, dUsed;
-    EM2_HIP(dSig.allocate(size_t(cellCount) * words * sizeof(uint64_t)));
-    EM2_HIP(dPairs.allocate(size_t(cellCount) * k * sizeof(em2_pair)));
-    EM2_HIP(dUsed.allocate(size_t(cellCount) * sizeof(uint32_t)));
-    EM2_HIP(hipMemcpy(dSig.p, signatures, size_t(cellCount) * words * sizeof(uint64_t), hipMemcpyHostToDevice));
-    const int rc = em2_dev_find_similar_pairs7(dSig.as<uint64_t>(), cellCount, 0, cellCount, lshCount, k, similarityThreshold,
-                                               sliceLengths, sliceLengthCount, maxCheck, log2BucketCount, dPairs.as<em2_pair>(),
-                                               dUsed.as<uint32_t>(), nullptr);
-    if (rc != EM2_OK) return rc;
-    if (k) EM2_HIP(hipMemcpy(pairs, dPairs.p, size_t(cellCount) * k * sizeof(em2_pair), hipMemcpyDeviceToHost));
-    EM2_HIP(hipMemcpy(usedCount, dUsed.p, size_t(cellCount) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return EM2_OK;
+    return hostFindSimilarPairs("em2_find_similar_pairs7", signatures, cellCount, lshCount, k, pairs, usedCount,
+                                [&](const uint64_t* dSig, em2_pair* dPairs, uint32_t* dUsed) {
+                                    return em2_dev_find_similar_pairs7(dSig, cellCount, 0, cellCount, lshCount, k, similarityThreshold,
+                                                                       sliceLengths, sliceLengthCount, maxCheck, log2BucketCount,
+                                                                       dPairs, dUsed, nullptr);
+                                });
 }
 
 
@@ -879,22 +865,12 @@ int em2_find_similar_pairs6(const uint64_t* signatures, uint32_t cellCount, uint
 {
     const int prc = prepareFsp6("em2_find_similar_pairs6", cellCount, lshCount, permutationCount, searchCount, permutedBitCount);
     if (prc != EM2_OK) return prc;
-    if (cellCount == 0) return EM2_OK;
-    if (!signatures || !usedCount || (!pairs && k)) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_find_similar_pairs6: null pointer");
-    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, "em2_find_similar_pairs6: no HIP device is visible (this library has no CPU path)");
-    const uint32_t words = wordCountOf(lshCount);
-    DeviceBuffer dSig, dPairs, dUsed;
-    EM2_HIP(dSig.allocate(size_t(cellCount) * words * sizeof(uint64_t)));
-    EM2_HIP(dPairs.allocate(size_t(cellCount) * k * sizeof(em2_pair)));
-    EM2_HIP(dUsed.allocate(size_t(cellCount) * sizeof(uint32_t)));
-    EM2_HIP(hipMemcpy(dSig.p, signatures, size_t(cellCount) * words * sizeof(uint64_t), hipMemcpyHostToDevice));
-    const int rc = em2_dev_find_similar_pairs6(dSig.as<uint64_t>(), cellCount, 0, cellCount, lshCount, k, similarityThreshold,
-                                               permutationCount, searchCount, permutedBitCount, seed, dPairs.as<em2_pair>(),
-                                               dUsed.as<uint32_t>(), nullptr);
-    if (rc != EM2_OK) return rc;
-    if (k) EM2_HIP(hipMemcpy(pairs, dPairs.p, size_t(cellCount) * k * sizeof(em2_pair), hipMemcpyDeviceToHost));
-    EM2_HIP(hipMemcpy(usedCount, dUsed.p, size_t(cellCount) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return EM2_OK;
+    return hostFindSimilarPairs("em2_find_similar_pairs6", signatures, cellCount, lshCount, k, pairs, usedCount,
+                                [&](const uint64_t* dSig, em2_pair* dPairs, uint32_t* dUsed) {
+                                    return em2_dev_find_similar_pairs6(dSig, cellCount, 0, cellCount, lshCount, k, similarityThreshold,
+                                                                       permutationCount, searchCount, permutedBitCount, seed, dPairs,
+                                                                       dUsed, nullptr);
+                                });
 }
 
 
@@ -1011,7 +987,7 @@ static int subsetFindSimilarPairs4(const uint64_t* globalToc, const em2_count* g
 
     const uint32_t words = wordCountOf(lshCount);
     CallTimer timer;
-    // ONE device block for the whole call, from the process's scratch cache (em2_fsp5.hip: capped, em2_dev_release_scratch()
+    // ONE device block for the whole call, from the process's scratch cache (em2_scratch.h: capped, em2_dev_release_scratch()
     // frees it): the signatures first, then whatever the current phase needs -- the CSR, its subset, the hyperplanes and the
     // projection's workspace; then, in the same place, the result and the scan's workspace.  A hipMalloc of gigabytes took
     // 1.6-4 s in one call of twelve on the boxes of the pool, whichever allocation it hit, so every large buffer of the call has
@@ -1036,8 +1012,8 @@ static int subsetFindSimilarPairs4(const uint64_t* globalToc, const em2_count* g
                               alignUp(size_t(geneCount) * lshCount * sizeof(double)) + alignUp(wsBytes) + alignUp(auxBytes) + 4096u;
     const size_t secondPhase = wantPairs && k ? alignUp(size_t(cellCount) * k * sizeof(em2_pair)) + alignUp(size_t(cellCount) * sizeof(uint32_t)) +
                                                     alignUp(scanWsBytes) + 4096u : 0;
-    DeviceBuffer arena;
-    EM2_HIP(arena.allocateCached(sigBytes + (firstPhase > secondPhase ? firstPhase : secondPhase) + 256u));
+    em2::CachedBuffer arena;          // (back into the cache when the call ends with arena.idle set)
+    EM2_HIP(arena.allocate(sigBytes + (firstPhase > secondPhase ? firstPhase : secondPhase) + 256u, true));
     size_t arenaAt = alignUp(reinterpret_cast<size_t>(arena.p)) - reinterpret_cast<size_t>(arena.p);
     auto carve = [&](size_t bytes) {
         Piece piece;
@@ -1178,27 +1154,18 @@ int em2_find_similar_pairs4(const uint64_t* signatures, uint32_t cellCount, uint
                             double similarityThreshold, em2_pair* pairs, uint32_t* usedCount)
 {
     if (lshCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_find_similar_pairs4: lshCount must be positive");
-    if (cellCount == 0) return EM2_OK;
-    if (!signatures || !usedCount || (!pairs && k)) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_find_similar_pairs4: null pointer");
-    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, "em2_find_similar_pairs4: no HIP device is visible (this library has no CPU path)");
-    const uint32_t words = wordCountOf(lshCount);
-    const size_t wsBytes = em2_dev_find_similar_pairs4_workspace(cellCount, cellCount, lshCount, k);
-    DeviceBuffer dSig, dPairs, dUsed, dWs;
-    EM2_HIP(dSig.allocate(size_t(cellCount) * words * sizeof(uint64_t)));
-    EM2_HIP(dPairs.allocate(size_t(cellCount) * k * sizeof(em2_pair)));
-    EM2_HIP(dUsed.allocate(size_t(cellCount) * sizeof(uint32_t)));
-    EM2_HIP(dWs.allocate(wsBytes));
-    EM2_HIP(hipMemcpy(dSig.p, signatures, size_t(cellCount) * words * sizeof(uint64_t), hipMemcpyHostToDevice));
-    const int rc = em2_dev_find_similar_pairs4(dSig.as<uint64_t>(), cellCount, 0, cellCount, lshCount, k,
-                                               similarityThreshold, dPairs.as<em2_pair>(), dUsed.as<uint32_t>(),
-                                               dWs.p, wsBytes, nullptr);
-    if (rc != EM2_OK) return rc;
-    EM2_HIP(hipStreamSynchronize(nullptr));
-    if (k) EM2_HIP(hipMemcpy(pairs, dPairs.p, size_t(cellCount) * k * sizeof(em2_pair), hipMemcpyDeviceToHost));
-    EM2_HIP(hipMemcpy(usedCount, dUsed.p, size_t(cellCount) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return EM2_OK;
+    return hostFindSimilarPairs("em2_find_similar_pairs4", signatures, cellCount, lshCount, k, pairs, usedCount,
+                                [&](const uint64_t* dSig, em2_pair* dPairs, uint32_t* dUsed) -> int {
+                                    const size_t wsBytes = em2_dev_find_similar_pairs4_workspace(cellCount, cellCount, lshCount, k);
+                                    DeviceBuffer dWs;
+                                    EM2_HIP(dWs.allocate(wsBytes));
+                                    const int rc = em2_dev_find_similar_pairs4(dSig, cellCount, 0, cellCount, lshCount, k,
+                                                                               similarityThreshold, dPairs, dUsed, dWs.p, wsBytes, nullptr);
+                                    if (rc != EM2_OK) return rc;
+                                    EM2_HIP(hipStreamSynchronize(nullptr));          // (the scan is asynchronous; dWs is freed here)
+                                    return EM2_OK;
+                                });
 }
-
 
 
 int em2_find_similar_pairs5(const uint64_t* signatures, uint32_t cellCount, uint32_t lshCount, uint32_t k,
@@ -1209,26 +1176,12 @@ int em2_find_similar_pairs5(const uint64_t* signatures, uint32_t cellCount, uint
     if (lshSliceLength == 0 || lshSliceLength > 32) {
         return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_find_similar_pairs5: lshSliceLength must be in [1,32] (the reference divides by zero for 0)");
     }
-    if (cellCount == 0) return EM2_OK;
-    if (!signatures || !usedCount || (!pairs && k)) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_find_similar_pairs5: null pointer");
-    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, "em2_find_similar_pairs5: no HIP device is visible (this library has no CPU path)");
-    const uint32_t words = wordCountOf(lshCount);
-    em2::DeviceTables tables;
-    const int rc = getDeviceTables(lshCount, similarityThreshold, tables);
-    if (rc != EM2_OK) return rc;
-    DeviceBuffer dSig, dPairs, dUsed;
-    EM2_HIP(dSig.allocate(size_t(cellCount) * words * sizeof(uint64_t)));
-    EM2_HIP(dPairs.allocate(size_t(cellCount) * k * sizeof(em2_pair)));
-    EM2_HIP(dUsed.allocate(size_t(cellCount) * sizeof(uint32_t)));
-    EM2_HIP(hipMemcpy(dSig.p, signatures, size_t(cellCount) * words * sizeof(uint64_t), hipMemcpyHostToDevice));
-    EM2_HIP(em2::runFsp5(dSig.as<uint64_t>(), cellCount, 0, cellCount, lshCount, k, lshSliceLength, bucketOverflow,
-                         tables, dPairs.as<em2::PairOut>(), dUsed.as<uint32_t>(), nullptr));
-    EM2_HIP(hipStreamSynchronize(nullptr));
-    if (k) EM2_HIP(hipMemcpy(pairs, dPairs.p, size_t(cellCount) * k * sizeof(em2_pair), hipMemcpyDeviceToHost));
-    EM2_HIP(hipMemcpy(usedCount, dUsed.p, size_t(cellCount) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return EM2_OK;
+    return hostFindSimilarPairs("em2_find_similar_pairs5", signatures, cellCount, lshCount, k, pairs, usedCount,
+                                [&](const uint64_t* dSig, em2_pair* dPairs, uint32_t* dUsed) {
+                                    return em2_dev_find_similar_pairs5(dSig, cellCount, 0, cellCount, lshCount, k, similarityThreshold,
+                                                                       lshSliceLength, bucketOverflow, dPairs, dUsed, nullptr);
+                                });
 }
-
 
 
 // pairs / usedCount on the host (em2_cell_graph_edges) or already on the device (em2_dev_cell_graph_edges: the

@@ -35,6 +35,7 @@
 // (beyond 512 of them: in global memory).
 
 #include "em2_device.h"
+#include "em2_hip_util.h"
 #include "em2_select_wave.h"
 
 #include <algorithm>
@@ -1235,23 +1236,22 @@ struct Pool {
         size = bytes;
         return hipMalloc(reinterpret_cast<void**>(&base), bytes ? bytes : 16);
     }
-    static size_t rounded(size_t bytes) { return (std::max<size_t>(bytes, 16) + 255u) & ~size_t(255); }
+    static size_t rounded(size_t bytes) { return alignUp(std::max<size_t>(bytes, 16)); }
 };
 
 struct Buffer {
+    DeviceBuffer own;          // empty when the buffer is a piece of a pool
     void* p = nullptr;
-    bool owned = false;
-    ~Buffer() { release(); }
     void release()
     {
-        if (p && owned) (void)hipFree(p);
+        own.release();
         p = nullptr;
-        owned = false;
     }
     hipError_t allocate(size_t bytes)
     {
-        owned = true;
-        return hipMalloc(&p, bytes ? bytes : 16);
+        const hipError_t e = own.allocate(bytes);
+        p = own.p;
+        return e;
     }
     hipError_t allocate(Pool& pool, size_t bytes)
     {
@@ -1259,7 +1259,6 @@ struct Buffer {
         if (pool.base && pool.used + need <= pool.size) {
             p = pool.base + pool.used;
             pool.used += need;
-            owned = false;
             return hipSuccess;
         }
         return allocate(bytes);
@@ -1464,12 +1463,6 @@ struct StreamHolder {
         }
     }
 };
-
-#define EM2_TRY(call)                        \
-    do {                                     \
-        hipError_t em2Err_ = (call);         \
-        if (em2Err_ != hipSuccess) return em2Err_; \
-    } while (0)
 
 }  // namespace
 

@@ -31,6 +31,7 @@
 //     undefined: EM2_ERROR_RUNTIME.
 
 #include "em2_device.h"
+#include "em2_hip_util.h"
 #include "em2_cluster_graph.h"
 #include "../../include/em2_lsh.h"
 
@@ -216,22 +217,6 @@ clusterEdgeKernel(const double* __restrict__ table, uint32_t geneCount, const ui
     }
 }
 
-struct Buffer {
-    void* p = nullptr;
-    ~Buffer() { release(); }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    hipError_t allocate(size_t bytes)
-    {
-        release();
-        return hipMalloc(&p, bytes ? bytes : 1);
-    }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-
 ClusterStatus ok() { return ClusterStatus{EM2_OK, std::string()}; }
 
 ClusterStatus hipFailure(hipError_t e, const char* what)
@@ -245,7 +230,7 @@ ClusterStatus hipFailure(hipError_t e, const char* what)
         if (em2Error_ != hipSuccess) return hipFailure(em2Error_, #call); \
     } while (0)
 
-uint32_t gridFor(uint64_t items, uint32_t perBlock) { return uint32_t((items + perBlock - 1u) / perBlock); }
+uint32_t blocksOf(uint64_t items, uint32_t perBlock) { return uint32_t((items + perBlock - 1u) / perBlock); }
 
 double secondsSince(std::chrono::steady_clock::time_point t0)
 {
@@ -256,7 +241,7 @@ double secondsSince(std::chrono::steady_clock::time_point t0)
 
 
 struct ClusterDevice::State {
-    Buffer toc, data, table, sx, sxx;
+    DeviceBuffer toc, data, table, sx, sxx;
     std::vector<uint64_t> hostToc;
     uint32_t rowCount = 0, geneCount = 0, clusterCount = 0;
 };
@@ -344,7 +329,7 @@ ClusterStatus ClusterDevice::averages(const char* who, const uint32_t* cellRows,
     }
     EM2_TRYC(s.table.allocate(tableBytes));
 
-    Buffer rows, positions, entryOffsets, factor, inverse, error, keysIn, keysOut, valuesIn, valuesOut, temp;
+    DeviceBuffer rows, positions, entryOffsets, factor, inverse, error, keysIn, keysOut, valuesIn, valuesOut, temp;
     EM2_TRYC(rows.allocate(listCount * sizeof(uint32_t)));
     EM2_TRYC(positions.allocate(listCount * sizeof(uint32_t)));
     EM2_TRYC(entryOffsets.allocate((listCount + 1) * sizeof(uint64_t)));
@@ -359,7 +344,7 @@ ClusterStatus ClusterDevice::averages(const char* who, const uint32_t* cellRows,
         EM2_TRYC(hipMemcpy(rows.p, cellRows, listCount * sizeof(uint32_t), hipMemcpyHostToDevice));
         EM2_TRYC(hipMemcpy(positions.p, clusterOfPosition.data(), listCount * sizeof(uint32_t), hipMemcpyHostToDevice));
         EM2_TRYC(hipMemcpy(entryOffsets.p, entryOffset.data(), (listCount + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-        clusterFactorKernel<<<dim3(gridFor(listCount, 256u)), dim3(256), 0, stream>>>(
+        clusterFactorKernel<<<dim3(blocksOf(listCount, 256u)), dim3(256), 0, stream>>>(
             s.toc.as<uint64_t>(), s.data.as<CountIn>(), geneCount, rows.as<uint32_t>(), listCount, factor.as<float>(), error.as<uint32_t>());
         EM2_TRYC(hipGetLastError());
         uint32_t inputError = 0;
@@ -373,7 +358,7 @@ ClusterStatus ClusterDevice::averages(const char* who, const uint32_t* cellRows,
         EM2_TRYC(valuesIn.allocate(entryCount * sizeof(float)));
         EM2_TRYC(valuesOut.allocate(entryCount * sizeof(float)));
         EM2_TRYC(temp.allocate(sortTempBytes));
-        clusterGatherKernel<<<dim3(gridFor(listCount, 4u)), dim3(256), 0, stream>>>(
+        clusterGatherKernel<<<dim3(blocksOf(listCount, 4u)), dim3(256), 0, stream>>>(
             s.toc.as<uint64_t>(), s.data.as<CountIn>(), geneCount, rows.as<uint32_t>(), positions.as<uint32_t>(),
             entryOffsets.as<uint64_t>(), factor.as<float>(), listCount, keysIn.as<uint64_t>(), valuesIn.as<float>());
         EM2_TRYC(hipGetLastError());
@@ -382,11 +367,11 @@ ClusterStatus ClusterDevice::averages(const char* who, const uint32_t* cellRows,
         while (endBit < 64u && (accumulatorCount >> endBit) != 0u) ++endBit;
         EM2_TRYC(rocprim::radix_sort_pairs(temp.p, sortTempBytes, keysIn.as<uint64_t>(), keysOut.as<uint64_t>(), valuesIn.as<float>(),
                                            valuesOut.as<float>(), size_t(entryCount), 0u, endBit, stream));
-        clusterRunKernel<<<dim3(gridFor(entryCount, 256u)), dim3(256), 0, stream>>>(keysOut.as<uint64_t>(), entryCount,
+        clusterRunKernel<<<dim3(blocksOf(entryCount, 256u)), dim3(256), 0, stream>>>(keysOut.as<uint64_t>(), entryCount,
                                                                                    s.table.as<unsigned long long>());
         EM2_TRYC(hipGetLastError());
     }
-    clusterSumKernel<<<dim3(gridFor(accumulatorCount, 256u)), dim3(256), 0, stream>>>(
+    clusterSumKernel<<<dim3(blocksOf(accumulatorCount, 256u)), dim3(256), 0, stream>>>(
         keysOut.as<uint64_t>(), valuesOut.as<float>(), entryCount, s.table.as<unsigned long long>(), accumulatorCount);
     EM2_TRYC(hipGetLastError());
     clusterNormalizeKernel<<<dim3(clusterCount), dim3(64), 0, stream>>>(s.table.as<double>(), geneCount, inverse.as<double>());
@@ -409,7 +394,7 @@ ClusterStatus ClusterDevice::similarities(const char* who, const uint32_t* edge0
         }
     }
     if (edgeCount == 0) return ok();
-    Buffer sx, sxx, sxy, d0, d1;
+    DeviceBuffer sx, sxx, sxy, d0, d1;
     EM2_TRYC(sx.allocate(size_t(clusterCount) * sizeof(double)));
     EM2_TRYC(sxx.allocate(size_t(clusterCount) * sizeof(double)));
     EM2_TRYC(sxy.allocate(edgeCount * sizeof(double)));

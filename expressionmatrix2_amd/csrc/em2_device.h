@@ -117,7 +117,7 @@ hipError_t launchProjectionScreened(const uint64_t* toc, const CountIn* data, ui
                                     void* workspace, hipStream_t stream);
 
 // findSimilarPairs5 (src/ExpressionMatrixLsh.cpp:355-496): bucket tables over all cells, results for the cells
-// [rowBegin,rowEnd).  Allocates its own scratch and synchronises the stream.  q = lshSliceLength in [1,32].
+// [rowBegin,rowEnd).  Allocates its own scratch (from the cache of em2_scratch.h) and synchronises the stream.  q = lshSliceLength in [1,32].
 // What the calling thread's last runFsp5 did (benchmarks): candidate ids gathered from the buckets (duplicates and the
 // cell itself included), cells queried, slices, batches, and the HIP-event durations of the candidate filter (the
 // gather of candidate signatures + popcounts) and of the selection over all batches.
@@ -126,12 +126,7 @@ struct Fsp5LaunchInfo {
     double distinctCandidates;      // what the filter read: the sizes of the cells' duplicate-free unions (the cell itself included); -1 in the sort form
 };
 Fsp5LaunchInfo fsp5LastLaunchInfo();
-// Frees the device scratch runFsp5 keeps between calls (em2_fsp5.hip: ScratchCache).
-void fsp5ReleaseScratch();
 void fsp4SetInboxEntriesPerCell(uint32_t entries);       // (this thread's symmetric scans: 0 = the default of 1024; em2_scan_symmetric.hip)
-// (em2_fsp5.hip) blocks of that cache for the library's other host-buffer entry points
-void* scratchTake(size_t bytes, size_t* got);
-void scratchGive(void* p, size_t bytes);
 
 hipError_t runFsp5(const uint64_t* d_sig, uint32_t cellCount, uint32_t rowBegin, uint32_t rowEnd, uint32_t lshCount,
                    uint32_t k, uint32_t q, uint64_t bucketOverflow, const DeviceTables& tables, PairOut* d_pairs,

@@ -22,6 +22,8 @@
 
 #include "../../include/em2_lsh.h"
 
+#include "em2_hip_util.h"
+
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -56,7 +58,7 @@ int fail(int code, const std::string& message)
         if (em2Rc_ != EM2_OK) return em2Rc_;   \
     } while (0)
 
-size_t alignUp(size_t x) { return (x + 255u) & ~size_t(255u); }
+using em2::alignUp;
 
 uint32_t shardSize(uint32_t cellCount, uint32_t world) { return (cellCount + world - 1u) / world; }
 
@@ -234,7 +236,7 @@ int em2_dist_find_similar_pairs4_with(const em2_collectives* c, const uint64_t* 
     if (stageMs) for (int i = 0; i < EM2_DIST_MS_COUNT; i++) stageMs[i] = 0.;
     Timer timer(stageMs, stream);
 
-    const uint32_t words = (lshCount - 1u) / 64u + 1u;
+    const uint32_t words = em2::wordCountOf(lshCount);
     const uint32_t shard = shardSize(cellCount, world);
     uint32_t begin = 0, end = 0;
     shardRange(cellCount, world, rank, begin, end);

@@ -20,6 +20,8 @@
 // The sorts are library primitives (rocPRIM); everything specific to the path is hand-written here.
 
 #include "em2_device.h"
+#include "em2_hip_util.h"
+#include "em2_scratch.h"
 #include "em2_select_wave.h"
 
 #include <chrono>
@@ -390,12 +392,6 @@ unionKernel(const uint32_t* __restrict__ runOfCellSlice, const uint32_t* __restr
     }
 }
 
-__device__ __forceinline__ void waveFence()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
-
 // One wave per cell: unique + mismatch filter in ascending id order (ExpressionMatrixLsh.cpp:436-445).  Uses no LDS
 // and few registers on purpose: the kernel is a latency-bound gather of candidate signatures and wants every wave
 // slot of the CU (the selection below, which stages lists in 48 KB of LDS, runs 3 waves per CU; as one fused kernel
@@ -430,7 +426,7 @@ filterKernel(const uint64_t* __restrict__ sig, uint32_t words, uint32_t batchBeg
         }
         const uint64_t mask = __builtin_amdgcn_ballot_w64(keep);
         if (keep) {
-            const uint32_t before = __builtin_amdgcn_mbcnt_hi(uint32_t(mask >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(mask), 0u));
+            const uint32_t before = lanesBelow(mask);
             Entry e;
             e.cell = cand;
             e.key = keyOfMismatch[m];
@@ -484,9 +480,9 @@ filterCooperativeKernel(const uint64_t* __restrict__ sig, uint32_t words, uint32
         }
         const uint64_t needMask = __builtin_amdgcn_ballot_w64(need);
         const uint32_t needCount = uint32_t(__builtin_popcountll(needMask));
-        const uint32_t myRank = __builtin_amdgcn_mbcnt_hi(uint32_t(needMask >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(needMask), 0u));
+        const uint32_t myRank = lanesBelow(needMask);
         if (need) candOfRank[myRank] = cand;
-        waveFence();
+        waveSync();
         // step s computes the counts of the candidates of rank s*perStep .. s*perStep+perStep-1; the count of rank r is
         // parked in lane r of mOfRank (a register indexed by lane) through a shuffle-free trick: lane r reads it from LDS
         uint32_t m = 0;
@@ -504,11 +500,11 @@ filterCooperativeKernel(const uint64_t* __restrict__ sig, uint32_t words, uint32
             const uint32_t got = uint32_t(__shfl(int(part), int(((myRank - first) % perStep) * lpc), 64));
             if (need && myRank >= first && myRank < first + perStep) m = got;
         }
-        waveFence();
+        waveSync();
         const bool keep = need && int32_t(m) <= mGlobal;
         const uint64_t mask = __builtin_amdgcn_ballot_w64(keep);
         if (keep) {
-            const uint32_t before = __builtin_amdgcn_mbcnt_hi(uint32_t(mask >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(mask), 0u));
+            const uint32_t before = lanesBelow(mask);
             Entry e;
             e.cell = cand;
             e.key = keyOfMismatch[m];
@@ -601,9 +597,9 @@ filterWideKernel(const uint64_t* __restrict__ sig, uint32_t words, uint32_t batc
         }
         const uint64_t needMask = __builtin_amdgcn_ballot_w64(need);
         const uint32_t needCount = uint32_t(__builtin_popcountll(needMask));
-        const uint32_t myRank = __builtin_amdgcn_mbcnt_hi(uint32_t(needMask >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(needMask), 0u));
+        const uint32_t myRank = lanesBelow(needMask);
         if (need) candOfRank[myRank] = cand;
-        waveFence();
+        waveSync();
         for (uint32_t first = 0; first < needCount; first += perStep * uint32_t(UNROLL)) {
             uint4 theirs[UNROLL][T];
             uint32_t rank[UNROLL];
@@ -649,17 +645,17 @@ filterWideKernel(const uint64_t* __restrict__ sig, uint32_t words, uint32_t batc
                 if (sub == 0u && rank[u] < needCount) countOfRank[rank[u]] = part[u];
             }
         }
-        waveFence();
+        waveSync();
         const uint32_t m = need ? countOfRank[myRank] : 0u;
         const bool keep = need && int32_t(m) <= mGlobal;                     // similarity > similarityThreshold (:441)
         const uint64_t mask = __builtin_amdgcn_ballot_w64(keep);
         if (keep) {
-            const uint32_t before = __builtin_amdgcn_mbcnt_hi(uint32_t(mask >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(mask), 0u));
+            const uint32_t before = lanesBelow(mask);
             const uint64_t entry = uint64_t(cand) | (uint64_t(keyOfMismatch[m]) << 32);          // Entry {cell, key}
             __builtin_nontemporal_store(entry, reinterpret_cast<uint64_t*>(list + n + before));
         }
         n += uint32_t(__builtin_popcountll(mask));
-        waveFence();          // (the next 64 candidates overwrite the two rank arrays)
+        waveSync();          // (the next 64 candidates overwrite the two rank arrays)
     }
     if (lane == 0u) listCounts[local] = n;
 }
@@ -697,11 +693,11 @@ selectKernel(uint32_t batchCells, const uint32_t* __restrict__ segmentBegin, Ent
             if (i < n) lds[i] = staged[j];
         }
     }
-    waveFence();
+    waveSync();
     if (n > k) {
         nthElementWaveT<uint16_t, false, Entry, 4>(lds, ldsL, ldsR, int(k), int(n), lane);
         n = k;
-        waveFence();
+        waveSync();
     }
     PairOut* out = outPairs + size_t(local) * k;
     for (uint32_t i = lane; i < n; i += 64u) {
@@ -716,12 +712,7 @@ selectKernel(uint32_t batchCells, const uint32_t* __restrict__ segmentBegin, Ent
         po.similarity = keySimilarity[e.key];
         out[rank] = po;
     }
-    for (uint32_t i = n + lane; i < k; i += 64u) {
-        PairOut zero;
-        zero.cell = 0u;
-        zero.similarity = 0.0f;
-        out[i] = zero;
-    }
+    clearRowTail(out, n, k, lane);
     if (lane == 0u) outUsed[local] = n;
 }
 
@@ -789,12 +780,12 @@ selectPackedKernel(uint32_t batchCells, const uint32_t* __restrict__ segmentBegi
             }
         }
     }
-    waveFence();
+    waveSync();
     EM2_SELECT_PHASE(0);
     if (n > k) {
         nthElementWaveT<uint16_t, false, PackedEntry, 4>(lds, ldsL, ldsR, int(k), int(n), lane);
         n = k;
-        waveFence();
+        waveSync();
     }
     EM2_SELECT_PHASE(1);
     // the survivors' cells, then the rank sort of SimilarPairs::copy + sort (:489-496) on (key, cell)
@@ -806,7 +797,7 @@ selectPackedKernel(uint32_t batchCells, const uint32_t* __restrict__ segmentBegi
         e.cell = list[lds[i].index].cell;
         kept[i] = e;
     }
-    waveFence();
+    waveSync();
     EM2_SELECT_PHASE(2);
     PairOut* out = outPairs + size_t(local) * k;
     uint32_t padded = 1;
@@ -836,12 +827,7 @@ selectPackedKernel(uint32_t batchCells, const uint32_t* __restrict__ segmentBegi
             out[rank] = po;
         }
     }
-    for (uint32_t i = n + lane; i < k; i += 64u) {
-        PairOut zero;
-        zero.cell = 0u;
-        zero.similarity = 0.0f;
-        out[i] = zero;
-    }
+    clearRowTail(out, n, k, lane);
     if (lane == 0u) outUsed[local] = n;
     EM2_SELECT_PHASE(4);
 }
@@ -882,140 +868,19 @@ selectGlobalKernel(uint32_t batchCells, const uint32_t* __restrict__ segmentBegi
         po.similarity = keySimilarity[e.key];
         out[rank] = po;
     }
-    for (uint32_t i = n + lane; i < k; i += 64u) {
-        PairOut zero;
-        zero.cell = 0u;
-        zero.similarity = 0.0f;
-        out[i] = zero;
-    }
+    clearRowTail(out, n, k, lane);
     if (lane == 0u) outUsed[local] = n;
 }
 
-// The scratch of a call (tables, candidate ids, lists: 10 GB at a million cells x 2048 bits) comes from a cache of device blocks
-// the process keeps between calls: hipMalloc of gigabytes costs anything between 4 and 200 ms per call depending on the state of
-// the box (measured: the same command, two leases), more than the tables' kernels.  A block goes back to the cache only when
-// the call completed (its stream synchronised); a call that returns early with an error frees its blocks (hipFree waits for the
-// device).  EM2_SCRATCH_CACHE_MB caps what is kept (default: an eighth of the device's memory; 0 = nothing is kept); em2_dev_release_scratch() frees it.
-class ScratchCache {
-public:
-    void* take(size_t bytes, int device, size_t* got)
-    {
-        std::lock_guard<std::mutex> guard(mutex_);
-        size_t best = blocks_.size();
-        for (size_t i = 0; i < blocks_.size(); ++i) {
-            const Block& b = blocks_[i];
-            if (b.device != device || b.bytes < bytes || b.bytes > bytes + bytes / 2u + (size_t(1) << 20)) continue;
-            if (best == blocks_.size() || b.bytes < blocks_[best].bytes) best = i;
-        }
-        if (best == blocks_.size()) return nullptr;
-        void* p = blocks_[best].p;
-        *got = blocks_[best].bytes;
-        total_ -= blocks_[best].bytes;
-        blocks_.erase(blocks_.begin() + long(best));
-        return p;
-    }
-    void give(void* p, size_t bytes, int device)
-    {
-        std::vector<Block> evicted;
-        bool kept = false;
-        {
-            std::lock_guard<std::mutex> guard(mutex_);
-            const size_t cap = capBytes();
-            if (bytes <= cap) {
-                // a block that fits the cap by itself makes room for itself: the OLDEST blocks go first (what the cache is for
-                // is the few large blocks of the last call -- the scan's workspace, the result -- not whatever arrived first)
-                while (!blocks_.empty() && (total_ + bytes > cap || blocks_.size() >= 256u)) {
-                    evicted.push_back(blocks_.front());
-                    total_ -= blocks_.front().bytes;
-                    blocks_.erase(blocks_.begin());
-                }
-                blocks_.push_back(Block{p, bytes, device});
-                total_ += bytes;
-                kept = true;
-            }
-        }
-        for (const Block& b : evicted) (void)hipFree(b.p);
-        if (!kept) (void)hipFree(p);
-    }
-    void clear()
-    {
-        std::vector<Block> freed;
-        {
-            std::lock_guard<std::mutex> guard(mutex_);
-            freed.swap(blocks_);
-            total_ = 0;
-        }
-        for (const Block& b : freed) (void)hipFree(b.p);
-    }
-    static ScratchCache& instance()
-    {
-        static ScratchCache* cache = new ScratchCache();          // (never destroyed: the HIP runtime may be gone at exit)
-        return *cache;
-    }
-
-private:
-    struct Block { void* p; size_t bytes; int device; };
-    static size_t capBytes()
-    {
-        // what a host process can live with: a sixteenth of the device's memory (18 GB of an MI355X's 288) unless
-        // EM2_SCRATCH_CACHE_MB says otherwise (0: nothing is kept).  One findSimilarPairs5 call's scratch at a million cells x
-        // 2048 bits is 10 GB; the scan workspace of em2_subset_find_similar_pairs4 at a million cells is 12 GB (round 5: 27, and an
-        // eighth of the memory to hold it), and it is the block that matters: its hipMalloc took 0.4 ms in 22 calls of 24 on one
-        // box and 2.7 and 4.0 s in the other two.
-        if (const char* v = getenv("EM2_SCRATCH_CACHE_MB")) return size_t(strtoull(v, nullptr, 10)) << 20;
-        static size_t share = 0;
-        if (!share) {
-            size_t freeBytes = 0, totalBytes = 0;
-            share = hipMemGetInfo(&freeBytes, &totalBytes) == hipSuccess && totalBytes ? totalBytes / 16u : size_t(4) << 30;
-        }
-        return share;
-    }
-    std::mutex mutex_;
-    std::vector<Block> blocks_;
-    size_t total_ = 0;
-};
-
+// The scratch of a call (tables, candidate ids, lists: 10 GB at a million cells x 2048 bits) comes from the cache of device blocks
+// the process keeps between calls (em2_scratch.h).  A block goes back to the cache only when the call completed (its stream
+// synchronised); a call that returns early with an error frees its blocks (hipFree waits for the device).
 thread_local bool scratchCallCompleted = false;          // set right before a call's normal return: its buffers may be cached
 
-struct Buffer {
-    void* p = nullptr;
-    size_t bytes = 0;
-    int device = 0;
+// (explicit releases happen behind a synchronisation of the stream: the block is idle)
+struct Buffer : CachedBuffer {
     ~Buffer() { drop(scratchCallCompleted); }
-    // (explicit releases happen behind a synchronisation of the stream: the block is idle)
-    void release() { drop(true); }
-    void drop(bool idle)
-    {
-        if (!p) return;
-        if (idle) ScratchCache::instance().give(p, bytes, device);
-        else (void)hipFree(p);
-        p = nullptr;
-    }
-    hipError_t allocate(size_t wanted)
-    {
-        drop(false);
-        wanted = wanted ? wanted : 1;
-        if (hipGetDevice(&device) != hipSuccess) device = 0;
-        p = ScratchCache::instance().take(wanted, device, &bytes);
-        if (p) return hipSuccess;
-        bytes = wanted;
-        const hipError_t e = hipMalloc(&p, wanted);
-        if (e != hipSuccess) {
-            // (memory held by the cache may be what is missing)
-            (void)hipGetLastError();
-            ScratchCache::instance().clear();
-            return hipMalloc(&p, wanted);
-        }
-        return e;
-    }
-    template <class T> T* as() const { return static_cast<T*>(p); }
 };
-
-uint32_t gridFor(uint64_t n)
-{
-    const uint64_t blocks = (n + 255) / 256;
-    return uint32_t(blocks > 16384 ? 16384 : (blocks ? blocks : 1));
-}
 
 uint64_t envBatchLog2()
 {
@@ -1031,12 +896,6 @@ uint32_t bitsFor(uint64_t maxValue)
     return b;
 }
 
-#define EM2_TRY(call)                        \
-    do {                                     \
-        hipError_t em2Err_ = (call);         \
-        if (em2Err_ != hipSuccess) return em2Err_; \
-    } while (0)
-
 }  // namespace
 
 
@@ -1049,36 +908,12 @@ thread_local Fsp5LaunchInfo lastFsp5Info = {0., 0., 0., 0., -1., -1., -1.};
 
 Fsp5LaunchInfo fsp5LastLaunchInfo() { return lastFsp5Info; }
 
-void fsp5ReleaseScratch() { ScratchCache::instance().clear(); }
-
-// The cache for other host-buffer entry points of the library (csrc/em2_capi.hip: the result and the scan workspace of
-// em2_subset_find_similar_pairs4 -- 6 GB at 1M cells, whose hipMalloc took 1.6-2.7 s in two calls of fourteen on one box and
-// 1.7 ms otherwise).  scratchTake: a cached block of at least `bytes` on the current device, or nullptr; scratchGive: an IDLE block
-// back (freed when the cache is full).
-void* scratchTake(size_t bytes, size_t* got)
-{
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess) return nullptr;
-    return ScratchCache::instance().take(bytes ? bytes : 1, device, got);
-}
-
-void scratchGive(void* p, size_t bytes)
-{
-    int device = 0;
-    if (!p) return;
-    if (hipGetDevice(&device) != hipSuccess) {
-        (void)hipFree(p);
-        return;
-    }
-    ScratchCache::instance().give(p, bytes, device);
-}
-
 hipError_t runFsp5(const uint64_t* d_sig, uint32_t cellCount, uint32_t rowBegin, uint32_t rowEnd, uint32_t lshCount,
                    uint32_t k, uint32_t q, uint64_t bucketOverflow, const DeviceTables& tables, PairOut* d_pairs,
                    uint32_t* d_used, hipStream_t stream)
 {
     const uint32_t rowCount = rowEnd - rowBegin;
-    const uint32_t words = (lshCount - 1u) / 64u + 1u;
+    const uint32_t words = wordCountOf(lshCount);
     const uint32_t sliceCount = lshCount / q;                       // ExpressionMatrixLsh.cpp:355
     if (rowCount == 0) return hipSuccess;
     scratchCallCompleted = false;

@@ -26,6 +26,8 @@
 //      always has the same key) and writes the first k.  Rows are processed in chunks that bound the lists' scratch.
 
 #include "em2_device.h"
+#include "em2_hip_util.h"
+#include "em2_wave.h"
 
 #include <cstring>
 
@@ -216,11 +218,6 @@ walkKernel(WalkArgs a, uint32_t rowBegin, uint32_t rowEnd, uint64_t* __restrict_
 
 #undef EM2_HEAP
 
-__device__ __forceinline__ uint32_t lanesBelow6(uint64_t mask)
-{
-    return __builtin_amdgcn_mbcnt_hi(uint32_t(mask >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(mask), 0u));
-}
-
 // One wave per row: sort the row's keys (bitonic, in LDS), unique, first k.
 __global__ void __launch_bounds__(64)
 selectKernel(const uint64_t* __restrict__ lists, const uint32_t* __restrict__ listCount, uint32_t listCapacity,
@@ -265,7 +262,7 @@ selectKernel(const uint64_t* __restrict__ lists, const uint32_t* __restrict__ li
             fresh = i == 0u || keys[i - 1u] != key;
         }
         const uint64_t mask = __builtin_amdgcn_ballot_w64(fresh);
-        const uint32_t rank = kept + lanesBelow6(mask);
+        const uint32_t rank = kept + lanesBelow(mask);
         if (fresh && rank < k) {
             PairOut po;
             po.cell = uint32_t(key);
@@ -275,34 +272,9 @@ selectKernel(const uint64_t* __restrict__ lists, const uint32_t* __restrict__ li
         kept += uint32_t(__builtin_popcountll(mask));
     }
     if (kept > k) kept = k;
-    for (uint32_t i = kept + lane; i < k; i += 64u) {
-        PairOut zero;
-        zero.cell = 0u;
-        zero.similarity = 0.0f;
-        out[i] = zero;
-    }
+    clearRowTail(out, kept, k, lane);
     if (lane == 0u) outUsed[local] = kept;
 }
-
-struct Buffer6 {
-    void* p = nullptr;
-    ~Buffer6() { if (p) (void)hipFree(p); }
-    void release() { if (p) { (void)hipFree(p); p = nullptr; } }
-    hipError_t allocate(size_t bytes) { release(); return hipMalloc(&p, bytes ? bytes : 1); }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-
-uint32_t gridFor6(uint64_t n)
-{
-    const uint64_t blocks = (n + 255) / 256;
-    return uint32_t(blocks > 16384 ? 16384 : (blocks ? blocks : 1));
-}
-
-#define EM2_TRY6(call)                       \
-    do {                                     \
-        hipError_t em2Err_ = (call);         \
-        if (em2Err_ != hipSuccess) return em2Err_; \
-    } while (0)
 
 }  // namespace
 
@@ -345,64 +317,64 @@ hipError_t runFsp6(const uint64_t* d_sig, uint32_t cellCount, uint32_t rowBegin,
         permutedBitCount > lshCount || permutedBitCount > kMaxPrefixWords * 64u) {
         return hipErrorInvalidValue;
     }
-    EM2_TRY6(hipMemsetAsync(d_used, 0, size_t(rowCount) * sizeof(uint32_t), stream));
-    if (k) EM2_TRY6(hipMemsetAsync(d_pairs, 0, size_t(rowCount) * k * sizeof(PairOut), stream));
+    EM2_TRY(hipMemsetAsync(d_used, 0, size_t(rowCount) * sizeof(uint32_t), stream));
+    if (k) EM2_TRY(hipMemsetAsync(d_pairs, 0, size_t(rowCount) * k * sizeof(PairOut), stream));
     if (k == 0 || listCapacity64 == 0 || tables.mGlobal < 0) return hipStreamSynchronize(stream);
     const uint32_t listCapacity = uint32_t(listCapacity64);
-    const uint32_t sigWords = (lshCount - 1u) / 64u + 1u;
-    const uint32_t prefixWords = (permutedBitCount - 1u) / 64u + 1u;
+    const uint32_t sigWords = wordCountOf(lshCount);
+    const uint32_t prefixWords = wordCountOf(permutedBitCount);
     const uint32_t n = cellCount;
     const size_t P = permutationCount;
 
     std::vector<uint32_t> perms;
     fsp6Permutations(lshCount, permutationCount, permutedBitCount, seed, perms);
-    Buffer6 dPerms, permWords, sortedPrefix, cellIds, position;
-    EM2_TRY6(dPerms.allocate(perms.size() * sizeof(uint32_t)));
-    EM2_TRY6(hipMemcpyAsync(dPerms.p, perms.data(), perms.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    EM2_TRY6(permWords.allocate(P * prefixWords * n * sizeof(uint64_t)));
-    EM2_TRY6(sortedPrefix.allocate(P * prefixWords * n * sizeof(uint64_t)));
-    EM2_TRY6(cellIds.allocate(P * n * sizeof(uint32_t)));
-    EM2_TRY6(position.allocate(P * n * sizeof(uint32_t)));
+    DeviceBuffer dPerms, permWords, sortedPrefix, cellIds, position;
+    EM2_TRY(dPerms.allocate(perms.size() * sizeof(uint32_t)));
+    EM2_TRY(hipMemcpyAsync(dPerms.p, perms.data(), perms.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    EM2_TRY(permWords.allocate(P * prefixWords * n * sizeof(uint64_t)));
+    EM2_TRY(sortedPrefix.allocate(P * prefixWords * n * sizeof(uint64_t)));
+    EM2_TRY(cellIds.allocate(P * n * sizeof(uint32_t)));
+    EM2_TRY(position.allocate(P * n * sizeof(uint32_t)));
     permuteKernel<<<dim3((n + 255u) / 256u, prefixWords, permutationCount), 256, 0, stream>>>(
         d_sig, sigWords, n, dPerms.as<uint32_t>(), permutedBitCount, prefixWords, permWords.as<uint64_t>());
-    EM2_TRY6(hipGetLastError());
+    EM2_TRY(hipGetLastError());
 
     // :932-1003: sort each permutation's (prefix words, id) pairs; LSD passes, each stable, the first over ascending ids
     {
-        Buffer6 keysIn, keysOut, idsIn, temp;
-        EM2_TRY6(keysIn.allocate(size_t(n) * sizeof(uint64_t)));
-        EM2_TRY6(keysOut.allocate(size_t(n) * sizeof(uint64_t)));
-        EM2_TRY6(idsIn.allocate(size_t(n) * sizeof(uint32_t)));
+        DeviceBuffer keysIn, keysOut, idsIn, temp;
+        EM2_TRY(keysIn.allocate(size_t(n) * sizeof(uint64_t)));
+        EM2_TRY(keysOut.allocate(size_t(n) * sizeof(uint64_t)));
+        EM2_TRY(idsIn.allocate(size_t(n) * sizeof(uint32_t)));
         size_t tempBytes = 0;
-        EM2_TRY6(rocprim::radix_sort_pairs(nullptr, tempBytes, keysIn.as<uint64_t>(), keysOut.as<uint64_t>(), idsIn.as<uint32_t>(),
+        EM2_TRY(rocprim::radix_sort_pairs(nullptr, tempBytes, keysIn.as<uint64_t>(), keysOut.as<uint64_t>(), idsIn.as<uint32_t>(),
                                            cellIds.as<uint32_t>(), size_t(n), 0u, 64u, stream));
-        EM2_TRY6(temp.allocate(tempBytes));
+        EM2_TRY(temp.allocate(tempBytes));
         for (uint32_t p = 0; p < permutationCount; ++p) {
             const uint64_t* words = permWords.as<uint64_t>() + size_t(p) * prefixWords * n;
             uint32_t* ids = cellIds.as<uint32_t>() + size_t(p) * n;
-            iotaKernel<<<gridFor6(n), 256, 0, stream>>>(ids, n);
-            EM2_TRY6(hipGetLastError());
+            iotaKernel<<<gridFor(n), 256, 0, stream>>>(ids, n);
+            EM2_TRY(hipGetLastError());
             for (uint32_t w = prefixWords; w-- > 0;) {
-                gatherWordKernel<<<gridFor6(n), 256, 0, stream>>>(words + size_t(w) * n, ids, n, keysIn.as<uint64_t>());
-                EM2_TRY6(hipGetLastError());
-                EM2_TRY6(hipMemcpyAsync(idsIn.p, ids, size_t(n) * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+                gatherWordKernel<<<gridFor(n), 256, 0, stream>>>(words + size_t(w) * n, ids, n, keysIn.as<uint64_t>());
+                EM2_TRY(hipGetLastError());
+                EM2_TRY(hipMemcpyAsync(idsIn.p, ids, size_t(n) * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
                 // All 64 bits, the last word's included (its bits after permutedBitCount are zero).  Sorting only that
                 // word's live high bits (begin_bit > 0) gave a wrong order from a few thousand cells on.
-                EM2_TRY6(rocprim::radix_sort_pairs(temp.p, tempBytes, keysIn.as<uint64_t>(), keysOut.as<uint64_t>(),
+                EM2_TRY(rocprim::radix_sort_pairs(temp.p, tempBytes, keysIn.as<uint64_t>(), keysOut.as<uint64_t>(),
                                                    idsIn.as<uint32_t>(), ids, size_t(n), 0u, 64u, stream));
             }
-            scatterKernel<<<gridFor6(n), 256, 0, stream>>>(words, ids, n, prefixWords, position.as<uint32_t>() + size_t(p) * n,
+            scatterKernel<<<gridFor(n), 256, 0, stream>>>(words, ids, n, prefixWords, position.as<uint32_t>() + size_t(p) * n,
                                                             sortedPrefix.as<uint64_t>() + size_t(p) * n * prefixWords);
-            EM2_TRY6(hipGetLastError());
+            EM2_TRY(hipGetLastError());
         }
-        EM2_TRY6(hipStreamSynchronize(stream));
+        EM2_TRY(hipStreamSynchronize(stream));
     }
 
     // :1005-1100, rows in chunks: the candidate lists take listCapacity keys per row
     uint32_t chunk = uint32_t(std::min<uint64_t>(rowCount, std::max<uint64_t>(64u, kListBudget / (uint64_t(listCapacity) * 8u))));
-    Buffer6 lists, counts;
-    EM2_TRY6(lists.allocate(size_t(chunk) * listCapacity * sizeof(uint64_t)));
-    EM2_TRY6(counts.allocate(size_t(chunk) * sizeof(uint32_t)));
+    DeviceBuffer lists, counts;
+    EM2_TRY(lists.allocate(size_t(chunk) * listCapacity * sizeof(uint64_t)));
+    EM2_TRY(counts.allocate(size_t(chunk) * sizeof(uint32_t)));
     WalkArgs args;
     args.sig = d_sig;
     args.permWords = permWords.as<uint64_t>();
@@ -425,11 +397,11 @@ hipError_t runFsp6(const uint64_t* d_sig, uint32_t cellCount, uint32_t rowBegin,
         const uint32_t end = rowEnd - begin < chunk ? rowEnd : begin + chunk;
         const uint32_t rows = end - begin;
         walkKernel<<<(rows + 63u) / 64u, 64, heapBytes, stream>>>(args, begin, end, lists.as<uint64_t>(), counts.as<uint32_t>());
-        EM2_TRY6(hipGetLastError());
+        EM2_TRY(hipGetLastError());
         selectKernel<<<rows, 64, selectBytes, stream>>>(lists.as<uint64_t>(), counts.as<uint32_t>(), listCapacity, rows,
                                                         tables.keySimilarity, k, d_pairs + size_t(begin - rowBegin) * k,
                                                         d_used + (begin - rowBegin));
-        EM2_TRY6(hipGetLastError());
+        EM2_TRY(hipGetLastError());
     }
     return hipStreamSynchronize(stream);
 }

@@ -20,6 +20,8 @@
 //      candidate; the k smallest keys by bisection on the key value, then a rank sort.
 
 #include "em2_device.h"
+#include "em2_hip_util.h"
+#include "em2_wave.h"
 
 #include <cstring>
 
@@ -100,17 +102,6 @@ runTablesKernel7(const uint64_t* __restrict__ sortedKeys, const uint32_t* __rest
     }
 }
 
-__device__ __forceinline__ uint32_t lanesBelow7(uint64_t mask)
-{
-    return __builtin_amdgcn_mbcnt_hi(uint32_t(mask >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(mask), 0u));
-}
-
-__device__ __forceinline__ void waveFence7()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
-    __builtin_amdgcn_wave_barrier();
-}
-
 // One wave per cell (grid-stride over the rows).
 __global__ void __launch_bounds__(64)
 traverseKernel(const uint64_t* __restrict__ sig, uint32_t words, uint32_t cellCount, uint32_t rowBegin, uint32_t rowEnd,
@@ -145,7 +136,7 @@ traverseKernel(const uint64_t* __restrict__ sig, uint32_t words, uint32_t cellCo
                 }
                 const uint64_t mask = __builtin_amdgcn_ballot_w64(fresh);
                 const uint32_t remaining = maxCheck - count;
-                const uint32_t sequence = lanesBelow7(mask);
+                const uint32_t sequence = lanesBelow(mask);
                 const bool accept = fresh && sequence < remaining;
                 bool pass = false;
                 uint32_t m = 0;
@@ -157,17 +148,17 @@ traverseKernel(const uint64_t* __restrict__ sig, uint32_t words, uint32_t cellCo
                     pass = uint64_t(m) < mismatchThreshold;                                 // :649
                 }
                 const uint64_t passMask = __builtin_amdgcn_ballot_w64(pass);
-                if (pass) neigh[n + lanesBelow7(passMask)] = (uint64_t(m) << 32) | member;
+                if (pass) neigh[n + lanesBelow(passMask)] = (uint64_t(m) << 32) | member;
                 n += uint32_t(__builtin_popcountll(passMask));
                 const uint32_t freshCount = uint32_t(__builtin_popcountll(mask));
                 count += freshCount < remaining ? freshCount : remaining;
                 done = count == maxCheck;                                                   // :652-661
-                waveFence7();       // the bitmap updates of this chunk are visible to the next chunk's loads
+                waveSyncGlobal();       // the bitmap updates of this chunk are visible to the next chunk's loads
             }
             // maxCheck == 0: the test after the member loop (:663) holds while no candidate has been found at all
             if (stopIfEmpty && count == 0u) done = true;
         }
-        waveFence7();
+        waveSyncGlobal();
 
         // keepBest(neighbors, k, less) + sort (:675-676): the k smallest (mismatch, id) keys, ascending
         uint32_t kept = n;
@@ -194,15 +185,14 @@ traverseKernel(const uint64_t* __restrict__ sig, uint32_t words, uint32_t cellCo
                     in = key <= lo;
                 }
                 const uint64_t inMask = __builtin_amdgcn_ballot_w64(in);
-                if (in) selected[out + lanesBelow7(inMask)] = key;
+                if (in) selected[out + lanesBelow(inMask)] = key;
                 out += uint32_t(__builtin_popcountll(inMask));
             }
             kept = k;           // keys are distinct (distinct cell ids), so exactly k are <= the k-th smallest
         } else {
             for (uint32_t i = lane; i < n; i += 64u) selected[i] = __hip_atomic_load(neigh + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        __builtin_amdgcn_wave_barrier();
+        waveSync();
         PairOut* out = outPairs + size_t(row - rowBegin) * k;
         for (uint32_t i = lane; i < kept; i += 64u) {
             const uint64_t key = selected[i];
@@ -213,44 +203,18 @@ traverseKernel(const uint64_t* __restrict__ sig, uint32_t words, uint32_t cellCo
             po.similarity = keySimilarity[keyOfMismatch[uint32_t(key >> 32)]];             // :679-684
             out[rank] = po;
         }
-        for (uint32_t i = kept + lane; i < k; i += 64u) {
-            PairOut zero;
-            zero.cell = 0u;
-            zero.similarity = 0.0f;
-            out[i] = zero;
-        }
+        clearRowTail(out, kept, k, lane);
         if (lane == 0u) outUsed[row - rowBegin] = kept;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        __builtin_amdgcn_wave_barrier();
+        waveSync();
 
         // clear the "seen" bits of this cell (:687-689)
         for (uint32_t i = lane; i < count; i += 64u) {
             const uint32_t member = __hip_atomic_load(cand + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_fetch_and(bitmap + (member >> 5), ~(1u << (member & 31u)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        waveFence7();
+        waveSyncGlobal();
     }
 }
-
-struct Buffer7 {
-    void* p = nullptr;
-    ~Buffer7() { if (p) (void)hipFree(p); }
-    void release() { if (p) { (void)hipFree(p); p = nullptr; } }
-    hipError_t allocate(size_t bytes) { release(); return hipMalloc(&p, bytes ? bytes : 1); }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-
-uint32_t gridFor7(uint64_t n)
-{
-    const uint64_t blocks = (n + 255) / 256;
-    return uint32_t(blocks > 16384 ? 16384 : (blocks ? blocks : 1));
-}
-
-#define EM2_TRY7(call)                       \
-    do {                                     \
-        hipError_t em2Err_ = (call);         \
-        if (em2Err_ != hipSuccess) return em2Err_; \
-    } while (0)
 
 }  // namespace
 
@@ -263,11 +227,11 @@ hipError_t runFsp7(const uint64_t* d_sig, uint32_t cellCount, uint32_t rowBegin,
                    uint64_t mismatchThreshold, const DeviceTables& tables, PairOut* d_pairs, uint32_t* d_used, hipStream_t stream)
 {
     const uint32_t rowCount = rowEnd - rowBegin;
-    const uint32_t words = (lshCount - 1u) / 64u + 1u;
+    const uint32_t words = wordCountOf(lshCount);
     if (rowCount == 0) return hipSuccess;
     if (k > kMaxK || log2BucketCount > kBucketBits) return hipErrorInvalidValue;
-    EM2_TRY7(hipMemsetAsync(d_used, 0, size_t(rowCount) * sizeof(uint32_t), stream));
-    if (k) EM2_TRY7(hipMemsetAsync(d_pairs, 0, size_t(rowCount) * k * sizeof(PairOut), stream));
+    EM2_TRY(hipMemsetAsync(d_used, 0, size_t(rowCount) * sizeof(uint32_t), stream));
+    if (k) EM2_TRY(hipMemsetAsync(d_pairs, 0, size_t(rowCount) * k * sizeof(PairOut), stream));
     std::vector<uint32_t> tableLength, tableSlice;
     for (uint32_t li = 0; li < sliceLengthCount; ++li) {
         const uint32_t length = uint32_t(sliceLengths[li]);
@@ -285,42 +249,42 @@ hipError_t runFsp7(const uint64_t* d_sig, uint32_t cellCount, uint32_t rowBegin,
     const uint64_t total = uint64_t(tableCount) * cellCount;
     if (total >= 0xffffffffULL || tableCount >= (1u << 23)) return hipErrorInvalidValue;
 
-    Buffer7 dLength, dSlice, keysA, keysB, cellsA, cellsB, temp;
-    EM2_TRY7(dLength.allocate(tableCount * sizeof(uint32_t)));
-    EM2_TRY7(dSlice.allocate(tableCount * sizeof(uint32_t)));
-    EM2_TRY7(hipMemcpyAsync(dLength.p, tableLength.data(), tableCount * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    EM2_TRY7(hipMemcpyAsync(dSlice.p, tableSlice.data(), tableCount * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    EM2_TRY7(keysA.allocate(total * sizeof(uint64_t)));
-    EM2_TRY7(keysB.allocate(total * sizeof(uint64_t)));
-    EM2_TRY7(cellsA.allocate(total * sizeof(uint32_t)));
-    EM2_TRY7(cellsB.allocate(total * sizeof(uint32_t)));
-    tableKeysKernel<<<gridFor7(total), 256, 0, stream>>>(d_sig, cellCount, words, dLength.as<uint32_t>(), dSlice.as<uint32_t>(), tableCount,
+    DeviceBuffer dLength, dSlice, keysA, keysB, cellsA, cellsB, temp;
+    EM2_TRY(dLength.allocate(tableCount * sizeof(uint32_t)));
+    EM2_TRY(dSlice.allocate(tableCount * sizeof(uint32_t)));
+    EM2_TRY(hipMemcpyAsync(dLength.p, tableLength.data(), tableCount * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    EM2_TRY(hipMemcpyAsync(dSlice.p, tableSlice.data(), tableCount * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    EM2_TRY(keysA.allocate(total * sizeof(uint64_t)));
+    EM2_TRY(keysB.allocate(total * sizeof(uint64_t)));
+    EM2_TRY(cellsA.allocate(total * sizeof(uint32_t)));
+    EM2_TRY(cellsB.allocate(total * sizeof(uint32_t)));
+    tableKeysKernel<<<gridFor(total), 256, 0, stream>>>(d_sig, cellCount, words, dLength.as<uint32_t>(), dSlice.as<uint32_t>(), tableCount,
                                                           log2BucketCount, keysA.as<uint64_t>(), cellsA.as<uint32_t>());
-    EM2_TRY7(hipGetLastError());
+    EM2_TRY(hipGetLastError());
     size_t tempBytes = 0;
-    EM2_TRY7(rocprim::radix_sort_pairs(nullptr, tempBytes, keysA.as<uint64_t>(), keysB.as<uint64_t>(), cellsA.as<uint32_t>(),
+    EM2_TRY(rocprim::radix_sort_pairs(nullptr, tempBytes, keysA.as<uint64_t>(), keysB.as<uint64_t>(), cellsA.as<uint32_t>(),
                                        cellsB.as<uint32_t>(), size_t(total), 0u, 64u, stream));
-    EM2_TRY7(temp.allocate(tempBytes));
-    EM2_TRY7(rocprim::radix_sort_pairs(temp.p, tempBytes, keysA.as<uint64_t>(), keysB.as<uint64_t>(), cellsA.as<uint32_t>(),
+    EM2_TRY(temp.allocate(tempBytes));
+    EM2_TRY(rocprim::radix_sort_pairs(temp.p, tempBytes, keysA.as<uint64_t>(), keysB.as<uint64_t>(), cellsA.as<uint32_t>(),
                                        cellsB.as<uint32_t>(), size_t(total), 0u, 64u, stream));
     const uint64_t* sortedKeys = keysB.as<uint64_t>();
     const uint32_t* sortedCells = cellsB.as<uint32_t>();
 
-    Buffer7 flags, scan, runStart, runOf, scanTemp;
-    EM2_TRY7(flags.allocate(total * sizeof(uint32_t)));
-    EM2_TRY7(scan.allocate(total * sizeof(uint32_t)));
-    EM2_TRY7(runStart.allocate((total + 1) * sizeof(uint32_t)));
-    EM2_TRY7(runOf.allocate(total * sizeof(uint32_t)));
-    runFlagsKernel7<<<gridFor7(total), 256, 0, stream>>>(sortedKeys, total, flags.as<uint32_t>());
-    EM2_TRY7(hipGetLastError());
+    DeviceBuffer flags, scan, runStart, runOf, scanTemp;
+    EM2_TRY(flags.allocate(total * sizeof(uint32_t)));
+    EM2_TRY(scan.allocate(total * sizeof(uint32_t)));
+    EM2_TRY(runStart.allocate((total + 1) * sizeof(uint32_t)));
+    EM2_TRY(runOf.allocate(total * sizeof(uint32_t)));
+    runFlagsKernel7<<<gridFor(total), 256, 0, stream>>>(sortedKeys, total, flags.as<uint32_t>());
+    EM2_TRY(hipGetLastError());
     size_t scanBytes = 0;
-    EM2_TRY7(rocprim::inclusive_scan(nullptr, scanBytes, flags.as<uint32_t>(), scan.as<uint32_t>(), size_t(total), rocprim::plus<uint32_t>(), stream));
-    EM2_TRY7(scanTemp.allocate(scanBytes));
-    EM2_TRY7(rocprim::inclusive_scan(scanTemp.p, scanBytes, flags.as<uint32_t>(), scan.as<uint32_t>(), size_t(total), rocprim::plus<uint32_t>(), stream));
-    runTablesKernel7<<<gridFor7(total), 256, 0, stream>>>(sortedKeys, sortedCells, flags.as<uint32_t>(), scan.as<uint32_t>(), total, cellCount,
+    EM2_TRY(rocprim::inclusive_scan(nullptr, scanBytes, flags.as<uint32_t>(), scan.as<uint32_t>(), size_t(total), rocprim::plus<uint32_t>(), stream));
+    EM2_TRY(scanTemp.allocate(scanBytes));
+    EM2_TRY(rocprim::inclusive_scan(scanTemp.p, scanBytes, flags.as<uint32_t>(), scan.as<uint32_t>(), size_t(total), rocprim::plus<uint32_t>(), stream));
+    runTablesKernel7<<<gridFor(total), 256, 0, stream>>>(sortedKeys, sortedCells, flags.as<uint32_t>(), scan.as<uint32_t>(), total, cellCount,
                                                            runStart.as<uint32_t>(), runOf.as<uint32_t>());
-    EM2_TRY7(hipGetLastError());
-    EM2_TRY7(hipStreamSynchronize(stream));
+    EM2_TRY(hipGetLastError());
+    EM2_TRY(hipStreamSynchronize(stream));
     keysA.release(); cellsA.release(); flags.release(); scan.release(); scanTemp.release(); temp.release(); keysB.release();
 
     // per-wave scratch: "seen" bitmap, candidate list (for the clean-up), neighbour keys
@@ -331,16 +295,16 @@ hipError_t runFsp7(const uint64_t* d_sig, uint32_t cellCount, uint32_t rowBegin,
     uint32_t waves = rowCount < 8192u ? rowCount : 8192u;
     const uint32_t bitmapWords = (cellCount + 31u) / 32u;
     while (waves > 64u && uint64_t(waves) * (uint64_t(limit) * 12u + uint64_t(bitmapWords) * 4u) > (8ull << 30)) waves /= 2u;
-    Buffer7 bitmaps, candidates, neighbors;
-    EM2_TRY7(bitmaps.allocate(size_t(waves) * bitmapWords * sizeof(uint32_t)));
-    EM2_TRY7(candidates.allocate(size_t(waves) * limit * sizeof(uint32_t)));
-    EM2_TRY7(neighbors.allocate(size_t(waves) * limit * sizeof(uint64_t)));
-    EM2_TRY7(hipMemsetAsync(bitmaps.p, 0, size_t(waves) * bitmapWords * sizeof(uint32_t), stream));
+    DeviceBuffer bitmaps, candidates, neighbors;
+    EM2_TRY(bitmaps.allocate(size_t(waves) * bitmapWords * sizeof(uint32_t)));
+    EM2_TRY(candidates.allocate(size_t(waves) * limit * sizeof(uint32_t)));
+    EM2_TRY(neighbors.allocate(size_t(waves) * limit * sizeof(uint64_t)));
+    EM2_TRY(hipMemsetAsync(bitmaps.p, 0, size_t(waves) * bitmapWords * sizeof(uint32_t), stream));
     traverseKernel<<<waves, 64, 0, stream>>>(d_sig, words, cellCount, rowBegin, rowEnd, runOf.as<uint32_t>(), runStart.as<uint32_t>(),
                                              sortedCells, tableCount, effectiveMaxCheck, maxCheck == 0, mismatchThreshold, limit, bitmapWords,
                                              bitmaps.as<uint32_t>(), candidates.as<uint32_t>(), neighbors.as<uint64_t>(),
                                              tables.keyOfMismatch, tables.keySimilarity, k, d_pairs, d_used);
-    EM2_TRY7(hipGetLastError());
+    EM2_TRY(hipGetLastError());
     return hipStreamSynchronize(stream);
 }
 

@@ -12,6 +12,7 @@
 // exclusive scan places the survivors.
 
 #include "em2_device.h"
+#include "em2_hip_util.h"
 
 #include <cstring>
 
@@ -103,19 +104,6 @@ filterEdgesKernel(const uint32_t* __restrict__ selVertex, const float* __restric
     if (!WRITE) keptCount[v0] = kept;
 }
 
-struct Buffer {
-    void* p = nullptr;
-    ~Buffer() { if (p) (void)hipFree(p); }
-    hipError_t allocate(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-
-#define EM2_TRY(call)                        \
-    do {                                     \
-        hipError_t em2Err_ = (call);         \
-        if (em2Err_ != hipSuccess) return em2Err_; \
-    } while (0)
-
 }  // namespace
 
 // All pointers are device pointers; graphSortedIds / graphVertexOfSorted = the graph's cell set sorted by id and the
@@ -130,7 +118,7 @@ hipError_t runCellGraphEdges(const PairOut* pairs, const uint32_t* usedCount, ui
 {
     *edgeCountHost = 0;
     if (graphCellCount == 0 || maxConnectivity == 0) return hipSuccess;
-    Buffer selVertex, selSim, selCount, kept, offsets, temp;
+    DeviceBuffer selVertex, selSim, selCount, kept, offsets, temp;
     const size_t slots = size_t(graphCellCount) * maxConnectivity;
     EM2_TRY(selVertex.allocate(slots * sizeof(uint32_t)));
     EM2_TRY(selSim.allocate(slots * sizeof(float)));

@@ -1,0 +1,55 @@
+// em2_hip_util.h -- the host-side plumbing every driver needs: bail out on a HIP error, a device allocation that frees
+// itself, the 1-D grid of a 256-thread kernel, 256-byte alignment, signature words.  (The device-side counterpart is
+// em2_wave.h; device scratch that outlives a call is em2_scratch.h.)
+#ifndef EM2_HIP_UTIL_H
+#define EM2_HIP_UTIL_H
+
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+// Returns the hipError_t of a failed call from the enclosing function.  (The call's text is not kept: the entry points
+// that report one, em2_capi.hip's EM2_HIP and em2_cluster_graph.hip's EM2_TRYC, have macros of their own.)
+#define EM2_TRY(call)                        \
+    do {                                     \
+        hipError_t em2Err_ = (call);         \
+        if (em2Err_ != hipSuccess) return em2Err_; \
+    } while (0)
+
+namespace em2 {
+
+// RAII device allocation.  allocate() frees what the buffer holds; 0 bytes allocate 1, so that p is never null after it.
+struct DeviceBuffer {
+    void* p = nullptr;
+    DeviceBuffer() = default;
+    DeviceBuffer(const DeviceBuffer&) = delete;
+    DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+    ~DeviceBuffer() { release(); }
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    }
+    hipError_t allocate(size_t bytes)
+    {
+        release();
+        return hipMalloc(&p, bytes ? bytes : 1);
+    }
+    template <class T> T* as() const { return static_cast<T*>(p); }
+};
+
+// Blocks of 256 threads for n items, at least 1 and at most 16384 (the kernels launched with it stride over the grid).
+inline uint32_t gridFor(uint64_t n)
+{
+    const uint64_t blocks = (n + 255) / 256;
+    return uint32_t(blocks > 16384 ? 16384 : (blocks ? blocks : 1));
+}
+
+inline size_t alignUp(size_t x) { return (x + 255u) & ~size_t(255u); }
+
+// 64-bit words of a signature of lshCount > 0 bits.
+inline uint32_t wordCountOf(uint32_t lshCount) { return (lshCount - 1u) / 64u + 1u; }
+
+}  // namespace em2
+
+#endif

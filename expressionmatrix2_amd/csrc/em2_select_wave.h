@@ -15,23 +15,9 @@
 #define EM2_SELECT_WAVE_H
 
 #include "em2_select.h"
+#include "em2_wave.h"
 
 namespace em2 {
-
-__device__ __forceinline__ void waveSync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// The same for arrays in global memory: what one lane stored must be what another lane of the wave loads next, and a
-// lane's loads may not come from a line its L1 fetched before that store -- the agent-scope fence writes back and
-// invalidates.
-__device__ __forceinline__ void waveSyncGlobal()
-{
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "agent");
-    __builtin_amdgcn_wave_barrier();
-}
 
 // Sorts lds[0, n) ascending by (key, cell) -- the order of the reference's final sort by similarity, ties by cell id
 // (src/ExpressionMatrixLsh.cpp:330-340 via keepBest) -- with a bitonic network over the next power of two (< 2n <= 2k
@@ -153,11 +139,6 @@ template <class E> __device__ __forceinline__ uint32_t medianToFirstLoaded(E* a,
     a[result] = em;
     a[m] = er;
     return uint32_t(em.key);            // (the partition's pivot: its caller hands it on instead of reading a[result] back)
-}
-
-__device__ __forceinline__ uint32_t lanesBelow(uint64_t mask)
-{
-    return __builtin_amdgcn_mbcnt_hi(uint32_t(mask >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(mask), 0u));
 }
 
 // __unguarded_partition(a+lo, a+hi, pivot = a[lo-1]); returns the cut (wave-uniform).  Index: uint16_t positions for lists

@@ -7,6 +7,7 @@
 // Index / byte work only; the counts are copied bit for bit.
 
 #include "em2_device.h"
+#include "em2_wave.h"
 
 #include <cstring>
 
@@ -16,11 +17,6 @@ namespace em2 {
 namespace {
 
 constexpr uint32_t kInvalid = 0xffffffffu;
-
-__device__ __forceinline__ uint32_t lanesBelowMask(uint64_t mask)
-{
-    return __builtin_amdgcn_mbcnt_hi(uint32_t(mask >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(mask), 0u));
-}
 
 template <bool FILL>
 __global__ void __launch_bounds__(256)
@@ -52,7 +48,7 @@ subsetKernel(const uint64_t* __restrict__ globalToc, const CountIn* __restrict__
             CountIn o;
             o.gene = localGene;
             o.count = e.count;
-            outData[out + lanesBelowMask(mask)] = o;
+            outData[out + lanesBelow(mask)] = o;
         }
         const uint32_t n = uint32_t(__builtin_popcountll(mask));
         kept += n;
