@@ -704,6 +704,16 @@ def dev_find_similar_pairs6(sig_ptr, cell_count, row_begin, row_end, lsh_count, 
                                              stream))
 
 
+def dev_find_similar_pairs7(sig_ptr, cell_count, row_begin, row_end, lsh_count, k, similarity_threshold, lsh_slice_lengths,
+                            max_check, log2_bucket_count, pairs_ptr, used_ptr, stream):
+    """Rows [row_begin, row_end) of findSimilarPairs7 into pairs_ptr / used_ptr (row_end - row_begin rows); the slice
+    lengths are a host sequence."""
+    lengths = np.ascontiguousarray(lsh_slice_lengths, dtype=np.int32)
+    check(load().em2_dev_find_similar_pairs7(sig_ptr, cell_count, row_begin, row_end, lsh_count, k, similarity_threshold,
+                                             _ptr(lengths), len(lengths), max_check, log2_bucket_count, pairs_ptr, used_ptr,
+                                             stream))
+
+
 def dev_find_similar_pairs0_workspace(cell_count, row_count, gene_count, k):
     return int(load().em2_dev_find_similar_pairs0_workspace(cell_count, row_count, gene_count, k))
 

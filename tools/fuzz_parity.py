@@ -4,7 +4,8 @@ result compared bit for bit with the CPU oracle.  SECONDS=300 python3 tools/fuzz
 FUZZ_ONLY=fsp4 restricts the sweep to one path, FUZZ_WIDTHS=1100,1500,2048 to those signature widths, FUZZ_MODE=triangle
 to one scan form with the matrix cores on.  The fsp6 leg compares with the C++ restatement (tests/fsp6_binding.py); shapes past
 its kernels' limits must answer EM2_ERROR_UNSUPPORTED and are counted apart (fsp6_unsupported), as are runs at the 8192
-clamp and runs over several row chunks."""
+clamp and runs over several row chunks.  Half the fsp7 draws go through the device entry on a random row range (fsp7_ranged);
+fsp7 draws the oracle would be slow for are skipped and counted (fsp7_skipped, see fsp7_oracle_is_slow)."""
 import os
 import sys
 import time
@@ -31,7 +32,7 @@ def main():
     deadline = time.time() + float(os.environ.get("SECONDS", "120"))
     restatement6 = fsp6_binding.load()
     runs = {"fsp4": 0, "fsp5": 0, "fsp6": 0, "fsp7": 0, "signatures": 0, "graph": 0, "labels": 0, "fsp6_unsupported": 0,
-            "fsp6_clamp8192": 0, "fsp6_chunks": 0}
+            "fsp6_clamp8192": 0, "fsp6_chunks": 0, "fsp7_ranged": 0, "fsp7_skipped": 0}
     while time.time() < deadline:
         for key in KNOBS:
             os.environ.pop(key, None)
@@ -110,14 +111,31 @@ def main():
             cell, sim, used = restatement6.find_similar_pairs6(sig, *args, rows=rows)
             pairs, gused = pairs[rows], gused[rows]
         elif what == "fsp7":
-            lengths = sorted(set(int(x) for x in rng.choice([1, 2, 5, 8, 13, 16, 24, 33, 64], size=int(rng.integers(1, 4)))), reverse=True)
+            # cell counts past the 8192 waves of the traversal (a wave then serves several rows), and k at its limit
+            cells7 = int(rng.choice([n, n, n, 9000, 20000]))
+            if cells7 != n:
+                n = cells7
+                sig = synth.clustered_signatures(n, L, cluster_count=clusters, flip=flip, seed=sig_seed)
+            k = int(rng.choice([k, k, k, k, 4096]))
+            lengths = sorted(set(int(x) for x in rng.choice([1, 2, 5, 8, 13, 16, 24, 33, 39, 40, 64], size=int(rng.integers(1, 4)))), reverse=True)
             max_check = int(rng.choice([0, 1, 7, 100, 100000]))
-            log2b = int(rng.choice([4, 10, 16, 24]))
+            log2b = int(rng.choice([1, 4, 10, 16, 24, 40]))
             if thr <= -1.0:
                 thr = -0.9            # the reference asserts when no mismatch count is below the threshold
-            label.update(lengths=lengths, max_check=max_check, log2b=log2b, thr=thr)
+            ranged = bool(rng.random() < 0.5)
+            begin, end = sorted(int(x) for x in rng.integers(0, n + 1, size=2)) if ranged else (0, n)
+            label.update(n=n, k=k, lengths=lengths, max_check=max_check, log2b=log2b, thr=thr, rows=[begin, end] if ranged else None)
+            if fsp7_oracle_is_slow(n, L, k, lengths, max_check, log2b):
+                runs["fsp7_skipped"] += 1
+                continue
             cell, sim, used = oracle.find_similar_pairs7(sig, L, k, thr, lengths, max_check, log2b)
-            pairs, gused = capi.find_similar_pairs7(sig, L, k, thr, lengths, max_check, log2b)
+            if ranged:
+                # the device entry on a row range, against the oracle's rows of that range
+                cell, sim, used = cell[begin:end], sim[begin:end], used[begin:end]
+                pairs, gused = fsp7_rows(sig, L, k, thr, lengths, max_check, log2b, begin, end)
+                runs["fsp7_ranged"] += 1
+            else:
+                pairs, gused = capi.find_similar_pairs7(sig, L, k, thr, lengths, max_check, log2b)
         elif what == "graph":
             cell, sim, used = oracle.find_similar_pairs4(sig, L, k, min(thr, 0.2))
             total = n + int(rng.integers(0, n + 1))
@@ -158,6 +176,36 @@ def main():
             raise SystemExit("PARITY FAILURE %s %r" % (what, label))
         runs[what] += 1
     print("fuzz ok", runs)
+
+
+def fsp7_oracle_is_slow(n, L, k, lengths, max_check, log2b):
+    """True for a draw with one of the large values (more than 4000 cells, k = 4096) that the CPU oracle would take more than
+    a few seconds for; the draws of the smaller ranges are never skipped.  The bounds: cells * k at most 4300 * 4096 (the
+    k = 4096 case of tests/test_gpu_fsp7.py, about 3 s); (table, cell) keys at most 3 * 10^7; cells * candidates * signature
+    words at most 2 * 10^9 popcounts; and, where maxCheck does not end the walk, cells * the bucket members a cell walks
+    past (buckets taken as evenly filled) at most 2 * 10^9 -- 4 * 10^9 of them were measured at 12 s."""
+    if n <= 4000 and k != 4096:
+        return False
+    tables = sum(L // length for length in lengths)
+    candidates = n if max_check == 0 else min(max_check, n)
+    walked = sum((L // length) * max(1.0, n / 2.0 ** min(length, log2b)) for length in lengths) if candidates == n else candidates
+    return (n * k > 4300 * 4096 or tables * n > 3 * 10 ** 7 or n * candidates * ((L - 1) // 64 + 1) > 2 * 10 ** 9 or
+            n * walked > 2 * 10 ** 9)
+
+
+def fsp7_rows(sig, L, k, thr, lengths, max_check, log2b, begin, end):
+    """capi.dev_find_similar_pairs7 for rows [begin, end) with torch supplying the device memory; the outputs are filled with
+    a non-zero pattern first.  Returns (pairs [rows, k], usedCount) as host arrays."""
+    import torch
+    rows = end - begin
+    d_sig = torch.from_numpy(sig.view(np.int64)).cuda()
+    d_pairs = torch.full((max(rows, 1), k, 2), 0x5a5a5a5a, dtype=torch.int32, device="cuda")
+    d_used = torch.full((max(rows, 1),), 0x5a5a5a5a, dtype=torch.int32, device="cuda")
+    capi.dev_find_similar_pairs7(d_sig.data_ptr(), len(sig), begin, end, L, k, thr, lengths, max_check, log2b, d_pairs.data_ptr(),
+                                 d_used.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    pairs = d_pairs.cpu().numpy().view(capi.PAIR_DTYPE)[:rows, :, 0]
+    return pairs, d_used.cpu().numpy().view(np.uint32)[:rows]
 
 
 def fsp6_case(rng, restatement, runs, label):

@@ -102,15 +102,12 @@ def main():
         lengths, max_check, log2b = [20, 14], int(os.environ.get("MAXCHECK", 1000)), 18
         sig = clustered_signatures_gpu(cells, L)
         host = sig.cpu().numpy().view(np.uint64)
-        import ctypes
-        lengths_arr = np.asarray(lengths, dtype=np.int32)
         d_pairs = torch.zeros((cells, k, 2), dtype=torch.int32, device="cuda")
         d_used = torch.zeros(cells, dtype=torch.int32, device="cuda")
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        capi.check(capi.load().em2_dev_find_similar_pairs7(sig.data_ptr(), cells, 0, cells, L, k, thr, capi._ptr(lengths_arr),
-                                                           len(lengths), max_check, log2b, d_pairs.data_ptr(), d_used.data_ptr(),
-                                                           stream))
+        capi.dev_find_similar_pairs7(sig.data_ptr(), cells, 0, cells, L, k, thr, lengths, max_check, log2b, d_pairs.data_ptr(),
+                                     d_used.data_ptr(), stream)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         u = d_used.cpu().numpy()
