@@ -2,10 +2,10 @@
 
 Only the hot path named in BASELINE.json lives here: signature projection, the findSimilarPairs4 /
 findSimilarPairs5 Hamming scans and the SimilarPairs / Lsh file formats around them, behind the reference's
-ExpressionMatrix method names.  The compute is in hand-written HIP (csrc/), reached through the C ABI of
+ExpressionMatrix method names; and the gene side's all-pairs search, findSimilarGenePairs0.  The compute is in hand-written HIP (csrc/), reached through the C ABI of
 include/em2_lsh.h.
 """
 from . import capi, files  # noqa: F401
-from .expression_matrix import ExpressionMatrix  # noqa: F401
+from .expression_matrix import ExpressionMatrix, NormalizationMethod  # noqa: F401
 
-__all__ = ["capi", "files", "ExpressionMatrix"]
+__all__ = ["capi", "files", "ExpressionMatrix", "NormalizationMethod"]

@@ -59,6 +59,17 @@ SYMBOLS = {
                                                _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "em2_matrix_find_similar_pairs0": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_char_p, _c.c_size_t,
                                                   _c.c_double]),
+    "em2_find_similar_gene_pairs0": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_int, _c.c_uint32,
+                                                _c.c_double, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "em2_set_gene_pairs_buffer_mb": (None, [_c.c_uint64]),
+    "em2_matrix_find_similar_gene_pairs0": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_int, _c.c_char_p,
+                                                       _c.c_size_t, _c.c_double]),
+    "em2_matrix_remove_similar_gene_pairs": (_c.c_int, [_c.c_void_p, _c.c_char_p]),
+    "em2_similar_gene_pairs_write": (_c.c_int, [_c.c_char_p, _c.c_char_p, _c.c_char_p, _c.c_char_p, _c.c_size_t, _c.c_int,
+                                                _c.c_uint32, _c.c_void_p, _c.c_void_p]),
+    "em2_similar_gene_pairs_read": (_c.c_int, [_c.c_char_p, _c.c_char_p, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64),
+                                               _c.POINTER(_c.c_int), _c.c_char_p, _c.c_char_p, _c.POINTER(_c.c_uint64),
+                                               _c.POINTER(_c.c_uint64), _c.c_void_p, _c.c_void_p]),
     "em2_analyze_similar_pairs": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_void_p, _c.c_void_p,
                                              _c.c_uint32, _c.c_void_p, _c.c_double, _c.c_char_p, _c.c_char_p, _c.c_void_p,
                                              _c.c_void_p, _c.c_void_p]),
@@ -500,6 +511,40 @@ def find_similar_pairs0(toc, data, gene_count, k=100, similarity_threshold=0.2):
     check(load().em2_find_similar_pairs0(_ptr(toc), _ptr(data), cell_count, gene_count, k, similarity_threshold, _ptr(pairs),
                                          _ptr(used), _ptr(lowest_index), _ptr(lowest)))
     return pairs, used, lowest_index, lowest
+
+
+GENE_PAIRS_BUFFER_MB_DEFAULT = 4096
+
+
+def apply_gene_pairs_buffer():
+    """EM2_GENE_PAIRS_BUFFER_MB (megabytes, default 4096): the device buffer findSimilarGenePairs0 passes its candidates
+    through, handed to the library (em2_set_gene_pairs_buffer_mb) before every call."""
+    text = os.environ.get("EM2_GENE_PAIRS_BUFFER_MB", "")
+    try:
+        megabytes = int(text) if text.strip() else GENE_PAIRS_BUFFER_MB_DEFAULT
+    except ValueError:
+        raise RuntimeError("EM2_GENE_PAIRS_BUFFER_MB must be a number of megabytes, not %r" % text) from None
+    if megabytes < 0:
+        raise RuntimeError("EM2_GENE_PAIRS_BUFFER_MB must not be negative")
+    load().em2_set_gene_pairs_buffer_mb(megabytes)
+
+
+def find_similar_gene_pairs0(toc, data, gene_count, normalization_method=2, k=100, similarity_threshold=0.2,
+                             all_similarities=False):
+    """findSimilarGenePairs0 (gene-gene correlations, all pairs) on a subset's host CSR -> (pairs [genes, k], usedCount),
+    or (pairs, usedCount, r [genes, genes] float32) with all_similarities: the -Pairs and -GeneInfo content.  pairs["cell"]
+    holds the partner's local gene id.  normalization_method: 0 none, 1 L1, 2 L2 (NormalizationMethod)."""
+    toc = np.ascontiguousarray(toc, dtype=np.uint64)
+    data = np.ascontiguousarray(data, dtype=COUNT_DTYPE)
+    cell_count = len(toc) - 1
+    pairs = np.zeros((gene_count, k), dtype=PAIR_DTYPE)
+    used = np.zeros(gene_count, dtype=np.uint32)
+    r = np.zeros((gene_count, gene_count), dtype=np.float32) if all_similarities else None
+    apply_gene_pairs_buffer()
+    check(load().em2_find_similar_gene_pairs0(_ptr(toc), _ptr(data), cell_count, gene_count, int(normalization_method), k,
+                                              similarity_threshold, _ptr(pairs), _ptr(used),
+                                              _ptr(r) if all_similarities else None))
+    return (pairs, used, r) if all_similarities else (pairs, used)
 
 
 def analyze_similar_pairs(toc, data, gene_count, pairs, used_count, global_cell_ids, csv_downsample, pairs_csv_path,

@@ -1493,6 +1493,76 @@ int em2_find_similar_pairs0(const uint64_t* toc, const em2_count* data, uint32_t
 }
 
 
+// ---- findSimilarGenePairs0 (em2_gene_pairs.hip) ----
+
+// std::sort by similarity alone, per gene (em2_host.cpp).
+extern "C" void em2_internal_sort_gene_pairs(em2_pair* pairs, const uint32_t* usedCount, uint32_t geneCount, uint32_t k);
+
+static const uint32_t kAllSimilaritiesMaxGenes = 8192;          // allSimilarities: 256 MB of floats at most
+
+void em2_set_gene_pairs_buffer_mb(uint64_t megabytes) { em2::setGenePairsBudgetMegabytes(megabytes); }
+
+int em2_find_similar_gene_pairs0(const uint64_t* toc, const em2_count* data, uint32_t cellCount, uint32_t geneCount,
+                                 int normalizationMethod, uint32_t k, double similarityThreshold, em2_pair* pairs,
+                                 uint32_t* usedCount, float* allSimilarities)
+{
+    const char* who = "em2_find_similar_gene_pairs0";
+    if (normalizationMethod < 0 || normalizationMethod > 2) {
+        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": invalid normalization method (0 none, 1 L1, 2 L2)");
+    }
+    if (geneCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": geneCount must be positive");
+    if (cellCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": cellCount must be positive");
+    if (!toc || !usedCount || (!pairs && k)) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+    if (allSimilarities && geneCount > kAllSimilaritiesMaxGenes) {
+        return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": allSimilarities is an aid for at most " +
+                                               std::to_string(kAllSimilaritiesMaxGenes) + " genes");
+    }
+    for (uint32_t c = 0; c < cellCount; ++c) {
+        if (toc[c] > toc[c + 1]) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": toc is not ascending");
+    }
+    const uint64_t nnz = toc[cellCount] - toc[0];
+    if (nnz && !data) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null data");
+    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
+    // (the device checks the gene ids before any kernel indexes with them)
+    std::vector<uint64_t> tocFromZero;
+    const uint64_t first = toc[0];
+    if (first) {
+        tocFromZero.resize(size_t(cellCount) + 1);
+        for (uint32_t c = 0; c <= cellCount; ++c) tocFromZero[c] = toc[c] - first;
+    }
+    const size_t allBytes = allSimilarities ? size_t(geneCount) * geneCount * sizeof(float) : 0;
+    DeviceBuffer dToc, dData, dPairs, dUsed, dAll;
+    EM2_HIP(dToc.allocate((size_t(cellCount) + 1) * sizeof(uint64_t)));
+    EM2_HIP(dData.allocate(nnz * sizeof(em2_count)));
+    EM2_HIP(dPairs.allocate(size_t(geneCount) * k * sizeof(em2_pair)));
+    EM2_HIP(dUsed.allocate(size_t(geneCount) * sizeof(uint32_t)));
+    if (allSimilarities) {
+        EM2_HIP(dAll.allocate(allBytes));
+        EM2_HIP(hipMemset(dAll.p, 0, allBytes));                                   // (the diagonal: the reference computes none)
+    }
+    EM2_HIP(hipMemcpy(dToc.p, first ? tocFromZero.data() : toc, (size_t(cellCount) + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+    if (nnz) EM2_HIP(hipMemcpy(dData.p, data + first, nnz * sizeof(em2_count), hipMemcpyHostToDevice));
+    em2::GenePairsStatus status;
+    EM2_HIP(em2::runGenePairs(dToc.as<uint64_t>(), dData.as<em2::CountIn>(), cellCount, geneCount, normalizationMethod, k,
+                              similarityThreshold, dPairs.as<em2::PairOut>(), dUsed.as<uint32_t>(), dAll.as<float>(), &status, nullptr));
+    if (status.inputError) return fsp0InputError(who, status.inputError);
+    if (status.overflow) {
+        return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": " + std::to_string(status.records) + " candidate records (" +
+                                               std::to_string(status.records * em2::kGenePairsBytesPerRecord >> 20) +
+                                               " MB with the sort's second buffer) fit neither the candidate buffer (" +
+                                               std::to_string(em2::genePairsBudgetRecords() * em2::kGenePairsBytesPerRecord >> 20) +
+                                               " MB, em2_set_gene_pairs_buffer_mb; the Python binding sets it from its environment variable) nor "
+                                               "the free device memory (" + std::to_string(status.freeBytes >> 20) +
+                                               " MB), so a larger buffer cannot help: raise the similarity threshold");
+    }
+    if (k) EM2_HIP(hipMemcpy(pairs, dPairs.p, size_t(geneCount) * k * sizeof(em2_pair), hipMemcpyDeviceToHost));
+    EM2_HIP(hipMemcpy(usedCount, dUsed.p, size_t(geneCount) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (allSimilarities) EM2_HIP(hipMemcpy(allSimilarities, dAll.p, allBytes, hipMemcpyDeviceToHost));
+    if (k) em2_internal_sort_gene_pairs(pairs, usedCount, geneCount, k);          // :186, the library's own std::sort
+    return EM2_OK;
+}
+
+
 // ExpressionMatrix::analyzeSimilarPairs (src/ExpressionMatrixLsh.cpp:55-150) after its lookups: the exact similarity of every
 // stored pair on the device, chunk of rows by chunk of rows; bins, the seeded draw and the csv lines on the host in the
 // reference's order (cell 0 ascending, stored order).

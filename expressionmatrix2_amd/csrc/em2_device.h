@@ -210,6 +210,27 @@ hipError_t launchStoredPairs(const uint64_t* toc, const CountIn* data, uint32_t 
                              uint32_t rowEnd, const PairOut* pairs, const uint32_t* usedCount, uint32_t k, void* workspace,
                              double* exact, hipStream_t stream);
 
+// em2_gene_pairs.hip: ExpressionMatrix::findSimilarGenePairs0 (src/ExpressionMatrixFindSimilarGenePairs.cpp:16-198) on a subset's
+// CSR in device memory: the dense standardised gene vectors, r of every unordered pair of genes (float products and float sums
+// in ascending cell order, no FMA), the survivors' stream, its sort and keepBest per gene.  d_pairs [geneCount][k] / d_used
+// [geneCount] hold every gene's kept candidates in the arrangement std::nth_element leaves (unused slots zero): the caller runs
+// the final std::sort (host::sortGenePairs).  method: the NormalizationMethod enum (0 none, 1 L1, 2 L2).  d_all: NULL or
+// [geneCount][geneCount], every r off the diagonal.  Allocates its own scratch and synchronises the stream.
+constexpr uint64_t kGenePairsBytesPerRecord = 24;         // key and value, twice (the sort alternates between two buffers)
+struct GenePairsStatus {
+    uint32_t inputError = 0;      // as runFsp0's; nothing was computed then
+    bool overflow = false;        // more survivors than the stream's budget AND than the device has memory for: nothing was selected
+    uint64_t records = 0;         // survivors, both directions counted
+    uint64_t freeBytes = 0;       // with overflow: what the device had free when the exact size was refused
+    int runs = 0;                 // of the pair kernel (2: the stream had to be sized exactly)
+    uint32_t longestList = 0;     // the longest candidate list that needed a selection
+};
+void setGenePairsBudgetMegabytes(uint64_t megabytes);       // em2_set_gene_pairs_buffer_mb; 4096 until it is called
+uint64_t genePairsBudgetRecords();
+hipError_t runGenePairs(const uint64_t* d_toc, const CountIn* d_data, uint32_t cellCount, uint32_t geneCount, int method, uint32_t k,
+                        double similarityThreshold, PairOut* d_pairs, uint32_t* d_used, float* d_all, GenePairsStatus* status,
+                        hipStream_t stream);
+
 }  // namespace em2
 
 #endif

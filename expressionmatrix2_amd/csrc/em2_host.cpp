@@ -19,6 +19,7 @@ extern "C" int em2_internal_subset_find_similar_pairs4(const uint64_t* globalToc
 #include <algorithm>
 #include <cerrno>
 #include <cfloat>
+#include <cstddef>
 #include <cmath>
 #include <cstring>
 #include <fstream>
@@ -91,6 +92,19 @@ struct SimilarPairsInfoRecord {
     uint64_t cellSetHash;
 };
 static_assert(sizeof(SimilarPairsInfoRecord) == 536, "SimilarPairs::Info layout");
+
+// SimilarGenePairs::Info (src/SimilarGenePairs.hpp:138-153): SimilarPairs::Info with the NormalizationMethod enum (an int)
+// appended at byte 536 and four bytes of padding, which the reference's value-initialisation leaves zero.
+struct SimilarGenePairsInfoRecord {
+    uint64_t k;
+    StaticString255 geneSetName;
+    uint64_t geneSetHash;
+    StaticString255 cellSetName;
+    uint64_t cellSetHash;
+    int32_t normalizationMethod;
+};
+static_assert(sizeof(SimilarGenePairsInfoRecord) == 544 && offsetof(SimilarGenePairsInfoRecord, normalizationMethod) == 536,
+              "SimilarGenePairs::Info layout");
 
 struct CellInfoRecord {                                   // src/SimilarPairs.hpp:165-179
     uint32_t usedCount;
@@ -549,6 +563,40 @@ void Matrix::findSimilarPairs0(const std::string& geneSetName, const std::string
     writer.finish(used.data(), lowestIndex.data(), lowest.data());
 }
 
+void Matrix::findSimilarGenePairs0(const std::string& geneSetName, const std::string& cellSetName, int normalizationMethod,
+                                   const std::string& similarGenePairsName, size_t k, double similarityThreshold) const
+{
+    // ExpressionMatrixFindSimilarGenePairs.cpp:46-73: gene set, then cell set, each "does not exist." / "is empty."
+    uint32_t cellCount = 0, geneCount = 0;
+    std::vector<uint64_t> toc;
+    std::vector<em2_count> data;
+    subset(geneSetName, cellSetName, toc, data, geneCount, cellCount);
+    if (k > 0xffffffffULL) fail(EM2_ERROR_INVALID_ARGUMENT, "findSimilarGenePairs0: k out of range");
+    // :77-188 on the device, the final sort included; :194-195 once that has succeeded, as in the reference
+    std::vector<em2_pair> pairs(size_t(geneCount) * k);
+    std::vector<uint32_t> used(geneCount);
+    const int rc = em2_find_similar_gene_pairs0(toc.data(), data.data(), cellCount, geneCount, normalizationMethod, uint32_t(k),
+                                                similarityThreshold, pairs.data(), used.data(), nullptr);
+    if (rc != EM2_OK) fail(rc, em2_last_error());
+    writeSimilarGenePairs(directoryName_, similarGenePairsName, geneSetName, cellSetName, k, normalizationMethod, geneCount,
+                          pairs.data(), used.data());
+}
+
+void Matrix::removeSimilarGenePairs(const std::string& similarGenePairsName) const
+{
+    // ExpressionMatrixFindSimilarGenePairs.cpp:223-232: open (with all consistency checks), then remove.
+    try {
+        SimilarGenePairsInfo info;
+        readSimilarGenePairs(directoryName_, similarGenePairsName, info, nullptr, nullptr);
+    } catch (const Error&) {
+        fail(EM2_ERROR_RUNTIME, "Error removing similar gene pairs object " + similarGenePairsName);
+    }
+    const std::string base = directoryName_ + "/SimilarGenePairs-" + similarGenePairsName;
+    removeFile(base + "-Info");                                               // SimilarGenePairs::remove, SimilarGenePairs.cpp:121-126
+    removeFile(base + "-GeneInfo");
+    removeFile(base + "-Pairs");
+}
+
 void Matrix::analyzeSimilarPairs(const std::string& similarPairsName, double csvDownsample, const std::string& outputDirectory) const
 {
     // ExpressionMatrixLsh.cpp:60-69: the stored object names its gene set and cell set
@@ -799,6 +847,102 @@ void readSimilarPairs(const std::string& directoryName, const std::string& simil
     }
 }
 
+// SimilarGenePairs::SimilarGenePairs for a new object (src/SimilarGenePairs.cpp:8-48).
+void writeSimilarGenePairs(const std::string& directoryName, const std::string& similarGenePairsName, const std::string& geneSetName,
+                           const std::string& cellSetName, size_t k, int normalizationMethod, uint32_t geneCount,
+                           const em2_pair* pairs, const uint32_t* usedCount)
+{
+    // accessGeneSet / accessCellSet (:101-118)
+    GeneSet genes;
+    genes.globalIds.openExisting(directoryName + "/GeneSet-" + geneSetName + "-GlobalIds", false, sizeof(uint32_t));
+    if (!isSorted(genes.genes(), genes.size())) fail(EM2_ERROR_RUNTIME, "Gene set " + geneSetName + " is not sorted.");
+    MappedFile cells;
+    cells.openExisting(directoryName + "/CellSet-" + cellSetName, false, sizeof(uint32_t));
+    if (!isSorted(static_cast<const uint32_t*>(cells.data()), cells.objectCount())) fail(EM2_ERROR_RUNTIME, "Cell set " + cellSetName + " is not sorted.");
+    if (genes.size() != geneCount) {                                          // :20-25
+        fail(EM2_ERROR_RUNTIME, "The gene pairs vector to create similar gene pairs " + similarGenePairsName +
+                                    " has length inconsistent with gene set " + geneSetName);
+    }
+    if (normalizationMethod < 0 || normalizationMethod > 2) fail(EM2_ERROR_INVALID_ARGUMENT, "SimilarGenePairs: invalid normalization method");
+    for (uint32_t g = 0; g < geneCount; ++g) {
+        if (usedCount[g] > k) fail(EM2_ERROR_INVALID_ARGUMENT, "SimilarGenePairs: a gene stores more than k pairs");
+    }
+    const std::string base = directoryName + "/SimilarGenePairs-" + similarGenePairsName;
+    MappedFile infoFile, pairsFile, geneInfoFile;
+    infoFile.createNew(base + "-Info", true, sizeof(SimilarGenePairsInfoRecord), 1);                    // :28-35
+    SimilarGenePairsInfoRecord* info = static_cast<SimilarGenePairsInfoRecord*>(infoFile.data());
+    info->k = k;
+    info->normalizationMethod = normalizationMethod;
+    setStaticString(info->geneSetName, geneSetName);
+    info->geneSetHash = hashOf(genes.globalIds, sizeof(uint32_t));
+    setStaticString(info->cellSetName, cellSetName);
+    info->cellSetHash = hashOf(cells, sizeof(uint32_t));
+    pairsFile.createNew(base + "-Pairs", false, sizeof(em2_pair), k * size_t(geneCount));               // :38-39
+    geneInfoFile.createNew(base + "-GeneInfo", false, sizeof(uint32_t), geneCount);
+    em2_pair* out = static_cast<em2_pair*>(pairsFile.data());
+    uint32_t* geneInfo = static_cast<uint32_t*>(geneInfoFile.data());
+    for (uint32_t g = 0; g < geneCount; ++g) {                                                          // :42-46
+        geneInfo[g] = usedCount[g];
+        std::copy(pairs + size_t(g) * k, pairs + size_t(g) * k + usedCount[g], out + size_t(g) * k);
+    }
+}
+
+// SimilarGenePairs::SimilarGenePairs for an existing object (src/SimilarGenePairs.cpp:53-89), its checks in its order.
+void readSimilarGenePairs(const std::string& directoryName, const std::string& similarGenePairsName, SimilarGenePairsInfo& info,
+                          std::vector<em2_pair>* pairs, std::vector<uint32_t>* usedCount)
+{
+    const std::string base = directoryName + "/SimilarGenePairs-" + similarGenePairsName;
+    MappedFile infoFile;
+    infoFile.openExisting(base + "-Info", true, sizeof(SimilarGenePairsInfoRecord));
+    const SimilarGenePairsInfoRecord* rec = static_cast<const SimilarGenePairsInfoRecord*>(infoFile.data());
+    info.k = rec->k;
+    info.geneSetName = getStaticString(rec->geneSetName);
+    info.geneSetHash = rec->geneSetHash;
+    info.cellSetName = getStaticString(rec->cellSetName);
+    info.cellSetHash = rec->cellSetHash;
+    info.normalizationMethod = rec->normalizationMethod;
+
+    GeneSet genes;
+    genes.globalIds.openExisting(directoryName + "/GeneSet-" + info.geneSetName + "-GlobalIds", false, sizeof(uint32_t));
+    if (!isSorted(genes.genes(), genes.size())) fail(EM2_ERROR_RUNTIME, "Gene set " + info.geneSetName + " is not sorted.");
+    MappedFile cells;
+    cells.openExisting(directoryName + "/CellSet-" + info.cellSetName, false, sizeof(uint32_t));
+    if (!isSorted(static_cast<const uint32_t*>(cells.data()), cells.objectCount())) fail(EM2_ERROR_RUNTIME, "Cell set " + info.cellSetName + " is not sorted.");
+    MappedFile pairsFile, geneInfoFile;
+    pairsFile.openExisting(base + "-Pairs", false, sizeof(em2_pair));
+    geneInfoFile.openExisting(base + "-GeneInfo", false, sizeof(uint32_t));
+    if (hashOf(genes.globalIds, sizeof(uint32_t)) != info.geneSetHash) {
+        fail(EM2_ERROR_RUNTIME, "Hash for gene set " + info.geneSetName + " is not consistent with the value at the time SimilarGenePairs object " + similarGenePairsName + " was created.");
+    }
+    if (hashOf(cells, sizeof(uint32_t)) != info.cellSetHash) {
+        fail(EM2_ERROR_RUNTIME, "Hash for cell set " + info.cellSetName + " is not consistent with the value at the time SimilarGenePairs object " + similarGenePairsName + " was created.");
+    }
+    if (geneInfoFile.objectCount() != genes.size()) {
+        fail(EM2_ERROR_RUNTIME, "SimilarGenePairs object " + similarGenePairsName + " has geneInfo vector of inconsistent length.");
+    }
+    if (pairsFile.objectCount() != info.k * size_t(genes.size())) {
+        fail(EM2_ERROR_RUNTIME, "SimilarGenePairs object " + similarGenePairsName + " has pairs vector of inconsistent length.");
+    }
+    info.geneCount = genes.size();
+    if (pairs) {
+        const em2_pair* p = static_cast<const em2_pair*>(pairsFile.data());
+        pairs->assign(p, p + pairsFile.objectCount());
+    }
+    if (usedCount) {
+        const uint32_t* u = static_cast<const uint32_t*>(geneInfoFile.data());
+        usedCount->assign(u, u + geneInfoFile.objectCount());
+    }
+}
+
+void sortGenePairs(em2_pair* pairs, const uint32_t* usedCount, uint32_t geneCount, size_t k)
+{
+    // OrderPairsBySecondGreater (src/orderPairs.hpp): the similarity alone, no tie-break on the id
+    for (uint32_t g = 0; g < geneCount; ++g) {
+        em2_pair* first = pairs + size_t(g) * k;
+        std::sort(first, first + usedCount[g], [](const em2_pair& x, const em2_pair& y) { return x.similarity > y.similarity; });
+    }
+}
+
 void writeLsh(const std::string& prefix, uint64_t cellCount, uint64_t lshCount, const uint64_t* signatures)
 {
     MappedFile infoFile;
@@ -882,3 +1026,9 @@ void createDirectoryFromCsr(const std::string& directoryName, uint32_t geneCount
 
 }  // namespace host
 }  // namespace em2
+
+// internal to the library (em2_capi.hip: the last step of em2_find_similar_gene_pairs0)
+extern "C" void em2_internal_sort_gene_pairs(em2_pair* pairs, const uint32_t* usedCount, uint32_t geneCount, uint32_t k)
+{
+    em2::host::sortGenePairs(pairs, usedCount, geneCount, k);
+}

@@ -108,6 +108,11 @@ public:
     // ExpressionMatrix::findSimilarPairs0 (src/ExpressionMatrixFindSimilarPairs.cpp:16-99): exact, all pairs.
     void findSimilarPairs0(const std::string& geneSetName, const std::string& cellSetName, const std::string& similarPairsName,
                            size_t k, double similarityThreshold) const;
+    // ExpressionMatrix::findSimilarGenePairs0 (src/ExpressionMatrixFindSimilarGenePairs.cpp:16-198) without its csv, and
+    // removeSimilarGenePairs (:223-232).
+    void findSimilarGenePairs0(const std::string& geneSetName, const std::string& cellSetName, int normalizationMethod,
+                               const std::string& similarGenePairsName, size_t k, double similarityThreshold) const;
+    void removeSimilarGenePairs(const std::string& similarGenePairsName) const;
     // ExpressionMatrix::analyzeSimilarPairs (src/ExpressionMatrixLsh.cpp:55-150): writes <name>-analysis.csv and
     // <name>-analysis-statistics.csv into outputDirectory (the reference: the working directory, "").
     void analyzeSimilarPairs(const std::string& similarPairsName, double csvDownsample, const std::string& outputDirectory) const;
@@ -167,6 +172,26 @@ struct SimilarPairsInfo {
 // Existing-object constructor of SimilarPairs (src/SimilarPairs.cpp:47-83) including its consistency checks.
 void readSimilarPairs(const std::string& directoryName, const std::string& similarPairsName,
                       SimilarPairsInfo& info, std::vector<em2_pair>* pairs, std::vector<uint32_t>* usedCount);
+
+// SimilarGenePairs files (src/SimilarGenePairs.cpp:8-48 create, :53-89 access): -Info, -Pairs (k slots per gene of the gene set,
+// local gene ids), -GeneInfo (usedCount).  The write takes pairs that are already selected and sorted.
+struct SimilarGenePairsInfo {
+    uint64_t k;
+    std::string geneSetName;
+    uint64_t geneSetHash;
+    std::string cellSetName;
+    uint64_t cellSetHash;
+    int32_t normalizationMethod;          // NormalizationMethod (src/NormalizationMethod.hpp:11-16): 0 none, 1 L1, 2 L2
+    uint64_t geneCount;
+};
+void writeSimilarGenePairs(const std::string& directoryName, const std::string& similarGenePairsName, const std::string& geneSetName,
+                           const std::string& cellSetName, size_t k, int normalizationMethod, uint32_t geneCount,
+                           const em2_pair* pairs, const uint32_t* usedCount);
+void readSimilarGenePairs(const std::string& directoryName, const std::string& similarGenePairsName, SimilarGenePairsInfo& info,
+                          std::vector<em2_pair>* pairs, std::vector<uint32_t>* usedCount);
+// The last step of findSimilarGenePairs0 (:186): std::sort of every gene's usedCount[g] pairs by similarity alone, descending
+// -- this library's libstdc++ introsort on the arrangement the selection left, as in the reference.
+void sortGenePairs(em2_pair* pairs, const uint32_t* usedCount, uint32_t geneCount, size_t k);
 
 // Lsh files (src/Lsh.hpp:136-141, src/Lsh.cpp:26-28,148): <prefix>-Info, <prefix>-Signatures.
 void writeLsh(const std::string& prefix, uint64_t cellCount, uint64_t lshCount, const uint64_t* signatures);

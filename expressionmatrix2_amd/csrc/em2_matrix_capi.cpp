@@ -158,6 +158,62 @@ int em2_matrix_remove_similar_pairs(em2_matrix* matrix, const char* similarPairs
     return guarded([&] { matrix->impl->removeSimilarPairs(similarPairsName); });
 }
 
+int em2_matrix_find_similar_gene_pairs0(em2_matrix* matrix, const char* geneSetName, const char* cellSetName, int normalizationMethod,
+                                        const char* similarGenePairsName, size_t k, double similarityThreshold)
+{
+    if (!matrix || !geneSetName || !cellSetName || !similarGenePairsName) return nullArgument("em2_matrix_find_similar_gene_pairs0");
+    return guarded([&] {
+        matrix->impl->findSimilarGenePairs0(geneSetName, cellSetName, normalizationMethod, similarGenePairsName, k, similarityThreshold);
+    });
+}
+
+int em2_matrix_remove_similar_gene_pairs(em2_matrix* matrix, const char* similarGenePairsName)
+{
+    if (!matrix || !similarGenePairsName) return nullArgument("em2_matrix_remove_similar_gene_pairs");
+    return guarded([&] { matrix->impl->removeSimilarGenePairs(similarGenePairsName); });
+}
+
+int em2_similar_gene_pairs_write(const char* directoryName, const char* similarGenePairsName, const char* geneSetName,
+                                 const char* cellSetName, size_t k, int normalizationMethod, uint32_t geneCount, const em2_pair* pairs,
+                                 const uint32_t* usedCount)
+{
+    if (!directoryName || !similarGenePairsName || !geneSetName || !cellSetName || (!usedCount && geneCount) || (!pairs && k && geneCount)) {
+        return nullArgument("em2_similar_gene_pairs_write");
+    }
+    return guarded([&] {
+        em2::host::writeSimilarGenePairs(directoryName, similarGenePairsName, geneSetName, cellSetName, k, normalizationMethod, geneCount,
+                                         pairs, usedCount);
+    });
+}
+
+int em2_similar_gene_pairs_read(const char* directoryName, const char* similarGenePairsName, uint64_t* k, uint64_t* geneCount,
+                                int* normalizationMethod, char* geneSetName, char* cellSetName, uint64_t* geneSetHash,
+                                uint64_t* cellSetHash, em2_pair* pairs, uint32_t* usedCount)
+{
+    if (!directoryName || !similarGenePairsName || !k || !geneCount) return nullArgument("em2_similar_gene_pairs_read");
+    return guarded([&] {
+        em2::host::SimilarGenePairsInfo info;
+        std::vector<em2_pair> p;
+        std::vector<uint32_t> u;
+        em2::host::readSimilarGenePairs(directoryName, similarGenePairsName, info, pairs ? &p : nullptr, usedCount ? &u : nullptr);
+        *k = info.k;
+        *geneCount = info.geneCount;
+        if (normalizationMethod) *normalizationMethod = info.normalizationMethod;
+        if (geneSetHash) *geneSetHash = info.geneSetHash;
+        if (cellSetHash) *cellSetHash = info.cellSetHash;
+        if (geneSetName) {
+            std::memset(geneSetName, 0, 256);
+            std::memcpy(geneSetName, info.geneSetName.data(), info.geneSetName.size());
+        }
+        if (cellSetName) {
+            std::memset(cellSetName, 0, 256);
+            std::memcpy(cellSetName, info.cellSetName.data(), info.cellSetName.size());
+        }
+        if (pairs && !p.empty()) std::memcpy(pairs, p.data(), p.size() * sizeof(em2_pair));
+        if (usedCount && !u.empty()) std::memcpy(usedCount, u.data(), u.size() * sizeof(uint32_t));
+    });
+}
+
 int em2_matrix_subset(em2_matrix* matrix, const char* geneSetName, const char* cellSetName, uint32_t* geneCount,
                       uint32_t* cellCount, uint64_t* nnz, uint64_t* toc, em2_count* data)
 {

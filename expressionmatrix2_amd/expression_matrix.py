@@ -10,12 +10,21 @@ Like the reference the methods return None and leave their result as files in th
 message text.  The work happens in libem2lsh.so (HIP, MI355X); when torch.distributed is initialised with more
 than one rank the calls are collective and the scan is row-sharded over the ranks (sharded.py)."""
 import ctypes
+import enum
 
 import numpy as np
 
 from . import capi, files
 
 _REQUIRED = object()
+
+
+class NormalizationMethod(enum.IntEnum):
+    """NormalizationMethod (src/NormalizationMethod.hpp:11-16) with the members the reference's module exposes
+    (src/PythonModule.cpp); `none` because None is a keyword."""
+    none = 0
+    L1 = 1
+    L2 = 2
 
 
 def _b(s):
@@ -78,6 +87,24 @@ class ExpressionMatrix:
             raise TypeError("findSimilarPairs0(): missing required argument 'similarPairsName'")
         capi.check(capi.load().em2_matrix_find_similar_pairs0(self._handle, _b(geneSetName), _b(cellSetName),
                                                               _b(similarPairsName), k, similarityThreshold))
+
+    # ---- src/PythonModule.cpp:966-980: gene-gene correlations, all pairs ----
+    def findSimilarGenePairs0(self, geneSetName="AllGenes", cellSetName="AllCells", normalizationMethod=NormalizationMethod.L2,
+                              similarGenePairsName=_REQUIRED, k=100, similarityThreshold=0.2, writeCsv=False):
+        """ExpressionMatrix::findSimilarGenePairs0 (src/ExpressionMatrixFindSimilarGenePairs.cpp:16-198): writes
+        SimilarGenePairs-<name>-{Info,Pairs,GeneInfo}."""
+        if similarGenePairsName is _REQUIRED:
+            raise TypeError("findSimilarGenePairs0(): missing required argument 'similarGenePairsName'")
+        if writeCsv:
+            raise NotImplementedError("findSimilarGenePairs0(): writeCsv=True (two text lines per pair of genes) is not "
+                                      "implemented; read the stored pairs with files.read_similar_gene_pairs")
+        method = NormalizationMethod(normalizationMethod)                   # (ValueError for anything else, None included)
+        capi.apply_gene_pairs_buffer()
+        capi.check(capi.load().em2_matrix_find_similar_gene_pairs0(self._handle, _b(geneSetName), _b(cellSetName), int(method),
+                                                                   _b(similarGenePairsName), k, similarityThreshold))
+
+    def removeSimilarGenePairs(self, similarGenePairsName):
+        capi.check(capi.load().em2_matrix_remove_similar_gene_pairs(self._handle, _b(similarGenePairsName)))
 
     # ---- src/PythonModule.cpp:755-771 ----
     def computeCellSimilarity(self, geneSetName="AllGenes", cellId0=_REQUIRED, cellId1=_REQUIRED):

@@ -1,5 +1,6 @@
 """The reference's on-disk objects of the LSH path, through the C ABI: SimilarPairs-<name>-{Info,Pairs,CellInfo}
-(src/SimilarPairs.cpp), Lsh-<name>-{Info,Signatures} (src/Lsh.cpp), plus test/bench tooling that creates a data
+(src/SimilarPairs.cpp), SimilarGenePairs-<name>-{Info,Pairs,GeneInfo} (src/SimilarGenePairs.cpp), Lsh-<name>-{Info,Signatures}
+(src/Lsh.cpp), plus test/bench tooling that creates a data
 directory holding exactly the files the path reads."""
 import ctypes
 
@@ -41,6 +42,46 @@ def similar_pairs_info(directory, name):
     capi.check(capi.load().em2_similar_pairs_info(_b(directory), _b(name), ctypes.byref(k), ctypes.byref(cells),
                                                   gene_set, cell_set))
     return int(k.value), int(cells.value), gene_set.value.decode("utf-8"), cell_set.value.decode("utf-8")
+
+
+def write_similar_gene_pairs(directory, name, gene_set_name, cell_set_name, k, normalization_method, pairs, used_count):
+    """SimilarGenePairs(directory, name, geneSetName, cellSetName, k, normalizationMethod, pairs) of
+    src/SimilarGenePairs.cpp:8-48 from already selected and sorted pairs [genes, k]."""
+    pairs = np.ascontiguousarray(pairs, dtype=capi.PAIR_DTYPE)
+    used_count = np.ascontiguousarray(used_count, dtype=np.uint32)
+    capi.check(capi.load().em2_similar_gene_pairs_write(_b(directory), _b(name), _b(gene_set_name), _b(cell_set_name), k,
+                                                        int(normalization_method), len(used_count), capi._ptr(pairs),
+                                                        capi._ptr(used_count)))
+
+
+def similar_gene_pairs_info(directory, name):
+    """SimilarGenePairs::Info (src/SimilarGenePairs.hpp:138-153) after the consistency checks of src/SimilarGenePairs.cpp:53-89
+    -> dict(k, geneCount, geneSetName, geneSetHash, cellSetName, cellSetHash, normalizationMethod)."""
+    k = ctypes.c_uint64(0)
+    genes = ctypes.c_uint64(0)
+    method = ctypes.c_int(0)
+    gene_hash = ctypes.c_uint64(0)
+    cell_hash = ctypes.c_uint64(0)
+    gene_set = ctypes.create_string_buffer(256)
+    cell_set = ctypes.create_string_buffer(256)
+    capi.check(capi.load().em2_similar_gene_pairs_read(_b(directory), _b(name), ctypes.byref(k), ctypes.byref(genes),
+                                                       ctypes.byref(method), gene_set, cell_set, ctypes.byref(gene_hash),
+                                                       ctypes.byref(cell_hash), None, None))
+    return {"k": int(k.value), "geneCount": int(genes.value), "geneSetName": gene_set.value.decode("utf-8"),
+            "geneSetHash": int(gene_hash.value), "cellSetName": cell_set.value.decode("utf-8"),
+            "cellSetHash": int(cell_hash.value), "normalizationMethod": int(method.value)}
+
+
+def read_similar_gene_pairs(directory, name):
+    """SimilarGenePairs(directory, name) of src/SimilarGenePairs.cpp:53-89 -> (k, pairs[genes, k], used_count[genes])."""
+    info = similar_gene_pairs_info(directory, name)
+    k = ctypes.c_uint64(0)
+    genes = ctypes.c_uint64(0)
+    pairs = np.zeros((info["geneCount"], info["k"]), dtype=capi.PAIR_DTYPE)
+    used = np.zeros(info["geneCount"], dtype=np.uint32)
+    capi.check(capi.load().em2_similar_gene_pairs_read(_b(directory), _b(name), ctypes.byref(k), ctypes.byref(genes), None, None,
+                                                       None, None, None, capi._ptr(pairs), capi._ptr(used)))
+    return int(k.value), pairs, used
 
 
 def write_lsh(directory, lsh_name, lsh_count, signatures):

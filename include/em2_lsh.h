@@ -136,6 +136,32 @@ int em2_find_similar_pairs0(const uint64_t* toc, const em2_count* data, uint32_t
                             double similarityThreshold, em2_pair* pairs, uint32_t* usedCount, uint32_t* lowestSimilarityIndex,
                             float* lowestSimilarity);
 
+/* ExpressionMatrix::findSimilarGenePairs0 after its lookups (src/ExpressionMatrixFindSimilarGenePairs.cpp:77-188, with
+ * ExpressionMatrixSubset::getDenseRepresentation, src/ExpressionMatrixSubset.cpp:142-174, and keepBest, src/heap.hpp:116-126):
+ * the Pearson correlation of every pair of genes over the cells of a subset's CSR (as em2_find_similar_pairs0: local gene ids
+ * below geneCount, strictly ascending within a cell).  Dense float vector per gene; cells scaled by float(1/sum1) (L1) or
+ * float(1/sqrt(sum2)) (L2) where that sum is not zero, every entry of the cell, zeros included; per gene, over the cells in
+ * ascending order: double sum, average = float(sum/cellCount), x -= average, double sum of the float squares, x *=
+ * float(1/sqrt(sum2)); r = acc over the cells ascending of acc = acc + (x0*x1), float product and float sum, no FMA, subnormals
+ * kept.  A pair with double(r) > similarityThreshold is a candidate of both genes (ascending partner id); a list longer than
+ * k goes through libstdc++'s std::nth_element (restated, csrc/em2_select.h) and is cut to k; every list is sorted by
+ * std::sort on the similarity alone (no tie-break on the id: ties are stored as those two algorithms leave them).  A gene
+ * without variance gives NaN or inf by IEEE rules; NaN passes no threshold.
+ * normalizationMethod: NormalizationMethod (src/NormalizationMethod.hpp:11-16) 0 none, 1 L1, 2 L2.
+ * pairs[geneCount][k] (em2_pair.cell holds the partner's local gene id; unused slots zero), usedCount[geneCount].
+ * allSimilarities: NULL, or [geneCount][geneCount] floats that receive every r (the diagonal 0): an aid for tests, refused
+ * (EM2_ERROR_UNSUPPORTED) above 8192 genes.
+ * The candidates pass through a device buffer of at most the megabytes em2_set_gene_pairs_buffer_mb set (default 4096; 24
+ * bytes per candidate and direction), or of the worst case geneCount*(geneCount-1) if that is smaller; if there are more,
+ * the pairs are evaluated once more into a buffer of the exact size, and if the device has no room for that the call fails
+ * with EM2_ERROR_UNSUPPORTED, naming the count and the setter.  It never truncates.
+ * em2_set_gene_pairs_buffer_mb is process-wide and takes effect for the calls that start after it; the Python binding calls
+ * it with the environment variable EM2_GENE_PAIRS_BUFFER_MB before every findSimilarGenePairs0. */
+void em2_set_gene_pairs_buffer_mb(uint64_t megabytes);
+int em2_find_similar_gene_pairs0(const uint64_t* toc, const em2_count* data, uint32_t cellCount, uint32_t geneCount,
+                                 int normalizationMethod, uint32_t k, double similarityThreshold, em2_pair* pairs,
+                                 uint32_t* usedCount, float* allSimilarities);
+
 /* ExpressionMatrixSubset + Lsh + findSimilarPairs4 in one call on host buffers (SURVEY.md 8(a) row a1 on the device:
  * src/ExpressionMatrixSubset.cpp:9-42 followed by src/Lsh.cpp:118-224 and src/ExpressionMatrixLsh.cpp:200-285): the
  * global CSR (CellExpressionCounts toc/data, global gene ids) restricted to the cells cellIds[0..cellCount) (NULL =
@@ -612,6 +638,16 @@ int em2_matrix_compare_similar_pairs(em2_matrix* matrix, const char* similarPair
 /* ExpressionMatrix::removeSimilarPairs (src/ExpressionMatrixFindSimilarPairs.cpp:126-135). */
 int em2_matrix_remove_similar_pairs(em2_matrix* matrix, const char* similarPairsName);
 
+/* ExpressionMatrix::findSimilarGenePairs0 (src/ExpressionMatrixFindSimilarGenePairs.cpp:16-198; bound at
+ * src/PythonModule.cpp:966-980, defaults AllGenes, AllCells, L2, k=100, similarityThreshold=0.2) without its csv: writes
+ * SimilarGenePairs-<name>-{Info,Pairs,GeneInfo}.  Errors in the reference's order: "Gene set X does not exist." / "is empty.",
+ * "Cell set X does not exist." / "is empty.". */
+int em2_matrix_find_similar_gene_pairs0(em2_matrix* matrix, const char* geneSetName, const char* cellSetName, int normalizationMethod,
+                                        const char* similarGenePairsName, size_t k, double similarityThreshold);
+
+/* ExpressionMatrix::removeSimilarGenePairs (src/ExpressionMatrixFindSimilarGenePairs.cpp:223-232). */
+int em2_matrix_remove_similar_gene_pairs(em2_matrix* matrix, const char* similarGenePairsName);
+
 /* ExpressionMatrixSubset (src/ExpressionMatrixSubset.cpp:9-42) as plain arrays, for drivers that shard the work
  * themselves: first call with toc == NULL to get the sizes, then with toc[cellCount+1] and data[nnz]. */
 int em2_matrix_subset(em2_matrix* matrix, const char* geneSetName, const char* cellSetName, uint32_t* geneCount,
@@ -630,6 +666,17 @@ int em2_similar_pairs_read(const char* directoryName, const char* similarPairsNa
  * built on; name buffers must hold 256 bytes.  Same consistency checks as em2_similar_pairs_read. */
 int em2_similar_pairs_info(const char* directoryName, const char* similarPairsName, uint64_t* k, uint64_t* cellCount,
                            char* geneSetName, char* cellSetName);
+
+/* SimilarGenePairs files: the constructor for a new object (src/SimilarGenePairs.cpp:8-48) from already selected and sorted
+ * pairs[geneCount][k] (local gene ids), and the existing-object constructor (:53-89) with its hash / length checks.
+ * SimilarGenePairs::Info (src/SimilarGenePairs.hpp:138-153) is SimilarPairs::Info with the NormalizationMethod enum appended
+ * (544 bytes, the enum at byte 536).  For the read every pointer after geneCount may be NULL; name buffers hold 256 bytes. */
+int em2_similar_gene_pairs_write(const char* directoryName, const char* similarGenePairsName, const char* geneSetName,
+                                 const char* cellSetName, size_t k, int normalizationMethod, uint32_t geneCount, const em2_pair* pairs,
+                                 const uint32_t* usedCount);
+int em2_similar_gene_pairs_read(const char* directoryName, const char* similarGenePairsName, uint64_t* k, uint64_t* geneCount,
+                                int* normalizationMethod, char* geneSetName, char* cellSetName, uint64_t* geneSetHash,
+                                uint64_t* cellSetHash, em2_pair* pairs, uint32_t* usedCount);
 
 /* A cell set of the data directory (CellSet-<name>, src/CellSets.hpp:15): pass ids == NULL to get the count. */
 int em2_matrix_cell_set(em2_matrix* matrix, const char* cellSetName, uint32_t* count, uint32_t* ids);
