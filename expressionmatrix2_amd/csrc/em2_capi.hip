@@ -6,6 +6,8 @@
 
 #include "em2_device.h"
 #include "em2_hip_util.h"
+#include "em2_csr.h"
+#include "em2_expression.h"
 #include "em2_scratch.h"
 #include "em2_cluster_graph.h"
 #include "em2_tables.h"
@@ -50,6 +52,15 @@ int failHip(hipError_t e, const char* what)
 using em2::alignUp;
 using em2::DeviceBuffer;
 using em2::wordCountOf;
+
+// An argument error under the caller's name: what UploadedCsr::check or em2::inputErrorText says.
+int failArgument(const char* who, const char* text) { return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": " + text); }
+
+// Ends an analysis that does not reach its end (an error return): closes the csv, frees the state.
+struct AnalysisCloser {
+    em2::AnalysisState*& state;
+    ~AnalysisCloser() { if (state) em2::analysisEnd(state, 0, nullptr, nullptr, nullptr, nullptr); }
+};
 
 bool haveDevice()
 {
@@ -1336,43 +1347,40 @@ int em2_analyze_lsh(const uint64_t* toc, const em2_count* data, uint32_t cellCou
         sums[2 * size_t(c) + 1] = s2;
     }
 
-    em2::AnalyzeLshState* state = em2::analyzeLshBegin(lshCount, seed, pairsCsvPath);
+    em2::AnalysisState* state = em2::analyzeLshBegin(lshCount, seed, pairsCsvPath);
     if (!state) return fail(EM2_ERROR_RUNTIME, std::string("em2_analyze_lsh: cannot open ") + pairsCsvPath);
-    struct Closer {
-        em2::AnalyzeLshState*& s;
-        ~Closer() { if (s) em2::analyzeLshEnd(s, 1, nullptr, nullptr, nullptr, nullptr); }
-    } closer{state};
+    AnalysisCloser closer{state};
 
     // rows in chunks of about 16M pairs: 192 MB of device output per chunk, walked by the host in order
     const uint64_t chunkPairs = 1ull << 24;
-    uint32_t maxRows = 0;
-    uint64_t maxPairs = 0;
-    for (uint32_t begin = 0; begin + 1 < cellCount;) {
+    const auto chunkEnd = [&](uint32_t begin, uint64_t& pairs) {
         uint32_t end = begin;
-        uint64_t pairs = 0;
-        while (end + 1 < cellCount && (end == begin || pairs + (cellCount - 1 - end) <= chunkPairs)) pairs += cellCount - 1 - end++;
+        for (pairs = 0; end + 1 < cellCount && (end == begin || pairs + (cellCount - 1 - end) <= chunkPairs);) pairs += cellCount - 1 - end++;
+        return end;
+    };
+    uint32_t maxRows = 0;
+    uint64_t maxPairs = 0, pairs = 0;
+    for (uint32_t begin = 0; begin + 1 < cellCount;) {
+        const uint32_t end = chunkEnd(begin, pairs);
         if (end - begin > maxRows) maxRows = end - begin;
         if (pairs > maxPairs) maxPairs = pairs;
         begin = end;
     }
-    DeviceBuffer dToc, dData, dSig, dProducts, dMismatches, dScratch;
-    EM2_HIP(dToc.allocate((size_t(cellCount) + 1) * sizeof(uint64_t)));
-    EM2_HIP(dData.allocate(nnz * sizeof(em2_count)));
+    em2::UploadedCsr csr;
+    (void)csr.check(toc, reinterpret_cast<const em2::CountIn*>(data), cellCount, false);      // (null data was refused above)
+    EM2_HIP(csr.upload());
+    DeviceBuffer dSig, dProducts, dMismatches, dScratch;
     EM2_HIP(dSig.allocate(size_t(cellCount) * words * sizeof(uint64_t)));
     EM2_HIP(dProducts.allocate(maxPairs * sizeof(double)));
     EM2_HIP(dMismatches.allocate(maxPairs * sizeof(uint32_t)));
     EM2_HIP(dScratch.allocate(em2::analyzeScratchBytes(geneCount, maxRows)));
-    EM2_HIP(hipMemcpy(dToc.p, toc, (size_t(cellCount) + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-    if (nnz) EM2_HIP(hipMemcpy(dData.p, data, nnz * sizeof(em2_count), hipMemcpyHostToDevice));
     EM2_HIP(hipMemcpy(dSig.p, signatures, size_t(cellCount) * words * sizeof(uint64_t), hipMemcpyHostToDevice));
     std::vector<double> products(maxPairs);
     std::vector<uint32_t> mismatches(maxPairs);
     uint64_t done = 0;
     for (uint32_t begin = 0; begin + 1 < cellCount;) {
-        uint32_t end = begin;
-        uint64_t pairs = 0;
-        while (end + 1 < cellCount && (end == begin || pairs + (cellCount - 1 - end) <= chunkPairs)) pairs += cellCount - 1 - end++;
-        EM2_HIP(em2::launchAnalyzePairs(dToc.as<uint64_t>(), dData.as<em2::CountIn>(), cellCount, geneCount, dSig.as<uint64_t>(), words,
+        const uint32_t end = chunkEnd(begin, pairs);
+        EM2_HIP(em2::launchAnalyzePairs(csr.toc.as<uint64_t>(), csr.data.as<em2::CountIn>(), cellCount, geneCount, dSig.as<uint64_t>(), words,
                                         begin, end, dScratch.p, dProducts.as<double>(), dMismatches.as<uint32_t>(), nullptr));
         EM2_HIP(hipStreamSynchronize(nullptr));
         EM2_HIP(hipMemcpy(products.data(), dProducts.p, pairs * sizeof(double), hipMemcpyDeviceToHost));
@@ -1386,9 +1394,9 @@ int em2_analyze_lsh(const uint64_t* toc, const em2_count* data, uint32_t cellCou
         done += pairs;
         begin = end;
     }
-    em2::AnalyzeLshState* finished = state;
+    em2::AnalysisState* finished = state;
     state = nullptr;
-    if (!em2::analyzeLshEnd(finished, lshCount, statisticsCsvPath, sum0, sum1, sum2)) {
+    if (!em2::analysisEnd(finished, lshCount, statisticsCsvPath, sum0, sum1, sum2)) {
         return fail(EM2_ERROR_RUNTIME, std::string("em2_analyze_lsh: cannot write ") + (statisticsCsvPath ? statisticsCsvPath : ""));
     }
     return EM2_OK;
@@ -1409,12 +1417,6 @@ static int prepareFsp0(const char* who, uint32_t cellCount, uint32_t geneCount, 
                                                " stored pairs per cell (min(k, cellCount-1)) is not supported");
     }
     return EM2_OK;
-}
-
-static int fsp0InputError(const char* who, uint32_t inputError)
-{
-    if (inputError & 1u) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": a local gene id is not below geneCount");
-    return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": the gene ids of a cell are not strictly ascending");
 }
 
 size_t em2_dev_find_similar_pairs0_workspace(uint32_t cellCount, uint32_t rowCount, uint32_t geneCount, uint32_t k)
@@ -1442,7 +1444,7 @@ int em2_dev_find_similar_pairs0(const uint64_t* d_toc, const em2_count* d_data, 
     EM2_HIP(em2::runFsp0(d_toc, reinterpret_cast<const em2::CountIn*>(d_data), cellCount, geneCount, rowBegin, rowEnd, k,
                          similarityThreshold, reinterpret_cast<em2::PairOut*>(d_pairs), d_usedCount, d_lowestSimilarityIndex,
                          d_lowestSimilarity, d_workspace, &inputError, static_cast<hipStream_t>(stream)));
-    if (inputError) return fsp0InputError(who, inputError);
+    if (inputError) return failArgument(who, em2::inputErrorText(inputError));
     return EM2_OK;
 }
 
@@ -1457,31 +1459,18 @@ int em2_find_similar_pairs0(const uint64_t* toc, const em2_count* data, uint32_t
     if (!toc || !usedCount || !lowestSimilarityIndex || !lowestSimilarity || (!pairs && k)) {
         return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
     }
-    for (uint32_t c = 0; c < cellCount; ++c) {
-        if (toc[c] > toc[c + 1]) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": toc is not ascending");
-    }
-    const uint64_t nnz = toc[cellCount] - toc[0];
-    if (nnz && !data) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null data");
+    em2::UploadedCsr csr;
+    if (const char* error = csr.check(toc, reinterpret_cast<const em2::CountIn*>(data), cellCount)) return failArgument(who, error);
     if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
-    // (the device checks the gene ids before any kernel indexes with them)
-    std::vector<uint64_t> tocFromZero;
-    const uint64_t first = toc[0];
-    if (first) {
-        tocFromZero.resize(size_t(cellCount) + 1);
-        for (uint32_t c = 0; c <= cellCount; ++c) tocFromZero[c] = toc[c] - first;
-    }
-    DeviceBuffer dToc, dData, dPairs, dUsed, dIndex, dLowest, dWorkspace;
+    EM2_HIP(csr.upload());                     // (the device checks the gene ids before any kernel indexes with them)
+    DeviceBuffer dPairs, dUsed, dIndex, dLowest, dWorkspace;
     const size_t workspaceBytes = em2::fsp0WorkspaceBytes(cellCount, cellCount, geneCount, k);
-    EM2_HIP(dToc.allocate((size_t(cellCount) + 1) * sizeof(uint64_t)));
-    EM2_HIP(dData.allocate(nnz * sizeof(em2_count)));
     EM2_HIP(dPairs.allocate(size_t(cellCount) * k * sizeof(em2_pair)));
     EM2_HIP(dUsed.allocate(size_t(cellCount) * sizeof(uint32_t)));
     EM2_HIP(dIndex.allocate(size_t(cellCount) * sizeof(uint32_t)));
     EM2_HIP(dLowest.allocate(size_t(cellCount) * sizeof(float)));
     EM2_HIP(dWorkspace.allocate(workspaceBytes));
-    EM2_HIP(hipMemcpy(dToc.p, first ? tocFromZero.data() : toc, (size_t(cellCount) + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-    if (nnz) EM2_HIP(hipMemcpy(dData.p, data + first, nnz * sizeof(em2_count), hipMemcpyHostToDevice));
-    const int rc = em2_dev_find_similar_pairs0(dToc.as<uint64_t>(), dData.as<em2_count>(), cellCount, geneCount, 0, cellCount, k,
+    const int rc = em2_dev_find_similar_pairs0(csr.toc.as<uint64_t>(), csr.data.as<em2_count>(), cellCount, geneCount, 0, cellCount, k,
                                                similarityThreshold, dPairs.as<em2_pair>(), dUsed.as<uint32_t>(), dIndex.as<uint32_t>(),
                                                dLowest.as<float>(), dWorkspace.p, workspaceBytes, nullptr);
     if (rc != EM2_OK) return rc;
@@ -1517,35 +1506,22 @@ int em2_find_similar_gene_pairs0(const uint64_t* toc, const em2_count* data, uin
         return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": allSimilarities is an aid for at most " +
                                                std::to_string(kAllSimilaritiesMaxGenes) + " genes");
     }
-    for (uint32_t c = 0; c < cellCount; ++c) {
-        if (toc[c] > toc[c + 1]) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": toc is not ascending");
-    }
-    const uint64_t nnz = toc[cellCount] - toc[0];
-    if (nnz && !data) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null data");
+    em2::UploadedCsr csr;
+    if (const char* error = csr.check(toc, reinterpret_cast<const em2::CountIn*>(data), cellCount)) return failArgument(who, error);
     if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
-    // (the device checks the gene ids before any kernel indexes with them)
-    std::vector<uint64_t> tocFromZero;
-    const uint64_t first = toc[0];
-    if (first) {
-        tocFromZero.resize(size_t(cellCount) + 1);
-        for (uint32_t c = 0; c <= cellCount; ++c) tocFromZero[c] = toc[c] - first;
-    }
+    EM2_HIP(csr.upload());                     // (the device checks the gene ids before any kernel indexes with them)
     const size_t allBytes = allSimilarities ? size_t(geneCount) * geneCount * sizeof(float) : 0;
-    DeviceBuffer dToc, dData, dPairs, dUsed, dAll;
-    EM2_HIP(dToc.allocate((size_t(cellCount) + 1) * sizeof(uint64_t)));
-    EM2_HIP(dData.allocate(nnz * sizeof(em2_count)));
+    DeviceBuffer dPairs, dUsed, dAll;
     EM2_HIP(dPairs.allocate(size_t(geneCount) * k * sizeof(em2_pair)));
     EM2_HIP(dUsed.allocate(size_t(geneCount) * sizeof(uint32_t)));
     if (allSimilarities) {
         EM2_HIP(dAll.allocate(allBytes));
         EM2_HIP(hipMemset(dAll.p, 0, allBytes));                                   // (the diagonal: the reference computes none)
     }
-    EM2_HIP(hipMemcpy(dToc.p, first ? tocFromZero.data() : toc, (size_t(cellCount) + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-    if (nnz) EM2_HIP(hipMemcpy(dData.p, data + first, nnz * sizeof(em2_count), hipMemcpyHostToDevice));
     em2::GenePairsStatus status;
-    EM2_HIP(em2::runGenePairs(dToc.as<uint64_t>(), dData.as<em2::CountIn>(), cellCount, geneCount, normalizationMethod, k,
+    EM2_HIP(em2::runGenePairs(csr.toc.as<uint64_t>(), csr.data.as<em2::CountIn>(), cellCount, geneCount, normalizationMethod, k,
                               similarityThreshold, dPairs.as<em2::PairOut>(), dUsed.as<uint32_t>(), dAll.as<float>(), &status, nullptr));
-    if (status.inputError) return fsp0InputError(who, status.inputError);
+    if (status.inputError) return failArgument(who, em2::inputErrorText(status.inputError));
     if (status.overflow) {
         return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": " + std::to_string(status.records) + " candidate records (" +
                                                std::to_string(status.records * em2::kGenePairsBytesPerRecord >> 20) +
@@ -1576,95 +1552,55 @@ int em2_analyze_similar_pairs(const uint64_t* toc, const em2_count* data, uint32
     if (!toc || !usedCount || !globalCellIds || !pairsCsvPath || !statisticsCsvPath || (!pairs && k && cellCount)) {
         return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
     }
+    em2::UploadedCsr csr;
+    if (const char* error = csr.check(toc, reinterpret_cast<const em2::CountIn*>(data), cellCount)) return failArgument(who, error);
+    if (cellCount && toc[0] != 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": toc must start at 0");
     uint64_t stored = 0;
     for (uint32_t c = 0; c < cellCount; ++c) {
-        if (toc[c] > toc[c + 1]) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": toc is not ascending");
         if (usedCount[c] > k) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": a cell stores more than k pairs");
         for (uint32_t t = 0; t < usedCount[c]; ++t) {
             if (pairs[size_t(c) * k + t].cell >= cellCount) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": a stored pair names a cell that does not exist");
         }
         stored += usedCount[c];
     }
-    const uint64_t nnz = cellCount ? toc[cellCount] : 0;
-    if (cellCount && toc[0] != 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": toc must start at 0");
-    if (nnz && !data) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null data");
     if (stored && !haveDevice()) return fail(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
 
-    std::ofstream csvOut(pairsCsvPath);
-    if (!csvOut) return fail(EM2_ERROR_RUNTIME, std::string(who) + ": cannot open " + pairsCsvPath);
-    csvOut << "GlobalCellId0,GlobalCellId1,ExactSimilarity,StoredSimilarity\n";                         // :73
-    const size_t binCount = 200;                                                                         // :76-80
-    const double binWidth = 2. / double(binCount);
-    std::vector<uint64_t> s0(binCount, 0);
-    std::vector<double> s1(binCount, 0.), s2(binCount, 0.);
-    std::mt19937 randomSource(231);                                    // :84-90; boost::mt19937 has std::mt19937's parameters
-    const double factor = 1.0 / (double(0xffffffffu) + 1.0);          // boost::uniform_01 over a 32-bit engine: eng() * 2^-32
+    em2::AnalysisState* state = em2::analyzeStoredBegin(pairsCsvPath);
+    if (!state) return fail(EM2_ERROR_RUNTIME, std::string(who) + ": cannot open " + pairsCsvPath);
+    AnalysisCloser closer{state};
 
     if (stored) {
         // rows in chunks of at most 2^24 slots (128 MB of doubles), one row at least
         const uint32_t chunkRows = std::max<uint32_t>(1u, uint32_t(std::min<uint64_t>(cellCount, (1ull << 24) / k)));
-        DeviceBuffer dToc, dData, dPairs, dUsed, dWorkspace, dExact;
-        EM2_HIP(dToc.allocate((size_t(cellCount) + 1) * sizeof(uint64_t)));
-        EM2_HIP(dData.allocate(nnz * sizeof(em2_count)));
+        const em2::PairOut* hostPairs = reinterpret_cast<const em2::PairOut*>(pairs);
+        DeviceBuffer dPairs, dUsed, dWorkspace, dExact;
+        EM2_HIP(csr.upload());
         EM2_HIP(dPairs.allocate(size_t(cellCount) * k * sizeof(em2_pair)));
         EM2_HIP(dUsed.allocate(size_t(cellCount) * sizeof(uint32_t)));
         EM2_HIP(dWorkspace.allocate(em2::storedPairsWorkspaceBytes(cellCount, chunkRows, geneCount)));
         EM2_HIP(dExact.allocate(size_t(chunkRows) * k * sizeof(double)));
-        EM2_HIP(hipMemcpy(dToc.p, toc, (size_t(cellCount) + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-        if (nnz) EM2_HIP(hipMemcpy(dData.p, data, nnz * sizeof(em2_count), hipMemcpyHostToDevice));
         EM2_HIP(hipMemcpy(dPairs.p, pairs, size_t(cellCount) * k * sizeof(em2_pair), hipMemcpyHostToDevice));
         EM2_HIP(hipMemcpy(dUsed.p, usedCount, size_t(cellCount) * sizeof(uint32_t), hipMemcpyHostToDevice));
         uint32_t inputError = 0;
-        EM2_HIP(em2::prepareStoredPairs(dToc.as<uint64_t>(), dData.as<em2::CountIn>(), cellCount, geneCount, dWorkspace.p, &inputError, nullptr));
-        if (inputError) return fsp0InputError(who, inputError);
+        EM2_HIP(em2::prepareStoredPairs(csr.toc.as<uint64_t>(), csr.data.as<em2::CountIn>(), cellCount, geneCount, dWorkspace.p, &inputError, nullptr));
+        if (inputError) return failArgument(who, em2::inputErrorText(inputError));
         std::vector<double> exact(size_t(chunkRows) * k);
         for (uint32_t begin = 0; begin < cellCount; begin += chunkRows) {
             const uint32_t end = uint32_t(std::min<uint64_t>(cellCount, uint64_t(begin) + chunkRows));
-            EM2_HIP(em2::launchStoredPairs(dToc.as<uint64_t>(), dData.as<em2::CountIn>(), cellCount, geneCount, begin, end,
+            EM2_HIP(em2::launchStoredPairs(csr.toc.as<uint64_t>(), csr.data.as<em2::CountIn>(), cellCount, geneCount, begin, end,
                                            dPairs.as<em2::PairOut>(), dUsed.as<uint32_t>(), k, dWorkspace.p, dExact.as<double>(), nullptr));
             EM2_HIP(hipStreamSynchronize(nullptr));
             EM2_HIP(hipMemcpy(exact.data(), dExact.p, size_t(end - begin) * k * sizeof(double), hipMemcpyDeviceToHost));
-            for (uint32_t localCellId0 = begin; localCellId0 < end; ++localCellId0) {                    // :95-125
-                for (uint32_t t = 0; t < usedCount[localCellId0]; ++t) {
-                    const em2_pair& p = pairs[size_t(localCellId0) * k + t];
-                    const float storedSimilarity = p.similarity;
-                    const double exactSimilarity = exact[size_t(localCellId0 - begin) * k + t];
-                    const double delta = storedSimilarity - exactSimilarity;
-                    const size_t bin = size_t(std::floor((exactSimilarity + 1.) / binWidth));
-                    if (!(bin < binCount)) {
-                        return fail(EM2_ERROR_RUNTIME, std::string(who) + ": Assertion failed: bin < binCount (a stored pair with exact "
-                                                       "similarity 1 or not finite; src/ExpressionMatrixLsh.cpp:111)");
-                    }
-                    ++s0[bin];
-                    s1[bin] += delta;
-                    s2[bin] += delta * delta;
-                    if (double(randomSource()) * factor < csvDownsample) {
-                        csvOut << globalCellIds[localCellId0] << ",";
-                        csvOut << globalCellIds[p.cell] << ",";
-                        csvOut << exactSimilarity << ",";
-                        csvOut << storedSimilarity << "\n";
-                    }
-                }
+            if (!em2::analyzeStoredRows(state, hostPairs, usedCount, k, globalCellIds, begin, end, exact.data(), csvDownsample)) {
+                return fail(EM2_ERROR_RUNTIME, std::string(who) + ": Assertion failed: bin < binCount (a stored pair with exact "
+                                               "similarity 1 or not finite; src/ExpressionMatrixLsh.cpp:111)");
             }
         }
     }
-    csvOut.close();
-    std::ofstream statsOut(statisticsCsvPath);                                                          // :133-148
-    if (!statsOut) return fail(EM2_ERROR_RUNTIME, std::string(who) + ": cannot open " + statisticsCsvPath);
-    statsOut << "Similarity,Bias,Rms\n";
-    for (size_t bin = 0; bin < binCount; bin++) {
-        if (s0[bin] < 2) continue;
-        const double similarity = (double(bin) + 0.5) * binWidth - 1.;
-        const double average = s1[bin] / double(s0[bin]);
-        const double sigma = std::sqrt(s2[bin] / double(s0[bin]));
-        statsOut << similarity << ",";
-        statsOut << average << ",";
-        statsOut << sigma << "\n";
-    }
-    for (size_t bin = 0; bin < binCount; bin++) {
-        if (sum0) sum0[bin] = s0[bin];
-        if (sum1) sum1[bin] = s1[bin];
-        if (sum2) sum2[bin] = s2[bin];
+    em2::AnalysisState* finished = state;
+    state = nullptr;
+    if (!em2::analysisEnd(finished, 0, statisticsCsvPath, sum0, sum1, sum2)) {
+        return fail(EM2_ERROR_RUNTIME, std::string(who) + ": cannot open " + statisticsCsvPath);
     }
     return EM2_OK;
 }

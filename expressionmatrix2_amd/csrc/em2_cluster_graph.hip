@@ -8,8 +8,8 @@
 //   * avg[g] += float(c * factor) over the cluster's cells in the order of ClusterGraphVertex::cells (:1194-1205);
 //   * sum += a*a over g ascending (:1231-1235); sx, sxx (per vertex) and sxy (per edge) over g ascending.
 // Additions into one (cluster, gene) accumulator are ordered; different accumulators are independent.  The device runs:
-//   1. clusterFactorKernel    one lane per listed cell: the norm's sequential sum, factor = float(1/sqrt(sum)); checks the
-//                             gene ids (below geneCount, strictly ascending) before any kernel builds an index from them;
+//   1. clusterFactorKernel    one lane per listed cell: the norm's sequential sum (em2_expression.h's cell walk, which
+//                             checks the gene ids before any kernel builds an index from them), factor = float(1/sqrt(sum));
 //   2. clusterGatherKernel    one wave per listed cell: (key = cluster * geneCount + gene, value = float(c * factor)) at
 //                             the cell's place in the concatenation of the clusters' cell lists;
 //   3. rocPRIM radix sort of the pairs by key (stable: equal keys keep the order of the cell lists);
@@ -31,7 +31,9 @@
 //     undefined: EM2_ERROR_RUNTIME.
 
 #include "em2_device.h"
+#include "em2_expression.h"
 #include "em2_hip_util.h"
+#include "em2_csr.h"
 #include "em2_cluster_graph.h"
 #include "../../include/em2_lsh.h"
 
@@ -59,19 +61,9 @@ clusterFactorKernel(const uint64_t* __restrict__ toc, const CountIn* __restrict_
 {
     const uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i >= listCount) return;
-    const uint32_t row = cellRows[i];
-    const uint64_t begin = toc[row], end = toc[row + 1u];
-    double sum = 0.;
-    uint32_t bad = 0u, previous = 0u;
-    for (uint64_t p = begin; p < end; ++p) {
-        const CountIn e = data[p];
-        if (e.gene >= geneCount) bad |= 1u;
-        if (p != begin && e.gene <= previous) bad |= 2u;
-        previous = e.gene;
-        sum += double(e.count * e.count);                            // p.second * p.second: a float product (:1286)
-    }
-    factor[i] = float(__ddiv_rn(1., __dsqrt_rn(sum)));               // :1288
-    if (bad) atomicOr(error, bad);
+    const CellWalk w = walkCell(toc, data, cellRows[i], geneCount);  // sum2: p.second * p.second, a float product (:1286)
+    factor[i] = float(__ddiv_rn(1., __dsqrt_rn(w.sum2)));            // :1288
+    if (w.bad) atomicOr(error, w.bad);
 }
 
 __global__ void __launch_bounds__(256)
@@ -230,8 +222,6 @@ ClusterStatus hipFailure(hipError_t e, const char* what)
         if (em2Error_ != hipSuccess) return hipFailure(em2Error_, #call); \
     } while (0)
 
-uint32_t blocksOf(uint64_t items, uint32_t perBlock) { return uint32_t((items + perBlock - 1u) / perBlock); }
-
 double secondsSince(std::chrono::steady_clock::time_point t0)
 {
     return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -241,8 +231,8 @@ double secondsSince(std::chrono::steady_clock::time_point t0)
 
 
 struct ClusterDevice::State {
-    DeviceBuffer toc, data, table, sx, sxx;
-    std::vector<uint64_t> hostToc;
+    UploadedCsr csr;
+    DeviceBuffer table, sx, sxx;
     uint32_t rowCount = 0, geneCount = 0, clusterCount = 0;
 };
 
@@ -252,19 +242,10 @@ ClusterDevice::~ClusterDevice() { delete state; }
 ClusterStatus ClusterDevice::upload(const char* who, const uint64_t* toc, const CountIn* data, uint32_t rowCount, uint32_t geneCount)
 {
     State& s = *state;
-    for (uint32_t r = 0; r < rowCount; ++r) {
-        if (toc[r] > toc[r + 1]) return ClusterStatus{EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": toc is not ascending"};
-    }
-    const uint64_t first = toc[0], nnz = toc[rowCount] - first;
-    if (nnz && !data) return ClusterStatus{EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null data"};
-    s.hostToc.resize(size_t(rowCount) + 1);
-    for (uint32_t r = 0; r <= rowCount; ++r) s.hostToc[r] = toc[r] - first;
+    if (const char* error = s.csr.check(toc, data, rowCount)) return ClusterStatus{EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": " + error};
     s.rowCount = rowCount;
     s.geneCount = geneCount;
-    EM2_TRYC(s.toc.allocate(s.hostToc.size() * sizeof(uint64_t)));
-    EM2_TRYC(s.data.allocate(nnz * sizeof(CountIn)));
-    EM2_TRYC(hipMemcpy(s.toc.p, s.hostToc.data(), s.hostToc.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-    if (nnz) EM2_TRYC(hipMemcpy(s.data.p, data + first, nnz * sizeof(CountIn), hipMemcpyHostToDevice));
+    EM2_TRYC(s.csr.upload());
     return ok();
 }
 
@@ -303,7 +284,7 @@ ClusterStatus ClusterDevice::averages(const char* who, const uint32_t* cellRows,
             if (row >= s.rowCount) return ClusterStatus{EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": a cluster names a cell that does not exist"};
             clusterOfPosition[i] = c;
             entryOffset[i] = entryCount;
-            entryCount += s.hostToc[row + 1] - s.hostToc[row];
+            entryCount += s.csr.hostToc[row + 1] - s.csr.hostToc[row];
         }
     }
     entryOffset[listCount] = entryCount;
@@ -345,12 +326,11 @@ ClusterStatus ClusterDevice::averages(const char* who, const uint32_t* cellRows,
         EM2_TRYC(hipMemcpy(positions.p, clusterOfPosition.data(), listCount * sizeof(uint32_t), hipMemcpyHostToDevice));
         EM2_TRYC(hipMemcpy(entryOffsets.p, entryOffset.data(), (listCount + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
         clusterFactorKernel<<<dim3(blocksOf(listCount, 256u)), dim3(256), 0, stream>>>(
-            s.toc.as<uint64_t>(), s.data.as<CountIn>(), geneCount, rows.as<uint32_t>(), listCount, factor.as<float>(), error.as<uint32_t>());
+            s.csr.toc.as<uint64_t>(), s.csr.data.as<CountIn>(), geneCount, rows.as<uint32_t>(), listCount, factor.as<float>(), error.as<uint32_t>());
         EM2_TRYC(hipGetLastError());
         uint32_t inputError = 0;
         EM2_TRYC(hipMemcpy(&inputError, error.p, sizeof(uint32_t), hipMemcpyDeviceToHost));
-        if (inputError & 1u) return ClusterStatus{EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": a local gene id is not below geneCount"};
-        if (inputError) return ClusterStatus{EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": the gene ids of a cell are not strictly ascending"};
+        if (inputError) return ClusterStatus{EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": " + inputErrorText(inputError)};
     }
     if (entryCount) {
         EM2_TRYC(keysIn.allocate(entryCount * sizeof(uint64_t)));
@@ -359,7 +339,7 @@ ClusterStatus ClusterDevice::averages(const char* who, const uint32_t* cellRows,
         EM2_TRYC(valuesOut.allocate(entryCount * sizeof(float)));
         EM2_TRYC(temp.allocate(sortTempBytes));
         clusterGatherKernel<<<dim3(blocksOf(listCount, 4u)), dim3(256), 0, stream>>>(
-            s.toc.as<uint64_t>(), s.data.as<CountIn>(), geneCount, rows.as<uint32_t>(), positions.as<uint32_t>(),
+            s.csr.toc.as<uint64_t>(), s.csr.data.as<CountIn>(), geneCount, rows.as<uint32_t>(), positions.as<uint32_t>(),
             entryOffsets.as<uint64_t>(), factor.as<float>(), listCount, keysIn.as<uint64_t>(), valuesIn.as<float>());
         EM2_TRYC(hipGetLastError());
         // the keys' live low bits only (begin_bit 0; the upper bits are zero)

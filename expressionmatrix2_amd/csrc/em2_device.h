@@ -184,12 +184,19 @@ size_t analyzeScratchBytes(uint32_t geneCount, uint32_t rowCount);
 hipError_t launchAnalyzePairs(const uint64_t* toc, const CountIn* data, uint32_t cellCount, uint32_t geneCount,
                               const uint64_t* signatures, uint32_t words, uint32_t rowBegin, uint32_t rowEnd, void* scratch,
                               double* scalarProducts, uint32_t* mismatches, hipStream_t stream);
-struct AnalyzeLshState;
-AnalyzeLshState* analyzeLshBegin(uint32_t lshCount, uint32_t seed, const char* pairsCsvPath);
-bool analyzeLshRows(AnalyzeLshState* s, const double* sums, uint32_t cellCount, uint32_t geneCount, const uint32_t* globalCellIds,
+// The host half of ExpressionMatrix::analyzeSimilarPairs (src/ExpressionMatrixLsh.cpp:55-150) takes the same three steps
+// over the exact similarities launchStoredPairs gives.  Begin returns NULL where the csv cannot be opened; Rows returns false
+// where the reference's bin assert throws; analysisEnd (lshCount 0 after analyzeStoredBegin) writes the statistics csv,
+// returns false where it cannot be opened, and deletes the state.
+struct AnalysisState;
+AnalysisState* analyzeLshBegin(uint32_t lshCount, uint32_t seed, const char* pairsCsvPath);
+bool analyzeLshRows(AnalysisState* s, const double* sums, uint32_t cellCount, uint32_t geneCount, const uint32_t* globalCellIds,
                     uint32_t rowBegin, uint32_t rowEnd, const double* scalarProducts, const uint32_t* mismatches, double csvDownsample,
                     double* exactOut, double* lshOut);
-bool analyzeLshEnd(AnalyzeLshState* s, uint32_t lshCount, const char* statisticsCsvPath, uint64_t* sum0, double* sum1, double* sum2);
+AnalysisState* analyzeStoredBegin(const char* pairsCsvPath);
+bool analyzeStoredRows(AnalysisState* s, const PairOut* pairs, const uint32_t* usedCount, uint32_t k, const uint32_t* globalCellIds,
+                       uint32_t rowBegin, uint32_t rowEnd, const double* exact, double csvDownsample);
+bool analysisEnd(AnalysisState* s, uint32_t lshCount, const char* statisticsCsvPath, uint64_t* sum0, double* sum1, double* sum2);
 
 // em2_fsp0.hip: ExpressionMatrix::findSimilarPairs0 (src/ExpressionMatrixFindSimilarPairs.cpp:16-99) for the cells
 // [rowBegin,rowEnd) against all cells: exact similarities, SimilarPairs::add replayed per cell, the lists sorted.  The

@@ -23,6 +23,7 @@
 #include "em2_hip_util.h"
 #include "em2_scratch.h"
 #include "em2_select_wave.h"
+#include "em2_wave.h"
 
 #include <chrono>
 #include <cstdio>
@@ -190,12 +191,7 @@ gatherKernel(const uint32_t* __restrict__ runOfSliceCell, const uint32_t* __rest
             if (bucketOverflow != 0 && uint64_t(size) > bucketOverflow) size = 0u;
         }
         // where each slice's bucket goes: exclusive prefix sum of the sizes, in slice order
-        uint32_t inclusive = size;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t below = uint32_t(__shfl_up(int(inclusive), d, 64));
-            if (lane >= uint32_t(d)) inclusive += below;
-        }
+        const uint32_t inclusive = waveInclusiveScan(size);
         const uint32_t offset = out + inclusive - size;
         const uint32_t slices = sliceCount - first < 64u ? sliceCount - first : 64u;
         for (uint32_t j = 0; j < slices; j += 4u) {
@@ -276,11 +272,7 @@ unionKernel(const uint32_t* __restrict__ runOfCellSlice, const uint32_t* __restr
         // ---- the buckets' begins and the prefix sums of their sizes (threads 0 .. 255 = waves 0 .. 3) ----
         uint32_t inclusiveSize = nextSize;
         if (t < kUnionSlices) {
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t below = uint32_t(__shfl_up(int(inclusiveSize), d, 64));
-                if (lane >= uint32_t(d)) inclusiveSize += below;
-            }
+            inclusiveSize = waveInclusiveScan(inclusiveSize);
             if (lane == 63u) waveTotals[wave] = inclusiveSize;
             bucketBegin[t] = nextBegin;
         }
@@ -335,12 +327,7 @@ unionKernel(const uint32_t* __restrict__ runOfCellSlice, const uint32_t* __restr
                 occupied |= (word != 0u ? 1u : 0u) << j;
             }
             // block-wide exclusive prefix sum of the counts
-            uint32_t inclusive = count;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t below = uint32_t(__shfl_up(int(inclusive), d, 64));
-                if (lane >= uint32_t(d)) inclusive += below;
-            }
+            const uint32_t inclusive = waveInclusiveScan(count);
             if (lane == 63u) waveTotals[wave] = inclusive;
             __syncthreads();
             uint32_t before = 0, total = 0;

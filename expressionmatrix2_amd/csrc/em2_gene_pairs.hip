@@ -5,7 +5,7 @@
 // src/ExpressionMatrixSubset.cpp:142-174), normalises the cells (L1 / L2 / none), shifts and scales every gene to zero mean
 // and unit norm (:117-135), and then computes r(g0, g1) = std::inner_product(x0, x1, 0.f) for every unordered pair (:153-177):
 // a float multiplication, then a float addition, per cell, in ascending cell order.  Here:
-//   * cellSumsKernel        computeSums (src/ExpressionMatrixSubset.cpp:47-58) and the checks the scatter's bounds rest on;
+//   * cellSumsKernel        computeSums and the checks the scatter's bounds rest on (em2_expression.h);
 //   * denseCellsKernel      the dense matrix, CELL-major (dense[cell][gene], the gene pitch a multiple of the tile), and the
 //                           cell normalisation: a block per cell, so the walk is contiguous;
 //   * standardizeKernel     :117-135 literally, a thread per gene walking the cells in ascending order (neighbouring threads
@@ -27,6 +27,7 @@
 // itself, as in the reference).
 
 #include "em2_device.h"
+#include "em2_expression.h"
 #include "em2_hip_util.h"
 #include "em2_wave.h"
 
@@ -59,27 +60,17 @@ struct GeneEntry {
     float key;
 };
 
-// computeSums, and the checks: gene ids below geneCount, strictly ascending within a cell.  A thread per cell, striding over
-// the grid (gridFor caps it).
+// computeSums and the input check (em2_expression.h).  A thread per cell, striding over the grid (gridFor caps it).
 __global__ void __launch_bounds__(256)
 cellSumsKernel(const uint64_t* __restrict__ toc, const CountIn* __restrict__ data, uint32_t cellCount, uint32_t geneCount,
                CellSums* __restrict__ sums, uint32_t* __restrict__ error)
 {
     uint32_t bad = 0u;
     for (uint64_t c = blockIdx.x * blockDim.x + threadIdx.x; c < cellCount; c += uint64_t(gridDim.x) * blockDim.x) {
-        double sum1 = 0., sum2 = 0.;
-        uint32_t previous = 0u;
-        const uint64_t begin = toc[c], end = toc[c + 1u];
-        for (uint64_t p = begin; p < end; ++p) {
-            const CountIn e = data[p];
-            if (e.gene >= geneCount) bad |= 1u;
-            if (p != begin && e.gene <= previous) bad |= 2u;
-            previous = e.gene;
-            sum1 += double(e.count);
-            sum2 += double(e.count * e.count);           // count*count is a float product (:55)
-        }
-        sums[c].sum1 = sum1;
-        sums[c].sum2 = sum2;
+        const CellWalk w = walkCell(toc, data, c, geneCount);
+        sums[c].sum1 = w.sum1;
+        sums[c].sum2 = w.sum2;
+        bad |= w.bad;
     }
     if (bad) atomicOr(error, bad);
 }
@@ -252,12 +243,7 @@ genePairsKernel(const float* __restrict__ dense, uint32_t pitch, uint32_t cellCo
     }
     // one cursor advance per wave: the lanes' counts, an inclusive scan, the last lane draws for all
     const uint32_t lane = tid & 63u;
-    uint32_t inclusive = mine;
-#pragma unroll
-    for (uint32_t step = 1u; step < 64u; step <<= 1) {
-        const uint32_t below = uint32_t(__shfl_up(int(inclusive), step, 64));
-        if (lane >= step) inclusive += below;
-    }
+    const uint32_t inclusive = waveInclusiveScan(mine);
     const uint32_t total = uint32_t(__shfl(int(inclusive), 63, 64));
     if (total == 0u) return;                                                   // (uniform over the wave)
     unsigned long long base = 0;
@@ -365,8 +351,6 @@ private:
     std::chrono::steady_clock::time_point last_;
 };
 
-uint32_t padTo(uint32_t x, uint32_t unit) { return (x + unit - 1u) / unit * unit; }
-
 }  // namespace
 
 
@@ -387,7 +371,7 @@ hipError_t runGenePairs(const uint64_t* d_toc, const CountIn* d_data, uint32_t c
 {
     *status = GenePairsStatus();
     GenePairsTimer timer;
-    const uint32_t pitch = padTo(geneCount, kTile), cellRows = padTo(cellCount, kChunk);
+    const uint32_t pitch = blocksOf(geneCount, kTile) * kTile, cellRows = blocksOf(cellCount, kChunk) * kChunk;
     DeviceBuffer sums, words, dense;
     EM2_TRY(sums.allocate(size_t(cellCount) * sizeof(CellSums)));
     EM2_TRY(words.allocate(256));                         // [0] input error, [1] longest list, [2..3] the cursor

@@ -1,5 +1,5 @@
 // em2_hip_util.h -- the host-side plumbing every driver needs: bail out on a HIP error, a device allocation that frees
-// itself, the 1-D grid of a 256-thread kernel, 256-byte alignment, signature words.  (The device-side counterpart is
+// itself, the 1-D grid of a 256-thread kernel, blocks per items, 256-byte alignment, signature words.  (The device-side counterpart is
 // em2_wave.h; device scratch that outlives a call is em2_scratch.h.)
 #ifndef EM2_HIP_UTIL_H
 #define EM2_HIP_UTIL_H
@@ -44,6 +44,9 @@ inline uint32_t gridFor(uint64_t n)
     const uint64_t blocks = (n + 255) / 256;
     return uint32_t(blocks > 16384 ? 16384 : (blocks ? blocks : 1));
 }
+
+// Blocks of perBlock items that hold `items` items.
+inline uint32_t blocksOf(uint64_t items, uint32_t perBlock) { return uint32_t((items + perBlock - 1u) / perBlock); }
 
 inline size_t alignUp(size_t x) { return (x + 255u) & ~size_t(255u); }
 

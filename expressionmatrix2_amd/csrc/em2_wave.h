@@ -28,6 +28,18 @@ __device__ __forceinline__ uint32_t lanesBelow(uint64_t mask)
     return __builtin_amdgcn_mbcnt_hi(uint32_t(mask >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(mask), 0u));
 }
 
+// The sum of `value` over this lane and the lanes below it (blocks are one-dimensional and whole waves, as everywhere here).
+__device__ __forceinline__ uint32_t waveInclusiveScan(uint32_t value)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+    for (uint32_t step = 1u; step < 64u; step <<= 1) {
+        const uint32_t below = uint32_t(__shfl_up(int(value), step, 64));
+        if (lane >= step) value += below;
+    }
+    return value;
+}
+
 // The unused tail of a row's k result slots: the wave writes {0, 0.0f} into out[kept, k).
 __device__ __forceinline__ void clearRowTail(PairOut* out, uint32_t kept, uint32_t k, uint32_t lane)
 {

@@ -117,6 +117,14 @@ def clustered(cells, genes, density, seed=12345, cluster_count=8, non_integer=Fa
     return toc, counts_of(g, cnt)
 
 
+def wide_matrix():
+    """1100 cells x 40 000 genes, about 20 non-integer counts per cell: more genes than LDS holds, so the kernels take their
+    global-memory form, and more rows than that form has blocks (1024), so 76 blocks load a second row into a scratch vector
+    that still holds the first row's values: only the bitmap may decide.  -> (toc, data, genes)"""
+    toc, data = clustered(1100, 40000, 0.0005, seed=1100, cluster_count=6, non_integer=True)
+    return toc, data, 40000
+
+
 def repeat_cells(toc, data, pattern):
     """Cell c of the input appears pattern[c] times in a row: identical cells have identical similarities to every third
     cell, which puts exact ties at the eviction boundary of SimilarPairs::add."""

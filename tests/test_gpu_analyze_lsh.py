@@ -44,6 +44,51 @@ def test_analyze_lsh_equals_oracle(oracle, tmp_path, cells, genes, L, density, s
         assert open(tmp_path / ("d-%s.csv" % name), "rb").read() == open(tmp_path / ("o-%s.csv" % name), "rb").read()
 
 
+def assert_equal_to_oracle(o, d, tmp_path):
+    assert o is not None
+    for name in ("exact", "lsh", "sum1", "sum2"):
+        assert np.array_equal(d[name].view(np.uint64), o[name].view(np.uint64)), name
+    assert np.array_equal(d["sum0"], o["sum0"])
+    for name in ("pairs", "stats"):
+        assert open(tmp_path / ("d-%s.csv" % name), "rb").read() == open(tmp_path / ("o-%s.csv" % name), "rb").read()
+
+
+def test_analyze_lsh_global_form_with_more_rows_than_blocks(oracle, tmp_path):
+    """40 000 genes do not fit LDS, and the global-memory form has 1024 blocks for the 1099 rows: 75 blocks load a second row
+    into a scratch vector that still holds the first row's values, and only the bitmap may decide."""
+    cells, genes = 1100, 40000
+    toc, g, c = synth.expression_matrix(cells, genes, density=0.0005, cluster_count=6, seed=1100)
+    c = (c.astype(np.float64) * (0.37 + synth.uniform01(1100, 77, np.arange(len(c), dtype=np.uint64)))).astype(np.float32)
+    ids = (np.arange(cells, dtype=np.uint32) * 3 + 5).astype(np.uint32)
+    o, d = run_both(oracle, tmp_path, toc, g, c, genes, 64, ids, 17, 0.01)
+    assert_equal_to_oracle(o, d, tmp_path)
+
+
+def largest_gene_count_in_lds():
+    """csrc/em2_expression.h: the row vector is geneCount floats and a bit per gene, each part padded to 8 bytes, and the LDS
+    form is taken while that fits the 160 KiB of a workgroup."""
+    row_vector_bytes = lambda genes: (genes * 4 + 7) // 8 * 8 + ((genes + 31) // 32 * 4 + 7) // 8 * 8
+    genes = 160 * 1024 // 4
+    while row_vector_bytes(genes) > 160 * 1024:
+        genes -= 1
+    assert row_vector_bytes(genes + 1) > 160 * 1024
+    return genes
+
+
+@pytest.mark.parametrize("beyond", [0, 1])
+def test_analyze_lsh_at_the_lds_limit(oracle, tmp_path, beyond):
+    """The largest gene set the LDS form takes, and one gene more (the global-memory form); the last genes are in use."""
+    cells, genes = 130, largest_gene_count_in_lds() + beyond
+    toc, g, c = synth.expression_matrix(cells, genes, density=0.001, cluster_count=4, seed=3)
+    c = c.astype(np.float32)
+    last = toc[1:].astype(np.int64) - 1                # every cell's last entry becomes one of the three highest genes
+    g[last] = genes - 1 - np.arange(cells) % 3
+    assert all((np.diff(g[int(toc[i]):int(toc[i + 1])].astype(np.int64)) > 0).all() for i in range(cells))
+    ids = np.arange(cells, dtype=np.uint32)
+    o, d = run_both(oracle, tmp_path, toc, g, c, genes, 128, ids, 3, 0.1)
+    assert_equal_to_oracle(o, d, tmp_path)
+
+
 def test_analyze_lsh_many_chunks(oracle, tmp_path, monkeypatch):
     """More pairs than one chunk of rows holds (2^24): the host walks the chunks in order, the bins and the random draws
     carry over."""

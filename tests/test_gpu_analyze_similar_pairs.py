@@ -74,6 +74,28 @@ def test_bin_assert_is_reported(restatement, tmp_path):
         capi.analyze_similar_pairs(toc, data, 40, pairs, used, ids, 1.0, str(tmp_path / "d.csv"), str(tmp_path / "ds.csv"))
 
 
+def test_global_memory_form(restatement, tmp_path):
+    """More genes than LDS holds and more rows than the global-memory form has blocks (fsp0_binding.wide_matrix).  The stored
+    object is a synthetic one as below: k = 8, usedCount varying, one cell that stores nothing."""
+    toc, data, genes = fsp0_binding.wide_matrix()
+    cells, k = len(toc) - 1, 8
+    pairs = np.zeros((cells, k), dtype=capi.PAIR_DTYPE)
+    pairs["cell"] = (np.arange(cells, dtype=np.uint32)[:, None] + 1 + np.arange(k, dtype=np.uint32)[None, :] * 7) % cells
+    pairs["similarity"] = 0.25
+    used = (k - (np.arange(cells) % 5)).astype(np.uint32)
+    used[1050] = 0
+    ids = (np.arange(cells, dtype=np.uint32) * 3 + 5).astype(np.uint32)
+    rc = restatement.analyze_similar_pairs(toc, data, genes, pairs["cell"], pairs["similarity"], used, ids, 0.5,
+                                           str(tmp_path / "r-pairs.csv"), str(tmp_path / "r-stats.csv"))
+    if rc == 1:
+        pytest.fail("the synthetic input holds a pair with exact similarity 1: choose another seed")
+    capi.analyze_similar_pairs(toc, data, genes, pairs, used, ids, 0.5, str(tmp_path / "d-pairs.csv"), str(tmp_path / "d-stats.csv"))
+    for name in ("pairs", "stats"):
+        assert open(tmp_path / ("d-%s.csv" % name), "rb").read() == open(tmp_path / ("r-%s.csv" % name), "rb").read()
+    assert len(open(tmp_path / "r-pairs.csv").read().splitlines()) > 1000
+    assert len(open(tmp_path / "r-stats.csv").read().splitlines()) > 2
+
+
 def test_more_stored_pairs_than_one_chunk(restatement, tmp_path):
     """The device works in chunks of 2^24 slots: 70 000 cells x k = 300 is 21M slots, two chunks; the bins and the draws carry
     over.  The stored object is a synthetic one (each cell's next 300 cells with a made-up similarity)."""

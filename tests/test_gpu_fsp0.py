@@ -51,6 +51,13 @@ def test_fsp0_equals_restatement(restatement, cells, genes, density, k, thr, non
         assert expected[2].sum() > 0
 
 
+def test_fsp0_global_form_with_more_rows_than_blocks(restatement):
+    toc, data, genes = fsp0_binding.wide_matrix()
+    expected = restatement.find_similar_pairs0(toc, data, genes, 12, 0.0)
+    assert_equal(capi.find_similar_pairs0(toc, data, genes, 12, 0.0), expected)
+    assert expected[2][1024:].sum() > 0                          # the rows a block takes second store pairs
+
+
 @pytest.mark.parametrize("k,thr", [(3, -1.0), (4, 0.0), (5, 0.05), (2, 0.3)])
 def test_fsp0_ties_at_the_eviction_boundary(restatement, k, thr):
     """Every cell 2-3 times, small k, low threshold: tests/test_fsp0_cpu.py::test_tie_input_is_not_a_plain_top_k shows that
