@@ -62,6 +62,19 @@ SYMBOLS = {
     "em2_find_similar_gene_pairs0": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_int, _c.c_uint32,
                                                 _c.c_double, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "em2_set_gene_pairs_buffer_mb": (None, [_c.c_uint64]),
+    "em2_gene_information_content": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_void_p, _c.c_void_p,
+                                                _c.c_void_p, _c.c_void_p]),
+    "em2_dev_gene_information_content_workspace": (_c.c_size_t, [_c.c_uint32, _c.c_uint32, _c.c_uint64]),
+    "em2_dev_gene_information_content": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_uint64, _c.c_void_p,
+                                                    _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "em2_set_gene_information_max_blocks": (None, [_c.c_uint32]),
+    "em2_cell_norm_inverses": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_void_p, _c.c_void_p]),
+    "em2_matrix_gene_information_content": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_int, _c.c_void_p]),
+    "em2_matrix_create_gene_set_using_information_content": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_int,
+                                                                        _c.c_double, _c.c_char_p]),
+    "em2_matrix_create_well_expressed_gene_set": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_char_p, _c.c_uint32]),
+    "em2_matrix_remove_gene_set": (_c.c_int, [_c.c_void_p, _c.c_char_p]),
+    "em2_tool_add_cells": (_c.c_int, [_c.c_char_p, _c.c_void_p, _c.c_void_p, _c.c_uint32]),
     "em2_matrix_find_similar_gene_pairs0": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_int, _c.c_char_p,
                                                        _c.c_size_t, _c.c_double]),
     "em2_matrix_remove_similar_gene_pairs": (_c.c_int, [_c.c_void_p, _c.c_char_p]),
@@ -514,6 +527,64 @@ def find_similar_pairs0(toc, data, gene_count, k=100, similarity_threshold=0.2):
 
 
 GENE_PAIRS_BUFFER_MB_DEFAULT = 4096
+
+
+def cell_norm_inverses(toc, data, gene_count):
+    """Cell::norm1Inverse / norm2Inverse of ExpressionMatrix::addCell (src/ExpressionMatrix.cpp:241-263) for the cells of a
+    host CSR -> (norm1Inverse, norm2Inverse), float64 [cells].  Host code."""
+    toc = np.ascontiguousarray(toc, dtype=np.uint64)
+    data = np.ascontiguousarray(data, dtype=COUNT_DTYPE)
+    cell_count = len(toc) - 1
+    norm1 = np.zeros(cell_count, dtype=np.float64)
+    norm2 = np.zeros(cell_count, dtype=np.float64)
+    check(load().em2_cell_norm_inverses(_ptr(toc), _ptr(data), cell_count, gene_count, _ptr(norm1), _ptr(norm2)))
+    return norm1, norm2
+
+
+def gene_information_content(toc, data, gene_count, norm_inverse=None):
+    """computeGeneInformationContent (src/ExpressionMatrix.cpp:1947-2018) for every gene of a subset's host CSR ->
+    (informationContent float32 [genes], the same as float64, expressingCellCount uint32 [genes]).  norm_inverse: None (no
+    normalisation) or float64 [cells], the cells' norm1Inverse or norm2Inverse."""
+    toc = np.ascontiguousarray(toc, dtype=np.uint64)
+    data = np.ascontiguousarray(data, dtype=COUNT_DTYPE)
+    cell_count = len(toc) - 1
+    if norm_inverse is not None:
+        norm_inverse = np.ascontiguousarray(norm_inverse, dtype=np.float64)
+        if len(norm_inverse) != cell_count:
+            raise ValueError("norm_inverse must have one value per cell")
+    single = np.zeros(gene_count, dtype=np.float32)
+    double = np.zeros(gene_count, dtype=np.float64)
+    expressing = np.zeros(gene_count, dtype=np.uint32)
+    check(load().em2_gene_information_content(_ptr(toc), _ptr(data), cell_count, gene_count,
+                                              _ptr(norm_inverse) if norm_inverse is not None else None, _ptr(single),
+                                              _ptr(double), _ptr(expressing)))
+    return single, double, expressing
+
+
+def dev_gene_information_content(toc, data, gene_count, norm_inverse=None):
+    """The same through em2_dev_gene_information_content on torch device buffers (a stream of torch's)."""
+    import torch
+    toc = np.ascontiguousarray(toc, dtype=np.uint64)
+    data = np.ascontiguousarray(data, dtype=COUNT_DTYPE)
+    cell_count, entries = len(toc) - 1, len(data)
+    lib = load()
+    device = torch.device("cuda")
+    d_toc = torch.from_numpy(toc.view(np.int64).copy()).to(device)
+    d_data = torch.from_numpy(data.view(np.uint8).reshape(-1).copy()).to(device)
+    d_norm = torch.from_numpy(np.ascontiguousarray(norm_inverse, dtype=np.float64)).to(device) if norm_inverse is not None else None
+    d_single = torch.zeros(gene_count, dtype=torch.float32, device=device)
+    d_double = torch.zeros(gene_count, dtype=torch.float64, device=device)
+    d_expressing = torch.zeros(gene_count, dtype=torch.int32, device=device)
+    workspace_bytes = lib.em2_dev_gene_information_content_workspace(cell_count, gene_count, entries)
+    d_workspace = torch.empty(workspace_bytes, dtype=torch.uint8, device=device)
+    stream = torch.cuda.Stream()
+    stream.wait_stream(torch.cuda.current_stream())
+    check(lib.em2_dev_gene_information_content(d_toc.data_ptr(), d_data.data_ptr(), cell_count, gene_count, entries,
+                                               d_norm.data_ptr() if d_norm is not None else None, d_single.data_ptr(),
+                                               d_double.data_ptr(), d_expressing.data_ptr(), d_workspace.data_ptr(),
+                                               workspace_bytes, stream.cuda_stream))
+    torch.cuda.current_stream().wait_stream(stream)
+    return d_single.cpu().numpy(), d_double.cpu().numpy(), d_expressing.cpu().numpy().view(np.uint32)
 
 
 def apply_gene_pairs_buffer():

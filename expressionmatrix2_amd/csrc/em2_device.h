@@ -238,6 +238,22 @@ hipError_t runGenePairs(const uint64_t* d_toc, const CountIn* d_data, uint32_t c
                         double similarityThreshold, PairOut* d_pairs, uint32_t* d_used, float* d_all, GenePairsStatus* status,
                         hipStream_t stream);
 
+// em2_gene_information.hip: ExpressionMatrix::computeGeneInformationContent (src/ExpressionMatrix.cpp:1947-2018) and the cells
+// expressing every gene (src/ExpressionMatrixGeneSets.cpp:336-350) on a subset's CSR in device memory (toc from 0, entryCount
+// entries).  d_normInverse: NULL (no normalisation) or the cells' norm1Inverse / norm2Inverse; launchCellNormInverses computes
+// them (method 1 or 2) from the cells' WHOLE rows as addCell does (:241-263).  logN = log(double(cellCount)) and log2 = log(2.)
+// come from the host's log.  d_informationContentDouble and d_expressingCellCount may be NULL.  *inputError != 0: nothing was
+// computed (bits 0, 1: as runFsp0's; bit 2: toc does not cover exactly entryCount entries, ascending from 0).  Synchronises the stream.
+constexpr uint32_t kGeneInformationChunk = 1024;          // entries of a gene one wave reduces (the reduction's shape)
+size_t geneInformationWorkspaceBytes(uint64_t entryCount, uint32_t geneCount);
+void setGeneInformationMaxBlocks(uint32_t blocks);      // em2_set_gene_information_max_blocks; 0 (the default): 65536
+hipError_t launchCellNormInverses(const uint64_t* toc, const CountIn* data, uint32_t cellCount, uint32_t geneCount, int method,
+                                  double* normInverse, hipStream_t stream);
+hipError_t runGeneInformation(const uint64_t* d_toc, const CountIn* d_data, uint32_t cellCount, uint32_t geneCount, uint64_t entryCount,
+                              const double* d_normInverse, double logN, double log2, float* d_informationContent,
+                              double* d_informationContentDouble, uint32_t* d_expressingCellCount, void* workspace, size_t workspaceBytes,
+                              uint32_t* inputError, hipStream_t stream);
+
 }  // namespace em2
 
 #endif

@@ -1,0 +1,383 @@
+// em2_gene_information.hip -- ExpressionMatrix::computeGeneInformationContent (src/ExpressionMatrix.cpp:1947-2018) and the
+// count of expressing cells of createWellExpressedGeneSet (src/ExpressionMatrixGeneSets.cpp:336-350) for every gene of a
+// subset's CSR in device memory.
+//
+// The reference walks gene by gene and looks every cell up with a binary search (getCellExpressionCount, :1035-1046).  Here
+// the stored entries are transposed once and every gene's entries are reduced where they then lie together:
+//   * cellNormInversesKernel   Cell::norm1Inverse / norm2Inverse as addCell defines them (:241-263): walkCell
+//                              (em2_expression.h) over the whole row of every cell, a thread per cell;
+//   * entriesKernel            a wave per cell: key = local gene, value = c = count * float(normInverse) (a float product,
+//                              :1981-1992), in stored order; the gene ids are checked as walkCell checks them; a cell whose
+//                              float(normInverse) is not finite raises the `poison` word (see geneSumsKernel);
+//   * rocPRIM's STABLE radix sort of (key, value) on the bits a gene id needs: every gene's values together, its cells still in
+//     ascending order, so the stream is a function of the input alone;
+//   * geneSegmentsKernel       the segment of every gene by binary search on the sorted keys; its length is the number of
+//                              expressing cells, stored zeros included; ceil(length / kChunk) chunks;
+//   * a scan over the chunk counts and chunkTableKernel: chunk t -> (gene, chunk within the gene).  The work of both passes is
+//     dealt by chunk, so a gene present in every cell and a gene present in one cell keep the machine equally busy;
+//   * chunkReduceKernel<PASS>  THE FIXED SHAPE.  A gene's segment is cut at kChunk, 2 kChunk, ... FROM ITS OWN START.  One wave
+//                              reduces one chunk: lane l adds the chunk's entries l, l + 64, l + 128, ... in ascending order
+//                              into a double that starts at +0, then the 64 lane sums are folded by waveSum (em2_wave.h:
+//                              lanes l and l ^ 32, then ^ 16, ... ^ 1).  Pass 0 adds double(c); pass 1 adds p * log(p) for
+//                              c > 0, p = double(c) * inverseSum(gene).  Which wave of which block reduces a chunk changes nothing;
+//   * geneSumsKernel / geneFinishKernel   a thread per gene adds the gene's chunk partials in ascending chunk order:
+//                              sum, inverseSum = 1 / sum; then I = (logN + s) / log2, float(I).
+// No floating-point atomics, no FMA (-ffp-contract=off), the device library's double log.
+//
+// A cell whose float(normInverse) is inf or NaN (an empty cell under L1 / L2): the reference multiplies the 0 of every gene
+// the cell does not store by it (:1981-1987) and adds the NaN to that gene's sum; a gene the cell does store gets inf or NaN
+// there.  Either way every gene with a positive entry ends as NaN and every other gene as log(N) / log(2).  geneSumsKernel
+// restates that by replacing every gene's sum with NaN when the poison word is set.
+
+#include "em2_device.h"
+#include "em2_expression.h"
+#include "em2_hip_util.h"
+#include "em2_wave.h"
+
+#include <cstring>            // (rocPRIM calls memset without including it)
+#include <rocprim/rocprim.hpp>
+
+#include <atomic>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+
+namespace em2 {
+namespace {
+
+constexpr uint32_t kChunk = kGeneInformationChunk;       // entries of a gene one wave reduces
+constexpr uint32_t kPerLane = kChunk / 64u;
+
+struct ChunkRef {
+    uint32_t gene;
+    uint32_t index;           // the chunk's number within its gene: entries [index * kChunk, + kChunk) of the segment
+};
+
+__global__ void __launch_bounds__(256)
+cellNormInversesKernel(const uint64_t* __restrict__ toc, const CountIn* __restrict__ data, uint32_t cellCount, uint32_t geneCount,
+                       int method, double* __restrict__ normInverse)
+{
+    for (uint64_t c = blockIdx.x * blockDim.x + threadIdx.x; c < cellCount; c += uint64_t(gridDim.x) * blockDim.x) {
+        const CellWalk w = walkCell(toc, data, c, geneCount);
+        normInverse[c] = method == 1 ? __ddiv_rn(1., w.sum1) : __ddiv_rn(1., __dsqrt_rn(w.sum2));      // :262-263
+    }
+}
+
+// words[0] |= the input error of walkCell (bit 2: toc does not cover exactly the entryCount entries, from 0 and ascending; such
+// a cell writes nothing), words[1] |= 1 where a cell's factor is not finite.  normInverse NULL: no scaling.
+__global__ void __launch_bounds__(256)
+entriesKernel(const uint64_t* __restrict__ toc, const CountIn* __restrict__ data, uint32_t cellCount, uint32_t geneCount,
+              uint64_t entryCount, const double* __restrict__ normInverse, uint32_t* __restrict__ keys, float* __restrict__ values,
+              uint32_t* __restrict__ words)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t waves = uint64_t(gridDim.x) * (blockDim.x >> 6);
+    uint32_t bad = 0u;
+    if (blockIdx.x == 0u && threadIdx.x == 0u && (toc[0] != 0u || toc[cellCount] != entryCount)) bad |= 4u;
+    for (uint64_t cell = uint64_t(blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6); cell < cellCount; cell += waves) {
+        const uint64_t begin = toc[cell];
+        uint64_t end = toc[cell + 1u];
+        if (end > entryCount || begin > end) {                 // (a toc that descends: cells would write each other's entries)
+            bad |= 4u;
+            end = begin;
+        }
+        float factor = 1.f;
+        if (normInverse) {
+            factor = float(normInverse[cell]);
+            if (lane == 0u && !(fabsf(factor) <= 3.402823466e38f)) atomicOr(words + 1, 1u);
+        }
+        for (uint64_t p = begin + lane; p < end; p += 64u) {
+            const CountIn e = data[p];
+            if (e.gene >= geneCount) bad |= 1u;
+            if (p != begin && e.gene <= data[p - 1u].gene) bad |= 2u;
+            keys[p] = e.gene;
+            values[p] = normInverse ? e.count * factor : e.count;
+        }
+    }
+    if (bad) atomicOr(words, bad);
+}
+
+__device__ __forceinline__ uint64_t lowerBound(const uint32_t* __restrict__ sorted, uint64_t count, uint32_t key)
+{
+    uint64_t low = 0, high = count;
+    while (low < high) {
+        const uint64_t middle = low + (high - low) / 2u;
+        if (sorted[middle] < key) low = middle + 1u;
+        else high = middle;
+    }
+    return low;
+}
+
+// offsets[g] = the first entry of gene g in the sorted stream (offsets[geneCount] = count); chunkCounts[g] = its chunks
+// (chunkCounts[geneCount] = 0, the scan's last input); expressing[g] (NULL or [geneCount]) = its entries.
+__global__ void __launch_bounds__(256)
+geneSegmentsKernel(const uint32_t* __restrict__ sortedKeys, uint64_t count, uint32_t geneCount, uint64_t* __restrict__ offsets,
+                   uint64_t* __restrict__ chunkCounts, uint32_t* __restrict__ expressing)
+{
+    for (uint64_t g = blockIdx.x * blockDim.x + threadIdx.x; g <= geneCount; g += uint64_t(gridDim.x) * blockDim.x) {
+        if (g == geneCount) {
+            offsets[g] = count;
+            chunkCounts[g] = 0u;
+            continue;
+        }
+        const uint64_t begin = lowerBound(sortedKeys, count, uint32_t(g));
+        const uint64_t end = g + 1u == geneCount ? count : lowerBound(sortedKeys, count, uint32_t(g + 1u));
+        offsets[g] = begin;
+        chunkCounts[g] = (end - begin + kChunk - 1u) / kChunk;
+        if (expressing) expressing[g] = uint32_t(end - begin);
+    }
+}
+
+// chunkStarts: the exclusive scan of chunkCounts, [geneCount + 1].  A thread per chunk finds its gene: the last g with
+// chunkStarts[g] <= t (genes without chunks share their start with the next gene and are passed over).
+__global__ void __launch_bounds__(256)
+chunkTableKernel(const uint64_t* __restrict__ chunkStarts, uint32_t geneCount, ChunkRef* __restrict__ table)
+{
+    const uint64_t total = chunkStarts[geneCount];
+    for (uint64_t t = blockIdx.x * blockDim.x + threadIdx.x; t < total; t += uint64_t(gridDim.x) * blockDim.x) {
+        uint32_t low = 0u, high = geneCount;               // the first g with chunkStarts[g] > t, in (0, geneCount]
+        while (low < high) {
+            const uint32_t middle = low + (high - low) / 2u;
+            if (chunkStarts[middle] <= t) low = middle + 1u;
+            else high = middle;
+        }
+        const uint32_t gene = low - 1u;
+        table[t] = ChunkRef{gene, uint32_t(t - chunkStarts[gene])};
+    }
+}
+
+// partials[t] for the chunks t = wave, wave + waves, ...  PASS 0: the sum of double(c).  PASS 1: the sum of p * log(p) over c > 0.
+template <int PASS>
+__global__ void __launch_bounds__(256)
+chunkReduceKernel(const float* __restrict__ sortedValues, const uint64_t* __restrict__ offsets, const uint64_t* __restrict__ chunkStarts,
+                  uint32_t geneCount, const ChunkRef* __restrict__ table, const double* __restrict__ inverseSums,
+                  double* __restrict__ partials)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t waves = uint64_t(gridDim.x) * (blockDim.x >> 6);
+    const uint64_t total = chunkStarts[geneCount];
+    for (uint64_t t = uint64_t(blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6); t < total; t += waves) {
+        const ChunkRef chunk = table[t];
+        const uint64_t begin = offsets[chunk.gene] + uint64_t(chunk.index) * kChunk;
+        const uint64_t segmentEnd = offsets[chunk.gene + 1u];
+        const uint64_t end = begin + kChunk < segmentEnd ? begin + kChunk : segmentEnd;
+        const double inverseSum = PASS == 1 ? inverseSums[chunk.gene] : 0.;
+        float c[kPerLane];
+#pragma unroll
+        for (uint32_t i = 0; i < kPerLane; ++i) {
+            const uint64_t p = begin + lane + 64u * i;
+            c[i] = p < end ? sortedValues[p] : 0.f;                    // (behind the end: +0, no term in either pass)
+        }
+        double mine = 0.;
+#pragma unroll
+        for (uint32_t i = 0; i < kPerLane; ++i) {
+            const uint64_t p = begin + lane + 64u * i;
+            if (PASS == 0) {
+                if (p < end) mine += double(c[i]);
+            } else if (p < end && c[i] > 0.f) {                         // :2007 (false for NaN)
+                const double probability = double(c[i]) * inverseSum;  // :2008
+                const double term = probability * log(probability);    // rounded
+                mine += term;                                           // rounded again: never an FMA
+            }
+        }
+        const double all = waveSum(mine);
+        if (lane == 0u) partials[t] = all;
+    }
+}
+
+// sums[g] = the gene's chunk partials added in ascending order from +0 (NaN instead where a cell poisons every sum),
+// inverseSums[g] = 1 / sums[g] (:2005).
+__global__ void __launch_bounds__(256)
+geneSumsKernel(const double* __restrict__ partials, const uint64_t* __restrict__ chunkStarts, uint32_t geneCount,
+               const uint32_t* __restrict__ words, double* __restrict__ sums, double* __restrict__ inverseSums)
+{
+    const bool poison = words[1] != 0u;
+    for (uint64_t g = blockIdx.x * blockDim.x + threadIdx.x; g < geneCount; g += uint64_t(gridDim.x) * blockDim.x) {
+        double sum = 0.;
+        for (uint64_t t = chunkStarts[g]; t < chunkStarts[g + 1u]; ++t) sum += partials[t];
+        if (poison) sum = __longlong_as_double(0x7ff8000000000000ll);
+        sums[g] = sum;
+        inverseSums[g] = __ddiv_rn(1., sum);
+    }
+}
+
+// :2004-2017: I = log(N) + the terms, / log(2), float.  logN and log2 are the host's.
+__global__ void __launch_bounds__(256)
+geneFinishKernel(const double* __restrict__ partials, const uint64_t* __restrict__ chunkStarts, uint32_t geneCount, double logN,
+                 double log2, float* __restrict__ informationContent, double* __restrict__ informationContentDouble)
+{
+    for (uint64_t g = blockIdx.x * blockDim.x + threadIdx.x; g < geneCount; g += uint64_t(gridDim.x) * blockDim.x) {
+        double terms = 0.;
+        for (uint64_t t = chunkStarts[g]; t < chunkStarts[g + 1u]; ++t) terms += partials[t];
+        const double information = __ddiv_rn(logN + terms, log2);
+        informationContent[g] = float(information);
+        if (informationContentDouble) informationContentDouble[g] = information;
+    }
+}
+
+class GeneInformationTimer {
+public:
+    GeneInformationTimer() : on_(getenv("EM2_TIMING") && getenv("EM2_TIMING")[0] == '1'), last_(std::chrono::steady_clock::now()) {}
+    // (synchronises the stream when the timing is on)
+    hipError_t stage(const char* name, hipStream_t stream)
+    {
+        if (!on_) return hipSuccess;
+        EM2_TRY(hipStreamSynchronize(stream));
+        const auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "[em2 timing] geneInformationContent: %s %.3f ms\n", name, std::chrono::duration<double, std::milli>(now - last_).count());
+        last_ = now;
+        return hipSuccess;
+    }
+private:
+    bool on_;
+    std::chrono::steady_clock::time_point last_;
+};
+
+uint32_t geneBitsOf(uint32_t geneCount)
+{
+    uint32_t bits = 0;
+    while (bits < 32u && (1ull << bits) < geneCount) ++bits;
+    return bits;
+}
+
+// Chunks of the whole problem at most: a gene wastes less than one.
+uint64_t chunkBound(uint64_t entryCount, uint32_t geneCount) { return entryCount / kChunk + geneCount; }
+
+std::atomic<uint32_t> maxBlocks{0};
+
+// Waves that stride over `items`: blocks of 4, at most 65536 blocks (or what setGeneInformationMaxBlocks asked for).
+uint32_t waveGridFor(uint64_t items)
+{
+    const uint64_t blocks = (items + 3u) / 4u;
+    const uint32_t asked = maxBlocks.load();
+    const uint32_t most = asked ? asked : 65536u;
+    return uint32_t(blocks > most ? most : (blocks ? blocks : 1u));
+}
+
+struct Layout {
+    size_t words, keysA, keysB, valuesA, valuesB, offsets, chunkCounts, chunkStarts, table, partials, sums, inverseSums, sortTemp, scanTemp, total;
+    size_t sortTempBytes, scanTempBytes;
+};
+
+hipError_t layoutOf(uint64_t entryCount, uint32_t geneCount, Layout& l)
+{
+    size_t at = 0;
+    const auto take = [&at](size_t bytes) {
+        const size_t here = at;
+        at += alignUp(bytes ? bytes : 1u);
+        return here;
+    };
+    const size_t perGene = (size_t(geneCount) + 1u) * sizeof(uint64_t);
+    l.words = take(256);
+    l.keysA = take(entryCount * sizeof(uint32_t));
+    l.keysB = take(entryCount * sizeof(uint32_t));
+    l.valuesA = take(entryCount * sizeof(float));
+    l.valuesB = take(entryCount * sizeof(float));
+    l.offsets = take(perGene);
+    l.chunkCounts = take(perGene);
+    l.chunkStarts = take(perGene);
+    l.table = take(chunkBound(entryCount, geneCount) * sizeof(ChunkRef));
+    l.partials = take(chunkBound(entryCount, geneCount) * sizeof(double));
+    l.sums = take(perGene);
+    l.inverseSums = take(perGene);
+    l.sortTempBytes = 0;
+    if (entryCount && geneBitsOf(geneCount)) {
+        rocprim::double_buffer<uint32_t> keys(nullptr, nullptr);
+        rocprim::double_buffer<float> values(nullptr, nullptr);
+        EM2_TRY(rocprim::radix_sort_pairs(nullptr, l.sortTempBytes, keys, values, size_t(entryCount), 0u, geneBitsOf(geneCount), hipStream_t(nullptr)));
+    }
+    l.scanTempBytes = 0;
+    uint64_t* none = nullptr;
+    EM2_TRY(rocprim::exclusive_scan(nullptr, l.scanTempBytes, none, none, uint64_t(0), size_t(geneCount) + 1u, rocprim::plus<uint64_t>(),
+                                    hipStream_t(nullptr)));
+    l.sortTemp = take(l.sortTempBytes);
+    l.scanTemp = take(l.scanTempBytes);
+    l.total = at;
+    return hipSuccess;
+}
+
+}  // namespace
+
+void setGeneInformationMaxBlocks(uint32_t blocks) { maxBlocks.store(blocks); }
+
+size_t geneInformationWorkspaceBytes(uint64_t entryCount, uint32_t geneCount)
+{
+    Layout l;
+    return layoutOf(entryCount, geneCount, l) == hipSuccess ? l.total : 0;
+}
+
+hipError_t launchCellNormInverses(const uint64_t* toc, const CountIn* data, uint32_t cellCount, uint32_t geneCount, int method,
+                                  double* normInverse, hipStream_t stream)
+{
+    if (cellCount == 0) return hipSuccess;
+    cellNormInversesKernel<<<dim3(gridFor(cellCount)), dim3(256), 0, stream>>>(toc, data, cellCount, geneCount, method, normInverse);
+    return hipGetLastError();
+}
+
+hipError_t runGeneInformation(const uint64_t* d_toc, const CountIn* d_data, uint32_t cellCount, uint32_t geneCount, uint64_t entryCount,
+                              const double* d_normInverse, double logN, double log2, float* d_informationContent,
+                              double* d_informationContentDouble, uint32_t* d_expressingCellCount, void* workspace, size_t workspaceBytes,
+                              uint32_t* inputError, hipStream_t stream)
+{
+    *inputError = 0;
+    Layout l;
+    EM2_TRY(layoutOf(entryCount, geneCount, l));
+    if (workspaceBytes < l.total) return hipErrorInvalidValue;
+    GeneInformationTimer timer;
+    char* base = static_cast<char*>(workspace);
+    uint32_t* words = reinterpret_cast<uint32_t*>(base + l.words);
+    uint64_t* offsets = reinterpret_cast<uint64_t*>(base + l.offsets);
+    uint64_t* chunkCounts = reinterpret_cast<uint64_t*>(base + l.chunkCounts);
+    uint64_t* chunkStarts = reinterpret_cast<uint64_t*>(base + l.chunkStarts);
+    ChunkRef* table = reinterpret_cast<ChunkRef*>(base + l.table);
+    double* partials = reinterpret_cast<double*>(base + l.partials);
+    double* sums = reinterpret_cast<double*>(base + l.sums);
+    double* inverseSums = reinterpret_cast<double*>(base + l.inverseSums);
+    rocprim::double_buffer<uint32_t> keys(reinterpret_cast<uint32_t*>(base + l.keysA), reinterpret_cast<uint32_t*>(base + l.keysB));
+    rocprim::double_buffer<float> values(reinterpret_cast<float*>(base + l.valuesA), reinterpret_cast<float*>(base + l.valuesB));
+
+    EM2_TRY(hipMemsetAsync(words, 0, 256, stream));
+    entriesKernel<<<dim3(waveGridFor(cellCount)), dim3(256), 0, stream>>>(d_toc, d_data, cellCount, geneCount, entryCount, d_normInverse,
+                                                                          keys.current(), values.current(), words);
+    EM2_TRY(hipGetLastError());
+    // the gene ids are the sort's keys and the segments' bounds: nothing goes on before they are known to be good
+    EM2_TRY(hipMemcpyAsync(inputError, words, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    EM2_TRY(hipStreamSynchronize(stream));
+    if (*inputError) return hipSuccess;
+    EM2_TRY(timer.stage("entries", stream));
+
+    // one gene (no key bits): the stream is in cell order already
+    if (entryCount && geneBitsOf(geneCount)) {
+        size_t tempBytes = l.sortTempBytes;
+        EM2_TRY(rocprim::radix_sort_pairs(base + l.sortTemp, tempBytes, keys, values, size_t(entryCount), 0u, geneBitsOf(geneCount), stream));
+    }
+    EM2_TRY(timer.stage("sort", stream));
+
+    geneSegmentsKernel<<<dim3(gridFor(uint64_t(geneCount) + 1u)), dim3(256), 0, stream>>>(keys.current(), entryCount, geneCount, offsets,
+                                                                                         chunkCounts, d_expressingCellCount);
+    EM2_TRY(hipGetLastError());
+    size_t scanBytes = l.scanTempBytes;
+    EM2_TRY(rocprim::exclusive_scan(base + l.scanTemp, scanBytes, chunkCounts, chunkStarts, uint64_t(0), size_t(geneCount) + 1u,
+                                    rocprim::plus<uint64_t>(), stream));
+    const uint64_t bound = chunkBound(entryCount, geneCount);
+    chunkTableKernel<<<dim3(gridFor(bound)), dim3(256), 0, stream>>>(chunkStarts, geneCount, table);
+    EM2_TRY(hipGetLastError());
+    EM2_TRY(timer.stage("segments and chunk table", stream));
+
+    chunkReduceKernel<0><<<dim3(waveGridFor(bound)), dim3(256), 0, stream>>>(values.current(), offsets, chunkStarts, geneCount, table, nullptr,
+                                                                            partials);
+    geneSumsKernel<<<dim3(gridFor(geneCount)), dim3(256), 0, stream>>>(partials, chunkStarts, geneCount, words, sums, inverseSums);
+    EM2_TRY(hipGetLastError());
+    EM2_TRY(timer.stage("pass 1 (sums)", stream));
+    chunkReduceKernel<1><<<dim3(waveGridFor(bound)), dim3(256), 0, stream>>>(values.current(), offsets, chunkStarts, geneCount, table,
+                                                                            inverseSums, partials);
+    geneFinishKernel<<<dim3(gridFor(geneCount)), dim3(256), 0, stream>>>(partials, chunkStarts, geneCount, logN, log2, d_informationContent,
+                                                                         d_informationContentDouble);
+    EM2_TRY(hipGetLastError());
+    EM2_TRY(hipStreamSynchronize(stream));
+    EM2_TRY(timer.stage("pass 2 (terms) and finish", stream));
+    return hipSuccess;
+}
+
+}  // namespace em2

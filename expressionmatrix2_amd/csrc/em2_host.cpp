@@ -9,6 +9,11 @@ extern "C" int em2_internal_subset_find_similar_pairs4(const uint64_t* globalToc
                                                        uint64_t* signatures, uint32_t k, double similarityThreshold, em2_pair* pairs,
                                                        uint32_t* usedCount);
 
+extern "C" int em2_internal_gene_information(const uint64_t* rowToc, const em2_count* rowData, uint32_t cellCount,
+                                             const uint32_t* geneLocalIds, uint32_t globalGeneCount, uint32_t geneCount,
+                                             int normalizationMethod, const double* normInverseOfRows, float* informationContent,
+                                             uint32_t* expressingCellCount);
+
 #include <chrono>
 #include <functional>
 #include <future>
@@ -105,6 +110,12 @@ struct SimilarGenePairsInfoRecord {
 };
 static_assert(sizeof(SimilarGenePairsInfoRecord) == 544 && offsetof(SimilarGenePairsInfoRecord, normalizationMethod) == 536,
               "SimilarGenePairs::Info layout");
+
+struct CellRecord {                                       // src/Cell.hpp:17-97
+    double sum1, sum2, norm2, norm1Inverse, norm2Inverse, sum1LargeExpressionCounts, sum2LargeExpressionCounts;
+};
+static_assert(sizeof(CellRecord) == 56 && offsetof(CellRecord, norm1Inverse) == 24 && offsetof(CellRecord, norm2Inverse) == 32,
+              "Cell layout");
 
 struct CellInfoRecord {                                   // src/SimilarPairs.hpp:165-179
     uint32_t usedCount;
@@ -597,6 +608,130 @@ void Matrix::removeSimilarGenePairs(const std::string& similarGenePairsName) con
     removeFile(base + "-Pairs");
 }
 
+void Matrix::geneInformation(const std::string& geneSetName, const std::string& cellSetName, int normalizationMethod,
+                             std::vector<float>* informationContent, std::vector<uint32_t>* expressingCellCount) const
+{
+    const GeneSet& genes = geneSet(geneSetName);                              // ExpressionMatrix.cpp:2030-2041: no emptiness checks
+    const MappedFile& cells = cellSet(cellSetName);
+    const uint32_t geneCount = genes.size(), cellCount = uint32_t(cells.objectCount());
+    const uint32_t* cellIds = static_cast<const uint32_t*>(cells.data());
+    const uint64_t globalCells = toc_.objectCount() - 1;
+    if (!isSorted(cellIds, cellCount)) fail(EM2_ERROR_RUNTIME, "Cell set " + cellSetName + " is not sorted.");
+    for (uint32_t local = 0; local < cellCount; local++) {
+        if (cellIds[local] >= globalCells) fail(EM2_ERROR_RUNTIME, "Cell set " + cellSetName + " refers to a cell that does not exist.");
+    }
+    if (normalizationMethod < 0 || normalizationMethod > 2) fail(EM2_ERROR_INVALID_ARGUMENT, "invalid normalization method (0 none, 1 L1, 2 L2)");
+    if (informationContent) informationContent->assign(geneCount, 0.f);
+    if (expressingCellCount) expressingCellCount->assign(geneCount, 0u);
+    if (geneCount == 0) return;
+    if (cellCount == 0) {
+        // no cell: log(0.) / log(2.) for every gene (:2004-2015), expressed nowhere
+        if (informationContent) informationContent->assign(geneCount, float(std::log(0.) / std::log(2.)));
+        return;
+    }
+    // the rows of the cell set, whole (the norms are those of the cell over all genes, :1976), with their global gene ids
+    const uint64_t* globalToc = static_cast<const uint64_t*>(toc_.data());
+    const em2_count* globalData = static_cast<const em2_count*>(data_.data());
+    std::vector<uint64_t> rowToc(size_t(cellCount) + 1, 0);
+    for (uint32_t i = 0; i < cellCount; i++) rowToc[i + 1] = rowToc[i] + (globalToc[cellIds[i] + 1] - globalToc[cellIds[i]]);
+    // consecutive cell ids (a sorted set may repeat an id: then, or with gaps, the rows are gathered)
+    bool contiguous = true;
+    for (uint32_t i = 1; i < cellCount && contiguous; i++) contiguous = cellIds[i] == cellIds[0] + i;
+    std::vector<em2_count> gathered;
+    const em2_count* rowData = globalData + globalToc[cellIds[0]];
+    if (!contiguous) {
+        gathered.resize(rowToc[cellCount]);
+        for (uint32_t i = 0; i < cellCount; i++) {
+            const uint64_t n = rowToc[i + 1] - rowToc[i];
+            if (n) std::memcpy(gathered.data() + rowToc[i], globalData + globalToc[cellIds[i]], n * sizeof(em2_count));
+        }
+        rowData = gathered.data();
+    }
+    std::vector<double> fromFile;
+    if (normalizationMethod != 0 && fileExists(directoryName_ + "/Cells")) {
+        MappedFile cellsFile;
+        cellsFile.openExisting(directoryName_ + "/Cells", false, sizeof(CellRecord));
+        if (cellsFile.objectCount() != globalCells) fail(EM2_ERROR_RUNTIME, "The Cells file has a number of cells inconsistent with the expression counts.");
+        const CellRecord* records = static_cast<const CellRecord*>(cellsFile.data());
+        fromFile.resize(cellCount);
+        for (uint32_t i = 0; i < cellCount; i++) {
+            fromFile[i] = normalizationMethod == 1 ? records[cellIds[i]].norm1Inverse : records[cellIds[i]].norm2Inverse;
+        }
+    }
+    const int rc = em2_internal_gene_information(rowToc.data(), rowData, cellCount, static_cast<const uint32_t*>(genes.localIds.data()),
+                                                 uint32_t(genes.localIds.objectCount()), geneCount, normalizationMethod,
+                                                 fromFile.empty() ? nullptr : fromFile.data(),
+                                                 informationContent ? informationContent->data() : nullptr,
+                                                 expressingCellCount ? expressingCellCount->data() : nullptr);
+    if (rc != EM2_OK) fail(rc, em2_last_error());
+}
+
+// "Gene set X already exists." (ExpressionMatrix.cpp:2044, ExpressionMatrixGeneSets.cpp:322): the sets this object knows, and
+// -- the reference keeps every set of the directory open, this object only those it found when it was opened -- a set whose
+// files another object has written into the directory since.
+void Matrix::failIfGeneSetExists(const std::string& name) const
+{
+    if (geneSets_.find(name) != geneSets_.end() || fileExists(directoryName_ + "/GeneSet-" + name + "-GlobalIds")) {
+        fail(EM2_ERROR_RUNTIME, "Gene set " + name + " already exists.");
+    }
+}
+
+void Matrix::addGeneSubset(const std::string& name, const GeneSet& from, const std::vector<bool>& keep)
+{
+    std::vector<uint32_t> ids;
+    for (uint32_t local = 0; local < from.size(); local++) {
+        if (keep[local]) ids.push_back(from.genes()[local]);
+    }
+    addGeneSet(directoryName_, name, ids.data(), uint32_t(ids.size()), 0);
+    std::unique_ptr<GeneSet> g(new GeneSet);
+    g->globalIds.openExisting(directoryName_ + "/GeneSet-" + name + "-GlobalIds", false, sizeof(uint32_t));
+    g->localIds.openExisting(directoryName_ + "/GeneSet-" + name + "-LocalIds", false, sizeof(uint32_t));
+    geneSets_[name] = g.release();            // (registered only once both files are open)
+}
+
+void Matrix::createGeneSetUsingInformationContent(const std::string& existingGeneSetName, const std::string& cellSetName,
+                                                  int normalizationMethod, double geneInformationContentThreshold,
+                                                  const std::string& newGeneSetName)
+{
+    // ExpressionMatrix.cpp:2030-2046: the existing gene set, the cell set, then the new name
+    const GeneSet& existing = geneSet(existingGeneSetName);
+    cellSet(cellSetName);
+    failIfGeneSetExists(newGeneSetName);
+    std::vector<float> informationContent;
+    geneInformation(existingGeneSetName, cellSetName, normalizationMethod, &informationContent, nullptr);
+    std::vector<bool> keep(existing.size());
+    for (uint32_t local = 0; local < existing.size(); local++) {
+        keep[local] = informationContent[local] > geneInformationContentThreshold;         // :2077, float > double; false for NaN
+    }
+    addGeneSubset(newGeneSetName, existing, keep);
+}
+
+void Matrix::createWellExpressedGeneSet(const std::string& inputGeneSetName, const std::string& inputCellSetName,
+                                        const std::string& outputGeneSetName, uint32_t minCellCount)
+{
+    // ExpressionMatrixGeneSets.cpp:322-329: the output name first, then the inputs
+    failIfGeneSetExists(outputGeneSetName);
+    const GeneSet& input = geneSet(inputGeneSetName);
+    cellSet(inputCellSetName);
+    std::vector<uint32_t> expressing;
+    geneInformation(inputGeneSetName, inputCellSetName, 0, nullptr, &expressing);
+    std::vector<bool> keep(input.size());
+    for (uint32_t local = 0; local < input.size(); local++) keep[local] = expressing[local] >= minCellCount;      // :356
+    addGeneSubset(outputGeneSetName, input, keep);
+}
+
+void Matrix::removeGeneSet(const std::string& geneSetName)
+{
+    // ExpressionMatrixGeneSets.cpp:12-32
+    if (geneSetName == "AllGenes") fail(EM2_ERROR_RUNTIME, "Gene set AllGenes cannot be removed.");
+    const auto it = geneSets_.find(geneSetName);
+    if (it == geneSets_.end()) fail(EM2_ERROR_RUNTIME, "Gene set " + geneSetName + " does not exist.");
+    delete it->second;
+    geneSets_.erase(it);
+    removeFile(directoryName_ + "/GeneSet-" + geneSetName + "-GlobalIds");
+    removeFile(directoryName_ + "/GeneSet-" + geneSetName + "-LocalIds");
+}
+
 void Matrix::analyzeSimilarPairs(const std::string& similarPairsName, double csvDownsample, const std::string& outputDirectory) const
 {
     // ExpressionMatrixLsh.cpp:60-69: the stored object names its gene set and cell set
@@ -1004,6 +1139,17 @@ void addCellSet(const std::string& directoryName, const std::string& name, const
     MappedFile f;
     f.createNew(directoryName + "/CellSet-" + name, false, sizeof(uint32_t), count);
     if (count) std::memcpy(f.data(), sortedCellIds, size_t(count) * sizeof(uint32_t));
+}
+
+void addCells(const std::string& directoryName, const double* norm1Inverse, const double* norm2Inverse, uint32_t cellCount)
+{
+    MappedFile f;
+    f.createNew(directoryName + "/Cells", false, sizeof(CellRecord), cellCount);
+    CellRecord* records = static_cast<CellRecord*>(f.data());
+    for (uint32_t i = 0; i < cellCount; i++) {
+        records[i].norm1Inverse = norm1Inverse[i];
+        records[i].norm2Inverse = norm2Inverse[i];
+    }
 }
 
 void createDirectoryFromCsr(const std::string& directoryName, uint32_t geneCount, uint32_t cellCount,

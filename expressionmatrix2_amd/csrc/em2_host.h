@@ -126,10 +126,27 @@ public:
     void analyzeLsh(const std::string& geneSetName, const std::string& cellSetName, size_t lshCount, unsigned int seed,
                     double csvDownsample, const std::string& outputDirectory) const;
 
+    // ExpressionMatrix::computeGeneInformationContent (src/ExpressionMatrix.cpp:1947-2018) for the genes of a gene set over a
+    // cell set, and the cells expressing every gene (src/ExpressionMatrixGeneSets.cpp:336-350); either vector may be NULL.
+    // The cells' norm inverses come from the Cells file where the directory has one.
+    void geneInformation(const std::string& geneSetName, const std::string& cellSetName, int normalizationMethod,
+                         std::vector<float>* informationContent, std::vector<uint32_t>* expressingCellCount) const;
+    // createGeneSetUsingInformationContent (src/ExpressionMatrix.cpp:2022-2082), createWellExpressedGeneSet
+    // (src/ExpressionMatrixGeneSets.cpp:314-362) and removeGeneSet (:12-32): the new set's files, and the set under its name.
+    void createGeneSetUsingInformationContent(const std::string& existingGeneSetName, const std::string& cellSetName,
+                                              int normalizationMethod, double geneInformationContentThreshold,
+                                              const std::string& newGeneSetName);
+    void createWellExpressedGeneSet(const std::string& inputGeneSetName, const std::string& inputCellSetName,
+                                    const std::string& outputGeneSetName, uint32_t minCellCount);
+    void removeGeneSet(const std::string& geneSetName);
+
     const GeneSet& geneSet(const std::string& name) const;                 // throws "Gene set X does not exist."
     const MappedFile& cellSet(const std::string& name) const;              // throws "Cell set X does not exist."
 
 private:
+    // Writes GeneSet-<name>-* for the genes of `from` that `keep` names (ascending local id) and opens the new set.
+    void addGeneSubset(const std::string& name, const GeneSet& from, const std::vector<bool>& keep);
+    void failIfGeneSetExists(const std::string& name) const;
     std::string directoryName_;
     MappedFile toc_;         // CellExpressionCounts.toc  (uint64)
     MappedFile data_;        // CellExpressionCounts.data (em2_count)
@@ -205,6 +222,8 @@ void addGeneSet(const std::string& directoryName, const std::string& name, const
                 uint32_t count, uint32_t totalGeneCount);
 void addCellSet(const std::string& directoryName, const std::string& name, const uint32_t* sortedCellIds,
                 uint32_t count);
+// A Cells file (MemoryMapped::Vector<Cell>, src/Cell.hpp) holding these inverses, zeros elsewhere.
+void addCells(const std::string& directoryName, const double* norm1Inverse, const double* norm2Inverse, uint32_t cellCount);
 
 }  // namespace host
 }  // namespace em2

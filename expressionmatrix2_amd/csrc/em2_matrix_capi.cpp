@@ -173,6 +173,46 @@ int em2_matrix_remove_similar_gene_pairs(em2_matrix* matrix, const char* similar
     return guarded([&] { matrix->impl->removeSimilarGenePairs(similarGenePairsName); });
 }
 
+int em2_matrix_gene_information_content(em2_matrix* matrix, const char* geneSetName, const char* cellSetName, int normalizationMethod,
+                                        float* out)
+{
+    if (!matrix || !geneSetName || !cellSetName) return nullArgument("em2_matrix_gene_information_content");
+    return guarded([&] {
+        std::vector<float> informationContent;
+        matrix->impl->geneInformation(geneSetName, cellSetName, normalizationMethod, &informationContent, nullptr);
+        if (!informationContent.empty()) {
+            if (!out) throw em2::host::Error{EM2_ERROR_INVALID_ARGUMENT, "em2_matrix_gene_information_content: null argument"};
+            std::memcpy(out, informationContent.data(), informationContent.size() * sizeof(float));
+        }
+    });
+}
+
+int em2_matrix_create_gene_set_using_information_content(em2_matrix* matrix, const char* existingGeneSetName, const char* cellSetName,
+                                                         int normalizationMethod, double geneInformationContentThreshold,
+                                                         const char* newGeneSetName)
+{
+    if (!matrix || !existingGeneSetName || !cellSetName || !newGeneSetName) {
+        return nullArgument("em2_matrix_create_gene_set_using_information_content");
+    }
+    return guarded([&] {
+        matrix->impl->createGeneSetUsingInformationContent(existingGeneSetName, cellSetName, normalizationMethod,
+                                                           geneInformationContentThreshold, newGeneSetName);
+    });
+}
+
+int em2_matrix_create_well_expressed_gene_set(em2_matrix* matrix, const char* inputGeneSetName, const char* inputCellSetName,
+                                              const char* outputGeneSetName, uint32_t minCellCount)
+{
+    if (!matrix || !inputGeneSetName || !inputCellSetName || !outputGeneSetName) return nullArgument("em2_matrix_create_well_expressed_gene_set");
+    return guarded([&] { matrix->impl->createWellExpressedGeneSet(inputGeneSetName, inputCellSetName, outputGeneSetName, minCellCount); });
+}
+
+int em2_matrix_remove_gene_set(em2_matrix* matrix, const char* geneSetName)
+{
+    if (!matrix || !geneSetName) return nullArgument("em2_matrix_remove_gene_set");
+    return guarded([&] { matrix->impl->removeGeneSet(geneSetName); });
+}
+
 int em2_similar_gene_pairs_write(const char* directoryName, const char* similarGenePairsName, const char* geneSetName,
                                  const char* cellSetName, size_t k, int normalizationMethod, uint32_t geneCount, const em2_pair* pairs,
                                  const uint32_t* usedCount)
@@ -336,6 +376,12 @@ int em2_tool_add_cell_set(const char* directoryName, const char* name, const uin
 {
     if (!directoryName || !name || (!sortedCellIds && count)) return nullArgument("em2_tool_add_cell_set");
     return guarded([&] { em2::host::addCellSet(directoryName, name, sortedCellIds, count); });
+}
+
+int em2_tool_add_cells(const char* directoryName, const double* norm1Inverse, const double* norm2Inverse, uint32_t cellCount)
+{
+    if (!directoryName || ((!norm1Inverse || !norm2Inverse) && cellCount)) return nullArgument("em2_tool_add_cells");
+    return guarded([&] { em2::host::addCells(directoryName, norm1Inverse, norm2Inverse, cellCount); });
 }
 
 }  // extern "C"

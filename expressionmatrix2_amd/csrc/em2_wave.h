@@ -40,6 +40,15 @@ __device__ __forceinline__ uint32_t waveInclusiveScan(uint32_t value)
     return value;
 }
 
+// The sum of `value` over the 64 lanes, in every lane, in one fixed order: lane l adds what lane l ^ 32 holds, then ^ 16,
+// ... ^ 1 (both lanes of a pair add the same two numbers, so all lanes end with the same bits).
+__device__ __forceinline__ double waveSum(double value)
+{
+#pragma unroll
+    for (int step = 32; step >= 1; step >>= 1) value += __shfl_xor(value, step, 64);
+    return value;
+}
+
 // The unused tail of a row's k result slots: the wave writes {0, 0.0f} into out[kept, k).
 __device__ __forceinline__ void clearRowTail(PairOut* out, uint32_t kept, uint32_t k, uint32_t lane)
 {

@@ -106,6 +106,58 @@ class ExpressionMatrix:
     def removeSimilarGenePairs(self, similarGenePairsName):
         capi.check(capi.load().em2_matrix_remove_similar_gene_pairs(self._handle, _b(similarGenePairsName)))
 
+    # ---- src/PythonModule.cpp:506-537 ----
+    def createGeneSetUsingInformationContent(self, existingGeneSetName="AllGenes", cellSetName="AllCells",
+                                             normalizationMethod=_REQUIRED, geneInformationContentThreshold=_REQUIRED,
+                                             newGeneSetName=_REQUIRED):
+        """ExpressionMatrix::createGeneSetUsingInformationContent (src/ExpressionMatrix.cpp:2022-2082): the genes of the
+        existing set whose information content over the cell set exceeds the threshold (bits), as a new gene set that the
+        next call can name."""
+        if _REQUIRED in (normalizationMethod, geneInformationContentThreshold, newGeneSetName):
+            raise TypeError("createGeneSetUsingInformationContent(): normalizationMethod, geneInformationContentThreshold and "
+                            "newGeneSetName are required")
+        method = NormalizationMethod(normalizationMethod)
+        capi.check(capi.load().em2_matrix_create_gene_set_using_information_content(
+            self._handle, _b(existingGeneSetName), _b(cellSetName), int(method), geneInformationContentThreshold,
+            _b(newGeneSetName)))
+
+    # ---- src/PythonModule.cpp:586-602 ----
+    def createWellExpressedGeneSet(self, inputGeneSetName="AllGenes", inputCellSetName="AllCells", outputGeneSetName=_REQUIRED,
+                                   minCellCount=_REQUIRED):
+        """ExpressionMatrix::createWellExpressedGeneSet (src/ExpressionMatrixGeneSets.cpp:314-362): the genes of the input set
+        with a stored entry in at least minCellCount cells of the cell set."""
+        if _REQUIRED in (outputGeneSetName, minCellCount):
+            raise TypeError("createWellExpressedGeneSet(): outputGeneSetName and minCellCount are required")
+        if not 0 <= int(minCellCount) <= 0xffffffff:             # CellId (src/Ids.hpp) is unsigned, 32 bits
+            raise ValueError("createWellExpressedGeneSet(): minCellCount must be in [0, 2**32)")
+        capi.check(capi.load().em2_matrix_create_well_expressed_gene_set(self._handle, _b(inputGeneSetName), _b(inputCellSetName),
+                                                                         _b(outputGeneSetName), int(minCellCount)))
+
+    def removeGeneSet(self, geneSetName):
+        """ExpressionMatrix::removeGeneSet (src/ExpressionMatrixGeneSets.cpp:12-32)."""
+        capi.check(capi.load().em2_matrix_remove_gene_set(self._handle, _b(geneSetName)))
+
+    def getGeneSetGenes(self, geneSetName):
+        """The global ids of the genes of a gene set, ascending (src/ExpressionMatrixGeneSets.cpp:57-63)."""
+        lib = capi.load()
+        count = ctypes.c_uint32(0)
+        capi.check(lib.em2_matrix_gene_set(self._handle, _b(geneSetName), ctypes.byref(count), None))
+        ids = np.zeros(count.value, dtype=np.uint32)
+        capi.check(lib.em2_matrix_gene_set(self._handle, _b(geneSetName), ctypes.byref(count), capi._ptr(ids)))
+        return ids.tolist()
+
+    def computeGeneInformationContent(self, geneSetName, cellSetName, normalizationMethod):
+        """ExpressionMatrix::computeGeneInformationContent (src/ExpressionMatrix.cpp:1947-2018) -> float32 array, one value
+        (bits) per gene of the gene set.  The reference keeps this method private and shows its values only in its HTTP page;
+        it is public here because createGeneSetUsingInformationContent is a threshold on exactly these floats."""
+        method = NormalizationMethod(normalizationMethod)
+        lib = capi.load()
+        count = ctypes.c_uint32(0)
+        capi.check(lib.em2_matrix_gene_set(self._handle, _b(geneSetName), ctypes.byref(count), None))
+        out = np.zeros(count.value, dtype=np.float32)
+        capi.check(lib.em2_matrix_gene_information_content(self._handle, _b(geneSetName), _b(cellSetName), int(method), capi._ptr(out)))
+        return out
+
     # ---- src/PythonModule.cpp:755-771 ----
     def computeCellSimilarity(self, geneSetName="AllGenes", cellId0=_REQUIRED, cellId1=_REQUIRED):
         """The exact similarity of two cells (global ids) over the genes of a gene set."""

@@ -119,3 +119,13 @@ def add_gene_set(directory, name, sorted_global_ids):
 def add_cell_set(directory, name, sorted_cell_ids):
     ids = np.ascontiguousarray(sorted_cell_ids, dtype=np.uint32)
     capi.check(capi.load().em2_tool_add_cell_set(_b(directory), _b(name), capi._ptr(ids), len(ids)))
+
+
+def add_cells(directory, norm1_inverse, norm2_inverse):
+    """A Cells file (MemoryMapped::Vector<Cell>, src/Cell.hpp: norm1Inverse at byte 24, norm2Inverse at byte 32 of every
+    56-byte record) with these inverses, one record per global cell."""
+    norm1 = np.ascontiguousarray(norm1_inverse, dtype=np.float64)
+    norm2 = np.ascontiguousarray(norm2_inverse, dtype=np.float64)
+    if len(norm1) != len(norm2):
+        raise ValueError("one norm1Inverse and one norm2Inverse per cell")
+    capi.check(capi.load().em2_tool_add_cells(_b(directory), capi._ptr(norm1), capi._ptr(norm2), len(norm1)))

@@ -162,6 +162,48 @@ int em2_find_similar_gene_pairs0(const uint64_t* toc, const em2_count* data, uin
                                  int normalizationMethod, uint32_t k, double similarityThreshold, em2_pair* pairs,
                                  uint32_t* usedCount, float* allSimilarities);
 
+/* ExpressionMatrix::computeGeneInformationContent (src/ExpressionMatrix.cpp:1947-2018) for every gene of a subset's CSR (as
+ * em2_find_similar_pairs0: local gene ids below geneCount, strictly ascending within a cell; else EM2_ERROR_INVALID_ARGUMENT),
+ * and the number of cells with a stored entry for the gene, stored zeros included (the counter of createWellExpressedGeneSet,
+ * src/ExpressionMatrixGeneSets.cpp:336-350).  It replaces the reference's binary search per (gene, cell)
+ * (getCellExpressionCount, :1035-1046) with one stable sort of the stored entries by gene and a segmented reduction.
+ * normInverse: NULL (NormalizationMethod none) or [cellCount], the cells' Cell::norm1Inverse (L1) or norm2Inverse (L2): those
+ * of the WHOLE cell over all genes (:1976), see em2_cell_norm_inverses.  c = count * float(normInverse) is a float product
+ * (:1981-1992).  Per gene: sum = the double sum of c over its stored entries, whatever their sign; I = log(double(cellCount))
+ * + the sum over c > 0 of p * log(p), p = double(c) * (1. / sum); I /= log(2.); informationContent = float(I) (:1997-2017).
+ * IEEE rules decide the odd cases (an inf count gives NaN); where float(normInverse) of a cell is inf or NaN the reference's
+ * product with the 0 of a gene the cell does not store is NaN, so every gene with a positive entry is NaN then.
+ * Pinned bit for bit: expressingCellCount, and informationContent of a gene without a positive entry (log(double(cellCount))
+ * and log(2.) are the host's, the gene gets float(logN / log2)); informationContent == float(informationContentDouble).  The
+ * last bits of the double of an expressed gene are not pinned (the reference's depend on its libm's log and on a sequential
+ * sum): they are held to an error bound, and they are a function of the input alone -- the same for every
+ * call, for the host and the device entry, whatever the grid.
+ * informationContentDouble and expressingCellCount may be NULL. */
+int em2_gene_information_content(const uint64_t* toc, const em2_count* data, uint32_t cellCount, uint32_t geneCount,
+                                 const double* normInverse, float* informationContent, double* informationContentDouble,
+                                 uint32_t* expressingCellCount);
+
+/* The most blocks (of four waves) the wave-per-cell and wave-per-chunk kernels of the call are launched with; 0 restores the
+ * default.  Process-wide and meant for this project's tests alone (the result does not depend on it, which is what they show
+ * with it): unsupported elsewhere, and a call that runs while another thread changes it may size its launches by either value. */
+void em2_set_gene_information_max_blocks(uint32_t blocks);
+
+/* The same on device pointers and a stream: d_toc[cellCount + 1] non-decreasing from 0 to entryCount (else
+ * EM2_ERROR_INVALID_ARGUMENT, and nothing is written outside the workspace), d_data[entryCount].  d_workspace: at
+ * least em2_dev_gene_information_content_workspace bytes.  Synchronises the stream. */
+size_t em2_dev_gene_information_content_workspace(uint32_t cellCount, uint32_t geneCount, uint64_t entryCount);
+int em2_dev_gene_information_content(const uint64_t* d_toc, const em2_count* d_data, uint32_t cellCount, uint32_t geneCount,
+                                     uint64_t entryCount, const double* d_normInverse, float* d_informationContent,
+                                     double* d_informationContentDouble, uint32_t* d_expressingCellCount, void* d_workspace,
+                                     size_t workspaceBytes, void* stream);
+
+/* Cell::norm1Inverse and norm2Inverse as ExpressionMatrix::addCell defines them (src/ExpressionMatrix.cpp:241-263) for the
+ * cells of a CSR: sum1 += value, sum2 += value * value (a float product), both sums double, in stored order;
+ * 1. / sum1 and 1. / sqrt(sum2).  (The reference sums in the order of ingest, before it sorts the row by gene id.)  Host
+ * code; the gene ids are checked as above. */
+int em2_cell_norm_inverses(const uint64_t* toc, const em2_count* data, uint32_t cellCount, uint32_t geneCount, double* norm1Inverse,
+                           double* norm2Inverse);
+
 /* ExpressionMatrixSubset + Lsh + findSimilarPairs4 in one call on host buffers (SURVEY.md 8(a) row a1 on the device:
  * src/ExpressionMatrixSubset.cpp:9-42 followed by src/Lsh.cpp:118-224 and src/ExpressionMatrixLsh.cpp:200-285): the
  * global CSR (CellExpressionCounts toc/data, global gene ids) restricted to the cells cellIds[0..cellCount) (NULL =
@@ -648,6 +690,32 @@ int em2_matrix_find_similar_gene_pairs0(em2_matrix* matrix, const char* geneSetN
 /* ExpressionMatrix::removeSimilarGenePairs (src/ExpressionMatrixFindSimilarGenePairs.cpp:223-232). */
 int em2_matrix_remove_similar_gene_pairs(em2_matrix* matrix, const char* similarGenePairsName);
 
+/* ExpressionMatrix::computeGeneInformationContent (src/ExpressionMatrix.cpp:1947-1964; private in the reference, shown in
+ * its HTTP page only) for the genes of a gene set over the cells of a cell set: out[size of the gene set].  The cells' norm
+ * inverses come from the Cells file of the data directory (MemoryMapped::Vector<Cell>, src/Cell.hpp: seven doubles,
+ * norm1Inverse at byte 24, norm2Inverse at byte 32, one record per global cell) where there is one, and are computed from the
+ * cells' whole rows otherwise.  Errors: "Gene set X does not exist.", "Cell set X does not exist.". */
+int em2_matrix_gene_information_content(em2_matrix* matrix, const char* geneSetName, const char* cellSetName, int normalizationMethod,
+                                        float* out);
+
+/* ExpressionMatrix::createGeneSetUsingInformationContent (src/ExpressionMatrix.cpp:2022-2082; bound at
+ * src/PythonModule.cpp:506-537): the genes of the existing set with double(information content) > threshold, in ascending
+ * local id, as GeneSet-<newGeneSetName>-{GlobalIds,LocalIds}; usable by name at once.  Errors in the reference's order:
+ * "Gene set X does not exist.", "Cell set X does not exist.", "Gene set X already exists.". */
+int em2_matrix_create_gene_set_using_information_content(em2_matrix* matrix, const char* existingGeneSetName, const char* cellSetName,
+                                                         int normalizationMethod, double geneInformationContentThreshold,
+                                                         const char* newGeneSetName);
+
+/* ExpressionMatrix::createWellExpressedGeneSet (src/ExpressionMatrixGeneSets.cpp:314-362; bound at
+ * src/PythonModule.cpp:586-602): the genes of the input set with a stored entry in at least minCellCount cells of the cell
+ * set.  "Gene set X already exists." is checked before the inputs are looked up (:322-329). */
+int em2_matrix_create_well_expressed_gene_set(em2_matrix* matrix, const char* inputGeneSetName, const char* inputCellSetName,
+                                              const char* outputGeneSetName, uint32_t minCellCount);
+
+/* ExpressionMatrix::removeGeneSet (src/ExpressionMatrixGeneSets.cpp:12-32): "Gene set AllGenes cannot be removed.",
+ * "Gene set X does not exist."; removes the two files. */
+int em2_matrix_remove_gene_set(em2_matrix* matrix, const char* geneSetName);
+
 /* ExpressionMatrixSubset (src/ExpressionMatrixSubset.cpp:9-42) as plain arrays, for drivers that shard the work
  * themselves: first call with toc == NULL to get the sizes, then with toc[cellCount+1] and data[nnz]. */
 int em2_matrix_subset(em2_matrix* matrix, const char* geneSetName, const char* cellSetName, uint32_t* geneCount,
@@ -699,6 +767,10 @@ int em2_tool_add_gene_set(const char* directoryName, const char* name, const uin
                           uint32_t count);
 int em2_tool_add_cell_set(const char* directoryName, const char* name, const uint32_t* sortedCellIds,
                           uint32_t count);
+
+/* Writes a Cells file (MemoryMapped::Vector<Cell>, src/Cell.hpp) whose records hold these norm1Inverse / norm2Inverse and
+ * zeros elsewhere: one record per global cell. */
+int em2_tool_add_cells(const char* directoryName, const double* norm1Inverse, const double* norm2Inverse, uint32_t cellCount);
 
 #ifdef __cplusplus
 }
