@@ -101,11 +101,14 @@ struct AnalysisState {
 
     static double binWidth() { return 2. / double(binCount); }
 
-    // False where the reference's CZI_ASSERT(bin < binCount) throws (:1322, :111).
+    // False where the reference's CZI_ASSERT(bin < binCount) throws (:1322, :111).  The reference converts the floor to size_t
+    // first, which is undefined for NaN, +-inf (a cell without variance) and negative values: here the assert fires for every
+    // value that is not one of the bins, whatever a compiler makes of that conversion.
     bool add(double exactSimilarity, double delta)
     {
-        const size_t bin = size_t(std::floor((exactSimilarity + 1.) / binWidth()));
-        if (!(bin < binCount)) return false;
+        const double binAsDouble = std::floor((exactSimilarity + 1.) / binWidth());
+        if (!(binAsDouble >= 0. && binAsDouble < double(binCount))) return false;
+        const size_t bin = size_t(binAsDouble);
         ++sum0[bin];
         sum1[bin] += delta;
         sum2[bin] += delta * delta;

@@ -931,8 +931,11 @@ int64_t em2o_analyze_lsh(const uint64_t* toc, const uint32_t* genes, const float
             const double lshSimilarity = table[countMismatches(signatures + localCellId0 * W, signatures + localCellId1 * W, W)];
 
             const double delta = lshSimilarity - exactSimilarity;                        // :1320
-            const size_t bin = size_t(std::floor((exactSimilarity + 1.) / binWidth));
-            if (!(bin < binCount)) return -1;                                            // :1322
+            // size_t(x) is undefined for a NaN, infinite or negative x (a cell without variance gives NaN or +-inf): what
+            // a compiler makes of it must not decide, the assert fires for every value that is not one of the 200 bins
+            const double binAsDouble = std::floor((exactSimilarity + 1.) / binWidth);
+            if (!(binAsDouble >= 0. && binAsDouble < double(binCount))) return -1;       // :1322
+            const size_t bin = size_t(binAsDouble);
             ++(sum0[bin]);
             sum1[bin] += delta;
             sum2[bin] += delta * delta;

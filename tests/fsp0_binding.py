@@ -34,6 +34,9 @@ class Fsp0Restatement:
         lib.em2r_count_similar_pairs_of_rows.restype = c.c_uint64
         lib.em2r_find_similar_pairs0.argtypes = [P, P, c.c_uint32, c.c_uint32, c.c_uint32, c.c_double, P, P, P, P, P]
         lib.em2r_find_similar_pairs0.restype = c.c_int
+        lib.em2r_find_similar_pairs0_rows.argtypes = [P, P, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, c.c_uint32, c.c_double,
+                                                      P, P, P, P, P]
+        lib.em2r_find_similar_pairs0_rows.restype = c.c_int
         lib.em2r_analyze_similar_pairs.argtypes = [P, P, c.c_uint32, c.c_uint32, P, P, P, c.c_uint32, P, c.c_double,
                                                    c.c_char_p, c.c_char_p]
         lib.em2r_analyze_similar_pairs.restype = c.c_int
@@ -58,17 +61,24 @@ class Fsp0Restatement:
         toc, data = self._csr(toc, data)
         return int(self.lib.em2r_count_similar_pairs_of_rows(_ptr(toc), _ptr(data), len(toc) - 1, gene_count, row_begin, row_end, thr))
 
-    def find_similar_pairs0(self, toc, data, gene_count, k, thr):
-        """-> (cell [n, k], similarity [n, k] float32, usedCount, lowestSimilarityIndex, lowestSimilarity); unused slots zero."""
+    def find_similar_pairs0(self, toc, data, gene_count, k, thr, rows=None):
+        """-> (cell [n, k], similarity [n, k] float32, usedCount, lowestSimilarityIndex, lowestSimilarity); unused slots zero.
+        rows = (begin, end): those rows only, each from its own candidates in ascending id (the arrays then have end - begin
+        rows); the cost is that of the rows, not of all pairs."""
         toc, data = self._csr(toc, data)
-        n = len(toc) - 1
+        cells = len(toc) - 1
+        n = cells if rows is None else rows[1] - rows[0]
         cell = np.zeros((n, k), dtype=np.uint32)
         sim = np.zeros((n, k), dtype=np.float32)
         used = np.zeros(n, dtype=np.uint32)
         low_index = np.zeros(n, dtype=np.uint32)
         low = np.zeros(n, dtype=np.float32)
-        rc = self.lib.em2r_find_similar_pairs0(_ptr(toc), _ptr(data), n, gene_count, k, thr, _ptr(cell), _ptr(sim), _ptr(used),
-                                               _ptr(low_index), _ptr(low))
+        if rows is None:
+            rc = self.lib.em2r_find_similar_pairs0(_ptr(toc), _ptr(data), cells, gene_count, k, thr, _ptr(cell), _ptr(sim), _ptr(used),
+                                                   _ptr(low_index), _ptr(low))
+        else:
+            rc = self.lib.em2r_find_similar_pairs0_rows(_ptr(toc), _ptr(data), cells, gene_count, rows[0], rows[1], k, thr, _ptr(cell),
+                                                        _ptr(sim), _ptr(used), _ptr(low_index), _ptr(low))
         if rc != 0:
             raise ValueError("the fsp0 restatement rejected the arguments (%d)" % rc)
         return cell, sim, used, low_index, low

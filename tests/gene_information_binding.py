@@ -191,8 +191,8 @@ def case(name):
     return out
 
 
-SHAPE_CASES = ["random-1000x1", "random-2x2", "random-1x255", "random-1000x256", "random-1000x257", "genes-65537", "segments",
-               "everywhere"]
+SHAPE_CASES = ["random-1000x1", "random-2x2", "random-1x255", "random-1000x256", "random-1000x257", "random-300x600", "genes-65537",
+               "segments", "everywhere"]
 ALL_CASES = SHAPE_CASES + ["odd", "empty-cell"]
 
 

@@ -186,6 +186,41 @@ int em2r_find_similar_pairs0(const uint64_t* toc, const void* data, uint32_t cel
     return 0;
 }
 
+// The same for the rows [rowBegin, rowEnd) only: cell / similarity [rowEnd - rowBegin][k] and the three per-row arrays
+// are indexed by row - rowBegin.  In the loop above cell c is offered (c1, s) for c1 < c while c is the inner index and
+// then for c1 > c while it is the outer one, i.e. its candidates in ascending id of the other cell, and add() touches
+// the state of that one cell only: the cells are independent, so a row's list is what its candidates in that order
+// leave.  cellSimilarity is called with the smaller id first, as above.  Returns 1 for similarityThreshold > 1, 2 for a
+// range that is not within the cells.
+int em2r_find_similar_pairs0_rows(const uint64_t* toc, const void* data, uint32_t cellCount, uint32_t geneCount, uint32_t rowBegin,
+                                  uint32_t rowEnd, uint32_t k, double similarityThreshold, uint32_t* cell, float* similarity,
+                                  uint32_t* usedCount, uint32_t* lowestSimilarityIndex, float* lowestSimilarity)
+{
+    if (!(similarityThreshold <= 1.)) return 1;
+    if (rowBegin > rowEnd || rowEnd > cellCount) return 2;
+    const Count* counts = static_cast<const Count*>(data);
+    const std::vector<Sums> sums = computeSums(toc, counts, cellCount);
+    for (uint32_t row = rowBegin; row < rowEnd; row++) {
+        std::vector<Pair> slots;
+        CellInfo info;
+        for (uint32_t other = 0; other < cellCount; other++) {
+            if (other == row) continue;
+            const double s = cellSimilarity(toc, counts, geneCount, sums, std::min(row, other), std::max(row, other));
+            if (s > similarityThreshold) add(slots, info, k, Pair(other, float(s)));
+        }
+        std::sort(slots.begin(), slots.end(), bySimilarityThenId);
+        const size_t at = size_t(row - rowBegin);
+        for (size_t i = 0; i < slots.size(); i++) {
+            cell[at * k + i] = slots[i].first;
+            similarity[at * k + i] = slots[i].second;
+        }
+        usedCount[at] = info.usedCount;
+        lowestSimilarityIndex[at] = info.lowestSimilarityIndex;
+        lowestSimilarity[at] = info.lowestSimilarity;
+    }
+    return 0;
+}
+
 // analyzeSimilarPairs after its lookups (src/ExpressionMatrixLsh.cpp:71-148).  Returns 1 where CZI_ASSERT(bin < binCount)
 // fires (:111), 2 where a file cannot be opened.
 int em2r_analyze_similar_pairs(const uint64_t* toc, const void* data, uint32_t cellCount, uint32_t geneCount, const uint32_t* cell,
@@ -209,8 +244,11 @@ int em2r_analyze_similar_pairs(const uint64_t* toc, const void* data, uint32_t c
             const float& storedSimilarity = similarity[size_t(cell0) * k + i];
             const double exactSimilarity = cellSimilarity(toc, counts, geneCount, sums, cell0, cell1);
             const double delta = storedSimilarity - exactSimilarity;                           // :109
-            const size_t bin = size_t(std::floor((exactSimilarity + 1.) / binWidth));          // :110
-            if (!(bin < binCount)) return 1;                                                   // :111
+            // :110-111; size_t(x) is undefined for a NaN, infinite or negative x (a cell without variance gives NaN or
+            // +-inf): the assert fires for every value that is not one of the 200 bins, whatever a compiler makes of it
+            const double binAsDouble = std::floor((exactSimilarity + 1.) / binWidth);
+            if (!(binAsDouble >= 0. && binAsDouble < double(binCount))) return 1;
+            const size_t bin = size_t(binAsDouble);
             ++sum0[bin];
             sum1[bin] += delta;
             sum2[bin] += delta * delta;

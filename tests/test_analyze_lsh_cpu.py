@@ -8,6 +8,7 @@ import math
 import os
 
 import numpy as np
+import pytest
 
 import synth
 
@@ -88,3 +89,21 @@ def test_oracle_analyze_lsh_assertion_cases(oracle, tmp_path):
     sig = signatures(oracle, toc2, g2, c2, genes, L)
     ids = np.arange(n, dtype=np.uint32)
     assert oracle.analyze_lsh(toc2, g2, c2, genes, sig, L, ids, 1, 1.0, str(tmp_path / "a.csv"), str(tmp_path / "b.csv")) is None
+
+
+def test_oracle_analyze_lsh_asserts_for_an_infinite_similarity(oracle, tmp_path):
+    """A cell with the same count in every gene has a denominator of 0; where the numerator rounds away from 0 the similarity is
+    +inf or -inf, not NaN.  size_t(floor(+inf)) is undefined (GCC on x86-64 gives 0, a valid bin), so the oracle decides on the
+    double: every value that is none of the 200 bins is the assert."""
+    import expression_cases as ec
+    import fsp0_binding
+    case = ec.INFINITE_SIMILARITY_CASE
+    toc, data = ec.matrix(case)
+    exact = fsp0_binding.load().pair_similarities(toc, data, 1025)
+    assert np.isposinf(exact).any() and not np.isnan(exact).any()
+    with pytest.raises(ec.Discarded, match="bin < binCount"):
+        ec.AnalyzeLsh.expect(case, oracle)
+    pairs = np.array([[1], [2], [1]], dtype=np.uint32)
+    rc = fsp0_binding.load().analyze_similar_pairs(toc, data, 1025, pairs, np.full((3, 1), 0.25, dtype=np.float32), np.ones(3, dtype=np.uint32),
+                                                   np.arange(3, dtype=np.uint32), 1.0, str(tmp_path / "r.csv"), str(tmp_path / "rs.csv"))
+    assert rc == 1

@@ -105,6 +105,41 @@ def test_selection_equals_a_python_slot_machine_on_clustered_input(restatement):
         assert same_result(restatement.find_similar_pairs0(toc, data, 500, k, thr), python_slot_machine(exact, 150, k, thr))
 
 
+def ranged_equals_slice(restatement, toc, data, genes, k, thr, ranges):
+    full = restatement.find_similar_pairs0(toc, data, genes, k, thr)
+    for begin, end in ranges:
+        ranged = restatement.find_similar_pairs0(toc, data, genes, k, thr, rows=(begin, end))
+        assert all(len(a) == end - begin for a in ranged)
+        assert same_result(ranged, tuple(a[begin:end] for a in full)), (k, thr, begin, end)
+    return full
+
+
+@pytest.mark.parametrize("k,thr", [(3, -1.0), (4, 0.0), (5, 0.05), (1, 0.3), (200, 0.2), (0, 0.2)])
+def test_ranged_restatement_equals_the_slice_of_a_full_run_on_tied_input(restatement, k, thr):
+    """The row range of the restatement (every row from its own candidates in ascending id of the other cell) against the
+    reference's loop over the unordered pairs, where ties make the order of the offers decide: the whole range, single rows
+    at both ends, an empty range and ranges inside."""
+    toc, data, genes = fsp0_binding.duplicated_cells_input()
+    n = len(toc) - 1
+    ranged_equals_slice(restatement, toc, data, genes, k, thr, [(0, n), (0, 1), (n - 1, n), (40, 40), (17, 93), (n - 8, n)])
+
+
+def test_ranged_restatement_equals_the_slice_of_a_full_run_with_evictions(restatement):
+    """Clustered non-integer input whose rows fill and then evict (k = 7 of 299 candidates at threshold -1), and an input
+    with an empty cell (NaN similarities, never stored) and a cell without variance."""
+    toc, data = fsp0_binding.clustered(300, 400, 0.06, seed=15, cluster_count=5, non_integer=True)
+    full = ranged_equals_slice(restatement, toc, data, 400, 7, -1.0, [(0, 300), (0, 8), (292, 300), (100, 101)])
+    assert (full[2] == 7).all()
+    toc2, data2 = fsp0_binding.repeat_cells(toc, data, [1] * 20)
+    flat = fsp0_binding.counts_of(np.arange(400, dtype=np.uint32), np.full(400, 1.5, dtype=np.float32))
+    toc2 = np.concatenate([toc2, toc2[-1:], toc2[-1:] + np.uint64(400)])         # cell 20 empty, cell 21 constant
+    data2 = np.concatenate([data2, flat])
+    full = ranged_equals_slice(restatement, toc2, data2, 400, 5, 0.0, [(0, 22), (19, 22), (20, 21)])
+    assert full[2][20] == 0                                   # (the constant cell's similarities are NaN or +-inf, as IEEE has it)
+    with pytest.raises(ValueError):
+        restatement.find_similar_pairs0(toc2, data2, 400, 5, 0.0, rows=(3, 23))
+
+
 def test_tie_input_is_not_a_plain_top_k(restatement):
     """On the duplicated-cells input the slot machine's result is NOT 'the k best by (similarity desc, id asc)': which of
     several tied entries is evicted depends on the slots' history.  Otherwise the GPU tie cases would prove nothing."""

@@ -7,6 +7,8 @@ import os
 import numpy as np
 import pytest
 
+import expression_cases as ec
+import fsp0_binding
 import synth
 from expressionmatrix2_amd import ExpressionMatrix, capi, files
 
@@ -120,6 +122,21 @@ def test_analyze_lsh_assertion_and_argument_errors(oracle, tmp_path):
         capi.analyze_lsh(toc, capi.make_counts(g, c), 5, sig, 64, ids, 1, 1.0, str(tmp_path / "p.csv"))
     with pytest.raises(RuntimeError, match="cannot open"):
         capi.analyze_lsh(toc[:3], capi.make_counts(g[:6], c[:6]), 10, sig[:2], 64, ids[:2], 1, 1.0, str(tmp_path / "no" / "p.csv"))
+
+
+def test_analyze_lsh_infinite_similarity_trips_the_bin_assert(oracle, tmp_path):
+    """Found by the sweep over tests/expression_cases.py (analyze_lsh, seed 122).  A cell with the same count in every gene has
+    no variance: the denominator is 0, and where the numerator rounds away from 0 the similarity is +inf, not NaN.  The
+    reference converts floor((s + 1) / binWidth) to size_t before CZI_ASSERT(bin < binCount), which is undefined for +inf: the
+    device entry answered "bin < binCount", while the oracle, compiled by GCC, got bin 0 out of that conversion and went on to
+    write inf into the csv.  The oracle, the analyzeSimilarPairs restatement and the library's host code now decide on the
+    double, before any conversion: a value that is none of the 200 bins trips the assert."""
+    case = ec.INFINITE_SIMILARITY_CASE
+    toc, data = ec.matrix(case)
+    exact = fsp0_binding.load().pair_similarities(toc, data, case["genes"])
+    assert np.isposinf(exact).any() and not np.isnan(exact).any()
+    with pytest.raises(ec.Discarded, match="bin < binCount"):
+        ec.AnalyzeLsh.check(case, oracle)                         # (the device entry raises the reference's text, the oracle returns None)
 
 
 def test_analyze_lsh_through_expression_matrix_api(oracle, tmp_path, monkeypatch):

@@ -4,6 +4,7 @@ files byte for byte, the bins' sums bit for bit."""
 import numpy as np
 import pytest
 
+import expression_cases as ec
 import fsp0_binding
 from expressionmatrix2_amd import ExpressionMatrix, capi, files
 
@@ -74,6 +75,22 @@ def test_bin_assert_is_reported(restatement, tmp_path):
         capi.analyze_similar_pairs(toc, data, 40, pairs, used, ids, 1.0, str(tmp_path / "d.csv"), str(tmp_path / "ds.csv"))
 
 
+def test_infinite_similarity_trips_the_bin_assert(restatement, tmp_path):
+    """The input of tests/test_gpu_analyze_lsh.py::test_analyze_lsh_infinite_similarity_trips_the_bin_assert: cell 0 has no
+    variance and its exact similarity to cell 1 is +inf.  Converting that to size_t is undefined; the assert must fire on both
+    sides whatever the compiler makes of it."""
+    toc, data = ec.matrix(ec.INFINITE_SIMILARITY_CASE)
+    assert np.isposinf(restatement.cell_similarity(toc, data, 1025, 0, 1))
+    pairs = np.zeros((3, 1), dtype=capi.PAIR_DTYPE)
+    pairs["cell"][:, 0], pairs["similarity"][:, 0] = [1, 2, 1], 0.25
+    used = np.array([1, 1, 1], dtype=np.uint32)
+    ids = np.arange(3, dtype=np.uint32)
+    assert restatement.analyze_similar_pairs(toc, data, 1025, pairs["cell"], pairs["similarity"], used, ids, 1.0,
+                                             str(tmp_path / "r.csv"), str(tmp_path / "rs.csv")) == 1
+    with pytest.raises(RuntimeError, match="bin < binCount"):
+        capi.analyze_similar_pairs(toc, data, 1025, pairs, used, ids, 1.0, str(tmp_path / "d.csv"), str(tmp_path / "ds.csv"))
+
+
 def test_global_memory_form(restatement, tmp_path):
     """More genes than LDS holds and more rows than the global-memory form has blocks (fsp0_binding.wide_matrix).  The stored
     object is a synthetic one as below: k = 8, usedCount varying, one cell that stores nothing."""
@@ -94,6 +111,28 @@ def test_global_memory_form(restatement, tmp_path):
         assert open(tmp_path / ("d-%s.csv" % name), "rb").read() == open(tmp_path / ("r-%s.csv" % name), "rb").read()
     assert len(open(tmp_path / "r-pairs.csv").read().splitlines()) > 1000
     assert len(open(tmp_path / "r-stats.csv").read().splitlines()) > 2
+
+
+@pytest.mark.parametrize("beyond", [0, 1])
+def test_at_the_lds_limit(restatement, tmp_path, beyond):
+    """storedPairsKernel has no LDS of its own, but its launch takes the cut-over of fsp0 with one slot: the largest gene count
+    that rule leaves in LDS, and one gene more (the global-memory form); every cell's last entry is on one of the three highest
+    genes.  The stored object is a synthetic one (expression_cases.stored_object): k = 65, a quarter of the cells full."""
+    cells, k = 130, 65
+    genes = ec.largest_gene_count_in_lds(ec.fsp0_own_lds_bytes(1)) + beyond
+    assert ec.stored_pairs_in_lds(genes) == (beyond == 0) and ec.row_vector_bytes(genes) <= 160 * 1024
+    toc, data = ec.lds_limit_input(cells, genes, non_integer=False)
+    pairs, used = ec.stored_object({"cells": cells, "k": k, "pairs_seed": 5})
+    assert (used == k).sum() > 10 and (pairs["cell"] != np.arange(cells)[:, None]).all()
+    ids = (np.arange(cells, dtype=np.uint32) * 3 + 5).astype(np.uint32)
+    rc = restatement.analyze_similar_pairs(toc, data, genes, pairs["cell"], pairs["similarity"], used, ids, 0.5,
+                                           str(tmp_path / "r-pairs.csv"), str(tmp_path / "r-stats.csv"))
+    if rc == 1:
+        pytest.fail("the synthetic input holds a pair with exact similarity 1: choose another seed")
+    capi.analyze_similar_pairs(toc, data, genes, pairs, used, ids, 0.5, str(tmp_path / "d-pairs.csv"), str(tmp_path / "d-stats.csv"))
+    for name in ("pairs", "stats"):
+        assert open(tmp_path / ("d-%s.csv" % name), "rb").read() == open(tmp_path / ("r-%s.csv" % name), "rb").read()
+    assert len(open(tmp_path / "r-pairs.csv").read().splitlines()) > 1000
 
 
 def test_more_stored_pairs_than_one_chunk(restatement, tmp_path):

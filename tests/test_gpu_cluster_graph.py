@@ -81,6 +81,84 @@ def test_averages_of_arbitrary_lists(restatement):
         assert not np.isnan(similarity).any()
 
 
+@pytest.mark.parametrize("density", [0.15, 0.4])
+@pytest.mark.parametrize("genes", [1023, 1024, 1025, 2049])
+def test_gene_counts_around_the_chunk_of_1024(restatement, genes, density):
+    """clusterNormalizeKernel, clusterVertexSumsKernel and clusterEdgeKernel add a vector's products in chunks of 1024 doubles:
+    one gene less than a chunk, exactly one, one gene into the second, one gene into the third.  Counts non-integer and spread
+    over 48 binary orders; lists as in test_averages_of_arbitrary_lists.  The generator draws most of a cell's genes from a small
+    pool, so density 0.15 does not store the 150 entries per cell it aims at but a median of 64 (128 at 2049 genes): the second
+    stride of clusterGatherKernel's 64 lanes in half the cells.  Density 0.4 stores a median of 130 (270): the third stride and
+    more in most cells.  (With these averages a few genes dominate every sum; what shows the ORDER inside a later chunk is
+    test_edge_sums_in_later_chunks.)"""
+    toc, data = fsp0_binding.clustered(300, genes, density, seed=31, cluster_count=4, non_integer=True)
+    data = cgb.wide_range(data)
+    lengths = np.diff(toc.astype(np.int64))
+    assert np.median(lengths) >= 64 and lengths.max() > 64 and (density < 0.4 or np.median(lengths) > 128)
+    assert genes < 2049 or (np.median(lengths) >= 128 and lengths.max() > 128)
+    cells = np.concatenate([cgb.interleave(np.zeros(300), seed=2)[:170], [5], [9, 9, 250, 3], np.arange(299, 100, -1)]).astype(np.uint32)
+    offsets = np.array([0, 170, 171, 175, len(cells)], dtype=np.uint64)
+    got = capi.cluster_average_expression(toc, data, genes, cells, offsets)
+    assert np.array_equal(cgb.bits(got), cgb.bits(restatement.average_expression(toc, data, genes, cells, offsets)))
+    e0, e1 = np.array([0, 0, 3, 2, 1], dtype=np.uint32), np.array([1, 3, 2, 0, 3], dtype=np.uint32)
+    similarity = capi.cluster_similarities(got, e0, e1)
+    assert np.array_equal(cgb.bits(similarity), cgb.bits(restatement.similarities(got, e0, e1)))
+    assert not np.isnan(similarity).any()
+
+
+@pytest.mark.parametrize("genes", [1025, 1027, 1040, 2049])
+def test_edge_sums_in_later_chunks(restatement, genes):
+    """The order of clusterEdgeKernel's additions inside the chunks behind the first: 24 vectors of signed values over 16 binary
+    orders (no gene dominates, the sums cancel, so one rounding of sxy shows in the quotient) and all 276 pairs of them through
+    capi.cluster_similarities.  Adding the products of the later chunks in descending order changes 13 of the 276 similarities at
+    1027 genes (a second chunk of three products), 48 at 1040, 253 at 2049, counted with the sums written out in Python; at 1025
+    genes the second chunk holds one product and only its place can show, not its order."""
+    rng = np.random.default_rng(71 + genes)
+    table = rng.standard_normal((24, genes)) * np.exp2(rng.integers(-8, 8, (24, genes)).astype(np.float64))
+    e0 = np.array([i for i in range(24) for j in range(i + 1, 24)], dtype=np.uint32)
+    e1 = np.array([j for i in range(24) for j in range(i + 1, 24)], dtype=np.uint32)
+    expected = restatement.similarities(table, e0, e1)
+    assert not np.isnan(expected).any() and len(set(cgb.bits(expected).tolist())) == 276
+    assert np.array_equal(cgb.bits(capi.cluster_similarities(table, e0, e1)), cgb.bits(expected))
+
+
+def test_create_at_1025_genes(restatement):
+    """One full createClusterGraph whose vectors reach into the second chunk: five planted clusters, two of them split over labels,
+    non-integer counts spread over 48 binary orders, through all three entry points."""
+    spec = [(120, 0, 0.), (100, 0, 0.25), (80, 0, 0.35), (60, 3, 0.), (40, 3, 0.3)]
+    toc, data, owner = cgb.planted(spec, 1025, 0.15, seed=51, non_integer=True, noise=0.2)
+    data = cgb.wide_range(data)
+    assert np.diff(toc.astype(np.int64)).max() > 128
+    piece = (synth.hash_u64(53, np.arange(len(owner), dtype=np.uint64)) % np.uint64(5)).astype(np.uint32)
+    labels = (owner * 5 + np.where(piece < 3, 0, piece)).astype(np.uint32)
+    toc, data, labels = cgb.shuffled(toc, data, labels, seed=54)
+    ids = sorted(set(labels.tolist()))
+    v0, v1 = cgb.edges_between(labels, [(a, b) for i, a in enumerate(ids) for b in ids[i + 1:] if (a + b) % 3])
+    case = cgb.Case(toc, data, 1025, labels, v0, v1, min_cluster_size=30, k=3, similarity_threshold=-1.)
+    got, expected = check_entry_points(restatement, case)
+    assert len(expected["clusterIds"]) >= 2 and len(expected["edgeSimilarity"]) > 0
+
+
+def test_more_edges_than_blocks(restatement):
+    """clusterEdgeKernel strides the edges over at most 2^20 blocks: 2^20 + 5 edges over 3 clusters x 8 genes, so five blocks take
+    a second edge -- between another pair of clusters than their first."""
+    rng = np.random.default_rng(61)
+    averages = rng.gamma(2.0, 1.5, (3, 8)) * np.exp2(rng.integers(-20, 20, (3, 8)).astype(np.float64))
+    edges = (1 << 20) + 5
+    at = np.arange(edges, dtype=np.uint64)
+    e0 = (synth.hash_u64(62, at) % np.uint64(3)).astype(np.uint32)
+    e1 = ((e0 + 1 + synth.hash_u64(63, at) % np.uint64(2)) % 3).astype(np.uint32)
+    for e in range(1 << 20, edges):                              # the strided edges join another pair than the block's first edge
+        first = e - (1 << 20)
+        e0[e] = (e0[first] + 1) % 3
+        e1[e] = (e0[e] + 1 + (e1[first] == (e0[e] + 1) % 3)) % 3
+        assert {int(e0[e]), int(e1[e])} != {int(e0[first]), int(e1[first])} and e0[e] != e1[e]
+    expected = restatement.similarities(averages, e0, e1)
+    assert len(set(cgb.bits(expected).tolist())) == 3 and not np.isnan(expected).any()
+    got = capi.cluster_similarities(averages, e0, e1)
+    assert np.array_equal(cgb.bits(got), cgb.bits(expected))
+
+
 def test_a_few_thousand_cells_many_labels(restatement):
     """3000 planted cells under 24 labels of very different size (three fifths of a cluster, and two slivers of it), integer and not."""
     for non_integer in (False, True):

@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import expression_cases as ec
 import fsp0_binding
 import synth
 from expressionmatrix2_amd import ExpressionMatrix, capi, files
@@ -106,6 +107,93 @@ def test_fsp0_row_range_of_the_device_entry(restatement):
         device = (out_pairs.cpu().numpy().view(capi.PAIR_DTYPE).reshape(rows, k), out_used.cpu().numpy().view(np.uint32),
                   out_index.cpu().numpy().view(np.uint32), out_low.cpu().numpy().view(np.float32))
         assert_equal(device, (cell[begin:end], sim[begin:end], used[begin:end], low_index[begin:end], low[begin:end]), (begin, end))
+
+
+@pytest.mark.parametrize("cells,genes,density,k,thr,threads", [
+    (1100, 12000, 0.004, 6, 0.0, 512),
+    (2100, 30000, 0.002, 5, 0.0, 1024),
+    (2100, 30000, 0.002, 300, -1.0, 1024),
+])
+def test_fsp0_second_and_third_batch_of_the_wider_blocks(restatement, cells, genes, density, k, thr, threads):
+    """The 512- and the 1024-thread form with more cells than twice the threads: three column batches per row, the last one
+    ragged, every row full after the first batch, so that the later batches replace (and, with k = 300, rescan 300 slots)."""
+    form = ec.fsp0_form(cells, genes, k)
+    assert form["in_lds"] and form["threads"] == threads and form["batches"] == 3
+    toc, data = fsp0_binding.clustered(cells, genes, density, seed=cells + k, cluster_count=6, non_integer=True)
+    expected = restatement.find_similar_pairs0(toc, data, genes, k, thr)
+    assert (expected[2] == k).all()
+    assert_equal(capi.find_similar_pairs0(toc, data, genes, k, thr), expected)
+
+
+def slots_input(cells):
+    """`cells` cells over 20 genes with about six non-integer counts each: thousands of candidates per cell at threshold -1 for next
+    to no arithmetic."""
+    toc, data = fsp0_binding.clustered(cells, 20, 0.3, seed=cells, cluster_count=6, non_integer=True)
+    return toc, data, 20
+
+
+@pytest.mark.parametrize("cells", [2060, 2300])
+def test_fsp0_4096_slots_with_evictions(restatement, cells):
+    """k = 2049, threshold -1: slotCapacity is 4096, every row takes all its candidates, those behind the 2049th against full
+    slots, so the rescan after a replacement walks 2049 slots (33 per lane) and the bitonic sort runs over 4096 entries of which
+    2047 are padding.  With 2060 cells a row sees 10 evictions, and slot 2048 never holds a row's minimum; with 2300 cells it sees
+    250, and in half the rows (rows 0 to 6 among them) a rescan that stopped at slot 2047 would choose another slot.  The device
+    computes all rows; the restatement, whose add() looks through the used slots at every offer (5 s and more for all rows),
+    restates three ranges of 40 rows: the first rows, rows in the middle and the last rows."""
+    k, thr = 2049, -1.0
+    toc, data, genes = slots_input(cells)
+    assert ec.fsp0_form(cells, genes, k)["slot_capacity"] == 4096
+    device = capi.find_similar_pairs0(toc, data, genes, k, thr)
+    assert (device[1] == k).all()
+    for begin, end in [(0, 40), (cells // 2 - 20, cells // 2 + 20), (cells - 40, cells)]:
+        expected = restatement.find_similar_pairs0(toc, data, genes, k, thr, rows=(begin, end))
+        assert (expected[2] == k).all()
+        assert_equal(tuple(a[begin:end] for a in device), expected, (begin, end))
+
+
+@pytest.mark.parametrize("cells,k", [(4100, 4096), (4097, 5000)])
+def test_fsp0_at_the_limit_of_support(restatement, cells, k):
+    """min(k, cells - 1) = 4096 is the most the kernel holds.  4100 cells with k = 4096: every slot is used and three candidates
+    meet full slots (a rescan over 4096 slots, a sort of 4096 without padding).  4097 cells with k = 5000: supported, since a cell
+    has 4096 candidates; nothing is replaced and the 904 slots behind the used ones are zero.  The device entry on the first and
+    the last rows against the ranged restatement."""
+    toc, data, genes = slots_input(cells)
+    form = ec.fsp0_form(cells, genes, k)
+    assert form["supported"] and form["slot_capacity"] == 4096
+    for begin, end in [(0, 8), (cells - 8, cells)]:
+        expected = restatement.find_similar_pairs0(toc, data, genes, k, -1.0, rows=(begin, end))
+        assert (expected[2] == 4096).all()
+        assert_equal(ec.fsp0_device_rows(toc, data, genes, k, -1.0, begin, end), expected, (begin, end))
+
+
+def test_fsp0_one_slot_more_is_not_supported():
+    toc, data, genes = slots_input(4098)
+    assert not ec.fsp0_form(4098, genes, 4097)["supported"]
+    with pytest.raises(RuntimeError, match="not supported"):
+        capi.find_similar_pairs0(toc, data, genes, 4097, -1.0)
+
+
+@pytest.mark.parametrize("beyond", [0, 1])
+@pytest.mark.parametrize("k", [1, 50])
+def test_fsp0_at_the_lds_limit_next_to_its_own_lds(restatement, k, beyond):
+    """The largest gene count whose row vector fits the 160 KiB of a workgroup NEXT TO the slots, the survivors and the state of
+    fsp0RowsKernel (csrc/em2_expression.h rowVectorBytes, csrc/em2_fsp0.hip fsp0Lds, restated in tests/expression_cases.py), and
+    one gene more, which takes the global-memory form: the workspace the library asks for grows by the row scratch exactly there."""
+    cells = 130
+    capacity = ec.slot_capacity(cells, k)
+    own = ec.fsp0_own_lds_bytes(capacity)
+    limit = ec.largest_gene_count_in_lds(own)
+    assert capacity == (1 if k == 1 else 64) and ec.row_vector_bytes(limit) + own <= 160 * 1024 < ec.row_vector_bytes(limit + 1) + own
+    small = capi.dev_find_similar_pairs0_workspace(cells, cells, 100, k)
+    assert capi.dev_find_similar_pairs0_workspace(cells, cells, limit, k) == small
+    scratch = capi.dev_find_similar_pairs0_workspace(cells, cells, limit + 1, k) - small
+    assert 0 <= scratch - ec.row_vector_bytes(limit + 1) * cells < 256
+    genes = limit + beyond
+    assert ec.fsp0_form(cells, genes, k)["in_lds"] == (beyond == 0)
+    toc, data = ec.lds_limit_input(cells, genes)
+    expected = restatement.find_similar_pairs0(toc, data, genes, k, 0.0)
+    assert expected[2].sum() > 0
+    assert_equal(capi.find_similar_pairs0(toc, data, genes, k, 0.0), expected)
 
 
 def test_fsp0_errors():

@@ -46,6 +46,11 @@ def test_shapes(restatement, name, method):
     single, double, expressing, theirs = check_case(restatement, name, method)
     if name == "random-1x255":                      # one cell: R = 0 for every gene (p = c * (1 / c) may be one unit below 1)
         assert np.all(np.abs(double) <= gib.bound(1, 1.))
+        # (and the shape whose cell has more entries than a wave has lanes: entriesKernel's second, third and fourth stride)
+        assert np.diff(gib.case(name)[0].astype(np.int64)).max() == 255
+    if name == "random-300x600":                    # many cells of 110 to 190 entries: the second and third stride in every wave
+        lengths = np.diff(gib.case(name)[0].astype(np.int64))
+        assert lengths.min() > 64 and (lengths > 128).sum() > 100
     if name == "segments":
         assert expressing.tolist() == [gib.CHUNK - 1, gib.CHUNK, gib.CHUNK + 1, 3 * gib.CHUNK + 5, 0]
     if name == "everywhere":

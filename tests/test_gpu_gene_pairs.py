@@ -91,6 +91,47 @@ def test_threshold_minus_one_with_lists_that_do_not_fit_lds(restatement):
         capi.find_similar_gene_pairs0(toc, data, genes, gpb.NONE, 3, -1.0, all_similarities=True)
 
 
+def dense_input(cells, genes, seed):
+    """Every cell stores every gene, with a non-integer count: every gene varies and no r is NaN."""
+    rng = np.random.default_rng(seed)
+    dense = (rng.gamma(2.0, 1.5, (cells, genes)) + 0.05).astype(np.float32)
+    assert (dense != dense[0:1, :]).any(axis=0).all()
+    return dense
+
+
+def assert_every_r_is_above_minus_one(dense):
+    """Every list holds all genes - 1 candidates at threshold -1 if no r is NaN or -1: the correlations once more in numpy doubles,
+    band by band, with a margin of 10^-6 that is a thousand times the float rounding of r."""
+    z = dense.astype(np.float64)
+    z = z - z.mean(axis=0)
+    z = z / np.sqrt((z * z).sum(axis=0))
+    lowest = min(float((z[:, begin:begin + 1024].T @ z).min()) for begin in range(0, z.shape[1], 1024))
+    assert lowest > -1. + 1e-6
+
+
+@pytest.mark.parametrize("k", [299, 298])
+def test_lists_at_the_length_k(restatement, k):
+    """300 genes that all vary, threshold -1: every list has 299 candidates.  k = 299 leaves the lists alone (n <= k, heap.hpp:118);
+    k = 298 is the shortest selection there is, the introselect of 298 among 299."""
+    dense = dense_input(50, 300, seed=29)
+    toc, data = gpb.dense_to_csr(dense)
+    gene, sim, used, r = check(restatement, toc, data, 300, gpb.L2, k, -1.0)
+    assert not np.isnan(r[~np.eye(300, dtype=bool)]).any() and (r[~np.eye(300, dtype=bool)].astype(np.float64) > -1.0).all()
+    assert (used == k).all()
+
+
+@pytest.mark.parametrize("genes", [8193, 8194])
+def test_lists_at_the_lds_boundary(restatement, genes):
+    """A dense 6-cell matrix in which every gene varies, threshold -1: with 8193 genes every list has exactly 8192 candidates, the
+    longest that is selected in LDS; with 8194 genes 8193, the shortest that is selected in global memory.  (allSimilarities is
+    refused above 8192 genes, so the lengths are asserted through numpy; the restatement needs about 3 s.)"""
+    dense = dense_input(6, genes, seed=genes)
+    assert_every_r_is_above_minus_one(dense)
+    toc, data = gpb.dense_to_csr(dense)
+    gene, sim, used, _ = check(restatement, toc, data, genes, gpb.NONE, 3, -1.0, all_similarities=False)
+    assert (used == 3).all() and not np.isnan(sim).any()
+
+
 def test_more_cells_than_one_grid_of_threads(restatement):
     """4 194 304 + 300 cells x 3 genes: the per-cell kernels run on a grid capped at 16 384 blocks of 256 threads and must
     stride over it; the cells behind the cap carry counts (so their sums and their normalisation show in every r) and, in

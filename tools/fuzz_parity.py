@@ -5,7 +5,15 @@ FUZZ_ONLY=fsp4 restricts the sweep to one path, FUZZ_WIDTHS=1100,1500,2048 to th
 to one scan form with the matrix cores on.  The fsp6 leg compares with the C++ restatement (tests/fsp6_binding.py); shapes past
 its kernels' limits must answer EM2_ERROR_UNSUPPORTED and are counted apart (fsp6_unsupported), as are runs at the 8192
 clamp and runs over several row chunks.  Half the fsp7 draws go through the device entry on a random row range (fsp7_ranged);
-fsp7 draws the oracle would be slow for are skipped and counted (fsp7_skipped, see fsp7_oracle_is_slow)."""
+fsp7 draws the oracle would be slow for are skipped and counted (fsp7_skipped, see fsp7_oracle_is_slow).
+
+Six more legs draw from tests/expression_cases.py, the generator tests/test_gpu_expression_sweep.py takes its fixed draws from:
+fsp0, stored_pairs (analyzeSimilarPairs), analyze_lsh, cluster_graph, gene_pairs and gene_information, each against its C++
+restatement (analyze_lsh: the oracle) with the comparison of its own test file.  FUZZ_ONLY=<leg> works for each.  A draw above
+the cost cap of its leg is counted as <leg>_skipped; one that reaches a place the reference leaves open or asserts in (a makeKnn
+tie or a NaN similarity of the cluster graph, bin < binCount of the two analyses -- the device entry must then answer with the
+reference's text) as <leg>_discarded.  On a difference the case dict is printed: expression_cases.ENTRIES[leg].check(case,
+reference) reproduces it."""
 import os
 import sys
 import time
@@ -15,6 +23,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import expression_cases  # noqa: E402
 import fsp6_binding  # noqa: E402
 import oracle_binding  # noqa: E402
 import synth  # noqa: E402
@@ -33,9 +42,16 @@ def main():
     restatement6 = fsp6_binding.load()
     runs = {"fsp4": 0, "fsp5": 0, "fsp6": 0, "fsp7": 0, "signatures": 0, "graph": 0, "labels": 0, "fsp6_unsupported": 0,
             "fsp6_clamp8192": 0, "fsp6_chunks": 0, "fsp7_ranged": 0, "fsp7_skipped": 0}
+    for name in expression_cases.ENTRIES:
+        runs.update({name: 0, name + "_skipped": 0, name + "_discarded": 0})
+    references = {}
     while time.time() < deadline:
         for key in KNOBS:
             os.environ.pop(key, None)
+        if os.environ.get("FUZZ_ONLY") in expression_cases.ENTRIES or (rng.random() < 0.35 and not os.environ.get("FUZZ_ONLY")):
+            name = os.environ.get("FUZZ_ONLY") or str(rng.choice(list(expression_cases.ENTRIES)))
+            expression_leg(rng, name, references, runs)
+            continue
         if os.environ.get("FUZZ_ONLY") == "labels" or (rng.random() < 0.15 and not os.environ.get("FUZZ_ONLY")):
             # label propagation over a random k-NN-like graph: every schedule against the serial oracle
             vertices = int(rng.choice([2, 3, 50, 64, 65, 1000, 5000, 30000, 70000]))
@@ -176,6 +192,28 @@ def main():
             raise SystemExit("PARITY FAILURE %s %r" % (what, label))
         runs[what] += 1
     print("fuzz ok", runs)
+
+
+def expression_leg(rng, name, references, runs):
+    """One draw of tests/expression_cases.py for the leg `name`: run, skipped (too slow for the CPU side) or discarded."""
+    entry = expression_cases.ENTRIES[name]
+    case = entry.draw(rng)
+    if not expression_cases.runnable(name, case):
+        runs[name + "_skipped"] += 1
+        return
+    if name not in references:
+        references[name] = entry.reference()
+    try:
+        difference = entry.check(case, references[name])
+    except expression_cases.Discarded:
+        runs[name + "_discarded"] += 1
+        return
+    except AssertionError as e:
+        raise SystemExit("PARITY FAILURE %s %r: %s" % (name, case, e))
+    if difference:
+        print(difference)
+        raise SystemExit("PARITY FAILURE %s %r" % (name, case))
+    runs[name] += 1
 
 
 def fsp7_oracle_is_slow(n, L, k, lengths, max_check, log2b):
