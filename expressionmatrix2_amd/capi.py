@@ -131,6 +131,17 @@ SYMBOLS = {
     "em2_cluster_graph_get": (_c.c_int, [_c.c_void_p] * 9),
     "em2_cluster_graph_facts": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint32]),
     "em2_cluster_graph_free": (None, [_c.c_void_p]),
+    "em2_signature_graph_create": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_uint64, _c.POINTER(_c.c_void_p)]),
+    "em2_dev_signature_graph_create": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_uint64, _c.POINTER(_c.c_void_p)]),
+    "em2_signature_graph_sizes": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint32), _c.POINTER(_c.c_uint32),
+                                             _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
+    "em2_signature_graph_get": (_c.c_int, [_c.c_void_p] * 6),
+    "em2_signature_graph_free": (None, [_c.c_void_p]),
+    "em2_lsh_signature_statistics": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_void_p]),
+    "em2_dev_lsh_signature_statistics": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_void_p]),
+    "em2_analyze_lsh_signatures": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_char_p]),
+    "em2_matrix_create_signature_graph": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_uint64, _c.POINTER(_c.c_void_p)]),
+    "em2_matrix_analyze_lsh_signatures": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_size_t, _c.c_uint, _c.c_char_p]),
     "em2_analyze_lsh": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_void_p, _c.c_uint32, _c.c_void_p,
                                    _c.c_uint32, _c.c_double, _c.c_char_p, _c.c_char_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
                                    _c.c_void_p, _c.c_void_p]),
@@ -487,6 +498,74 @@ def cluster_graph_create(toc, data, gene_count, vertex_rows, edge_vertex0, edge_
     finally:
         lib.em2_cluster_graph_free(handle)
     return out
+
+
+def signature_graph_take(handle):
+    """The content of an em2_signature_graph as a dict, and the handle freed: distinctCount, vertexSignatures uint64 [V, W],
+    cellOffsets uint64 [V + 1], cells uint32 (ids local to the cell set), edgeVertex0 / edgeVertex1 uint32 [E]."""
+    lib = load()
+    try:
+        distinct, cells, edges = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        vertices, words = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        check(lib.em2_signature_graph_sizes(handle, ctypes.byref(distinct), ctypes.byref(vertices), ctypes.byref(words),
+                                            ctypes.byref(cells), ctypes.byref(edges)))
+        out = {
+            "vertexSignatures": np.zeros((vertices.value, words.value), dtype=np.uint64),
+            "cellOffsets": np.zeros(vertices.value + 1, dtype=np.uint64),
+            "cells": np.zeros(cells.value, dtype=np.uint32),
+            "edgeVertex0": np.zeros(edges.value, dtype=np.uint32),
+            "edgeVertex1": np.zeros(edges.value, dtype=np.uint32),
+        }
+        check(lib.em2_signature_graph_get(handle, *[_ptr(out[key]) for key in (
+            "vertexSignatures", "cellOffsets", "cells", "edgeVertex0", "edgeVertex1")]))
+        out["distinctCount"] = distinct.value
+    finally:
+        lib.em2_signature_graph_free(handle)
+    return out
+
+
+def _signatures_2d(signatures, lsh_count):
+    signatures = np.ascontiguousarray(signatures, dtype=np.uint64)
+    if signatures.ndim != 2 or signatures.shape[1] != word_count(lsh_count):
+        raise ValueError("signatures must be [cells, %d] uint64 for %d bits" % (word_count(lsh_count), lsh_count))
+    return signatures
+
+
+def signature_graph_create(signatures, lsh_count, min_cell_count=0):
+    """createSignatureGraph after its lookups (em2_signature_graph_create) on host signatures [cells, words] -> the dict
+    of signature_graph_take."""
+    signatures = _signatures_2d(signatures, lsh_count)
+    handle = ctypes.c_void_p(None)
+    check(load().em2_signature_graph_create(_ptr(signatures), signatures.shape[0], lsh_count, min_cell_count, ctypes.byref(handle)))
+    return signature_graph_take(handle)
+
+
+def dev_signature_graph_create(signatures, lsh_count, min_cell_count=0):
+    """The same through em2_dev_signature_graph_create on a torch device buffer."""
+    import torch
+    signatures = _signatures_2d(signatures, lsh_count)
+    d_signatures = torch.from_numpy(signatures.view(np.int64).copy()).to(torch.device("cuda"))
+    torch.cuda.synchronize()
+    handle = ctypes.c_void_p(None)
+    check(load().em2_dev_signature_graph_create(d_signatures.data_ptr(), signatures.shape[0], lsh_count, min_cell_count,
+                                                ctypes.byref(handle)))
+    return signature_graph_take(handle)
+
+
+def lsh_signature_statistics(signatures, lsh_count):
+    """The counts of Lsh::writeSignatureStatistics (em2_lsh_signature_statistics): the cells with every bit set, uint64 [lshCount]."""
+    signatures = _signatures_2d(signatures, lsh_count)
+    set_count = np.zeros(lsh_count, dtype=np.uint64)
+    check(load().em2_lsh_signature_statistics(_ptr(signatures), signatures.shape[0], lsh_count, _ptr(set_count)))
+    return set_count
+
+
+def analyze_lsh_signatures(signatures, lsh_count, directory=None):
+    """analyzeLshSignatures from its signatures on (em2_analyze_lsh_signatures): writes Signatures.csv, Histogram.csv and
+    LshSignatureStatistics.csv into `directory` (None: the working directory)."""
+    signatures = _signatures_2d(signatures, lsh_count)
+    check(load().em2_analyze_lsh_signatures(_ptr(signatures), signatures.shape[0], lsh_count,
+                                            os.fsencode(directory) if directory else None))
 
 
 def analyze_lsh(toc, data, gene_count, signatures, lsh_count, global_cell_ids, seed, csv_downsample, pairs_csv_path,

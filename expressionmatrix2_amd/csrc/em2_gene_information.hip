@@ -216,24 +216,6 @@ geneFinishKernel(const double* __restrict__ partials, const uint64_t* __restrict
     }
 }
 
-class GeneInformationTimer {
-public:
-    GeneInformationTimer() : on_(getenv("EM2_TIMING") && getenv("EM2_TIMING")[0] == '1'), last_(std::chrono::steady_clock::now()) {}
-    // (synchronises the stream when the timing is on)
-    hipError_t stage(const char* name, hipStream_t stream)
-    {
-        if (!on_) return hipSuccess;
-        EM2_TRY(hipStreamSynchronize(stream));
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[em2 timing] geneInformationContent: %s %.3f ms\n", name, std::chrono::duration<double, std::milli>(now - last_).count());
-        last_ = now;
-        return hipSuccess;
-    }
-private:
-    bool on_;
-    std::chrono::steady_clock::time_point last_;
-};
-
 uint32_t geneBitsOf(uint32_t geneCount)
 {
     uint32_t bits = 0;
@@ -324,7 +306,7 @@ hipError_t runGeneInformation(const uint64_t* d_toc, const CountIn* d_data, uint
     Layout l;
     EM2_TRY(layoutOf(entryCount, geneCount, l));
     if (workspaceBytes < l.total) return hipErrorInvalidValue;
-    GeneInformationTimer timer;
+    StageTimer timer("geneInformationContent");
     char* base = static_cast<char*>(workspace);
     uint32_t* words = reinterpret_cast<uint32_t*>(base + l.words);
     uint64_t* offsets = reinterpret_cast<uint64_t*>(base + l.offsets);

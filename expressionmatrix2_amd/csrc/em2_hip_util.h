@@ -1,5 +1,5 @@
 // em2_hip_util.h -- the host-side plumbing every driver needs: bail out on a HIP error, a device allocation that frees
-// itself, the 1-D grid of a 256-thread kernel, blocks per items, 256-byte alignment, signature words.  (The device-side counterpart is
+// itself, the 1-D grid of a 256-thread kernel, blocks per items, 256-byte alignment, signature words, the stage timer.  (The device-side counterpart is
 // em2_wave.h; device scratch that outlives a call is em2_scratch.h.)
 #ifndef EM2_HIP_UTIL_H
 #define EM2_HIP_UTIL_H
@@ -7,6 +7,10 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
 
 // Returns the hipError_t of a failed call from the enclosing function.  (The call's text is not kept: the entry points
 // that report one, em2_capi.hip's EM2_HIP and em2_cluster_graph.hip's EM2_TRYC, have macros of their own.)
@@ -52,6 +56,27 @@ inline size_t alignUp(size_t x) { return (x + 255u) & ~size_t(255u); }
 
 // 64-bit words of a signature of lshCount > 0 bits.
 inline uint32_t wordCountOf(uint32_t lshCount) { return (lshCount - 1u) / 64u + 1u; }
+
+// EM2_TIMING=1: the wall time of the stages of a device call on stderr, "[em2 timing] <what>: <stage> <ms> ms" (measurements
+// only).  stage() synchronises the stream when the timing is on, and does nothing else when it is off.
+class StageTimer {
+public:
+    explicit StageTimer(const char* what)
+        : what_(what), on_(getenv("EM2_TIMING") && getenv("EM2_TIMING")[0] == '1'), last_(std::chrono::steady_clock::now()) {}
+    hipError_t stage(const char* name, hipStream_t stream)
+    {
+        if (!on_) return hipSuccess;
+        EM2_TRY(hipStreamSynchronize(stream));
+        const auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "[em2 timing] %s: %s %.3f ms\n", what_, name, std::chrono::duration<double, std::milli>(now - last_).count());
+        last_ = now;
+        return hipSuccess;
+    }
+private:
+    const char* what_;
+    bool on_;
+    std::chrono::steady_clock::time_point last_;
+};
 
 }  // namespace em2
 

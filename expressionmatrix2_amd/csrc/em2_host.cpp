@@ -464,6 +464,36 @@ void Matrix::analyzeLsh(const std::string& geneSetName, const std::string& cellS
     if (rc != EM2_OK) fail(rc, em2_last_error());
 }
 
+void Matrix::createSignatureGraph(const std::string& cellSetName, const std::string& lshName, uint64_t minCellCount,
+                                  em2_signature_graph** graph) const
+{
+    // ExpressionMatrixSignatureGraph.cpp:50-67
+    const MappedFile& cells = cellSet(cellSetName);
+    const uint64_t cellCount = cells.objectCount();
+    if (cellCount == 0) fail(EM2_ERROR_RUNTIME, "Cell set " + cellSetName + " is empty.");
+    uint64_t lshCells = 0, lshCount = 0;
+    std::vector<uint64_t> signatures;
+    readLsh(directoryName_ + "/Lsh-" + lshName, lshCells, lshCount, signatures);
+    if (lshCells != cellCount) {
+        fail(EM2_ERROR_RUNTIME, "LSH object " + lshName + " has a number of cells inconsistent with cell set " + cellSetName + ".");
+    }
+    if (lshCount > 0xffffffffULL) fail(EM2_ERROR_INVALID_ARGUMENT, "createSignatureGraph: lshCount out of range");
+    const int rc = em2_signature_graph_create(signatures.data(), uint32_t(cellCount), uint32_t(lshCount), minCellCount, graph);
+    if (rc != EM2_OK) fail(rc, em2_last_error());
+}
+
+void Matrix::analyzeLshSignatures(const std::string& geneSetName, const std::string& cellSetName, size_t lshCount, unsigned int seed,
+                                  const std::string& outputDirectory) const
+{
+    // ExpressionMatrixLsh.cpp:1379-1409: the lookups, the subset and its Lsh object -- here the signatures alone
+    if (lshCount == 0 || lshCount > 0xffffffffULL) fail(EM2_ERROR_INVALID_ARGUMENT, "analyzeLshSignatures: lshCount out of range");
+    uint32_t cellCount = 0;
+    std::vector<uint64_t> signatures;
+    runLshPath("analyzeLshSignatures", geneSetName, cellSetName, lshCount, seed, cellCount, &signatures, 0, 0., nullptr, nullptr);
+    const int rc = em2_analyze_lsh_signatures(signatures.data(), cellCount, uint32_t(lshCount), outputDirectory.c_str());
+    if (rc != EM2_OK) fail(rc, em2_last_error());
+}
+
 void Matrix::findSimilarPairs5(const std::string& geneSetName, const std::string& cellSetName,
                                const std::string& lshName, const std::string& similarPairsName, size_t k,
                                double similarityThreshold, size_t lshSliceLength, size_t bucketOverflow) const

@@ -126,6 +126,15 @@ public:
     void analyzeLsh(const std::string& geneSetName, const std::string& cellSetName, size_t lshCount, unsigned int seed,
                     double csvDownsample, const std::string& outputDirectory) const;
 
+    // ExpressionMatrix::createSignatureGraph (src/ExpressionMatrixSignatureGraph.cpp:42-150) without its name bookkeeping: the
+    // lookups and their errors, then em2_signature_graph_create on the signatures of Lsh-<lshName>.  The caller frees *graph.
+    void createSignatureGraph(const std::string& cellSetName, const std::string& lshName, uint64_t minCellCount,
+                              em2_signature_graph** graph) const;
+    // ExpressionMatrix::analyzeLshSignatures (src/ExpressionMatrixLsh.cpp:1372-1474): writes Signatures.csv, Histogram.csv and
+    // LshSignatureStatistics.csv into outputDirectory (the reference: the working directory, "").
+    void analyzeLshSignatures(const std::string& geneSetName, const std::string& cellSetName, size_t lshCount, unsigned int seed,
+                              const std::string& outputDirectory) const;
+
     // ExpressionMatrix::computeGeneInformationContent (src/ExpressionMatrix.cpp:1947-2018) for the genes of a gene set over a
     // cell set, and the cells expressing every gene (src/ExpressionMatrixGeneSets.cpp:336-350); either vector may be NULL.
     // The cells' norm inverses come from the Cells file where the directory has one.

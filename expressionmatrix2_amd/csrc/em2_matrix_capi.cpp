@@ -86,6 +86,23 @@ int em2_matrix_analyze_lsh(em2_matrix* matrix, const char* geneSetName, const ch
     });
 }
 
+int em2_matrix_create_signature_graph(em2_matrix* matrix, const char* cellSetName, const char* lshName, uint64_t minCellCount,
+                                      em2_signature_graph** graph)
+{
+    if (!matrix || !cellSetName || !lshName || !graph) return nullArgument("em2_matrix_create_signature_graph");
+    *graph = nullptr;
+    return guarded([&] { matrix->impl->createSignatureGraph(cellSetName, lshName, minCellCount, graph); });
+}
+
+int em2_matrix_analyze_lsh_signatures(em2_matrix* matrix, const char* geneSetName, const char* cellSetName, size_t lshCount,
+                                      unsigned int seed, const char* outputDirectory)
+{
+    if (!matrix || !geneSetName || !cellSetName) return nullArgument("em2_matrix_analyze_lsh_signatures");
+    return guarded([&] {
+        matrix->impl->analyzeLshSignatures(geneSetName, cellSetName, lshCount, seed, outputDirectory ? outputDirectory : "");
+    });
+}
+
 int em2_matrix_find_similar_pairs5(em2_matrix* matrix, const char* geneSetName, const char* cellSetName,
                                    const char* lshName, const char* similarPairsName, size_t k,
                                    double similarityThreshold, size_t lshSliceLength, size_t bucketOverflow)

@@ -53,9 +53,11 @@ class ExpressionMatrix:
         self._handle = ctypes.c_void_p(None)
         self._cellGraphs = {}          # ExpressionMatrix::cellGraphs (src/ExpressionMatrix.hpp): in memory only
         self._clusterGraphs = {}       # ExpressionMatrix::clusterGraphs, likewise
+        self._signatureGraphs = {}     # ExpressionMatrix::signatureGraphs, likewise
         capi.check(capi.load().em2_matrix_open(_b(directoryName), ctypes.byref(self._handle)))
 
     def close(self):
+        self._signatureGraphs = {}
         if self._handle:
             capi.load().em2_matrix_close(self._handle)
             self._handle = ctypes.c_void_p(None)
@@ -194,6 +196,67 @@ class ExpressionMatrix:
         (src/ExpressionMatrixLsh.cpp:1303, :1345)."""
         capi.check(capi.load().em2_matrix_analyze_lsh(self._handle, _b(geneSetName), _b(cellSetName), lshCount, seed,
                                                       csvDownsample, None))
+
+    # ---- src/PythonModule.cpp:954-962 ----
+    def analyzeLshSignatures(self, geneSetName="AllGenes", cellSetName="AllCells", lshCount=1024, seed=231):
+        """ExpressionMatrix::analyzeLshSignatures (src/ExpressionMatrixLsh.cpp:1372-1474): writes Signatures.csv, Histogram.csv
+        and LshSignatureStatistics.csv into the working directory.  The cells are grouped by signature and the bits counted on
+        the GPU (em2_analyze_lsh_signatures)."""
+        capi.check(capi.load().em2_matrix_analyze_lsh_signatures(self._handle, _b(geneSetName), _b(cellSetName), lshCount, seed,
+                                                                 None))
+
+    # ---- src/PythonModule.cpp:984-1004 ----
+    def createSignatureGraph(self, signatureGraphName=_REQUIRED, cellSetName="AllCells", lshName=_REQUIRED,
+                             minCellCount=_REQUIRED):
+        """ExpressionMatrix::createSignatureGraph (src/ExpressionMatrixSignatureGraph.cpp:42-150): a vertex per signature that
+        at least minCellCount cells of the cell set share, an edge between signatures that differ in one bit
+        (em2_signature_graph_create, on the GPU).  The graph lives in memory, like the reference's; SignatureGraph.svg is not
+        written."""
+        if _REQUIRED in (signatureGraphName, lshName, minCellCount):
+            raise TypeError("createSignatureGraph(): signatureGraphName, lshName and minCellCount are required")
+        _b(signatureGraphName)
+        if isinstance(minCellCount, float) or not 0 <= int(minCellCount) < 2 ** 64:        # size_t (:46)
+            raise ValueError("createSignatureGraph(): minCellCount must be an integer in [0, 2**64)")
+        if signatureGraphName in self._signatureGraphs:
+            raise RuntimeError("Signature graph " + signatureGraphName + " already exists.")       # :22-24
+        handle = ctypes.c_void_p(None)
+        capi.check(capi.load().em2_matrix_create_signature_graph(self._handle, _b(cellSetName), _b(lshName), int(minCellCount),
+                                                                 ctypes.byref(handle)))
+        graph = capi.signature_graph_take(handle)
+        graph["cellSet"] = self._cell_set(cellSetName)
+        self._signatureGraphs[signatureGraphName] = graph
+
+    def removeSignatureGraph(self, signatureGraphName):
+        self._signature_graph(signatureGraphName)
+        del self._signatureGraphs[signatureGraphName]
+
+    def _signature_graph(self, signatureGraphName):
+        if signatureGraphName not in self._signatureGraphs:
+            raise RuntimeError("Signature graph " + signatureGraphName + " does not exists.")      # sic, :34, :157
+        return self._signatureGraphs[signatureGraphName]
+
+    # The reference shows a signature graph through its HTTP pages only; these four accessors are this package's.
+    def getSignatureGraphNames(self):
+        return sorted(self._signatureGraphs)
+
+    def getSignatureGraphVertices(self, signatureGraphName):
+        """(signatures uint64 [vertices, words], cell counts uint64 [vertices]), in vertex order: the order of the reference's
+        std::map of signatures."""
+        g = self._signature_graph(signatureGraphName)
+        return g["vertexSignatures"].copy(), np.diff(g["cellOffsets"])
+
+    def getSignatureGraphCells(self, signatureGraphName, vertexId):
+        """(local cell ids, global cell ids) of a vertex: SignatureGraphVertex::localCellIds / globalCellIds, ascending."""
+        g = self._signature_graph(signatureGraphName)
+        if not 0 <= vertexId < len(g["cellOffsets"]) - 1:
+            raise RuntimeError("Vertex " + str(vertexId) + " of signature graph " + signatureGraphName + " does not exist.")
+        local = g["cells"][int(g["cellOffsets"][vertexId]):int(g["cellOffsets"][vertexId + 1])]
+        return local.copy(), g["cellSet"][local]
+
+    def getSignatureGraphEdges(self, signatureGraphName):
+        """(vertex 0, vertex 1) per edge, uint32, in the order SignatureGraph::createEdges adds them; vertex 1 > vertex 0."""
+        g = self._signature_graph(signatureGraphName)
+        return g["edgeVertex0"].copy(), g["edgeVertex1"].copy()
 
     # ---- src/PythonModule.cpp:852-865 ----
     def findSimilarPairs5(self, geneSetName="AllGenes", cellSetName="AllCells", lshName=_REQUIRED,

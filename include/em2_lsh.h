@@ -601,6 +601,61 @@ int em2_cluster_graph_facts(const em2_cluster_graph* graph, double* values, uint
 void em2_cluster_graph_free(em2_cluster_graph* graph);
 
 /* ------------------------------------------------------------------------------------------------------
+ * The signature graph and the signature diagnostics: the consumers of the Lsh-<name> objects that group the cells by equal
+ * signature.  csrc/em2_signature_graph.hip, DESIGN.md 3.13.  Integer work: every output is bit-exact.
+ * A signature is wordCount = (lshCount - 1) / 64 + 1 words, the first bit the most significant of word 0, the bits at or beyond
+ * lshCount zero (src/BitSet.hpp:46-62; EM2_ERROR_INVALID_ARGUMENT where one is set).  lshCount above 65536:
+ * EM2_ERROR_UNSUPPORTED.
+ * The reference is only defined for lshCount <= 64: BitSet's copy constructor and operator= allocate ONE word
+ * (src/BitSet.hpp:184, :200), and both SignatureGraph::createEdges (src/SignatureGraph.cpp:37) and the comparator of
+ * analyzeLshSignatures' sort (src/ExpressionMatrixLsh.cpp:1435) go through them.  For more words this library continues the same
+ * contract: the order of std::lexicographical_compare over the words, one-bit neighbours across all words.
+ * ------------------------------------------------------------------------------------------------------ */
+
+/* ExpressionMatrix::createSignatureGraph (src/ExpressionMatrixSignatureGraph.cpp:42-150) after its lookups and
+ * SignatureGraph::createEdges (src/SignatureGraph.cpp:23-48):
+ *   groups     all cells with the same signature, in the order of the reference's std::map<BitSetPointer, vector<CellId>>
+ *              (:72-75; src/BitSet.hpp:157-160: ascending by word 0, then word 1, ... as unsigned integers), the cell ids of
+ *              a group ascending; *distinctCount of them ("Found ... populated signatures", :76);
+ *   vertices   the groups of at least minCellCount cells (:118-120, a size_t comparison: 0 and 1 keep everything), numbered
+ *              from 0 in that order;
+ *   edges      for v0 ascending and bit 0 .. lshCount-1 ascending: where the bit is 0 in v0's signature and a VERTEX v1 has
+ *              that signature with the bit set, the edge (v0, v1) -- v1 > v0 always; Boost's add_edge order.
+ * signatures: [cellCount][wordCount], host memory (em2_dev_signature_graph_create: device memory).  cellCount 0 is an
+ * error, as the reference's empty cell set is.  The result is an object: em2_signature_graph_sizes, then
+ * em2_signature_graph_get into arrays of those sizes (any may be NULL):
+ *   vertexSignatures[vertexCount][wordCount], cellOffsets[vertexCount + 1], cells[cellCount of the sizes] (ids local to the
+ *   cell set, i.e. row numbers of `signatures`), edgeVertex0 / edgeVertex1[edgeCount].
+ * A graph without vertices (minCellCount above every group's size) is a valid result.
+ * Not built: SignatureGraph.svg and the layout behind it (:145-147), the colouring by meta data, the progress lines. */
+typedef struct em2_signature_graph em2_signature_graph;
+int em2_signature_graph_create(const uint64_t* signatures, uint32_t cellCount, uint32_t lshCount, uint64_t minCellCount,
+                               em2_signature_graph** graph);
+int em2_dev_signature_graph_create(const uint64_t* d_signatures, uint32_t cellCount, uint32_t lshCount, uint64_t minCellCount,
+                                   em2_signature_graph** graph);
+int em2_signature_graph_sizes(const em2_signature_graph* graph, uint64_t* distinctCount, uint32_t* vertexCount, uint32_t* wordCount,
+                              uint64_t* cellCount, uint64_t* edgeCount);
+int em2_signature_graph_get(const em2_signature_graph* graph, uint64_t* vertexSignatures, uint64_t* cellOffsets, uint32_t* cells,
+                            uint32_t* edgeVertex0, uint32_t* edgeVertex1);
+void em2_signature_graph_free(em2_signature_graph* graph);
+
+/* The counts of Lsh::writeSignatureStatistics (src/Lsh.cpp:279-303): setCount[i] = the cells with bit i set, i < lshCount.
+ * Host signatures (em2_dev_lsh_signature_statistics: device memory); setCount is a host array in both. */
+int em2_lsh_signature_statistics(const uint64_t* signatures, uint32_t cellCount, uint32_t lshCount, uint64_t* setCount);
+int em2_dev_lsh_signature_statistics(const uint64_t* d_signatures, uint32_t cellCount, uint32_t lshCount, uint64_t* setCount);
+
+/* ExpressionMatrix::analyzeLshSignatures (src/ExpressionMatrixLsh.cpp:1372-1474) from its signatures on: three files in
+ * `directory` (NULL or "": the working directory, where the reference writes them).
+ *   Signatures.csv              a line per distinct signature, x for a set bit and _ for a clear one (BitSetPointer::getString,
+ *                               src/BitSet.hpp:124-136), a comma, the number of cells; ordered by std::sort with
+ *                               OrderPairsBySecondGreater (src/orderPairs.hpp:56-62) over the groups in map order -- not
+ *                               stable: this library's own std::sort runs on that sequence, as for renumberClusters;
+ *   Histogram.csv               for every group size i that occurs, ascending: i,frequency,frequency*i,running sum (no header);
+ *   LshSignatureStatistics.csv  Bit,Set,Unset,Total and a line per bit.
+ * The groups and the counts come from the device, the text is written on the host.  Host signatures. */
+int em2_analyze_lsh_signatures(const uint64_t* signatures, uint32_t cellCount, uint32_t lshCount, const char* directory);
+
+/* ------------------------------------------------------------------------------------------------------
  * ExpressionMatrix-level entry points: the methods the reference binds to Python (src/PythonModule.cpp),
  * operating by NAME on a data directory in the reference's memory-mapped formats.  Results are files in
  * that directory (SimilarPairs-<name>-{Info,Pairs,CellInfo}, Lsh-<name>-{Info,Signatures}), byte-compatible
@@ -630,6 +685,20 @@ int em2_matrix_compute_lsh_signatures(em2_matrix* matrix, const char* geneSetNam
  * (NULL or "": the working directory) says where. */
 int em2_matrix_analyze_lsh(em2_matrix* matrix, const char* geneSetName, const char* cellSetName, size_t lshCount,
                            unsigned int seed, double csvDownsample, const char* outputDirectory);
+
+/* ExpressionMatrix::createSignatureGraph's lookups (src/ExpressionMatrixSignatureGraph.cpp:50-67; bound at
+ * src/PythonModule.cpp:984-1004) and em2_signature_graph_create on the signatures of Lsh-<lshName>: "Cell set X does not
+ * exist." / "... is empty.", "LSH object L has a number of cells inconsistent with cell set C.".  The cells of the graph are
+ * ids local to the cell set (em2_matrix_cell_set gives the global ones).  The names of the graphs ("Signature graph X already
+ * exists." / "... does not exists.") are kept by the caller: the reference keeps its graphs in memory only. */
+int em2_matrix_create_signature_graph(em2_matrix* matrix, const char* cellSetName, const char* lshName, uint64_t minCellCount,
+                                      em2_signature_graph** graph);
+
+/* ExpressionMatrix::analyzeLshSignatures (src/ExpressionMatrixLsh.cpp:1372-1474; bound at src/PythonModule.cpp:954-962 with
+ * the defaults AllGenes, AllCells, 1024, 231): the subset, its signatures (the projection of em2_matrix_compute_lsh_signatures;
+ * no tmp-Lsh files are created), then em2_analyze_lsh_signatures into outputDirectory (NULL or "": the working directory). */
+int em2_matrix_analyze_lsh_signatures(em2_matrix* matrix, const char* geneSetName, const char* cellSetName, size_t lshCount,
+                                      unsigned int seed, const char* outputDirectory);
 
 /* ExpressionMatrix::findSimilarPairs5 (src/ExpressionMatrixLsh.cpp:312-501; src/PythonModule.cpp:852-865,
  * default bucketOverflow=1000). */
