@@ -142,6 +142,17 @@ SYMBOLS = {
     "em2_analyze_lsh_signatures": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_char_p]),
     "em2_matrix_create_signature_graph": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_uint64, _c.POINTER(_c.c_void_p)]),
     "em2_matrix_analyze_lsh_signatures": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_size_t, _c.c_uint, _c.c_char_p]),
+    "em2_gene_graph_create": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_uint32,
+                                         _c.c_double, _c.c_uint64, _c.POINTER(_c.c_void_p)]),
+    "em2_dev_gene_graph_create": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_uint32,
+                                             _c.c_double, _c.c_uint64, _c.POINTER(_c.c_void_p)]),
+    "em2_gene_graph_sizes": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_uint32), _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint32)]),
+    "em2_gene_graph_get": (_c.c_int, [_c.c_void_p] * 8),
+    "em2_gene_graph_free": (None, [_c.c_void_p]),
+    "em2_matrix_create_gene_graph": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_int64, _c.c_double, _c.POINTER(_c.c_void_p)]),
+    "em2_matrix_create_gene_set_intersection": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.POINTER(_c.c_int)]),
+    "em2_matrix_create_gene_set_union": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.POINTER(_c.c_int)]),
+    "em2_matrix_create_gene_set_difference": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_char_p, _c.POINTER(_c.c_int)]),
     "em2_analyze_lsh": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_void_p, _c.c_uint32, _c.c_void_p,
                                    _c.c_uint32, _c.c_double, _c.c_char_p, _c.c_char_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
                                    _c.c_void_p, _c.c_void_p]),
@@ -566,6 +577,71 @@ def analyze_lsh_signatures(signatures, lsh_count, directory=None):
     signatures = _signatures_2d(signatures, lsh_count)
     check(load().em2_analyze_lsh_signatures(_ptr(signatures), signatures.shape[0], lsh_count,
                                             os.fsencode(directory) if directory else None))
+
+
+GENE_GRAPH_KEYS = ("vertices", "edgeGene0", "edgeGene1", "edgeSimilarity", "connectivityOffsets", "connectivityGenes",
+                   "connectivitySimilarities")
+
+
+def gene_graph_take(handle):
+    """The content of an em2_gene_graph as a dict, and the handle freed: vertices uint32 [V] (the genes that stay), edgeGene0 /
+    edgeGene1 uint32 [E] and edgeSimilarity float32 [E] in insertion order, connectivityOffsets uint64 [genes + 1],
+    connectivityGenes uint32 [2 E] and connectivitySimilarities float32 [2 E] (the neighbours of a gene ascending), removedCount.
+    Every id is local to the graph's gene set."""
+    lib = load()
+    try:
+        vertices, removed, edges = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint64(0)
+        check(lib.em2_gene_graph_sizes(handle, ctypes.byref(vertices), ctypes.byref(edges), ctypes.byref(removed)))
+        out = {
+            "vertices": np.zeros(vertices.value, dtype=np.uint32),
+            "edgeGene0": np.zeros(edges.value, dtype=np.uint32),
+            "edgeGene1": np.zeros(edges.value, dtype=np.uint32),
+            "edgeSimilarity": np.zeros(edges.value, dtype=np.float32),
+            "connectivityOffsets": np.zeros(vertices.value + removed.value + 1, dtype=np.uint64),
+            "connectivityGenes": np.zeros(2 * edges.value, dtype=np.uint32),
+            "connectivitySimilarities": np.zeros(2 * edges.value, dtype=np.float32),
+        }
+        check(lib.em2_gene_graph_get(handle, *[_ptr(out[key]) for key in GENE_GRAPH_KEYS]))
+        out["removedCount"] = removed.value
+    finally:
+        lib.em2_gene_graph_free(handle)
+    return out
+
+
+def _gene_graph_arguments(pairs, used_count, pairs_gene_set, graph_gene_set):
+    pairs = np.ascontiguousarray(pairs, dtype=PAIR_DTYPE)
+    used_count = np.ascontiguousarray(used_count, dtype=np.uint32)
+    pairs_genes = np.ascontiguousarray(pairs_gene_set, dtype=np.uint32)
+    graph_genes = np.ascontiguousarray(graph_gene_set, dtype=np.uint32)
+    if pairs.ndim != 2 or pairs.shape[0] != len(pairs_genes) or used_count.shape != (len(pairs_genes),):
+        raise ValueError("pairs must be [genes of the pairs' gene set, k] and used_count [genes of the pairs' gene set]")
+    return pairs, used_count, pairs_genes, graph_genes
+
+
+def gene_graph_create(pairs, used_count, pairs_gene_set, graph_gene_set, similarity_threshold, max_connectivity):
+    """The GeneGraph constructor and getConnectivity (em2_gene_graph_create) on a host SimilarGenePairs content -> the dict of
+    gene_graph_take.  max_connectivity is the reference's int: 0 and negative values mean no limit."""
+    pairs, used_count, pairs_genes, graph_genes = _gene_graph_arguments(pairs, used_count, pairs_gene_set, graph_gene_set)
+    handle = ctypes.c_void_p(None)
+    check(load().em2_gene_graph_create(_ptr(pairs), _ptr(used_count), len(pairs_genes), pairs.shape[1], _ptr(pairs_genes),
+                                       _ptr(graph_genes), len(graph_genes), similarity_threshold, int(max_connectivity) % 2 ** 64,
+                                       ctypes.byref(handle)))
+    return gene_graph_take(handle)
+
+
+def dev_gene_graph_create(pairs, used_count, pairs_gene_set, graph_gene_set, similarity_threshold, max_connectivity):
+    """The same through em2_dev_gene_graph_create: pairs and used_count go to torch device buffers first."""
+    import torch
+    pairs, used_count, pairs_genes, graph_genes = _gene_graph_arguments(pairs, used_count, pairs_gene_set, graph_gene_set)
+    device = torch.device("cuda")
+    d_pairs = torch.from_numpy(pairs.view(np.int64).reshape(-1).copy()).to(device)
+    d_used = torch.from_numpy(used_count.view(np.int32).copy()).to(device)
+    torch.cuda.synchronize()
+    handle = ctypes.c_void_p(None)
+    check(load().em2_dev_gene_graph_create(d_pairs.data_ptr() if d_pairs.numel() else None, d_used.data_ptr() if d_used.numel() else None,
+                                           len(pairs_genes), pairs.shape[1], _ptr(pairs_genes), _ptr(graph_genes), len(graph_genes),
+                                           similarity_threshold, int(max_connectivity) % 2 ** 64, ctypes.byref(handle)))
+    return gene_graph_take(handle)
 
 
 def analyze_lsh(toc, data, gene_count, signatures, lsh_count, global_cell_ids, seed, csv_downsample, pairs_csv_path,

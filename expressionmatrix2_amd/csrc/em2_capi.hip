@@ -11,6 +11,7 @@
 #include "em2_scratch.h"
 #include "em2_cluster_graph.h"
 #include "em2_signature_graph.h"
+#include "em2_gene_graph.h"
 #include "em2_tables.h"
 
 #include <algorithm>
@@ -2155,5 +2156,116 @@ int em2_analyze_lsh_signatures(const uint64_t* signatures, uint32_t cellCount, u
     }
     return EM2_OK;
 }
+
+// ---- the gene graph (em2_gene_graph.hip) ----
+
+struct em2_gene_graph {
+    em2::GeneGraphResult result;
+};
+
+// Strictly ascending: what a stored GeneSet is once sorted (src/GeneSet.cpp), and what both id look-ups rely on.
+static bool strictlyAscending(const uint32_t* ids, uint32_t count)
+{
+    for (uint32_t i = 1; i < count; i++) {
+        if (ids[i - 1] >= ids[i]) return false;
+    }
+    return true;
+}
+
+static int geneGraphCreate(const char* who, bool pairsOnDevice, const em2_pair* pairs, const uint32_t* usedCount, uint32_t pairsGeneCount,
+                           uint32_t k, const uint32_t* pairsGeneSet, const uint32_t* graphGeneSet, uint32_t graphGeneCount,
+                           double similarityThreshold, uint64_t maxConnectivity, em2_gene_graph** graph)
+{
+    if (!graph) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+    *graph = nullptr;
+    if (graphGeneCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": graphGeneCount must be positive");
+    if (!graphGeneSet || (pairsGeneCount && (!pairsGeneSet || !usedCount || (!pairs && k)))) {
+        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+    }
+    if (!strictlyAscending(pairsGeneSet, pairsGeneCount) || !strictlyAscending(graphGeneSet, graphGeneCount)) {
+        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": a gene set is not in strictly ascending order");
+    }
+    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
+    // src/GeneGraph.cpp:80-83 increments and then tests for equality, so 0 -- and a negative Python int, converted to size_t --
+    // never matches: no limit.  A gene never selects more than its k stored pairs either way.
+    const uint32_t effective = (maxConnectivity == 0 || maxConnectivity > k) ? k : uint32_t(maxConnectivity);
+    // (sets of consecutive ids need no search on the device and are not sent there)
+    const bool pairsConsecutive = pairsGeneCount && pairsGeneSet[pairsGeneCount - 1] - pairsGeneSet[0] == pairsGeneCount - 1;
+    const bool graphConsecutive = graphGeneSet[graphGeneCount - 1] - graphGeneSet[0] == graphGeneCount - 1;
+    DeviceBuffer dPairs, dUsed, dPairsSet, dGraphSet;
+    if (!pairsOnDevice) {
+        EM2_HIP(dPairs.allocate(size_t(pairsGeneCount) * k * sizeof(em2_pair)));
+        EM2_HIP(dUsed.allocate(size_t(pairsGeneCount) * sizeof(uint32_t)));
+        if (pairsGeneCount && k) EM2_HIP(hipMemcpy(dPairs.p, pairs, size_t(pairsGeneCount) * k * sizeof(em2_pair), hipMemcpyHostToDevice));
+        if (pairsGeneCount) EM2_HIP(hipMemcpy(dUsed.p, usedCount, size_t(pairsGeneCount) * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    if (!pairsConsecutive) {
+        EM2_HIP(dPairsSet.allocate(size_t(pairsGeneCount) * sizeof(uint32_t)));
+        if (pairsGeneCount) EM2_HIP(hipMemcpy(dPairsSet.p, pairsGeneSet, size_t(pairsGeneCount) * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    if (!graphConsecutive) {
+        EM2_HIP(dGraphSet.allocate(size_t(graphGeneCount) * sizeof(uint32_t)));
+        EM2_HIP(hipMemcpy(dGraphSet.p, graphGeneSet, size_t(graphGeneCount) * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    em2_gene_graph* g = new em2_gene_graph;
+    uint32_t inputError = 0;
+    const hipError_t status = em2::runGeneGraph(
+        pairsOnDevice ? reinterpret_cast<const em2::PairOut*>(pairs) : dPairs.as<em2::PairOut>(), pairsOnDevice ? usedCount : dUsed.as<uint32_t>(),
+        pairsGeneCount, k, pairsConsecutive ? nullptr : dPairsSet.as<uint32_t>(), pairsConsecutive, pairsGeneCount ? pairsGeneSet[0] : 0u,
+        graphConsecutive ? nullptr : dGraphSet.as<uint32_t>(), graphConsecutive, graphGeneSet[0], graphGeneCount, similarityThreshold,
+        effective, g->result, &inputError, nullptr);
+    if (status != hipSuccess || inputError) {
+        delete g;
+        EM2_HIP(status);
+        if (inputError & em2::kGeneGraphUsedCount) return failArgument(who, "a usedCount is above k");
+        if (inputError & em2::kGeneGraphPartnerRange) return failArgument(who, "a stored pair names a gene outside the pairs' gene set");
+        return failArgument(who, "a stored pair names its own gene");
+    }
+    *graph = g;
+    return EM2_OK;
+}
+
+int em2_gene_graph_create(const em2_pair* pairs, const uint32_t* usedCount, uint32_t pairsGeneCount, uint32_t k,
+                          const uint32_t* pairsGeneSet, const uint32_t* graphGeneSet, uint32_t graphGeneCount,
+                          double similarityThreshold, uint64_t maxConnectivity, em2_gene_graph** graph)
+{
+    return geneGraphCreate("em2_gene_graph_create", false, pairs, usedCount, pairsGeneCount, k, pairsGeneSet, graphGeneSet, graphGeneCount,
+                           similarityThreshold, maxConnectivity, graph);
+}
+
+int em2_dev_gene_graph_create(const em2_pair* d_pairs, const uint32_t* d_usedCount, uint32_t pairsGeneCount, uint32_t k,
+                              const uint32_t* pairsGeneSet, const uint32_t* graphGeneSet, uint32_t graphGeneCount,
+                              double similarityThreshold, uint64_t maxConnectivity, em2_gene_graph** graph)
+{
+    return geneGraphCreate("em2_dev_gene_graph_create", true, d_pairs, d_usedCount, pairsGeneCount, k, pairsGeneSet, graphGeneSet,
+                           graphGeneCount, similarityThreshold, maxConnectivity, graph);
+}
+
+int em2_gene_graph_sizes(const em2_gene_graph* graph, uint32_t* vertexCount, uint64_t* edgeCount, uint32_t* removedCount)
+{
+    if (!graph) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_gene_graph_sizes: null pointer");
+    const em2::GeneGraphResult& r = graph->result;
+    if (vertexCount) *vertexCount = uint32_t(r.vertices.size());
+    if (edgeCount) *edgeCount = r.edge0.size();
+    if (removedCount) *removedCount = r.geneCount - uint32_t(r.vertices.size());
+    return EM2_OK;
+}
+
+int em2_gene_graph_get(const em2_gene_graph* graph, uint32_t* vertices, uint32_t* edgeGene0, uint32_t* edgeGene1, float* edgeSimilarity,
+                       uint64_t* connectivityOffsets, uint32_t* connectivityGenes, float* connectivitySimilarities)
+{
+    if (!graph) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_gene_graph_get: null pointer");
+    const em2::GeneGraphResult& r = graph->result;
+    if (vertices) std::copy(r.vertices.begin(), r.vertices.end(), vertices);
+    if (edgeGene0) std::copy(r.edge0.begin(), r.edge0.end(), edgeGene0);
+    if (edgeGene1) std::copy(r.edge1.begin(), r.edge1.end(), edgeGene1);
+    if (edgeSimilarity) std::copy(r.edgeSimilarity.begin(), r.edgeSimilarity.end(), edgeSimilarity);
+    if (connectivityOffsets) std::copy(r.connectivityOffsets.begin(), r.connectivityOffsets.end(), connectivityOffsets);
+    if (connectivityGenes) std::copy(r.connectivityGenes.begin(), r.connectivityGenes.end(), connectivityGenes);
+    if (connectivitySimilarities) std::copy(r.connectivitySimilarities.begin(), r.connectivitySimilarities.end(), connectivitySimilarities);
+    return EM2_OK;
+}
+
+void em2_gene_graph_free(em2_gene_graph* graph) { delete graph; }
 
 }  // extern "C"

@@ -1,0 +1,253 @@
+// em2_gene_graph.hip -- the GeneGraph constructor (src/GeneGraph.cpp:22-104) behind ExpressionMatrix::createGeneGraph
+// (src/ExpressionMatrixGeneGraph.cpp:44-89) and GeneGraph::getConnectivity (src/GeneGraph.cpp:108-143) on a SimilarGenePairs
+// object in device memory.  Integer / index work only, nothing is computed from a similarity: every output is
+// bit-exact.
+//
+// The reference adds a vertex per gene of the graph's gene set S, walks every gene's stored list (add_edge into a boost::setS
+// container: an edge that exists is not added again but still counts towards maxConnectivity), removes the vertices without an
+// edge and, for getConnectivity, iterates every vertex's out-edge set.  Here:
+//   * checkStoredPairsKernel    every stored pair of the SimilarGenePairs object names another gene of its gene set P, every
+//                               usedCount is at most k -- nothing below reads a list before this has passed;
+//   * runCellGraphEdges (em2_graph.hip)   the selection rule and the duplicate filter are the cell graph's: sel(v) = the first
+//                               <= maxConnectivity stored pairs at or above the threshold whose partner is in S; the edges in
+//                               insertion order are, for v0 ascending and v1 in sel(v0): (v0, v1) unless it is already in
+//                               sel(v0) or (v1 < v0 and v0 in sel(v1)).  Both id maps (S -> P for the row, P -> global -> S for
+//                               the partner) and their `consecutive` shortcut are that code's;
+//   * edgeRecordsKernel         two directed records per edge: key = vertex << 32 | neighbour, value = the similarity's bits;
+//   * rocPRIM's radix sort of the records by key.  An undirected edge exists once, so the keys are unique and the order is a
+//     function of the input alone: per vertex, the neighbours ascending;
+//   * connectivityOffsetsKernel the lower bound of v << 32 among the sorted keys for every v in [0, |S|]: the offsets of the
+//                               lists; a gene is alive where its list is not empty.  No degree is counted with atomics;
+//   * an exclusive scan of the alive flags, then geneGraphCompactKernel: the surviving genes in ascending order, and the
+//     neighbour half of every sorted key.
+
+#include "em2_gene_graph.h"
+#include "em2_hip_util.h"
+#include "em2_scratch.h"
+
+#include <cstring>            // (rocPRIM calls memset without including it)
+#include <rocprim/rocprim.hpp>
+
+namespace em2 {
+namespace {
+
+// Slot i = g * k + j of the pairs, for j < usedCount[g]: the partner is a local id of P other than g (findSimilarGenePairs0
+// writes nothing else; the walk would index P's id table with it).  Gene g: usedCount[g] <= k.
+__global__ void __launch_bounds__(256)
+checkStoredPairsKernel(const PairOut* __restrict__ pairs, const uint32_t* __restrict__ usedCount, uint32_t geneCount, uint32_t k,
+                       uint32_t* __restrict__ error)
+{
+    uint32_t bad = 0u;
+    const uint64_t stride = uint64_t(gridDim.x) * blockDim.x;
+    const uint64_t first = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    for (uint64_t g = first; g < geneCount; g += stride) {
+        if (usedCount[g] > k) bad |= kGeneGraphUsedCount;
+    }
+    const uint64_t slots = uint64_t(geneCount) * k;
+    for (uint64_t i = first; i < slots; i += stride) {
+        const uint32_t g = uint32_t(i / k);
+        const uint32_t j = uint32_t(i - uint64_t(g) * k);
+        if (j >= usedCount[g]) continue;
+        const uint32_t partner = pairs[i].cell;
+        if (partner >= geneCount) bad |= kGeneGraphPartnerRange;
+        else if (partner == g) bad |= kGeneGraphSelfPair;
+    }
+    if (bad) atomicOr(error, bad);
+}
+
+__global__ void __launch_bounds__(256)
+edgeRecordsKernel(const uint32_t* __restrict__ edge0, const uint32_t* __restrict__ edge1, const float* __restrict__ edgeSimilarity,
+                  uint64_t edgeCount, uint64_t* __restrict__ keys, uint32_t* __restrict__ values)
+{
+    for (uint64_t e = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; e < edgeCount; e += uint64_t(gridDim.x) * blockDim.x) {
+        const uint64_t v0 = edge0[e], v1 = edge1[e];
+        const uint32_t bits = __float_as_uint(edgeSimilarity[e]);
+        keys[2u * e] = v0 << 32 | v1;
+        keys[2u * e + 1u] = v1 << 32 | v0;
+        values[2u * e] = bits;
+        values[2u * e + 1u] = bits;
+    }
+}
+
+// The first of the ascending keys[0, n) that is not below `key`, n where there is none.
+__device__ __forceinline__ uint64_t lowerBound(const uint64_t* __restrict__ keys, uint64_t n, uint64_t key)
+{
+    uint64_t low = 0, high = n;
+    while (low < high) {
+        const uint64_t middle = low + (high - low) / 2u;
+        if (keys[middle] < key) low = middle + 1u;
+        else high = middle;
+    }
+    return low;
+}
+
+// offsets[v] = where the records of vertex v begin, v in [0, geneCount]; alive[v] = 1 where v has one, alive[geneCount] = 0
+// (the scan's last input: its output there is the number of vertices that stay).
+__global__ void __launch_bounds__(256)
+connectivityOffsetsKernel(const uint64_t* __restrict__ keys, uint64_t recordCount, uint32_t geneCount, uint64_t* __restrict__ offsets,
+                          uint32_t* __restrict__ alive)
+{
+    for (uint64_t v = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; v <= geneCount; v += uint64_t(gridDim.x) * blockDim.x) {
+        const uint64_t begin = lowerBound(keys, recordCount, v << 32);
+        offsets[v] = begin;
+        alive[v] = v < geneCount && begin < recordCount && (keys[begin] >> 32) == v ? 1u : 0u;
+    }
+}
+
+// vertices[rank[v]] = v for the genes that are alive (rank: the exclusive scan of alive); neighbours[i] = the low half of the
+// i-th sorted key.
+__global__ void __launch_bounds__(256)
+geneGraphCompactKernel(const uint32_t* __restrict__ alive, const uint64_t* __restrict__ rank, uint32_t geneCount,
+                       const uint64_t* __restrict__ keys, uint64_t recordCount, uint32_t* __restrict__ vertices,
+                       uint32_t* __restrict__ neighbours)
+{
+    const uint64_t stride = uint64_t(gridDim.x) * blockDim.x;
+    const uint64_t first = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    for (uint64_t v = first; v < geneCount; v += stride) {
+        if (alive[v]) vertices[rank[v]] = uint32_t(v);
+    }
+    for (uint64_t i = first; i < recordCount; i += stride) neighbours[i] = uint32_t(keys[i]);
+}
+
+template <class T> hipError_t toHost(std::vector<T>& to, const void* from, size_t count, hipStream_t stream)
+{
+    to.resize(count);
+    if (count == 0) return hipSuccess;
+    return hipMemcpyAsync(to.data(), from, count * sizeof(T), hipMemcpyDeviceToHost, stream);
+}
+
+}  // namespace
+
+hipError_t runGeneGraph(const PairOut* d_pairs, const uint32_t* d_usedCount, uint32_t pairsGeneCount, uint32_t k,
+                        const uint32_t* d_pairsGeneSet, bool pairsConsecutive, uint32_t pairsFirst, const uint32_t* d_graphGeneSet,
+                        bool graphConsecutive, uint32_t graphFirst, uint32_t graphGeneCount, double similarityThreshold,
+                        uint32_t maxConnectivity, GeneGraphResult& out, uint32_t* inputError, hipStream_t stream)
+{
+    *inputError = 0;
+    out = GeneGraphResult();
+    out.geneCount = graphGeneCount;
+    StageTimer timer("geneGraph");
+    const dim3 threads(256);
+    size_t at = 0;
+    const auto take = [&at](size_t bytes) {
+        const size_t here = at;
+        at += alignUp(bytes ? bytes : 1u);
+        return here;
+    };
+
+    // the stored pairs, then the edges in insertion order
+    const size_t slots = size_t(graphGeneCount) * maxConnectivity;
+    const size_t n1 = size_t(graphGeneCount) + 1u;
+    const size_t offError = take(256);
+    const size_t offEdge0 = take(slots * sizeof(uint32_t));
+    const size_t offEdge1 = take(slots * sizeof(uint32_t));
+    const size_t offEdgeSimilarity = take(slots * sizeof(float));
+    const size_t offOffsets = take(n1 * sizeof(uint64_t));
+    const size_t offAlive = take(n1 * sizeof(uint32_t));
+    const size_t offRank = take(n1 * sizeof(uint64_t));
+    const size_t offVertices = take(size_t(graphGeneCount) * sizeof(uint32_t));
+    size_t scanBytes = 0;
+    {
+        uint32_t* in = nullptr;
+        uint64_t* to = nullptr;
+        EM2_TRY(rocprim::exclusive_scan(nullptr, scanBytes, in, to, uint64_t(0), n1, rocprim::plus<uint64_t>(), stream));
+    }
+    const size_t offScanTemp = take(scanBytes);
+    CachedBuffer arena, recordArena;
+    EM2_TRY(arena.allocate(at));
+    char* base = arena.as<char>();
+    uint32_t* error = reinterpret_cast<uint32_t*>(base + offError);
+    uint32_t* edge0 = reinterpret_cast<uint32_t*>(base + offEdge0);
+    uint32_t* edge1 = reinterpret_cast<uint32_t*>(base + offEdge1);
+    float* edgeSimilarity = reinterpret_cast<float*>(base + offEdgeSimilarity);
+    uint64_t* offsets = reinterpret_cast<uint64_t*>(base + offOffsets);
+    uint32_t* alive = reinterpret_cast<uint32_t*>(base + offAlive);
+    uint64_t* rank = reinterpret_cast<uint64_t*>(base + offRank);
+    uint32_t* vertices = reinterpret_cast<uint32_t*>(base + offVertices);
+
+    EM2_TRY(hipMemsetAsync(error, 0, 256, stream));
+    checkStoredPairsKernel<<<dim3(gridFor(uint64_t(pairsGeneCount) * (k ? k : 1u))), threads, 0, stream>>>(d_pairs, d_usedCount, pairsGeneCount,
+                                                                                                         k, error);
+    EM2_TRY(hipGetLastError());
+    EM2_TRY(hipMemcpyAsync(inputError, error, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    EM2_TRY(hipStreamSynchronize(stream));
+    if (*inputError) {
+        arena.idle = true;
+        return hipSuccess;
+    }
+    EM2_TRY(timer.stage("check", stream));
+
+    // S is ascending: a gene's vertex is its position, the sorted ids are the set itself
+    uint64_t edgeCount = 0;
+    EM2_TRY(runCellGraphEdges(d_pairs, d_usedCount, pairsGeneCount, k, d_pairsGeneSet, d_graphGeneSet, d_graphGeneSet, nullptr,
+                              graphGeneCount, similarityThreshold, maxConnectivity, edge0, edge1, edgeSimilarity, &edgeCount, stream,
+                              pairsConsecutive, pairsFirst, graphConsecutive, graphFirst));
+    EM2_TRY(timer.stage("selection and edges", stream));
+    if (edgeCount > slots) {
+        arena.idle = true;
+        return hipErrorUnknown;
+    }
+
+    // the adjacency: 2 E directed records in (vertex, neighbour) order
+    const uint64_t recordCount = 2u * edgeCount;
+    const uint64_t* sortedKeys = nullptr;
+    const uint32_t* sortedValues = nullptr;
+    uint32_t* neighbours = nullptr;
+    if (recordCount) {
+        at = 0;
+        const size_t offKeysA = take(recordCount * sizeof(uint64_t));
+        const size_t offKeysB = take(recordCount * sizeof(uint64_t));
+        const size_t offValuesA = take(recordCount * sizeof(uint32_t));
+        const size_t offValuesB = take(recordCount * sizeof(uint32_t));
+        const size_t offNeighbours = take(recordCount * sizeof(uint32_t));
+        size_t sortBytes = 0;
+        {
+            rocprim::double_buffer<uint64_t> keys(nullptr, nullptr);
+            rocprim::double_buffer<uint32_t> values(nullptr, nullptr);
+            EM2_TRY(rocprim::radix_sort_pairs(nullptr, sortBytes, keys, values, size_t(recordCount), 0u, 64u, stream));
+        }
+        const size_t offSortTemp = take(sortBytes);
+        EM2_TRY(recordArena.allocate(at));
+        char* recordBase = recordArena.as<char>();
+        rocprim::double_buffer<uint64_t> keys(reinterpret_cast<uint64_t*>(recordBase + offKeysA), reinterpret_cast<uint64_t*>(recordBase + offKeysB));
+        rocprim::double_buffer<uint32_t> values(reinterpret_cast<uint32_t*>(recordBase + offValuesA), reinterpret_cast<uint32_t*>(recordBase + offValuesB));
+        neighbours = reinterpret_cast<uint32_t*>(recordBase + offNeighbours);
+        edgeRecordsKernel<<<dim3(gridFor(edgeCount)), threads, 0, stream>>>(edge0, edge1, edgeSimilarity, edgeCount, keys.current(),
+                                                                           values.current());
+        EM2_TRY(hipGetLastError());
+        EM2_TRY(rocprim::radix_sort_pairs(recordBase + offSortTemp, sortBytes, keys, values, size_t(recordCount), 0u, 64u, stream));
+        sortedKeys = keys.current();
+        sortedValues = values.current();
+        EM2_TRY(timer.stage("records and sort", stream));
+    }
+
+    // (with no record the searches find nothing and read nothing: every offset 0, nobody alive)
+    connectivityOffsetsKernel<<<dim3(gridFor(n1)), threads, 0, stream>>>(sortedKeys, recordCount, graphGeneCount, offsets, alive);
+    EM2_TRY(hipGetLastError());
+    EM2_TRY(rocprim::exclusive_scan(base + offScanTemp, scanBytes, alive, rank, uint64_t(0), n1, rocprim::plus<uint64_t>(), stream));
+    geneGraphCompactKernel<<<dim3(gridFor(recordCount > graphGeneCount ? recordCount : graphGeneCount)), threads, 0, stream>>>(
+        alive, rank, graphGeneCount, sortedKeys, recordCount, vertices, neighbours);
+    EM2_TRY(hipGetLastError());
+    uint64_t vertexCount = 0;
+    EM2_TRY(hipMemcpyAsync(&vertexCount, rank + graphGeneCount, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    EM2_TRY(hipStreamSynchronize(stream));
+    EM2_TRY(timer.stage("offsets and vertices", stream));
+    if (vertexCount > graphGeneCount) {
+        arena.idle = recordArena.idle = true;
+        return hipErrorUnknown;
+    }
+
+    EM2_TRY(toHost(out.vertices, vertices, size_t(vertexCount), stream));
+    EM2_TRY(toHost(out.edge0, edge0, size_t(edgeCount), stream));
+    EM2_TRY(toHost(out.edge1, edge1, size_t(edgeCount), stream));
+    EM2_TRY(toHost(out.edgeSimilarity, edgeSimilarity, size_t(edgeCount), stream));
+    EM2_TRY(toHost(out.connectivityOffsets, offsets, n1, stream));
+    EM2_TRY(toHost(out.connectivityGenes, neighbours, size_t(recordCount), stream));
+    EM2_TRY(toHost(out.connectivitySimilarities, sortedValues, size_t(recordCount), stream));
+    EM2_TRY(hipStreamSynchronize(stream));
+    EM2_TRY(timer.stage("results to the host", stream));
+    arena.idle = recordArena.idle = true;                       // (everything that used the blocks has been waited for)
+    return hipSuccess;
+}
+
+}  // namespace em2

@@ -28,6 +28,7 @@ extern "C" int em2_internal_gene_information(const uint64_t* rowToc, const em2_c
 #include <cmath>
 #include <cstring>
 #include <fstream>
+#include <iterator>
 #include <dirent.h>
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -699,11 +700,14 @@ void Matrix::geneInformation(const std::string& geneSetName, const std::string& 
 // "Gene set X already exists." (ExpressionMatrix.cpp:2044, ExpressionMatrixGeneSets.cpp:322): the sets this object knows, and
 // -- the reference keeps every set of the directory open, this object only those it found when it was opened -- a set whose
 // files another object has written into the directory since.
+bool Matrix::knowsGeneSet(const std::string& name) const
+{
+    return geneSets_.find(name) != geneSets_.end() || fileExists(directoryName_ + "/GeneSet-" + name + "-GlobalIds");
+}
+
 void Matrix::failIfGeneSetExists(const std::string& name) const
 {
-    if (geneSets_.find(name) != geneSets_.end() || fileExists(directoryName_ + "/GeneSet-" + name + "-GlobalIds")) {
-        fail(EM2_ERROR_RUNTIME, "Gene set " + name + " already exists.");
-    }
+    if (knowsGeneSet(name)) fail(EM2_ERROR_RUNTIME, "Gene set " + name + " already exists.");
 }
 
 void Matrix::addGeneSubset(const std::string& name, const GeneSet& from, const std::vector<bool>& keep)
@@ -712,6 +716,11 @@ void Matrix::addGeneSubset(const std::string& name, const GeneSet& from, const s
     for (uint32_t local = 0; local < from.size(); local++) {
         if (keep[local]) ids.push_back(from.genes()[local]);
     }
+    addGeneSetOf(name, ids);
+}
+
+void Matrix::addGeneSetOf(const std::string& name, const std::vector<uint32_t>& ids)
+{
     addGeneSet(directoryName_, name, ids.data(), uint32_t(ids.size()), 0);
     std::unique_ptr<GeneSet> g(new GeneSet);
     g->globalIds.openExisting(directoryName_ + "/GeneSet-" + name + "-GlobalIds", false, sizeof(uint32_t));
@@ -760,6 +769,86 @@ void Matrix::removeGeneSet(const std::string& geneSetName)
     geneSets_.erase(it);
     removeFile(directoryName_ + "/GeneSet-" + geneSetName + "-GlobalIds");
     removeFile(directoryName_ + "/GeneSet-" + geneSetName + "-LocalIds");
+}
+
+bool Matrix::createGeneSetIntersectionOrUnion(const std::string& commaSeparatedInputSetsNames, const std::string& outputSetName,
+                                              bool doUnion, std::string& message)
+{
+    // ExpressionMatrixGeneSets.cpp:196-212: the output name, then every input in order
+    if (knowsGeneSet(outputSetName)) {
+        message = "Gene set " + outputSetName + " already exists.";
+        return false;
+    }
+    std::vector<std::string> names(1);                       // boost::split on ",": empty pieces stay
+    for (const char c : commaSeparatedInputSetsNames) {
+        if (c == ',') names.emplace_back();
+        else names.back().push_back(c);
+    }
+    for (const std::string& name : names) {
+        if (geneSets_.find(name) == geneSets_.end()) {
+            message = "gene set " + name + " does not exists.";       // sic, :209
+            return false;
+        }
+    }
+    std::vector<uint32_t> result;                            // :215-238
+    for (size_t i = 0; i < names.size(); i++) {
+        const GeneSet& input = geneSet(names[i]);
+        const uint32_t* first = input.genes();
+        const uint32_t* last = first + input.size();
+        if (i == 0) {
+            result.assign(first, last);
+            continue;
+        }
+        std::vector<uint32_t> next;
+        if (doUnion) std::set_union(result.begin(), result.end(), first, last, std::back_inserter(next));
+        else std::set_intersection(result.begin(), result.end(), first, last, std::back_inserter(next));
+        result.swap(next);
+    }
+    addGeneSetOf(outputSetName, result);
+    return true;
+}
+
+bool Matrix::createGeneSetDifference(const std::string& inputSetName0, const std::string& inputSetName1, const std::string& outputSetName,
+                                     std::string& message)
+{
+    // ExpressionMatrixGeneSets.cpp:259-281
+    if (knowsGeneSet(outputSetName)) {
+        message = "Gene set " + outputSetName + " already exists.";
+        return false;
+    }
+    for (const std::string* name : {&inputSetName0, &inputSetName1}) {
+        if (geneSets_.find(*name) == geneSets_.end()) {
+            message = "Gene set " + *name + " does not exists.";      // sic, :270, :277
+            return false;
+        }
+    }
+    const GeneSet& input0 = geneSet(inputSetName0);
+    const GeneSet& input1 = geneSet(inputSetName1);
+    std::vector<uint32_t> result;
+    std::set_difference(input0.genes(), input0.genes() + input0.size(), input1.genes(), input1.genes() + input1.size(),
+                        std::back_inserter(result));
+    addGeneSetOf(outputSetName, result);
+    return true;
+}
+
+void Matrix::createGeneGraph(const std::string& geneSetName, const std::string& similarGenePairsName, int64_t k, double similarityThreshold,
+                             em2_gene_graph** graph) const
+{
+    // ExpressionMatrixGeneGraph.cpp:65-77: the gene set, not empty, then the SimilarGenePairs object with all its checks
+    const GeneSet& genes = geneSet(geneSetName);
+    if (genes.size() == 0) fail(EM2_ERROR_RUNTIME, "Gene set " + geneSetName + " is empty.");
+    SimilarGenePairsInfo info;
+    std::vector<em2_pair> pairs;
+    std::vector<uint32_t> used;
+    readSimilarGenePairs(directoryName_, similarGenePairsName, info, &pairs, &used);
+    if (info.k > 0xffffffffULL) fail(EM2_ERROR_INVALID_ARGUMENT, "createGeneGraph: k of the SimilarGenePairs object out of range");
+    // the gene set of the pairs, from the file the reader has just checked against the object's hash (SimilarGenePairs.cpp:64)
+    MappedFile pairsGenes;
+    pairsGenes.openExisting(directoryName_ + "/GeneSet-" + info.geneSetName + "-GlobalIds", false, sizeof(uint32_t));
+    const int rc = em2_gene_graph_create(pairs.data(), used.data(), uint32_t(info.geneCount), uint32_t(info.k),
+                                         static_cast<const uint32_t*>(pairsGenes.data()), genes.genes(), genes.size(), similarityThreshold,
+                                         uint64_t(k), graph);                                       // (size_t) int, GeneGraph.cpp:28
+    if (rc != EM2_OK) fail(rc, em2_last_error());
 }
 
 void Matrix::analyzeSimilarPairs(const std::string& similarPairsName, double csvDownsample, const std::string& outputDirectory) const

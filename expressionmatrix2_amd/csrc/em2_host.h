@@ -135,6 +135,18 @@ public:
     void analyzeLshSignatures(const std::string& geneSetName, const std::string& cellSetName, size_t lshCount, unsigned int seed,
                               const std::string& outputDirectory) const;
 
+    // ExpressionMatrix::createGeneGraph (src/ExpressionMatrixGeneGraph.cpp:54-89) without its name bookkeeping: the lookups and
+    // their errors, then em2_gene_graph_create on SimilarGenePairs-<similarGenePairsName>.  k is the reference's int, which the
+    // GeneGraph constructor takes as a size_t.  The caller frees *graph.
+    void createGeneGraph(const std::string& geneSetName, const std::string& similarGenePairsName, int64_t k, double similarityThreshold,
+                         em2_gene_graph** graph) const;
+    // createGeneSetIntersection / createGeneSetUnion (src/ExpressionMatrixGeneSets.cpp:183-250) and createGeneSetDifference
+    // (:254-305).  false and `message` = the line the reference prints where it returns false; it does not throw for these.
+    bool createGeneSetIntersectionOrUnion(const std::string& commaSeparatedInputSetsNames, const std::string& outputSetName, bool doUnion,
+                                          std::string& message);
+    bool createGeneSetDifference(const std::string& inputSetName0, const std::string& inputSetName1, const std::string& outputSetName,
+                                 std::string& message);
+
     // ExpressionMatrix::computeGeneInformationContent (src/ExpressionMatrix.cpp:1947-2018) for the genes of a gene set over a
     // cell set, and the cells expressing every gene (src/ExpressionMatrixGeneSets.cpp:336-350); either vector may be NULL.
     // The cells' norm inverses come from the Cells file where the directory has one.
@@ -155,6 +167,9 @@ public:
 private:
     // Writes GeneSet-<name>-* for the genes of `from` that `keep` names (ascending local id) and opens the new set.
     void addGeneSubset(const std::string& name, const GeneSet& from, const std::vector<bool>& keep);
+    // The same for ascending global ids.
+    void addGeneSetOf(const std::string& name, const std::vector<uint32_t>& ids);
+    bool knowsGeneSet(const std::string& name) const;
     void failIfGeneSetExists(const std::string& name) const;
     std::string directoryName_;
     MappedFile toc_;         // CellExpressionCounts.toc  (uint64)

@@ -38,6 +38,17 @@ int nullArgument(const char* function)
     return EM2_ERROR_INVALID_ARGUMENT;
 }
 
+// The set operations' "false": EM2_OK, *created = 0 and the reference's line as the last error.
+template <class F> int geneSetOperation(int* created, F f)
+{
+    *created = 0;
+    return guarded([&] {
+        std::string message;
+        *created = f(message) ? 1 : 0;
+        if (!*created) em2_internal_set_last_error(message.c_str());
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -100,6 +111,39 @@ int em2_matrix_analyze_lsh_signatures(em2_matrix* matrix, const char* geneSetNam
     if (!matrix || !geneSetName || !cellSetName) return nullArgument("em2_matrix_analyze_lsh_signatures");
     return guarded([&] {
         matrix->impl->analyzeLshSignatures(geneSetName, cellSetName, lshCount, seed, outputDirectory ? outputDirectory : "");
+    });
+}
+
+int em2_matrix_create_gene_graph(em2_matrix* matrix, const char* geneSetName, const char* similarGenePairsName, int64_t k,
+                                 double similarityThreshold, em2_gene_graph** graph)
+{
+    if (!matrix || !geneSetName || !similarGenePairsName || !graph) return nullArgument("em2_matrix_create_gene_graph");
+    *graph = nullptr;
+    return guarded([&] { matrix->impl->createGeneGraph(geneSetName, similarGenePairsName, k, similarityThreshold, graph); });
+}
+
+int em2_matrix_create_gene_set_intersection(em2_matrix* matrix, const char* inputSetsNames, const char* outputSetName, int* created)
+{
+    if (!matrix || !inputSetsNames || !outputSetName || !created) return nullArgument("em2_matrix_create_gene_set_intersection");
+    return geneSetOperation(created, [&](std::string& message) {
+        return matrix->impl->createGeneSetIntersectionOrUnion(inputSetsNames, outputSetName, false, message);
+    });
+}
+
+int em2_matrix_create_gene_set_union(em2_matrix* matrix, const char* inputSetsNames, const char* outputSetName, int* created)
+{
+    if (!matrix || !inputSetsNames || !outputSetName || !created) return nullArgument("em2_matrix_create_gene_set_union");
+    return geneSetOperation(created, [&](std::string& message) {
+        return matrix->impl->createGeneSetIntersectionOrUnion(inputSetsNames, outputSetName, true, message);
+    });
+}
+
+int em2_matrix_create_gene_set_difference(em2_matrix* matrix, const char* inputSetName0, const char* inputSetName1,
+                                          const char* outputSetName, int* created)
+{
+    if (!matrix || !inputSetName0 || !inputSetName1 || !outputSetName || !created) return nullArgument("em2_matrix_create_gene_set_difference");
+    return geneSetOperation(created, [&](std::string& message) {
+        return matrix->impl->createGeneSetDifference(inputSetName0, inputSetName1, outputSetName, message);
     });
 }
 

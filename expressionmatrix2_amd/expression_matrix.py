@@ -54,10 +54,12 @@ class ExpressionMatrix:
         self._cellGraphs = {}          # ExpressionMatrix::cellGraphs (src/ExpressionMatrix.hpp): in memory only
         self._clusterGraphs = {}       # ExpressionMatrix::clusterGraphs, likewise
         self._signatureGraphs = {}     # ExpressionMatrix::signatureGraphs, likewise
+        self._geneGraphs = {}          # ExpressionMatrix::geneGraphs, likewise
         capi.check(capi.load().em2_matrix_open(_b(directoryName), ctypes.byref(self._handle)))
 
     def close(self):
         self._signatureGraphs = {}
+        self._geneGraphs = {}
         if self._handle:
             capi.load().em2_matrix_close(self._handle)
             self._handle = ctypes.c_void_p(None)
@@ -138,6 +140,28 @@ class ExpressionMatrix:
     def removeGeneSet(self, geneSetName):
         """ExpressionMatrix::removeGeneSet (src/ExpressionMatrixGeneSets.cpp:12-32)."""
         capi.check(capi.load().em2_matrix_remove_gene_set(self._handle, _b(geneSetName)))
+
+    # ---- src/PythonModule.cpp:539-584 ----
+    def _gene_set_operation(self, entry, *names):
+        created = ctypes.c_int(0)
+        capi.check(entry(self._handle, *[_b(name) for name in names], ctypes.byref(created)))
+        if not created.value:
+            print(capi.last_error())             # the reference writes the line to cout and returns false; it does not throw
+        return bool(created.value)
+
+    def createGeneSetIntersection(self, inputSets, outputSet):
+        """ExpressionMatrix::createGeneSetIntersection (src/ExpressionMatrixGeneSets.cpp:183-250): inputSets is a
+        comma-separated list of gene set names.  False, and a printed line, when the output exists or an input is missing."""
+        return self._gene_set_operation(capi.load().em2_matrix_create_gene_set_intersection, inputSets, outputSet)
+
+    def createGeneSetUnion(self, inputSets, outputSet):
+        """ExpressionMatrix::createGeneSetUnion (src/ExpressionMatrixGeneSets.cpp:187-250), as createGeneSetIntersection."""
+        return self._gene_set_operation(capi.load().em2_matrix_create_gene_set_union, inputSets, outputSet)
+
+    def createGeneSetDifference(self, inputSet0, inputSet1, outputSet):
+        """ExpressionMatrix::createGeneSetDifference (src/ExpressionMatrixGeneSets.cpp:254-305): the genes of inputSet0 that
+        are not in inputSet1.  False, and a printed line, when the output exists or an input is missing."""
+        return self._gene_set_operation(capi.load().em2_matrix_create_gene_set_difference, inputSet0, inputSet1, outputSet)
 
     def getGeneSetGenes(self, geneSetName):
         """The global ids of the genes of a gene set, ascending (src/ExpressionMatrixGeneSets.cpp:57-63)."""
@@ -257,6 +281,62 @@ class ExpressionMatrix:
         """(vertex 0, vertex 1) per edge, uint32, in the order SignatureGraph::createEdges adds them; vertex 1 > vertex 0."""
         g = self._signature_graph(signatureGraphName)
         return g["edgeVertex0"].copy(), g["edgeVertex1"].copy()
+
+    # ---- src/PythonModule.cpp:1137-1161 ----
+    def createGeneGraph(self, geneGraphName=_REQUIRED, geneSetName="AllGenes", similarGenePairsName=_REQUIRED, k=_REQUIRED,
+                        similarityThreshold=_REQUIRED):
+        """ExpressionMatrix::createGeneGraph (src/ExpressionMatrixGeneGraph.cpp:44-89): a vertex per gene of the gene set, an
+        edge to each of the first k stored similar genes at or above similarityThreshold that are in the gene set too (k <= 0:
+        no limit), the vertices without an edge removed (em2_gene_graph_create, on the GPU).  Prints the reference's message.
+        The graph lives in memory, like the reference's; nothing is laid out or drawn."""
+        if _REQUIRED in (geneGraphName, similarGenePairsName, k, similarityThreshold):
+            raise TypeError("createGeneGraph(): geneGraphName, similarGenePairsName, k and similarityThreshold are required")
+        _b(geneGraphName)
+        if isinstance(k, float) or not -2 ** 31 <= int(k) < 2 ** 31:                       # int (:48)
+            raise ValueError("createGeneGraph(): k must be an integer that fits an int")
+        if geneGraphName in self._signatureGraphs:                                         # sic: the signature graphs (:63)
+            raise RuntimeError("Signature graph " + geneGraphName + " already exists.")
+        handle = ctypes.c_void_p(None)
+        capi.check(capi.load().em2_matrix_create_gene_graph(self._handle, _b(geneSetName), _b(similarGenePairsName), int(k),
+                                                            similarityThreshold, ctypes.byref(handle)))
+        graph = capi.gene_graph_take(handle)
+        graph["geneSet"] = np.array(self.getGeneSetGenes(geneSetName), dtype=np.uint32)
+        print("The gene graph has %d vertices and %d edges\nafter %d vertices were removed. " % (
+            len(graph["vertices"]), len(graph["edgeGene0"]), graph["removedCount"]))       # src/GeneGraph.cpp:101-103
+        self._geneGraphs.setdefault(geneGraphName, graph)       # map::insert (:88): under an existing name the FIRST graph stays
+
+    def removeGeneGraph(self, geneGraphName):
+        self._gene_graph(geneGraphName)
+        del self._geneGraphs[geneGraphName]
+
+    def _gene_graph(self, geneGraphName):
+        if geneGraphName not in self._geneGraphs:
+            raise RuntimeError("Gene graph " + geneGraphName + " does not exists.")        # sic, :29, :97
+        return self._geneGraphs[geneGraphName]
+
+    def getGeneGraphConnectivity(self, geneGraphName):
+        """ExpressionMatrix::getGeneGraphConnectivity (src/ExpressionMatrixGeneGraph.cpp:103-110): for every local gene id of
+        the graph's gene set the list of (local gene id of the neighbour, similarity); empty for a gene whose vertex was
+        removed.  Within a list the neighbours ascend by local id (the reference's order there is that of heap addresses)."""
+        g = self._gene_graph(geneGraphName)
+        offsets = g["connectivityOffsets"].tolist()
+        pairs = list(zip(g["connectivityGenes"].tolist(), g["connectivitySimilarities"].tolist()))
+        return [pairs[offsets[v]:offsets[v + 1]] for v in range(len(offsets) - 1)]
+
+    # The reference shows a gene graph through getGeneGraphConnectivity and its HTTP pages only; these accessors are this package's.
+    def getGeneGraphNames(self):
+        return sorted(self._geneGraphs)
+
+    def getGeneGraphVertices(self, geneGraphName):
+        """The global ids of the genes that kept a vertex, ascending (uint32)."""
+        g = self._gene_graph(geneGraphName)
+        return g["geneSet"][g["vertices"]]
+
+    def getGeneGraphEdges(self, geneGraphName):
+        """(local gene id 0, local gene id 1, similarity) per edge, in the order the reference's add_edge created them; the ids
+        are local to the graph's gene set, as in getGeneGraphConnectivity."""
+        g = self._gene_graph(geneGraphName)
+        return g["edgeGene0"].copy(), g["edgeGene1"].copy(), g["edgeSimilarity"].copy()
 
     # ---- src/PythonModule.cpp:852-865 ----
     def findSimilarPairs5(self, geneSetName="AllGenes", cellSetName="AllCells", lshName=_REQUIRED,

@@ -656,6 +656,52 @@ int em2_dev_lsh_signature_statistics(const uint64_t* d_signatures, uint32_t cell
 int em2_analyze_lsh_signatures(const uint64_t* signatures, uint32_t cellCount, uint32_t lshCount, const char* directory);
 
 /* ------------------------------------------------------------------------------------------------------
+ * The gene graph: the consumer of the SimilarGenePairs-<name> objects.  csrc/em2_gene_graph.hip, DESIGN.md 3.14.
+ * Integer / index work, nothing is computed from a similarity: every output is bit-exact.
+ * ------------------------------------------------------------------------------------------------------ */
+
+/* The GeneGraph constructor (src/GeneGraph.cpp:22-104), which ExpressionMatrix::createGeneGraph
+ * (src/ExpressionMatrixGeneGraph.cpp:44-89) calls after its lookups, and GeneGraph::getConnectivity (src/GeneGraph.cpp:108-143):
+ *   vertices   one per gene of the graph's gene set S, in set order (:40-43);
+ *   edges      for every gene g0 of S in order that is also in the pairs' gene set P (:61-64), its stored list is walked up to
+ *              the first entry with float similarity < double similarityThreshold (:71: equal stays, a NaN stays and the walk
+ *              goes on); a partner outside S is skipped and does not count (:76-77); every other one is an add_edge and counts,
+ *              and the walk ends when the count EQUALS maxConnectivity (:80-83: 0, and the negative Python int that size_t
+ *              turned into 2^64 - 1, never match -- no limit).  The out-edge container is boost::setS (src/GeneGraph.hpp:33-38):
+ *              an add_edge of an edge that exists adds nothing, STILL COUNTS, and the edge keeps the similarity of its first
+ *              insertion.  The edges come out in the order they were created;
+ *   removal    every vertex without an edge is removed (:88-99); a gene whose own list selected nothing stays where another
+ *              gene selected it;
+ *   connectivity   per local id of S the (local id in S of the neighbour, similarity) of every incident edge; nothing for a
+ *              removed gene.  WITHIN A LIST THE NEIGHBOURS ASCEND BY LOCAL ID.  That is this library's definition: the reference
+ *              iterates a std::set keyed on listS vertex descriptors, which are heap pointers, so its order is undefined.
+ * pairs [pairsGeneCount][k] (local ids in P) and usedCount [pairsGeneCount]: the SimilarGenePairs object, host memory
+ * (em2_dev_gene_graph_create: device memory).  pairsGeneSet / graphGeneSet: the global ids of P and S, host memory in both
+ * entries, strictly ascending (EM2_ERROR_INVALID_ARGUMENT otherwise).  graphGeneCount 0 is an error, as the reference's empty gene
+ * set is; pairsGeneCount 0 is a graph without vertices.
+ * Outside the contract, EM2_ERROR_INVALID_ARGUMENT and no guess: a stored pair (any of the usedCount[g] first of a gene of P,
+ * walked or not) whose partner is the gene itself or a local id >= pairsGeneCount -- findSimilarGenePairs0 writes neither --
+ * and a usedCount above k.
+ * The result is an object: em2_gene_graph_sizes (vertices that stay, edges, vertices removed: the three numbers of the
+ * reference's message, :101-103), then em2_gene_graph_get into arrays of those sizes (any may be NULL):
+ *   vertices[vertexCount]          the local ids in S of the genes that stay, ascending;
+ *   edgeGene0 / edgeGene1 / edgeSimilarity[edgeCount]   local ids in S, in insertion order;
+ *   connectivityOffsets[graphGeneCount + 1], connectivityGenes / connectivitySimilarities[2 * edgeCount].
+ * Not built: the Graphviz output, the layout, the SVG and the colouring by meta data (src/GeneGraph.cpp:146-,
+ * src/ExpressionMatrixGeneGraph.cpp:114-173). */
+typedef struct em2_gene_graph em2_gene_graph;
+int em2_gene_graph_create(const em2_pair* pairs, const uint32_t* usedCount, uint32_t pairsGeneCount, uint32_t k,
+                          const uint32_t* pairsGeneSet, const uint32_t* graphGeneSet, uint32_t graphGeneCount,
+                          double similarityThreshold, uint64_t maxConnectivity, em2_gene_graph** graph);
+int em2_dev_gene_graph_create(const em2_pair* d_pairs, const uint32_t* d_usedCount, uint32_t pairsGeneCount, uint32_t k,
+                              const uint32_t* pairsGeneSet, const uint32_t* graphGeneSet, uint32_t graphGeneCount,
+                              double similarityThreshold, uint64_t maxConnectivity, em2_gene_graph** graph);
+int em2_gene_graph_sizes(const em2_gene_graph* graph, uint32_t* vertexCount, uint64_t* edgeCount, uint32_t* removedCount);
+int em2_gene_graph_get(const em2_gene_graph* graph, uint32_t* vertices, uint32_t* edgeGene0, uint32_t* edgeGene1, float* edgeSimilarity,
+                       uint64_t* connectivityOffsets, uint32_t* connectivityGenes, float* connectivitySimilarities);
+void em2_gene_graph_free(em2_gene_graph* graph);
+
+/* ------------------------------------------------------------------------------------------------------
  * ExpressionMatrix-level entry points: the methods the reference binds to Python (src/PythonModule.cpp),
  * operating by NAME on a data directory in the reference's memory-mapped formats.  Results are files in
  * that directory (SimilarPairs-<name>-{Info,Pairs,CellInfo}, Lsh-<name>-{Info,Signatures}), byte-compatible
@@ -699,6 +745,28 @@ int em2_matrix_create_signature_graph(em2_matrix* matrix, const char* cellSetNam
  * no tmp-Lsh files are created), then em2_analyze_lsh_signatures into outputDirectory (NULL or "": the working directory). */
 int em2_matrix_analyze_lsh_signatures(em2_matrix* matrix, const char* geneSetName, const char* cellSetName, size_t lshCount,
                                       unsigned int seed, const char* outputDirectory);
+
+/* ExpressionMatrix::createGeneGraph's lookups (src/ExpressionMatrixGeneGraph.cpp:65-77; bound at src/PythonModule.cpp:1137-1161)
+ * and em2_gene_graph_create on SimilarGenePairs-<similarGenePairsName>: "Gene set X does not exist." / "Gene set X is empty.",
+ * then the errors of em2_similar_gene_pairs_read for a missing or inconsistent object.  k is the reference's int: it becomes
+ * maxConnectivity as (size_t) k, so 0 and every negative value mean no limit.  The ids of the graph are local to the gene set
+ * (em2_matrix_gene_set gives the global ones).  The names of the graphs are kept by the caller, the reference's slips with them:
+ * the name is checked against the SIGNATURE graphs ("Signature graph X already exists.", :63) and a second gene graph under an
+ * existing name is built and then dropped by map::insert (:88); "Gene graph X does not exists." */
+int em2_matrix_create_gene_graph(em2_matrix* matrix, const char* geneSetName, const char* similarGenePairsName, int64_t k,
+                                 double similarityThreshold, em2_gene_graph** graph);
+
+/* ExpressionMatrix::createGeneSetIntersection / createGeneSetUnion (src/ExpressionMatrixGeneSets.cpp:183-250) and
+ * createGeneSetDifference (:254-305), on the host.  inputSetsNames: names separated by commas, split as boost::split does (an
+ * empty piece is a name; nothing is trimmed); the result is std::set_intersection / std::set_union folded from the left, for the
+ * difference std::set_difference of set 0 and set 1.  The reference does not throw here: it prints a line and returns false.
+ * *created = 0 and EM2_OK then, and em2_last_error() is that line: "Gene set X already exists." for the output, then for the
+ * first missing input "gene set X does not exists." (intersection, union; sic) / "Gene set X does not exists." (difference).
+ * An empty result is a gene set without genes. */
+int em2_matrix_create_gene_set_intersection(em2_matrix* matrix, const char* inputSetsNames, const char* outputSetName, int* created);
+int em2_matrix_create_gene_set_union(em2_matrix* matrix, const char* inputSetsNames, const char* outputSetName, int* created);
+int em2_matrix_create_gene_set_difference(em2_matrix* matrix, const char* inputSetName0, const char* inputSetName1,
+                                          const char* outputSetName, int* created);
 
 /* ExpressionMatrix::findSimilarPairs5 (src/ExpressionMatrixLsh.cpp:312-501; src/PythonModule.cpp:852-865,
  * default bucketOverflow=1000). */
