@@ -19,6 +19,7 @@ PAIR_DTYPE = np.dtype([("cell", "<u4"), ("similarity", "<f4")])
 COUNT_DTYPE = np.dtype([("gene", "<u4"), ("count", "<f4")])
 
 EM2_OK = 0
+EM2_ERROR_INVALID_ARGUMENT = 1
 EM2_ERROR_NO_DEVICE = 2
 EM2_ERROR_UNSUPPORTED = 6
 
@@ -153,6 +154,22 @@ SYMBOLS = {
     "em2_matrix_create_gene_set_intersection": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.POINTER(_c.c_int)]),
     "em2_matrix_create_gene_set_union": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.POINTER(_c.c_int)]),
     "em2_matrix_create_gene_set_difference": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_char_p, _c.POINTER(_c.c_int)]),
+    "em2_dev_dense_expression_workspace": (_c.c_size_t, [_c.c_uint32]),
+    "em2_dev_dense_expression": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_uint32, _c.c_uint32,
+                                            _c.c_int, _c.c_uint32, _c.c_uint32, _c.c_int, _c.c_void_p, _c.c_uint64, _c.c_void_p,
+                                            _c.c_size_t, _c.c_void_p]),
+    "em2_dense_expression": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_uint32,
+                                        _c.c_uint32, _c.c_int, _c.c_int, _c.c_void_p, _c.c_uint64]),
+    "em2_matrix_dense_expression": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_int, _c.c_int, _c.c_uint32, _c.c_uint32,
+                                               _c.c_void_p]),
+    "em2_matrix_cell_expression_counts": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.POINTER(_c.c_uint64), _c.c_void_p]),
+    "em2_matrix_create_cell_set": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_void_p, _c.c_uint32]),
+    "em2_matrix_create_cell_set_intersection": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p]),
+    "em2_matrix_create_cell_set_union": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p]),
+    "em2_matrix_create_cell_set_difference": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_char_p]),
+    "em2_matrix_downsample_cell_set": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_double, _c.c_int]),
+    "em2_matrix_remove_cell_set": (_c.c_int, [_c.c_void_p, _c.c_char_p]),
+    "em2_matrix_cell_set_names": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_uint64), _c.c_void_p]),
     "em2_analyze_lsh": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_void_p, _c.c_uint32, _c.c_void_p,
                                    _c.c_uint32, _c.c_double, _c.c_char_p, _c.c_char_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
                                    _c.c_void_p, _c.c_void_p]),
@@ -740,6 +757,65 @@ def dev_gene_information_content(toc, data, gene_count, norm_inverse=None):
                                                workspace_bytes, stream.cuda_stream))
     torch.cuda.current_stream().wait_stream(stream)
     return d_single.cpu().numpy(), d_double.cpu().numpy(), d_expressing.cpu().numpy().view(np.uint32)
+
+
+DENSE_FLOAT64, DENSE_FLOAT32 = 0, 1
+DENSE_ELEMENT_TYPES = {np.dtype(np.float64): DENSE_FLOAT64, np.dtype(np.float32): DENSE_FLOAT32}
+
+
+def dense_element_type(dtype):
+    """EM2_DENSE_FLOAT64 / EM2_DENSE_FLOAT32 for np.float64 / np.float32; ValueError for anything else."""
+    try:
+        return DENSE_ELEMENT_TYPES[np.dtype(dtype)]
+    except (KeyError, TypeError):
+        raise ValueError("dtype must be np.float64 or np.float32, got %r" % (dtype,)) from None
+
+
+def dense_expression(toc, data, gene_count, normalization_method=0, dtype=np.float64, cell_ids=None, gene_local_ids=None, pitch=None):
+    """getDenseExpressionMatrix (src/PythonModule.cpp:112-138) of a host CSR through em2_dense_expression -> ndarray
+    [cells, gene_count] (the first gene_count columns of an array [cells, pitch] when pitch is given).  cell_ids: the rows of the
+    CSR the result has, in that order; gene_local_ids: a GeneSet-*-LocalIds table for a CSR in global gene ids."""
+    toc = np.ascontiguousarray(toc, dtype=np.uint64)
+    data = np.ascontiguousarray(data, dtype=COUNT_DTYPE)
+    csr_cells = len(toc) - 1
+    if cell_ids is not None:
+        cell_ids = np.ascontiguousarray(cell_ids, dtype=np.uint32)
+    if gene_local_ids is not None:
+        gene_local_ids = np.ascontiguousarray(gene_local_ids, dtype=np.uint32)
+    cells = csr_cells if cell_ids is None else len(cell_ids)
+    pitch = gene_count if pitch is None else pitch
+    out = np.zeros((cells, pitch), dtype=dtype)
+    check(load().em2_dense_expression(_ptr(toc), _ptr(data), csr_cells, _ptr(cell_ids) if cell_ids is not None else None, cells,
+                                      _ptr(gene_local_ids) if gene_local_ids is not None else None,
+                                      len(gene_local_ids) if gene_local_ids is not None else 0, gene_count, int(normalization_method),
+                                      dense_element_type(dtype), _ptr(out), pitch))
+    return out[:, :gene_count]
+
+
+def dev_dense_expression(d_toc, d_data, cell_count, gene_count, normalization_method, d_out, pitch=None, row_begin=0, row_end=None,
+                         d_cell_ids=None, d_gene_local_ids=None, global_gene_count=0, d_workspace=None, stream=None):
+    """em2_dev_dense_expression on torch tensors: d_toc int64 [cells of the CSR + 1], d_data the (gene, count) records as bytes,
+    d_out a float64 or float32 tensor of at least (row_end - row_begin) * pitch elements, which receives the rows
+    [row_begin, row_end) of the result (cell_count rows: the CSR's, or those of d_cell_ids).  Runs on `stream` (a
+    torch.cuda.Stream; default: the current one) and synchronises it."""
+    import torch
+    lib = load()
+    row_end = cell_count if row_end is None else row_end
+    pitch = gene_count if pitch is None else pitch
+    if d_out.dtype not in (torch.float64, torch.float32):
+        raise ValueError("d_out must be a float64 or float32 tensor")
+    if not d_out.is_contiguous() or d_out.numel() < max(row_end - row_begin, 0) * pitch:
+        raise ValueError("d_out must be contiguous and hold (row_end - row_begin) * pitch elements")
+    element_type = DENSE_FLOAT64 if d_out.dtype == torch.float64 else DENSE_FLOAT32
+    workspace_bytes = lib.em2_dev_dense_expression_workspace(max(row_end - row_begin, 0))
+    if d_workspace is None:
+        d_workspace = torch.empty(workspace_bytes, dtype=torch.uint8, device=d_out.device)
+    stream = torch.cuda.current_stream() if stream is None else stream
+    check(lib.em2_dev_dense_expression(d_toc.data_ptr(), d_data.data_ptr(), d_cell_ids.data_ptr() if d_cell_ids is not None else None,
+                                       cell_count, d_gene_local_ids.data_ptr() if d_gene_local_ids is not None else None,
+                                       global_gene_count, gene_count, int(normalization_method), row_begin, row_end, element_type,
+                                       d_out.data_ptr(), pitch, d_workspace.data_ptr(), d_workspace.numel(), stream.cuda_stream))
+    return d_out
 
 
 def apply_gene_pairs_buffer():

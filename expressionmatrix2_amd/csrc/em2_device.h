@@ -254,6 +254,15 @@ hipError_t runGeneInformation(const uint64_t* d_toc, const CountIn* d_data, uint
                               double* d_informationContentDouble, uint32_t* d_expressingCellCount, void* workspace, size_t workspaceBytes,
                               uint32_t* inputError, hipStream_t stream);
 
+// em2_dense.hip: getDenseExpressionMatrix (src/PythonModule.cpp:112-138) for the rows [rowBegin, rowEnd) of a cell list (NULL: the
+// CSR's own rows) into d_out[(row - rowBegin) * pitchElements + gene], floats or doubles; d_geneLocalIds NULL: the CSR is in
+// local ids already.  *inputError != 0 (walkCell's word over the kept entries): nothing was written.  Synchronises the stream.
+size_t denseExpressionWorkspaceBytes(uint32_t rowCount);
+hipError_t runDenseExpression(const uint64_t* d_toc, const CountIn* d_data, const uint32_t* d_cellIds, const uint32_t* d_geneLocalIds,
+                              uint32_t globalGeneCount, uint32_t geneCount, int method, uint32_t rowBegin, uint32_t rowEnd,
+                              bool elementsAreDouble, void* d_out, size_t pitchElements, void* workspace, size_t workspaceBytes,
+                              uint32_t* inputError, hipStream_t stream);
+
 }  // namespace em2
 
 #endif

@@ -29,6 +29,7 @@ extern "C" int em2_internal_gene_information(const uint64_t* rowToc, const em2_c
 #include <cstring>
 #include <fstream>
 #include <iterator>
+#include <random>
 #include <dirent.h>
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -829,6 +830,165 @@ bool Matrix::createGeneSetDifference(const std::string& inputSetName0, const std
                         std::back_inserter(result));
     addGeneSetOf(outputSetName, result);
     return true;
+}
+
+bool Matrix::knowsCellSet(const std::string& name) const
+{
+    return cellSets_.find(name) != cellSets_.end() || fileExists(directoryName_ + "/CellSet-" + name);
+}
+
+void Matrix::failIfCellSetExists(const std::string& name) const
+{
+    if (knowsCellSet(name)) fail(EM2_ERROR_RUNTIME, "Cell set " + name + " already exists.");
+}
+
+void Matrix::addCellSetOf(const std::string& name, std::vector<uint32_t>& ids)
+{
+    std::sort(ids.begin(), ids.end());                                        // deduplicate (src/deduplicate.hpp:9-13)
+    ids.resize(size_t(std::unique(ids.begin(), ids.end()) - ids.begin()));
+    addCellSet(directoryName_, name, ids.data(), uint32_t(ids.size()));
+    std::unique_ptr<MappedFile> f(new MappedFile);
+    f->openExisting(directoryName_ + "/CellSet-" + name, false, sizeof(uint32_t));
+    cellSets_[name] = f.release();
+}
+
+void Matrix::createCellSet(const std::string& cellSetName, std::vector<uint32_t> cellIds)
+{
+    failIfCellSetExists(cellSetName);                                         // ExpressionMatrix.cpp:1629-1631
+    for (const uint32_t id : cellIds) {
+        if (id >= cellCount()) fail(EM2_ERROR_INVALID_ARGUMENT, "createCellSet: cell id " + std::to_string(id) + " is not below the cell count.");
+    }
+    addCellSetOf(cellSetName, cellIds);
+}
+
+void Matrix::createCellSetIntersectionOrUnion(const std::string& commaSeparatedInputSetsNames, const std::string& outputSetName, bool doUnion)
+{
+    failIfCellSetExists(outputSetName);                                       // :1653-1655
+    std::vector<std::string> names(1);                                        // boost::split on ",": empty pieces stay
+    for (const char c : commaSeparatedInputSetsNames) {
+        if (c == ',') names.emplace_back();
+        else names.back().push_back(c);
+    }
+    for (const std::string& name : names) cellSet(name);                      // :1662-1666: "Cell set X does not exist."
+    std::vector<uint32_t> result;                                             // :1669-1690
+    for (size_t i = 0; i < names.size(); i++) {
+        const MappedFile& input = cellSet(names[i]);
+        const uint32_t* first = static_cast<const uint32_t*>(input.data());
+        const uint32_t* last = first + input.objectCount();
+        if (i == 0) {
+            result.assign(first, last);
+            continue;
+        }
+        std::vector<uint32_t> next;
+        if (doUnion) std::set_union(result.begin(), result.end(), first, last, std::back_inserter(next));
+        else std::set_intersection(result.begin(), result.end(), first, last, std::back_inserter(next));
+        result.swap(next);
+    }
+    addCellSetOf(outputSetName, result);
+}
+
+void Matrix::createCellSetDifference(const std::string& inputSetName0, const std::string& inputSetName1, const std::string& outputSetName)
+{
+    failIfCellSetExists(outputSetName);                                       // :1706-1708
+    const MappedFile* inputs[2] = {nullptr, nullptr};
+    const std::string* names[2] = {&inputSetName0, &inputSetName1};
+    for (int i = 0; i < 2; i++) {
+        const auto it = cellSets_.find(*names[i]);
+        if (it == cellSets_.end()) fail(EM2_ERROR_RUNTIME, "Cell set " + *names[i] + " does not exists.");      // sic, :1715, :1720
+        inputs[i] = it->second;
+    }
+    const uint32_t* first0 = static_cast<const uint32_t*>(inputs[0]->data());
+    const uint32_t* first1 = static_cast<const uint32_t*>(inputs[1]->data());
+    std::vector<uint32_t> result;
+    std::set_difference(first0, first0 + inputs[0]->objectCount(), first1, first1 + inputs[1]->objectCount(), std::back_inserter(result));
+    addCellSetOf(outputSetName, result);
+}
+
+void Matrix::downsampleCellSet(const std::string& inputCellSetName, const std::string& outputCellSetName, double probability, int seed)
+{
+    const auto it = cellSets_.find(inputCellSetName);
+    if (it == cellSets_.end()) fail(EM2_ERROR_RUNTIME, "Cell set " + inputCellSetName + " does not exists.");  // sic, :1752
+    failIfCellSetExists(outputCellSetName);                                   // ours: the reference maps a new file over the old one
+    const uint32_t* input = static_cast<const uint32_t*>(it->second->data());
+    const size_t inputSize = it->second->objectCount();
+    // boost::uniform_01<> on boost::mt19937(seed): one 32-bit draw times 2^-32 (boost::mt19937 has std::mt19937's parameters;
+    // the int seed converts to the engine's 32-bit unsigned)
+    std::mt19937 randomSource{uint32_t(seed)};
+    const double factor = 1.0 / 4294967296.0;
+    std::vector<uint32_t> result;
+    for (size_t i = 0; i < inputSize; i++) {                                  // :1768-1772
+        if (double(randomSource()) * factor < probability) result.push_back(input[i]);
+    }
+    addCellSetOf(outputCellSetName, result);
+}
+
+void Matrix::removeCellSet(const std::string& cellSetName)
+{
+    // ours: without AllCells the directory cannot be opened again (removeGeneSet guards AllGenes in the reference itself)
+    if (cellSetName == "AllCells") fail(EM2_ERROR_RUNTIME, "Cell set AllCells cannot be removed.");
+    const auto it = cellSets_.find(cellSetName);
+    if (it == cellSets_.end()) fail(EM2_ERROR_RUNTIME, "Cell set " + cellSetName + " does not exist.");      // CellSets.cpp:91-93
+    delete it->second;
+    cellSets_.erase(it);
+    removeFile(directoryName_ + "/CellSet-" + cellSetName);
+}
+
+std::vector<std::string> Matrix::cellSetNames() const
+{
+    std::vector<std::string> names;
+    for (const auto& p : cellSets_) names.push_back(p.first);
+    return names;
+}
+
+void Matrix::denseExpression(const std::string& geneSetName, const std::string& cellSetName, int normalizationMethod, int elementType,
+                             uint32_t rowBegin, uint32_t rowEnd, void* out) const
+{
+    const GeneSet* genes = nullptr;
+    const uint32_t* cellIds = nullptr;
+    uint32_t cellCount = 0;
+    lookupSubset(geneSetName, cellSetName, genes, cellIds, cellCount);        // PythonModule.cpp:83-102, the same four checks
+    if (normalizationMethod < 0 || normalizationMethod > 2) fail(EM2_ERROR_RUNTIME, "Invalid normalization method.");      // :129
+    if (elementType != EM2_DENSE_FLOAT64 && elementType != EM2_DENSE_FLOAT32) {
+        fail(EM2_ERROR_INVALID_ARGUMENT, "em2_matrix_dense_expression: elementType must be 0 (float64) or 1 (float32)");
+    }
+    if (rowBegin > rowEnd || rowEnd > cellCount) {
+        fail(EM2_ERROR_INVALID_ARGUMENT, "em2_matrix_dense_expression: rowBegin <= rowEnd <= the size of the cell set is required");
+    }
+    if (rowBegin == rowEnd) return;
+    if (!out) fail(EM2_ERROR_INVALID_ARGUMENT, "em2_matrix_dense_expression: null argument");
+    // the rows asked for, whole, with their global gene ids: the gene set is applied on the device
+    const uint64_t* globalToc = static_cast<const uint64_t*>(toc_.data());
+    const em2_count* globalData = static_cast<const em2_count*>(data_.data());
+    const uint32_t rows = rowEnd - rowBegin;
+    const uint32_t* ids = cellIds + rowBegin;
+    std::vector<uint64_t> rowToc(size_t(rows) + 1, 0);
+    for (uint32_t i = 0; i < rows; i++) rowToc[i + 1] = rowToc[i] + (globalToc[ids[i] + 1] - globalToc[ids[i]]);
+    bool contiguous = true;
+    for (uint32_t i = 1; i < rows && contiguous; i++) contiguous = ids[i] == ids[0] + i;
+    std::vector<em2_count> gathered;
+    const em2_count* rowData = globalData + globalToc[ids[0]];
+    if (!contiguous) {
+        gathered.resize(rowToc[rows]);
+        for (uint32_t i = 0; i < rows; i++) {
+            const uint64_t n = rowToc[i + 1] - rowToc[i];
+            if (n) std::memcpy(gathered.data() + rowToc[i], globalData + globalToc[ids[i]], n * sizeof(em2_count));
+        }
+        rowData = gathered.data();
+    }
+    const int rc = em2_dense_expression(rowToc.data(), rowData, rows, nullptr, rows, static_cast<const uint32_t*>(genes->localIds.data()),
+                                        uint32_t(genes->localIds.objectCount()), genes->size(), normalizationMethod, elementType, out,
+                                        genes->size());
+    if (rc != EM2_OK) fail(rc, em2_last_error());
+}
+
+void Matrix::cellExpressionCounts(uint32_t cellId, const em2_count*& entries, uint64_t& count) const
+{
+    if (cellId >= cellCount()) {
+        fail(EM2_ERROR_INVALID_ARGUMENT, "em2_matrix_cell_expression_counts: cell id " + std::to_string(cellId) + " is not below the cell count.");
+    }
+    const uint64_t* globalToc = static_cast<const uint64_t*>(toc_.data());
+    entries = static_cast<const em2_count*>(data_.data()) + globalToc[cellId];
+    count = globalToc[cellId + 1] - globalToc[cellId];
 }
 
 void Matrix::createGeneGraph(const std::string& geneSetName, const std::string& similarGenePairsName, int64_t k, double similarityThreshold,

@@ -161,6 +161,23 @@ public:
                                     const std::string& outputGeneSetName, uint32_t minCellCount);
     void removeGeneSet(const std::string& geneSetName);
 
+    // createCellSet (src/ExpressionMatrix.cpp:1626-1633, CellSets::addCellSet src/CellSets.cpp:65-83),
+    // createCellSetIntersection / Union (:1642-1696), createCellSetDifference (:1700-1737), downsampleCellSet (:1742-1777) and
+    // removeCellSet (src/CellSets.cpp:88-97).  These throw in the reference and here; include/em2_lsh.h states the departures.
+    void createCellSet(const std::string& cellSetName, std::vector<uint32_t> cellIds);
+    void createCellSetIntersectionOrUnion(const std::string& commaSeparatedInputSetsNames, const std::string& outputSetName, bool doUnion);
+    void createCellSetDifference(const std::string& inputSetName0, const std::string& inputSetName1, const std::string& outputSetName);
+    void downsampleCellSet(const std::string& inputCellSetName, const std::string& outputCellSetName, double probability, int seed);
+    void removeCellSet(const std::string& cellSetName);
+    std::vector<std::string> cellSetNames() const;           // std::map order
+
+    // getDenseExpressionMatrix (src/PythonModule.cpp:78-154): the checks in the reference's order, then the rows
+    // [rowBegin, rowEnd) of the cell set, with their global gene ids, through em2_dense_expression into out.
+    void denseExpression(const std::string& geneSetName, const std::string& cellSetName, int normalizationMethod, int elementType,
+                         uint32_t rowBegin, uint32_t rowEnd, void* out) const;
+    // The stored entries of a cell (getCellExpressionCounts, src/ExpressionMatrix.cpp:1066-1075) in the mapped file.
+    void cellExpressionCounts(uint32_t cellId, const em2_count*& entries, uint64_t& count) const;
+
     const GeneSet& geneSet(const std::string& name) const;                 // throws "Gene set X does not exist."
     const MappedFile& cellSet(const std::string& name) const;              // throws "Cell set X does not exist."
 
@@ -171,6 +188,11 @@ private:
     void addGeneSetOf(const std::string& name, const std::vector<uint32_t>& ids);
     bool knowsGeneSet(const std::string& name) const;
     void failIfGeneSetExists(const std::string& name) const;
+    // CellSets::exists for the sets this object knows and, as knowsGeneSet, a file another object has written since.
+    bool knowsCellSet(const std::string& name) const;
+    void failIfCellSetExists(const std::string& name) const;
+    // CellSets::addCellSet: sorts and deduplicates, writes CellSet-<name> and opens it under its name.
+    void addCellSetOf(const std::string& name, std::vector<uint32_t>& ids);
     std::string directoryName_;
     MappedFile toc_;         // CellExpressionCounts.toc  (uint64)
     MappedFile data_;        // CellExpressionCounts.data (em2_count)

@@ -274,6 +274,82 @@ int em2_matrix_remove_gene_set(em2_matrix* matrix, const char* geneSetName)
     return guarded([&] { matrix->impl->removeGeneSet(geneSetName); });
 }
 
+int em2_matrix_create_cell_set(em2_matrix* matrix, const char* cellSetName, const uint32_t* cellIds, uint32_t count)
+{
+    if (!matrix || !cellSetName || (!cellIds && count)) return nullArgument("em2_matrix_create_cell_set");
+    return guarded([&] { matrix->impl->createCellSet(cellSetName, std::vector<uint32_t>(cellIds, cellIds + count)); });
+}
+
+int em2_matrix_create_cell_set_intersection(em2_matrix* matrix, const char* inputSetsNames, const char* outputSetName)
+{
+    if (!matrix || !inputSetsNames || !outputSetName) return nullArgument("em2_matrix_create_cell_set_intersection");
+    return guarded([&] { matrix->impl->createCellSetIntersectionOrUnion(inputSetsNames, outputSetName, false); });
+}
+
+int em2_matrix_create_cell_set_union(em2_matrix* matrix, const char* inputSetsNames, const char* outputSetName)
+{
+    if (!matrix || !inputSetsNames || !outputSetName) return nullArgument("em2_matrix_create_cell_set_union");
+    return guarded([&] { matrix->impl->createCellSetIntersectionOrUnion(inputSetsNames, outputSetName, true); });
+}
+
+int em2_matrix_create_cell_set_difference(em2_matrix* matrix, const char* inputSetName0, const char* inputSetName1,
+                                          const char* outputSetName)
+{
+    if (!matrix || !inputSetName0 || !inputSetName1 || !outputSetName) return nullArgument("em2_matrix_create_cell_set_difference");
+    return guarded([&] { matrix->impl->createCellSetDifference(inputSetName0, inputSetName1, outputSetName); });
+}
+
+int em2_matrix_downsample_cell_set(em2_matrix* matrix, const char* inputCellSetName, const char* outputCellSetName, double probability,
+                                   int seed)
+{
+    if (!matrix || !inputCellSetName || !outputCellSetName) return nullArgument("em2_matrix_downsample_cell_set");
+    return guarded([&] { matrix->impl->downsampleCellSet(inputCellSetName, outputCellSetName, probability, seed); });
+}
+
+int em2_matrix_remove_cell_set(em2_matrix* matrix, const char* cellSetName)
+{
+    if (!matrix || !cellSetName) return nullArgument("em2_matrix_remove_cell_set");
+    return guarded([&] { matrix->impl->removeCellSet(cellSetName); });
+}
+
+int em2_matrix_cell_set_names(em2_matrix* matrix, uint64_t* bytes, char* names)
+{
+    if (!matrix || !bytes) return nullArgument("em2_matrix_cell_set_names");
+    return guarded([&] {
+        std::string all;
+        for (const std::string& name : matrix->impl->cellSetNames()) all.append(name).push_back('\0');
+        if (names) {
+            if (*bytes < all.size()) throw em2::host::Error{EM2_ERROR_INVALID_ARGUMENT, "em2_matrix_cell_set_names: the buffer is too small"};
+            std::memcpy(names, all.data(), all.size());
+        }
+        *bytes = all.size();
+    });
+}
+
+int em2_matrix_dense_expression(em2_matrix* matrix, const char* geneSetName, const char* cellSetName, int normalizationMethod,
+                                int elementType, uint32_t rowBegin, uint32_t rowEnd, void* out)
+{
+    if (!matrix || !geneSetName || !cellSetName) return nullArgument("em2_matrix_dense_expression");
+    return guarded([&] {
+        matrix->impl->denseExpression(geneSetName, cellSetName, normalizationMethod, elementType, rowBegin, rowEnd, out);
+    });
+}
+
+int em2_matrix_cell_expression_counts(em2_matrix* matrix, uint32_t cellId, uint64_t* count, em2_count* out)
+{
+    if (!matrix || !count) return nullArgument("em2_matrix_cell_expression_counts");
+    return guarded([&] {
+        const em2_count* entries = nullptr;
+        uint64_t stored = 0;
+        matrix->impl->cellExpressionCounts(cellId, entries, stored);
+        if (out) {
+            if (*count < stored) throw em2::host::Error{EM2_ERROR_INVALID_ARGUMENT, "em2_matrix_cell_expression_counts: the buffer is too small"};
+            if (stored) std::memcpy(out, entries, stored * sizeof(em2_count));
+        }
+        *count = stored;
+    });
+}
+
 int em2_similar_gene_pairs_write(const char* directoryName, const char* similarGenePairsName, const char* geneSetName,
                                  const char* cellSetName, size_t k, int normalizationMethod, uint32_t geneCount, const em2_pair* pairs,
                                  const uint32_t* usedCount)

@@ -18,6 +18,10 @@ from . import capi, files
 
 _REQUIRED = object()
 
+# getDenseExpressionMatrix fills its result in chunks of rows of at most this many bytes (one row at least): the bound of its
+# device buffer.  Tests set it small to run several chunks.
+DENSE_CHUNK_BYTES = 1 << 30
+
 
 class NormalizationMethod(enum.IntEnum):
     """NormalizationMethod (src/NormalizationMethod.hpp:11-16) with the members the reference's module exposes
@@ -381,6 +385,149 @@ class ExpressionMatrix:
     # ---- src/PythonModule.cpp:926-934 ----
     def removeSimilarPairs(self, similarPairsName):
         capi.check(capi.load().em2_matrix_remove_similar_pairs(self._handle, _b(similarPairsName)))
+
+    # ---- src/PythonModule.cpp:616-750: cell sets (those made from meta data are not offered: there is no meta data store) ----
+    def createCellSet(self, cellSetName, cellIds):
+        """ExpressionMatrix::createCellSet (src/ExpressionMatrix.cpp:1626-1633): the cells with these global ids, sorted and
+        deduplicated, as CellSet-<cellSetName>, usable by name at once.  "Cell set X already exists."; an id not below the
+        cell count is refused (the reference stores it)."""
+        ids = [int(i) for i in cellIds]
+        if any(not 0 <= i <= 0xffffffff for i in ids):                   # CellId (src/Ids.hpp) is unsigned, 32 bits
+            raise ValueError("createCellSet(): cell ids must be in [0, 2**32)")
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        capi.check(capi.load().em2_matrix_create_cell_set(self._handle, _b(cellSetName), capi._ptr(ids), len(ids)))
+
+    def createCellSetIntersection(self, inputSetsNames, outputSetName):
+        """ExpressionMatrix::createCellSetIntersection (src/ExpressionMatrix.cpp:1642-1696): inputSetsNames is a comma-separated
+        list of cell set names.  Returns None and raises RuntimeError where the output exists or an input is missing (the
+        reference throws, whatever its docstring says)."""
+        capi.check(capi.load().em2_matrix_create_cell_set_intersection(self._handle, _b(inputSetsNames), _b(outputSetName)))
+
+    def createCellSetUnion(self, inputSetsNames, outputSetName):
+        """ExpressionMatrix::createCellSetUnion (src/ExpressionMatrix.cpp:1646-1696), as createCellSetIntersection."""
+        capi.check(capi.load().em2_matrix_create_cell_set_union(self._handle, _b(inputSetsNames), _b(outputSetName)))
+
+    def createCellSetDifference(self, inputSetName0, inputSetName1, outputSetName):
+        """ExpressionMatrix::createCellSetDifference (src/ExpressionMatrix.cpp:1700-1737): the cells of inputSetName0 that are
+        not in inputSetName1."""
+        capi.check(capi.load().em2_matrix_create_cell_set_difference(self._handle, _b(inputSetName0), _b(inputSetName1),
+                                                                     _b(outputSetName)))
+
+    def downsampleCellSet(self, inputCellSetName="AllCells", newCellSetName=_REQUIRED, probability=_REQUIRED, seed=_REQUIRED):
+        """ExpressionMatrix::downsampleCellSet (src/ExpressionMatrix.cpp:1742-1777): every cell of the input set is kept with
+        the given probability, one draw of mt19937(seed) per cell in set order.  seed is the reference's int: it wraps to 32
+        bits.  A new set's name that exists is refused (the reference overwrites the file)."""
+        if _REQUIRED in (newCellSetName, probability, seed):
+            raise TypeError("downsampleCellSet(): newCellSetName, probability and seed are required")
+        if isinstance(seed, float):
+            raise TypeError("downsampleCellSet(): seed must be an integer")
+        wrapped = int(seed) & 0xffffffff
+        wrapped -= (wrapped & 0x80000000) << 1
+        capi.check(capi.load().em2_matrix_downsample_cell_set(self._handle, _b(inputCellSetName), _b(newCellSetName),
+                                                              float(probability), wrapped))
+
+    def getCellSetNames(self):
+        """The names of the cell sets, in std::map order (src/ExpressionMatrix.cpp, getCellSetNames)."""
+        lib = capi.load()
+        size = ctypes.c_uint64(0)
+        capi.check(lib.em2_matrix_cell_set_names(self._handle, ctypes.byref(size), None))
+        buffer = ctypes.create_string_buffer(max(int(size.value), 1))
+        capi.check(lib.em2_matrix_cell_set_names(self._handle, ctypes.byref(size), buffer))
+        return [name.decode("utf-8") for name in buffer.raw[:size.value].split(b"\0")[:-1]]
+
+    def getCellSet(self, cellSetName):
+        """The global cell ids of a cell set, ascending; an empty list for a name that does not exist
+        (src/ExpressionMatrixHttpServerCells.cpp:865-875)."""
+        if cellSetName not in self.getCellSetNames():
+            return []
+        return self._cell_set(cellSetName).tolist()
+
+    def removeCellSet(self, cellSetName):
+        """ExpressionMatrix::removeCellSet (src/CellSets.cpp:88-97): "Cell set X does not exist."; the file goes.  AllCells
+        cannot be removed (this package's guard)."""
+        capi.check(capi.load().em2_matrix_remove_cell_set(self._handle, _b(cellSetName)))
+
+    # ---- src/PythonModule.cpp:404-478: the stored counts of cells (global ids) ----
+    @staticmethod
+    def _gene_id(geneId):
+        if isinstance(geneId, str):
+            raise TypeError("gene names are not offered: this package reads no GeneNames table; pass a gene id")
+        return int(geneId)
+
+    def _cell_counts(self, cellId):
+        lib = capi.load()
+        count = ctypes.c_uint64(0)
+        capi.check(lib.em2_matrix_cell_expression_counts(self._handle, int(cellId), ctypes.byref(count), None))
+        entries = np.zeros(count.value, dtype=capi.COUNT_DTYPE)
+        capi.check(lib.em2_matrix_cell_expression_counts(self._handle, int(cellId), ctypes.byref(count), capi._ptr(entries)))
+        return entries
+
+    def getCellExpressionCounts(self, cellId):
+        """[(geneId, count)] of a cell, every stored entry (a stored zero too), ascending by gene id
+        (src/ExpressionMatrix.cpp:1066-1075).  A cell id out of range raises RuntimeError (the reference reads out of bounds)."""
+        entries = self._cell_counts(cellId)
+        return list(zip(entries["gene"].tolist(), entries["count"].tolist()))
+
+    def getCellsExpressionCounts(self, cellIds):
+        """getCellExpressionCounts for every cell of cellIds, in their order (src/ExpressionMatrix.cpp:1113-1122)."""
+        return [self.getCellExpressionCounts(cellId) for cellId in cellIds]
+
+    def getCellExpressionCount(self, cellId, geneId):
+        """The count of a gene in a cell, 0.0 where nothing is stored: a binary search of the cell's entries
+        (src/ExpressionMatrix.cpp:1035-1046)."""
+        geneId = self._gene_id(geneId)
+        entries = self._cell_counts(cellId)
+        at = int(np.searchsorted(entries["gene"], geneId))
+        if at == len(entries) or int(entries["gene"][at]) != geneId:
+            return 0.0
+        return float(entries["count"][at])
+
+    def getCellsExpressionCount(self, cellIds, geneId):
+        """getCellExpressionCount for every cell of cellIds, in their order (src/ExpressionMatrix.cpp:1083-1091)."""
+        geneId = self._gene_id(geneId)
+        return [self.getCellExpressionCount(cellId, geneId) for cellId in cellIds]
+
+    def getCellsExpressionCountsForGenes(self, cellIds, geneIds):
+        """For every cell of cellIds, in their order, its stored (global gene id, count) entries whose gene is in geneIds
+        (src/ExpressionMatrix.cpp:1132-1168)."""
+        wanted = np.unique(np.asarray([self._gene_id(g) for g in geneIds], dtype=np.int64))
+        result = []
+        for cellId in cellIds:
+            entries = self._cell_counts(cellId)
+            entries = entries[np.isin(entries["gene"], wanted)]
+            result.append(list(zip(entries["gene"].tolist(), entries["count"].tolist())))
+        return result
+
+    # ---- src/PythonModule.cpp:479-496 ----
+    def getDenseExpressionMatrix(self, geneSetName="AllGenes", cellSetName="AllCells", normalizationMethod=NormalizationMethod.none,
+                                 dtype=np.float64):
+        """ExpressionMatrix::getDenseExpressionMatrix (src/PythonModule.cpp:78-154): ndarray [cells of the cell set][genes of
+        the gene set], indexed by the ids local to the sets; every stored count times the cell's factor (none: 1, L1:
+        1 / sum, L2: 1 / sqrt(sum of squares), over the cell's entries within the gene set), zero elsewhere.  There is no guard
+        against a zero sum, as in the reference: such a cell's stored entries are NaN or inf.
+
+        dtype is np.float64 (the reference's) or np.float32, which holds the same values: every element is a float before
+        the reference widens it.  The matrix is filled on the GPU (em2_matrix_dense_expression) in chunks of rows, so that
+        the device buffer holds at most DENSE_CHUNK_BYTES bytes (a module attribute, 1 GiB) or one row, whichever is
+        larger, whatever the size of the result."""
+        method = NormalizationMethod(normalizationMethod) if normalizationMethod in (0, 1, 2) else None
+        element_type = capi.dense_element_type(dtype)
+        lib = capi.load()
+        gene, cell = _b(geneSetName), _b(cellSetName)
+        # the reference's checks, in its order, before anything is sized (an unknown method is its "Invalid normalization method.")
+        capi.check(lib.em2_matrix_dense_expression(self._handle, gene, cell, int(method) if method is not None else -1, element_type,
+                                                   0, 0, None))
+        gene_count = ctypes.c_uint32(0)
+        capi.check(lib.em2_matrix_gene_set(self._handle, gene, ctypes.byref(gene_count), None))
+        cell_count = len(self._cell_set(cellSetName))
+        out = np.empty((cell_count, gene_count.value), dtype=dtype)
+        row_bytes = gene_count.value * out.itemsize
+        chunk_rows = max(1, int(DENSE_CHUNK_BYTES) // row_bytes)
+        for row_begin in range(0, cell_count, chunk_rows):
+            row_end = min(cell_count, row_begin + chunk_rows)
+            capi.check(lib.em2_matrix_dense_expression(self._handle, gene, cell, int(method), element_type, row_begin, row_end,
+                                                       capi._ptr(out[row_begin:row_end])))
+        return out
 
     def _cell_set(self, cellSetName):
         lib = capi.load()

@@ -204,6 +204,42 @@ int em2_dev_gene_information_content(const uint64_t* d_toc, const em2_count* d_d
 int em2_cell_norm_inverses(const uint64_t* toc, const em2_count* data, uint32_t cellCount, uint32_t geneCount, double* norm1Inverse,
                            double* norm2Inverse);
 
+/* ExpressionMatrix::getDenseExpressionMatrix (src/PythonModule.cpp:78-154, the arithmetic :112-138; bound at :479-496) on the
+ * GPU: out[cell][gene], row-major, zero where the cell stores nothing for the gene.  (NOT getDenseRepresentation of
+ * findSimilarGenePairs0, which is gene-major, float, and guards a zero sum.)
+ *   factor of a cell (:117-130)   none: 1.f    L1: float(1. / sum1)    L2: float(1. / sqrt(sum2)),
+ *   sum1, sum2 = ExpressionMatrixSubset::computeSums (src/ExpressionMatrixSubset.cpp:47-58) over the cell's entries WITHIN THE
+ *   GENE SET in stored order: doubles; count * count is a float product.  Every stored entry becomes double(factor * count), a
+ *   float product, then widened (:135-136).  There is no guard against a zero sum, as in the reference: a cell whose kept
+ *   entries are all stored zeros gives inf * 0 = NaN at those entries (0 elsewhere), a cell without a kept entry is a row of
+ *   zeros, counts that cancel give +-inf.  The sign and payload of such a NaN are the hardware's.
+ * elementType: EM2_DENSE_FLOAT64 is the reference's array.  EM2_DENSE_FLOAT32 holds the same values -- every element is a float
+ * before the reference widens it -- in half the bytes.
+ *
+ * em2_dev_dense_expression: everything in device memory.  The rows [rowBegin, rowEnd) of the result, rowEnd <= cellCount, go to
+ * d_out[(row - rowBegin) * pitchElements + gene]; pitchElements >= geneCount, and what lies behind geneCount in a row is not
+ * touched.  d_cellIds NULL: row r is cell r of the CSR; else row r is cell d_cellIds[r], cellCount ids (as em2_dev_subset_*;
+ * like there, the ids are the caller's to vouch for: this entry is not told how many cells the CSR has).  d_geneLocalIds
+ * NULL: the CSR is in local ids already; else it is GeneSet-<name>-LocalIds of globalGeneCount words (0xffffffff: not in the
+ * set) and the CSR holds global ids: the gene mapping is fused, no restricted CSR is built.  geneCount is the gene set's size.
+ * A kept gene id not below geneCount, or kept ids not strictly ascending within a cell: EM2_ERROR_INVALID_ARGUMENT and nothing
+ * is written.  d_out is aligned to its element; the workspace is em2_dev_dense_expression_workspace(rowEnd - rowBegin) bytes.
+ * Synchronises the stream.
+ *
+ * em2_dense_expression: the same on host buffers, the whole matrix (cellCount rows into out[row * pitchElements + gene]),
+ * through a device buffer of at most 1 GiB.  toc / data have csrCellCount cells; cellIds NULL: cellCount == csrCellCount.
+ * A cell id not below csrCellCount: EM2_ERROR_INVALID_ARGUMENT (the reference reads out of bounds). */
+#define EM2_DENSE_FLOAT64 0
+#define EM2_DENSE_FLOAT32 1
+size_t em2_dev_dense_expression_workspace(uint32_t rowCount);
+int em2_dev_dense_expression(const uint64_t* d_toc, const em2_count* d_data, const uint32_t* d_cellIds, uint32_t cellCount,
+                             const uint32_t* d_geneLocalIds, uint32_t globalGeneCount, uint32_t geneCount, int normalizationMethod,
+                             uint32_t rowBegin, uint32_t rowEnd, int elementType, void* d_out, uint64_t pitchElements,
+                             void* d_workspace, size_t workspaceBytes, void* stream);
+int em2_dense_expression(const uint64_t* toc, const em2_count* data, uint32_t csrCellCount, const uint32_t* cellIds, uint32_t cellCount,
+                         const uint32_t* geneLocalIds, uint32_t globalGeneCount, uint32_t geneCount, int normalizationMethod,
+                         int elementType, void* out, uint64_t pitchElements);
+
 /* ExpressionMatrixSubset + Lsh + findSimilarPairs4 in one call on host buffers (SURVEY.md 8(a) row a1 on the device:
  * src/ExpressionMatrixSubset.cpp:9-42 followed by src/Lsh.cpp:118-224 and src/ExpressionMatrixLsh.cpp:200-285): the
  * global CSR (CellExpressionCounts toc/data, global gene ids) restricted to the cells cellIds[0..cellCount) (NULL =
@@ -852,6 +888,55 @@ int em2_matrix_create_well_expressed_gene_set(em2_matrix* matrix, const char* in
 /* ExpressionMatrix::removeGeneSet (src/ExpressionMatrixGeneSets.cpp:12-32): "Gene set AllGenes cannot be removed.",
  * "Gene set X does not exist."; removes the two files. */
 int em2_matrix_remove_gene_set(em2_matrix* matrix, const char* geneSetName);
+
+/* Cell sets (host code).  A new set is the file CellSet-<name> (MemoryMapped::Vector<CellId>), known to this matrix under its
+ * name at once and to every matrix opened on the directory afterwards.  Unlike the gene set operations these throw in the
+ * reference, so every refusal is EM2_ERROR_RUNTIME with the reference's text.
+ *   em2_matrix_create_cell_set     ExpressionMatrix::createCellSet (src/ExpressionMatrix.cpp:1626-1633) with
+ *                                  CellSets::addCellSet (src/CellSets.cpp:65-83): "Cell set X already exists."; the ids are
+ *                                  sorted and deduplicated.  DEPARTURE: an id not below the cell count is refused with
+ *                                  EM2_ERROR_INVALID_ARGUMENT; the reference stores it and reads out of bounds later.
+ *   ..._intersection / ..._union   createCellSetIntersectionOrUnion (:1642-1696): the output name first ("Cell set X already
+ *                                  exists."), then the comma-separated input names, split at every comma (an empty piece is a
+ *                                  name that does not exist): "Cell set X does not exist."; then std::set_intersection /
+ *                                  std::set_union folded from left to right.
+ *   ..._difference                 createCellSetDifference (:1700-1737): "Cell set X already exists.", then "Cell set X does
+ *                                  not exists." (sic, :1715, :1720) for input 0, then input 1; std::set_difference.
+ *   em2_matrix_downsample_cell_set downsampleCellSet (:1742-1777): "Cell set X does not exists." (sic, :1752); one draw of
+ *                                  mt19937(seed) per input cell in set order, kept when draw * 2^-32 < probability
+ *                                  (boost::uniform_01<> on boost::mt19937); the int seed wraps to 32 bits.  DEPARTURE: the
+ *                                  reference does not look whether the output exists -- it maps a new file over the old one
+ *                                  while its table keeps the old entry; here the call answers "Cell set X already exists."
+ *                                  (after the input's check).
+ *   em2_matrix_remove_cell_set     removeCellSet (src/ExpressionMatrixCells.cpp:113-116, src/CellSets.cpp:88-97): "Cell set X
+ *                                  does not exist."; the file is removed.  DEPARTURE: the reference has no guard for AllCells
+ *                                  and would leave a directory it cannot open again; here "Cell set AllCells cannot be
+ *                                  removed." (ours, after removeGeneSet's for AllGenes).
+ *   em2_matrix_cell_set_names      the names in std::map order (CellSets::cellSets, src/CellSets.hpp), each followed by a 0
+ *                                  byte: pass names == NULL to get *bytes, then a buffer of that size. */
+int em2_matrix_create_cell_set(em2_matrix* matrix, const char* cellSetName, const uint32_t* cellIds, uint32_t count);
+int em2_matrix_create_cell_set_intersection(em2_matrix* matrix, const char* inputSetsNames, const char* outputSetName);
+int em2_matrix_create_cell_set_union(em2_matrix* matrix, const char* inputSetsNames, const char* outputSetName);
+int em2_matrix_create_cell_set_difference(em2_matrix* matrix, const char* inputSetName0, const char* inputSetName1,
+                                          const char* outputSetName);
+int em2_matrix_downsample_cell_set(em2_matrix* matrix, const char* inputCellSetName, const char* outputCellSetName, double probability,
+                                   int seed);
+int em2_matrix_remove_cell_set(em2_matrix* matrix, const char* cellSetName);
+int em2_matrix_cell_set_names(em2_matrix* matrix, uint64_t* bytes, char* names);
+
+/* getDenseExpressionMatrix (src/PythonModule.cpp:78-154) for a gene set and a cell set of the directory: the rows
+ * [rowBegin, rowEnd) of the cell set into out[(row - rowBegin) * geneSetSize + localGene] (see em2_dev_dense_expression for the
+ * arithmetic and elementType).  Only those rows travel to the device, with the gene set applied there.  In the reference's
+ * order: "Gene set X does not exist.", "Gene set X is empty.", "Cell set X does not exist.", "Cell set X is empty.", "Invalid
+ * normalization method." (EM2_ERROR_RUNTIME); then rowBegin <= rowEnd <= the cell set's size and elementType
+ * (EM2_ERROR_INVALID_ARGUMENT).  rowBegin == rowEnd makes the checks and writes nothing (out may be NULL). */
+int em2_matrix_dense_expression(em2_matrix* matrix, const char* geneSetName, const char* cellSetName, int normalizationMethod,
+                                int elementType, uint32_t rowBegin, uint32_t rowEnd, void* out);
+
+/* The stored (gene id, count) entries of a cell, ascending by global gene id -- what ExpressionMatrix::getCellExpressionCounts
+ * (src/ExpressionMatrix.cpp:1030-1168 with its siblings) reads -- from the memory-mapped row: pass out == NULL to get *count,
+ * then out[*count].  A cell id not below the cell count: EM2_ERROR_INVALID_ARGUMENT (the reference reads out of bounds). */
+int em2_matrix_cell_expression_counts(em2_matrix* matrix, uint32_t cellId, uint64_t* count, em2_count* out);
 
 /* ExpressionMatrixSubset (src/ExpressionMatrixSubset.cpp:9-42) as plain arrays, for drivers that shard the work
  * themselves: first call with toc == NULL to get the sizes, then with toc[cellCount+1] and data[nnz]. */
