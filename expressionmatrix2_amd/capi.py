@@ -230,6 +230,28 @@ SYMBOLS = {
     "em2_tool_create_directory": (_c.c_int, [_c.c_char_p, _c.c_uint32, _c.c_uint32, _c.c_void_p, _c.c_void_p]),
     "em2_tool_add_gene_set": (_c.c_int, [_c.c_char_p, _c.c_char_p, _c.c_void_p, _c.c_uint32]),
     "em2_tool_add_cell_set": (_c.c_int, [_c.c_char_p, _c.c_char_p, _c.c_void_p, _c.c_uint32]),
+    "em2_contingency_create": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_uint32, _c.c_uint32, _c.c_int,
+                                          _c.POINTER(_c.c_void_p)]),
+    "em2_dev_contingency": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_uint32, _c.c_uint32, _c.c_int,
+                                       _c.POINTER(_c.c_void_p)]),
+    "em2_contingency_sizes": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_uint32), _c.POINTER(_c.c_uint32), _c.POINTER(_c.c_uint64),
+                                         _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_int)]),
+    "em2_contingency_get": (_c.c_int, [_c.c_void_p] * 7),
+    "em2_contingency_free": (None, [_c.c_void_p]),
+    "em2_rand_index": (_c.c_int, [_c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_uint64, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
+    "em2_matrix_set_cell_meta_data": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_char_p, _c.c_char_p]),
+    "em2_matrix_get_cell_meta_data_value": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_char_p, _c.POINTER(_c.c_uint64), _c.c_void_p]),
+    "em2_matrix_get_cell_meta_data": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.POINTER(_c.c_uint64), _c.c_void_p]),
+    "em2_matrix_remove_cell_meta_data": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p]),
+    "em2_matrix_create_cell_set_using_meta_data": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_char_p, _c.c_int]),
+    "em2_matrix_compute_meta_data_rand_index": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_char_p,
+                                                           _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
+    "em2_matrix_meta_data_table": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_char_p, _c.POINTER(_c.c_void_p)]),
+    "em2_meta_data_table_sizes": (_c.c_int, [_c.c_void_p] + [_c.POINTER(_c.c_uint64)] * 5 + [_c.POINTER(_c.c_int)]),
+    "em2_meta_data_table_get": (_c.c_int, [_c.c_void_p] * 9),
+    "em2_meta_data_table_free": (None, [_c.c_void_p]),
+    "em2_matrix_flush": (_c.c_int, [_c.c_void_p]),
+    "em2_tool_create_meta_data": (_c.c_int, [_c.c_char_p, _c.c_uint32, _c.c_uint64, _c.c_uint64]),
 }
 
 
@@ -659,6 +681,94 @@ def dev_gene_graph_create(pairs, used_count, pairs_gene_set, graph_gene_set, sim
                                            len(pairs_genes), pairs.shape[1], _ptr(pairs_genes), _ptr(graph_genes), len(graph_genes),
                                            similarity_threshold, int(max_connectivity) % 2 ** 64, ctypes.byref(handle)))
     return gene_graph_take(handle)
+
+
+CONTINGENCY_AUTOMATIC, CONTINGENCY_LDS, CONTINGENCY_SORT = 0, 1, 2
+CONTINGENCY_LDS_CELLS = 16384
+
+
+def contingency_take(handle):
+    """The content of an em2_contingency as a dict, and the handle freed: rowTotals uint64 [n0], columnTotals uint64 [n1], the
+    cells that are not zero as i0 / i1 uint32 and count uint64, ascending by (i0, i1), the three sums as Python ints (sumCells,
+    sumRows, sumColumns), n, and path: the one that ran (CONTINGENCY_LDS or CONTINGENCY_SORT)."""
+    lib = load()
+    try:
+        n0, n1, path = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_int(0)
+        n, nonzero = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        check(lib.em2_contingency_sizes(handle, ctypes.byref(n0), ctypes.byref(n1), ctypes.byref(n), ctypes.byref(nonzero),
+                                        ctypes.byref(path)))
+        out = {
+            "rowTotals": np.zeros(n0.value, dtype=np.uint64),
+            "columnTotals": np.zeros(n1.value, dtype=np.uint64),
+            "i0": np.zeros(nonzero.value, dtype=np.uint32),
+            "i1": np.zeros(nonzero.value, dtype=np.uint32),
+            "count": np.zeros(nonzero.value, dtype=np.uint64),
+        }
+        sums = np.zeros(3, dtype=np.uint64)
+        check(lib.em2_contingency_get(handle, *[_ptr(out[key]) for key in ("rowTotals", "columnTotals", "i0", "i1", "count")],
+                                      _ptr(sums)))
+        out["sumCells"], out["sumRows"], out["sumColumns"] = (int(x) for x in sums)
+        out["n"] = int(n.value)
+        out["path"] = path.value
+    finally:
+        lib.em2_contingency_free(handle)
+    return out
+
+
+def _contingency_ids(id0, id1):
+    id0 = np.ascontiguousarray(id0, dtype=np.uint32)
+    id1 = np.ascontiguousarray(id1, dtype=np.uint32)
+    if id0.ndim != 1 or id0.shape != id1.shape:
+        raise ValueError("id0 and id1 must be one-dimensional and equally long")
+    return id0, id1
+
+
+def contingency(id0, id1, n0, n1, path=CONTINGENCY_AUTOMATIC):
+    """The contingency table of two labelings (em2_contingency_create) -> the dict of contingency_take."""
+    id0, id1 = _contingency_ids(id0, id1)
+    handle = ctypes.c_void_p(None)
+    check(load().em2_contingency_create(_ptr(id0), _ptr(id1), len(id0), n0, n1, path, ctypes.byref(handle)))
+    return contingency_take(handle)
+
+
+def dev_contingency(d_id0_ptr, d_id1_ptr, n, n0, n1, path=CONTINGENCY_AUTOMATIC):
+    """The same on ids that are in device memory already (em2_dev_contingency): two device pointers to n uint32 each."""
+    handle = ctypes.c_void_p(None)
+    check(load().em2_dev_contingency(d_id0_ptr, d_id1_ptr, n, n0, n1, path, ctypes.byref(handle)))
+    return contingency_take(handle)
+
+
+def rand_index(sum_cells, sum_rows, sum_columns, n):
+    """computeRandIndex (src/randIndex.hpp:58-97) from the three sums of a contingency table -> (randIndex, adjustedRandIndex)."""
+    ri, ari = ctypes.c_double(0.), ctypes.c_double(0.)
+    check(load().em2_rand_index(sum_cells, sum_rows, sum_columns, n, ctypes.byref(ri), ctypes.byref(ari)))
+    return ri.value, ari.value
+
+
+def meta_data_table_take(handle):
+    """The content of an em2_meta_data_table as a dict, and the handle freed: values0 / values1 (lists of str) with counts0 /
+    counts1 (lists of int) in histogram order, triples [(row, column, count)], sums (four ints: the three of the contingency
+    table and n), path."""
+    lib = load()
+    try:
+        sizes = [ctypes.c_uint64(0) for _ in range(5)]
+        path = ctypes.c_int(0)
+        check(lib.em2_meta_data_table_sizes(handle, *[ctypes.byref(s) for s in sizes], ctypes.byref(path)))
+        count0, count1, bytes0, bytes1, nonzero = (int(s.value) for s in sizes)
+        values = [ctypes.create_string_buffer(max(bytes0, 1)), ctypes.create_string_buffer(max(bytes1, 1))]
+        counts = [np.zeros(count0, dtype=np.uint64), np.zeros(count1, dtype=np.uint64)]
+        triples = [np.zeros(nonzero, dtype=np.uint64) for _ in range(3)]
+        sums = np.zeros(4, dtype=np.uint64)
+        check(lib.em2_meta_data_table_get(handle, values[0], _ptr(counts[0]), values[1], _ptr(counts[1]), _ptr(triples[0]),
+                                          _ptr(triples[1]), _ptr(triples[2]), _ptr(sums)))
+        out = {"path": path.value, "sums": [int(x) for x in sums],
+               "triples": list(zip(*(t.tolist() for t in triples)))}
+        for f, size in enumerate((bytes0, bytes1)):
+            out["values%d" % f] = [v.decode("utf-8", "surrogateescape") for v in values[f].raw[:size].split(b"\0")[:-1]]
+            out["counts%d" % f] = counts[f].tolist()
+    finally:
+        lib.em2_meta_data_table_free(handle)
+    return out
 
 
 def analyze_lsh(toc, data, gene_count, signatures, lsh_count, global_cell_ids, seed, csv_downsample, pairs_csv_path,

@@ -12,6 +12,7 @@
 #include "em2_cluster_graph.h"
 #include "em2_signature_graph.h"
 #include "em2_gene_graph.h"
+#include "em2_contingency.h"
 #include "em2_tables.h"
 
 #include <algorithm>
@@ -2372,5 +2373,90 @@ int em2_gene_graph_get(const em2_gene_graph* graph, uint32_t* vertices, uint32_t
 }
 
 void em2_gene_graph_free(em2_gene_graph* graph) { delete graph; }
+
+// ---- the contingency table of two labelings (em2_contingency.hip) ----
+
+struct em2_contingency {
+    em2::ContingencyResult result;
+};
+
+static int contingencyCreate(const char* who, bool idsOnDevice, const uint32_t* id0, const uint32_t* id1, uint64_t n, uint32_t n0,
+                             uint32_t n1, int path, em2_contingency** out)
+{
+    if (!out) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+    *out = nullptr;
+    if (n && (!id0 || !id1)) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+    if (n0 == 0 || n1 == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": n0 and n1 must be positive");
+    if (path != em2::kContingencyAutomatic && path != em2::kContingencyLds && path != em2::kContingencySort) {
+        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": path must be 0 (automatic), 1 (LDS) or 2 (sort)");
+    }
+    if (path == em2::kContingencyLds && uint64_t(n0) * n1 > em2::kContingencyLdsCells) {
+        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": the LDS path holds a table of at most " +
+                                                    std::to_string(em2::kContingencyLdsCells) + " cells");
+    }
+    // (the three sums are at most n (n - 1), and a run's first element is kept in 32 bits)
+    if (n > 0xffffffffull) return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 1 elements are not supported");
+    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
+    DeviceBuffer d0, d1;
+    if (!idsOnDevice && n) {
+        EM2_HIP(d0.allocate(size_t(n) * sizeof(uint32_t)));
+        EM2_HIP(d1.allocate(size_t(n) * sizeof(uint32_t)));
+        EM2_HIP(hipMemcpy(d0.p, id0, size_t(n) * sizeof(uint32_t), hipMemcpyHostToDevice));
+        EM2_HIP(hipMemcpy(d1.p, id1, size_t(n) * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    em2_contingency* c = new em2_contingency;
+    uint32_t inputError = 0;
+    const hipError_t status = em2::runContingency(idsOnDevice || !n ? id0 : d0.as<uint32_t>(), idsOnDevice || !n ? id1 : d1.as<uint32_t>(), n,
+                                                  n0, n1, path, c->result, &inputError, nullptr);
+    if (status != hipSuccess || inputError) {
+        delete c;
+        EM2_HIP(status);
+        return failArgument(who, "an id is not below its count (id0 < n0, id1 < n1)");
+    }
+    *out = c;
+    return EM2_OK;
+}
+
+int em2_contingency_create(const uint32_t* id0, const uint32_t* id1, uint64_t n, uint32_t n0, uint32_t n1, int path, em2_contingency** out)
+{
+    return contingencyCreate("em2_contingency", false, id0, id1, n, n0, n1, path, out);
+}
+
+int em2_dev_contingency(const uint32_t* d_id0, const uint32_t* d_id1, uint64_t n, uint32_t n0, uint32_t n1, int path, em2_contingency** out)
+{
+    return contingencyCreate("em2_dev_contingency", true, d_id0, d_id1, n, n0, n1, path, out);
+}
+
+int em2_contingency_sizes(const em2_contingency* table, uint32_t* n0, uint32_t* n1, uint64_t* n, uint64_t* nonZeroCount, int* path)
+{
+    if (!table) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_contingency_sizes: null pointer");
+    const em2::ContingencyResult& r = table->result;
+    if (n0) *n0 = r.n0;
+    if (n1) *n1 = r.n1;
+    if (n) *n = r.n;
+    if (nonZeroCount) *nonZeroCount = r.count.size();
+    if (path) *path = r.path;
+    return EM2_OK;
+}
+
+int em2_contingency_get(const em2_contingency* table, uint64_t* rowTotals, uint64_t* columnTotals, uint32_t* i0, uint32_t* i1,
+                        uint64_t* count, uint64_t* sums)
+{
+    if (!table) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_contingency_get: null pointer");
+    const em2::ContingencyResult& r = table->result;
+    if (rowTotals) std::copy(r.rowTotals.begin(), r.rowTotals.end(), rowTotals);
+    if (columnTotals) std::copy(r.columnTotals.begin(), r.columnTotals.end(), columnTotals);
+    if (i0) std::copy(r.i0.begin(), r.i0.end(), i0);
+    if (i1) std::copy(r.i1.begin(), r.i1.end(), i1);
+    if (count) std::copy(r.count.begin(), r.count.end(), count);
+    if (sums) {
+        sums[0] = r.sumCells;
+        sums[1] = r.sumRows;
+        sums[2] = r.sumColumns;
+    }
+    return EM2_OK;
+}
+
+void em2_contingency_free(em2_contingency* table) { delete table; }
 
 }  // extern "C"

@@ -1,0 +1,363 @@
+// em2_contingency.hip -- the contingency table of two labelings of n cells: what ExpressionMatrix::computeMetaDataRandIndex
+// (src/ExpressionMatrix.cpp:1328-1390) fills with two std::map look-ups per cell and what computeRandIndex (src/randIndex.hpp:38-85)
+// sums over it, as a histogram of n pairs of integers.  Integer work only: every output is exact, and no
+// floating-point number is formed on the device.
+//
+// The table is kept sparse -- the cells that are not zero as (i0, i1, count), ascending -- because a field with many values
+// (createMetaDataFromClusterGraph gives every unclustered cell a value of its own) makes n0 x n1 far larger than n.  Two paths:
+//   * LDS path, n0 * n1 <= 16384:
+//       ldsCountKernel       every workgroup keeps a private copy of the table as 32-bit counters in LDS (at most 64 KiB), reads
+//                            its slice of the two id arrays with 16-byte loads, counts with LDS atomics and adds the counters
+//                            that are not zero to the 64-bit table in memory with vector atomics;
+//       denseTriplesKernel   one workgroup turns that table into the ascending triples (a scan over its 256 threads);
+//   * sort path, any n0 and n1:
+//       keysKernel           key = id0 << bits(n1) | id1;
+//       rocPRIM's radix sort of the keys over exactly bits(n0) + bits(n1) bits;
+//       headFlagsKernel, an inclusive scan of the flags, runStartsKernel, runCountsKernel: a run of equal keys is a table cell.
+// Both end the same way: triplesTotalsKernel adds every triple to its row and column total (vector atomics on 64-bit words) and
+// sums v (v - 1); pairSumKernel sums t (t - 1) over the row totals and over the column totals.
+// Every kernel that reads an id tests it against n0 / n1 before an address is formed with it, writes nothing for an element
+// that fails and raises the error word; the host reads that word before anything derived from the ids is used.
+
+#include "em2_contingency.h"
+#include "em2_hip_util.h"
+#include "em2_scratch.h"
+#include "em2_wave.h"
+
+#include <cstring>            // (rocPRIM calls memset without including it)
+#include <rocprim/rocprim.hpp>
+
+namespace em2 {
+namespace {
+
+typedef unsigned long long u64;      // (the type HIP's 64-bit atomicAdd takes)
+
+// The bits that hold every id below n (n >= 1): 0 for n == 1.
+inline uint32_t bitsFor(uint32_t n)
+{
+    uint32_t bits = 0;
+    while (bits < 32u && (uint64_t(1) << bits) < n) bits++;
+    return bits;
+}
+
+// The sum of `value` over the 64 lanes, in every lane.
+__device__ __forceinline__ u64 waveSumU64(u64 value)
+{
+#pragma unroll
+    for (int step = 32; step >= 1; step >>= 1) value += __shfl_xor(value, step, 64);
+    return value;
+}
+
+// Block b counts the elements [b * perBlock, min(n, (b + 1) * perBlock)); perBlock is a multiple of 4.  Wide: both id arrays
+// are 16-byte aligned, so is then every slice's first element.  Dynamic LDS: n0 * n1 counters.
+template <bool Wide>
+__global__ void __launch_bounds__(256)
+ldsCountKernel(const uint32_t* __restrict__ id0, const uint32_t* __restrict__ id1, uint64_t n, uint32_t n0, uint32_t n1,
+               uint64_t perBlock, u64* __restrict__ table, uint32_t* __restrict__ error)
+{
+    extern __shared__ uint32_t counters[];
+    const uint32_t cells = n0 * n1;
+    for (uint32_t c = threadIdx.x; c < cells; c += 256u) counters[c] = 0u;
+    __syncthreads();
+
+    const uint64_t begin = uint64_t(blockIdx.x) * perBlock;
+    const uint64_t end = begin < n ? (n - begin < perBlock ? n : begin + perBlock) : begin;
+    bool bad = false;
+    const auto add = [&](uint32_t a, uint32_t b) {
+        if (a < n0 && b < n1) atomicAdd(&counters[a * n1 + b], 1u);
+        else bad = true;
+    };
+    if (Wide) {
+        const uint64_t wholeEnd = begin + ((end - begin) & ~uint64_t(3));
+        for (uint64_t i = begin + 4u * threadIdx.x; i < wholeEnd; i += 1024u) {
+            const uint4 a = *reinterpret_cast<const uint4*>(id0 + i);
+            const uint4 b = *reinterpret_cast<const uint4*>(id1 + i);
+            add(a.x, b.x);
+            add(a.y, b.y);
+            add(a.z, b.z);
+            add(a.w, b.w);
+        }
+        const uint64_t i = wholeEnd + threadIdx.x;               // (at most 3 elements, in the last slice only)
+        if (i < end) add(id0[i], id1[i]);
+    } else {
+        for (uint64_t i = begin + threadIdx.x; i < end; i += 256u) add(id0[i], id1[i]);
+    }
+    __syncthreads();
+
+    for (uint32_t c = threadIdx.x; c < cells; c += 256u) {
+        const uint32_t v = counters[c];
+        if (v) atomicAdd(&table[c], u64(v));
+    }
+    if (bad) atomicOr(error, 1u);
+}
+
+// One workgroup: the cells of table[cells] that are not zero as (c / n1, c % n1, value), ascending by c; their number to *nnz.
+__global__ void __launch_bounds__(256)
+denseTriplesKernel(const u64* __restrict__ table, uint32_t cells, uint32_t n1, uint32_t* __restrict__ i0, uint32_t* __restrict__ i1,
+                   u64* __restrict__ count, u64* __restrict__ nnz)
+{
+    __shared__ uint32_t waveTotals[4];
+    const uint32_t chunk = (cells + 255u) / 256u;
+    const uint32_t begin = threadIdx.x * chunk < cells ? threadIdx.x * chunk : cells;
+    const uint32_t end = cells - begin < chunk ? cells : begin + chunk;
+    uint32_t mine = 0u;
+    for (uint32_t c = begin; c < end; c++) mine += table[c] != 0u ? 1u : 0u;
+    const uint32_t inclusive = waveInclusiveScan(mine);
+    const uint32_t wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63u) == 63u) waveTotals[wave] = inclusive;
+    __syncthreads();
+    uint32_t at = inclusive - mine;
+    for (uint32_t w = 0; w < wave; w++) at += waveTotals[w];
+    if (threadIdx.x == 255u) *nnz = u64(at) + mine;
+    for (uint32_t c = begin; c < end; c++) {
+        const u64 v = table[c];
+        if (!v) continue;
+        i0[at] = c / n1;
+        i1[at] = c % n1;
+        count[at] = v;
+        at++;
+    }
+}
+
+// keys[i] = id0[i] << bits1 | id1[i] for the elements whose ids are in range.
+__global__ void __launch_bounds__(256)
+keysKernel(const uint32_t* __restrict__ id0, const uint32_t* __restrict__ id1, uint64_t n, uint32_t n0, uint32_t n1, uint32_t bits1,
+           uint64_t* __restrict__ keys, uint32_t* __restrict__ error)
+{
+    bool bad = false;
+    for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += uint64_t(gridDim.x) * blockDim.x) {
+        const uint32_t a = id0[i], b = id1[i];
+        if (a < n0 && b < n1) keys[i] = uint64_t(a) << bits1 | b;
+        else bad = true;
+    }
+    if (bad) atomicOr(error, 1u);
+}
+
+// flags[i] = 1 where a run of equal keys begins.
+__global__ void __launch_bounds__(256)
+headFlagsKernel(const uint64_t* __restrict__ keys, uint64_t n, uint32_t* __restrict__ flags)
+{
+    for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += uint64_t(gridDim.x) * blockDim.x) {
+        flags[i] = i == 0u || keys[i] != keys[i - 1u] ? 1u : 0u;
+    }
+}
+
+// rank: the inclusive scan of the flags.  Run r = rank[i] - 1 begins at the i whose flag is set: its first element and its ids.
+__global__ void __launch_bounds__(256)
+runStartsKernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ flags, const uint32_t* __restrict__ rank, uint64_t n,
+                uint32_t bits1, uint32_t* __restrict__ starts, uint32_t* __restrict__ i0, uint32_t* __restrict__ i1)
+{
+    const uint64_t mask1 = (uint64_t(1) << bits1) - 1u;
+    for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += uint64_t(gridDim.x) * blockDim.x) {
+        if (!flags[i]) continue;
+        const uint32_t r = rank[i] - 1u;                         // (rank[i] in [1, i + 1]: r <= i < n, the arrays' size)
+        const uint64_t key = keys[i];
+        starts[r] = uint32_t(i);
+        i0[r] = uint32_t(key >> bits1);
+        i1[r] = uint32_t(key & mask1);
+    }
+}
+
+// count[r] = the length of run r; *nnz = the number of runs = rank[n - 1].
+__global__ void __launch_bounds__(256)
+runCountsKernel(const uint32_t* __restrict__ starts, const uint32_t* __restrict__ rank, uint64_t n, u64* __restrict__ count,
+                u64* __restrict__ nnz)
+{
+    const uint64_t runs = rank[n - 1u];
+    for (uint64_t r = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; r < runs; r += uint64_t(gridDim.x) * blockDim.x) {
+        count[r] = (r + 1u < runs ? uint64_t(starts[r + 1u]) : n) - starts[r];
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) *nnz = runs;
+}
+
+// rowTotals[i0] += count, columnTotals[i1] += count for every triple (the ids were tested where the triples were made);
+// *sumCells += v (v - 1).
+__global__ void __launch_bounds__(256)
+triplesTotalsKernel(const uint32_t* __restrict__ i0, const uint32_t* __restrict__ i1, const u64* __restrict__ count,
+                    const u64* __restrict__ nnz, u64* __restrict__ rowTotals, u64* __restrict__ columnTotals, u64* __restrict__ sumCells)
+{
+    const uint64_t triples = *nnz;
+    u64 sum = 0u;
+    for (uint64_t r = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; r < triples; r += uint64_t(gridDim.x) * blockDim.x) {
+        const u64 v = count[r];
+        atomicAdd(&rowTotals[i0[r]], v);
+        atomicAdd(&columnTotals[i1[r]], v);
+        sum += v * (v - 1u);
+    }
+    sum = waveSumU64(sum);
+    if ((threadIdx.x & 63u) == 0u && sum) atomicAdd(sumCells, sum);
+}
+
+// *sum += t (t - 1) over totals[count].
+__global__ void __launch_bounds__(256)
+pairSumKernel(const u64* __restrict__ totals, uint32_t count, u64* __restrict__ sum)
+{
+    u64 mine = 0u;
+    for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < count; i += uint64_t(gridDim.x) * blockDim.x) {
+        const u64 t = totals[i];
+        if (t) mine += t * (t - 1u);
+    }
+    mine = waveSumU64(mine);
+    if ((threadIdx.x & 63u) == 0u && mine) atomicAdd(sum, mine);
+}
+
+template <class T> hipError_t toHost(std::vector<T>& to, const void* from, size_t count, hipStream_t stream)
+{
+    to.resize(count);
+    if (count == 0) return hipSuccess;
+    return hipMemcpyAsync(to.data(), from, count * sizeof(T), hipMemcpyDeviceToHost, stream);
+}
+
+}  // namespace
+
+hipError_t runContingency(const uint32_t* d_id0, const uint32_t* d_id1, uint64_t n, uint32_t n0, uint32_t n1, int path,
+                          ContingencyResult& out, uint32_t* inputError, hipStream_t stream)
+{
+    *inputError = 0;
+    out = ContingencyResult();
+    out.n0 = n0;
+    out.n1 = n1;
+    out.n = n;
+    const uint64_t cells64 = uint64_t(n0) * n1;
+    const bool lds = path == kContingencyLds || (path == kContingencyAutomatic && cells64 <= kContingencyLdsCells);
+    out.path = lds ? kContingencyLds : kContingencySort;
+    out.rowTotals.assign(n0, 0u);
+    out.columnTotals.assign(n1, 0u);
+    if (n == 0) return hipSuccess;
+
+    StageTimer timer(lds ? "contingency (LDS)" : "contingency (sort)");
+    const dim3 threads(256);
+    const size_t capacity = lds ? size_t(cells64) : size_t(n);            // of the triples: the cells that are not zero
+    size_t at = 0;
+    const auto take = [&at](size_t bytes) {
+        const size_t here = at;
+        at += alignUp(bytes ? bytes : 1u);
+        return here;
+    };
+    // (everything up to offZeroEnd starts as zero)
+    const size_t offWords = take(256);                                      // error, nnz, the three sums
+    const size_t offRowTotals = take(size_t(n0) * sizeof(u64));
+    const size_t offColumnTotals = take(size_t(n1) * sizeof(u64));
+    const size_t offTable = take(lds ? size_t(cells64) * sizeof(u64) : 0u);
+    const size_t offZeroEnd = at;
+    const size_t offI0 = take(capacity * sizeof(uint32_t));
+    const size_t offI1 = take(capacity * sizeof(uint32_t));
+    const size_t offCount = take(capacity * sizeof(u64));
+    size_t offKeysA = 0, offKeysB = 0, offFlags = 0, offRank = 0, offStarts = 0, offTemp = 0, sortBytes = 0, scanBytes = 0;
+    const uint32_t bits1 = bitsFor(n1);
+    const uint32_t keyBits = bitsFor(n0) + bits1 ? bitsFor(n0) + bits1 : 1u;      // (n0 == n1 == 1: every key is 0, one bit)
+    if (!lds) {
+        offKeysA = take(size_t(n) * sizeof(uint64_t));
+        offKeysB = take(size_t(n) * sizeof(uint64_t));
+        offFlags = take(size_t(n) * sizeof(uint32_t));
+        offRank = take(size_t(n) * sizeof(uint32_t));
+        offStarts = take(size_t(n) * sizeof(uint32_t));
+        {
+            rocprim::double_buffer<uint64_t> keys(nullptr, nullptr);
+            EM2_TRY(rocprim::radix_sort_keys(nullptr, sortBytes, keys, size_t(n), 0u, keyBits, stream));
+            uint32_t* in = nullptr;
+            EM2_TRY(rocprim::inclusive_scan(nullptr, scanBytes, in, in, size_t(n), rocprim::plus<uint32_t>(), stream));
+        }
+        offTemp = take(sortBytes > scanBytes ? sortBytes : scanBytes);
+    }
+    CachedBuffer arena;
+    EM2_TRY(arena.allocate(at));
+    char* base = arena.as<char>();
+    uint32_t* error = reinterpret_cast<uint32_t*>(base + offWords);
+    u64* nnz = reinterpret_cast<u64*>(base + offWords + 8);
+    u64* sums = reinterpret_cast<u64*>(base + offWords + 16);               // cells, rows, columns
+    u64* rowTotals = reinterpret_cast<u64*>(base + offRowTotals);
+    u64* columnTotals = reinterpret_cast<u64*>(base + offColumnTotals);
+    u64* table = reinterpret_cast<u64*>(base + offTable);
+    uint32_t* i0 = reinterpret_cast<uint32_t*>(base + offI0);
+    uint32_t* i1 = reinterpret_cast<uint32_t*>(base + offI1);
+    u64* count = reinterpret_cast<u64*>(base + offCount);
+    EM2_TRY(hipMemsetAsync(base, 0, offZeroEnd, stream));
+
+    // an id out of range: nothing was written for it, and nothing below may use what the kernel left
+    const auto inputChecked = [&]() -> hipError_t {
+        EM2_TRY(hipMemcpyAsync(inputError, error, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        return hipStreamSynchronize(stream);
+    };
+
+    if (lds) {
+        // slices of at least four elements per table cell, so that adding a workgroup's table to memory does not cost more
+        // than counting; at most two workgroups for each of the 256 CUs
+        const uint64_t atLeast = 4u * cells64 > 4096u ? 4u * cells64 : 4096u;
+        uint64_t blocks = (n + atLeast - 1u) / atLeast;
+        if (blocks > 512u) blocks = 512u;
+        const uint64_t perBlock = ((n + blocks - 1u) / blocks + 3u) & ~uint64_t(3);
+        blocks = (n + perBlock - 1u) / perBlock;
+        const size_t ldsBytes = size_t(cells64) * sizeof(uint32_t);
+        const bool wide = ((reinterpret_cast<uintptr_t>(d_id0) | reinterpret_cast<uintptr_t>(d_id1)) & 15u) == 0u;
+        const void* kernel = wide ? reinterpret_cast<const void*>(&ldsCountKernel<true>) : reinterpret_cast<const void*>(&ldsCountKernel<false>);
+        EM2_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, int(kContingencyLdsCells * sizeof(uint32_t))));
+        if (wide) {
+            ldsCountKernel<true><<<dim3(uint32_t(blocks)), threads, ldsBytes, stream>>>(d_id0, d_id1, n, n0, n1, perBlock, table, error);
+        } else {
+            ldsCountKernel<false><<<dim3(uint32_t(blocks)), threads, ldsBytes, stream>>>(d_id0, d_id1, n, n0, n1, perBlock, table, error);
+        }
+        EM2_TRY(hipGetLastError());
+        EM2_TRY(inputChecked());
+        if (*inputError) {
+            arena.idle = true;
+            return hipSuccess;
+        }
+        EM2_TRY(timer.stage("count", stream));
+        denseTriplesKernel<<<dim3(1), threads, 0, stream>>>(table, uint32_t(cells64), n1, i0, i1, count, nnz);
+        EM2_TRY(hipGetLastError());
+    } else {
+        rocprim::double_buffer<uint64_t> keys(reinterpret_cast<uint64_t*>(base + offKeysA), reinterpret_cast<uint64_t*>(base + offKeysB));
+        uint32_t* flags = reinterpret_cast<uint32_t*>(base + offFlags);
+        uint32_t* rank = reinterpret_cast<uint32_t*>(base + offRank);
+        uint32_t* starts = reinterpret_cast<uint32_t*>(base + offStarts);
+        keysKernel<<<dim3(gridFor(n)), threads, 0, stream>>>(d_id0, d_id1, n, n0, n1, bits1, keys.current(), error);
+        EM2_TRY(hipGetLastError());
+        EM2_TRY(inputChecked());
+        if (*inputError) {
+            arena.idle = true;
+            return hipSuccess;
+        }
+        EM2_TRY(timer.stage("keys", stream));
+        EM2_TRY(rocprim::radix_sort_keys(base + offTemp, sortBytes, keys, size_t(n), 0u, keyBits, stream));
+        EM2_TRY(timer.stage("sort", stream));
+        const uint64_t* sorted = keys.current();
+        headFlagsKernel<<<dim3(gridFor(n)), threads, 0, stream>>>(sorted, n, flags);
+        EM2_TRY(hipGetLastError());
+        EM2_TRY(rocprim::inclusive_scan(base + offTemp, scanBytes, flags, rank, size_t(n), rocprim::plus<uint32_t>(), stream));
+        runStartsKernel<<<dim3(gridFor(n)), threads, 0, stream>>>(sorted, flags, rank, n, bits1, starts, i0, i1);
+        EM2_TRY(hipGetLastError());
+        runCountsKernel<<<dim3(gridFor(n)), threads, 0, stream>>>(starts, rank, n, count, nnz);
+        EM2_TRY(hipGetLastError());
+    }
+    EM2_TRY(timer.stage("triples", stream));
+
+    triplesTotalsKernel<<<dim3(gridFor(capacity)), threads, 0, stream>>>(i0, i1, count, nnz, rowTotals, columnTotals, sums);
+    EM2_TRY(hipGetLastError());
+    pairSumKernel<<<dim3(gridFor(n0)), threads, 0, stream>>>(rowTotals, n0, sums + 1);
+    EM2_TRY(hipGetLastError());
+    pairSumKernel<<<dim3(gridFor(n1)), threads, 0, stream>>>(columnTotals, n1, sums + 2);
+    EM2_TRY(hipGetLastError());
+    u64 words[4] = {0, 0, 0, 0};                                            // nnz and the three sums
+    EM2_TRY(hipMemcpyAsync(words, nnz, sizeof(words), hipMemcpyDeviceToHost, stream));
+    EM2_TRY(hipStreamSynchronize(stream));
+    EM2_TRY(timer.stage("totals and sums", stream));
+    if (words[0] > capacity) {
+        arena.idle = true;
+        return hipErrorUnknown;
+    }
+    out.sumCells = words[1];
+    out.sumRows = words[2];
+    out.sumColumns = words[3];
+    EM2_TRY(toHost(out.rowTotals, rowTotals, n0, stream));
+    EM2_TRY(toHost(out.columnTotals, columnTotals, n1, stream));
+    EM2_TRY(toHost(out.i0, i0, size_t(words[0]), stream));
+    EM2_TRY(toHost(out.i1, i1, size_t(words[0]), stream));
+    EM2_TRY(toHost(out.count, count, size_t(words[0]), stream));
+    EM2_TRY(hipStreamSynchronize(stream));
+    EM2_TRY(timer.stage("results to the host", stream));
+    arena.idle = true;                                                      // (everything that used the block has been waited for)
+    return hipSuccess;
+}
+
+}  // namespace em2

@@ -252,7 +252,7 @@ template <class Map> void deleteAll(Map& m)
 }
 }  // namespace
 
-Matrix::Matrix(const std::string& directoryName) : directoryName_(directoryName)
+Matrix::Matrix(const std::string& directoryName) : directoryName_(directoryName), metaData_(nullptr)
 {
   try {
     DIR* dir = ::opendir(directoryName.c_str());
@@ -288,6 +288,7 @@ Matrix::Matrix(const std::string& directoryName) : directoryName_(directoryName)
     }
     if (cellSets_.find("AllCells") == cellSets_.end()) fail(EM2_ERROR_RUNTIME, "Cell set \"AllCells\" is missing.");
     if (geneSets_.find("AllGenes") == geneSets_.end()) fail(EM2_ERROR_RUNTIME, "Gene set \"AllGenes\" is missing.");
+    openMetaData();                                                                               // ExpressionMatrix.cpp:118-121
   } catch (...) {
     deleteAll(geneSets_);
     deleteAll(cellSets_);
@@ -297,6 +298,7 @@ Matrix::Matrix(const std::string& directoryName) : directoryName_(directoryName)
 
 Matrix::~Matrix()
 {
+    closeMetaData();
     deleteAll(geneSets_);
     deleteAll(cellSets_);
 }

@@ -30,6 +30,9 @@ struct Error {
     std::string message;
 };
 
+class MetaDataStore;       // em2_meta_data.h
+struct MetaDataTable;
+
 // A read-only or writable mapping of one MemoryMapped file.
 class MappedFile {
 public:
@@ -178,6 +181,26 @@ public:
     // The stored entries of a cell (getCellExpressionCounts, src/ExpressionMatrix.cpp:1066-1075) in the mapped file.
     void cellExpressionCounts(uint32_t cellId, const em2_count*& entries, uint64_t& count) const;
 
+    // Cell meta data (em2_meta_data.cpp; the store's formats are in em2_meta_data.h).  The store is read when the directory is
+    // opened -- a directory without the CellMetaData* files is one where no cell has a field -- kept in host memory, created
+    // by the first write and written back by flush() and by the destructor.
+    //   setCellMetaData             src/ExpressionMatrix.cpp:942-967; cellMetaDataValue / cellMetaData :880-922;
+    //   removeCellMetaData          :998-1029; createCellSetUsingMetaData :1560-1622;
+    //   metaDataTable               histogramMetaData (:1301-1323) of one field (metaDataName1 == NULL) or two and the
+    //                               contingency table of :1369-1381, through em2_contingency_create;
+    //   computeMetaDataRandIndex    :1328-1390.
+    void setCellMetaData(uint32_t cellId, const std::string& name, const std::string& value);
+    std::string cellMetaDataValue(uint32_t cellId, const std::string& name) const;
+    std::vector<std::pair<std::string, std::string>> cellMetaData(uint32_t cellId) const;
+    void removeCellMetaData(const std::string& cellSetName, const std::string& metaDataName);
+    void createCellSetUsingMetaData(const std::string& cellSetName, const std::string& metaDataFieldName, const std::string& matchString,
+                                    bool useRegex);
+    void metaDataTable(const std::string& cellSetName, const std::string& metaDataName0, const std::string* metaDataName1,
+                       MetaDataTable& out) const;
+    void computeMetaDataRandIndex(const std::string& cellSetName, const std::string& metaDataName0, const std::string& metaDataName1,
+                                  double& randIndex, double& adjustedRandIndex) const;
+    void flush();
+
     const GeneSet& geneSet(const std::string& name) const;                 // throws "Gene set X does not exist."
     const MappedFile& cellSet(const std::string& name) const;              // throws "Cell set X does not exist."
 
@@ -198,6 +221,11 @@ private:
     MappedFile data_;        // CellExpressionCounts.data (em2_count)
     std::map<std::string, GeneSet*> geneSets_;
     std::map<std::string, MappedFile*> cellSets_;
+    void openMetaData();
+    void closeMetaData();
+    void checkCellId(const char* who, uint32_t cellId) const;
+    const MappedFile& cellSetForMetaData(const std::string& cellSetName) const;    // throws "Cell set X not found."
+    MetaDataStore* metaData_;
 };
 
 // SimilarPairs files (src/SimilarPairs.cpp:11-42 create, :369-379 copy): -Info, -Pairs, -CellInfo.

@@ -1,8 +1,11 @@
 // em2_matrix_capi.cpp -- C ABI of the ExpressionMatrix-level entry points (include/em2_lsh.h): translates
 // em2::host::Error into status codes + em2_last_error().
 #include "em2_host.h"
+#include "em2_meta_data.h"
 
+#include <algorithm>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 
@@ -11,6 +14,10 @@ extern "C" void em2_internal_set_last_error(const char* message);
 
 struct em2_matrix {
     em2::host::Matrix* impl;
+};
+
+struct em2_meta_data_table {
+    em2::host::MetaDataTable table;
 };
 
 namespace {
@@ -47,6 +54,16 @@ template <class F> int geneSetOperation(int* created, F f)
         *created = f(message) ? 1 : 0;
         if (!*created) em2_internal_set_last_error(message.c_str());
     });
+}
+
+// The two-call protocol of the entries that return bytes: value == NULL asks for *bytes, else *bytes is the buffer's size.
+void copyOut(const char* who, const std::string& from, uint64_t* bytes, char* to)
+{
+    if (to) {
+        if (*bytes < from.size()) throw em2::host::Error{EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": the buffer is too small"};
+        if (!from.empty()) std::memcpy(to, from.data(), from.size());
+    }
+    *bytes = from.size();
 }
 
 }  // namespace
@@ -519,6 +536,136 @@ int em2_tool_add_cells(const char* directoryName, const double* norm1Inverse, co
 {
     if (!directoryName || ((!norm1Inverse || !norm2Inverse) && cellCount)) return nullArgument("em2_tool_add_cells");
     return guarded([&] { em2::host::addCells(directoryName, norm1Inverse, norm2Inverse, cellCount); });
+}
+
+// ---- cell meta data (em2_meta_data.cpp) ----
+
+int em2_matrix_set_cell_meta_data(em2_matrix* matrix, uint32_t cellId, const char* name, const char* value)
+{
+    if (!matrix || !name || !value) return nullArgument("em2_matrix_set_cell_meta_data");
+    return guarded([&] { matrix->impl->setCellMetaData(cellId, name, value); });
+}
+
+int em2_matrix_get_cell_meta_data_value(em2_matrix* matrix, uint32_t cellId, const char* metaDataName, uint64_t* bytes, char* value)
+{
+    if (!matrix || !metaDataName || !bytes) return nullArgument("em2_matrix_get_cell_meta_data_value");
+    return guarded([&] { copyOut("em2_matrix_get_cell_meta_data_value", matrix->impl->cellMetaDataValue(cellId, metaDataName), bytes, value); });
+}
+
+int em2_matrix_get_cell_meta_data(em2_matrix* matrix, uint32_t cellId, uint64_t* bytes, char* pairs)
+{
+    if (!matrix || !bytes) return nullArgument("em2_matrix_get_cell_meta_data");
+    return guarded([&] {
+        std::string all;
+        for (const auto& p : matrix->impl->cellMetaData(cellId)) {
+            all.append(p.first).push_back('\0');
+            all.append(p.second).push_back('\0');
+        }
+        copyOut("em2_matrix_get_cell_meta_data", all, bytes, pairs);
+    });
+}
+
+int em2_matrix_remove_cell_meta_data(em2_matrix* matrix, const char* cellSetName, const char* metaDataName)
+{
+    if (!matrix || !cellSetName || !metaDataName) return nullArgument("em2_matrix_remove_cell_meta_data");
+    return guarded([&] { matrix->impl->removeCellMetaData(cellSetName, metaDataName); });
+}
+
+int em2_matrix_create_cell_set_using_meta_data(em2_matrix* matrix, const char* cellSetName, const char* metaDataFieldName,
+                                               const char* matchString, int useRegex)
+{
+    if (!matrix || !cellSetName || !metaDataFieldName || !matchString) return nullArgument("em2_matrix_create_cell_set_using_meta_data");
+    return guarded([&] { matrix->impl->createCellSetUsingMetaData(cellSetName, metaDataFieldName, matchString, useRegex != 0); });
+}
+
+int em2_matrix_compute_meta_data_rand_index(em2_matrix* matrix, const char* cellSetName, const char* metaDataName0,
+                                            const char* metaDataName1, double* randIndex, double* adjustedRandIndex)
+{
+    if (!matrix || !cellSetName || !metaDataName0 || !metaDataName1 || !randIndex || !adjustedRandIndex) {
+        return nullArgument("em2_matrix_compute_meta_data_rand_index");
+    }
+    return guarded([&] { matrix->impl->computeMetaDataRandIndex(cellSetName, metaDataName0, metaDataName1, *randIndex, *adjustedRandIndex); });
+}
+
+int em2_matrix_meta_data_table(em2_matrix* matrix, const char* cellSetName, const char* metaDataName0, const char* metaDataName1,
+                               em2_meta_data_table** table)
+{
+    if (!matrix || !cellSetName || !metaDataName0 || !table) return nullArgument("em2_matrix_meta_data_table");
+    *table = nullptr;
+    return guarded([&] {
+        std::unique_ptr<em2_meta_data_table> t(new em2_meta_data_table);
+        const std::string name1 = metaDataName1 ? metaDataName1 : "";
+        matrix->impl->metaDataTable(cellSetName, metaDataName0, metaDataName1 ? &name1 : nullptr, t->table);
+        *table = t.release();
+    });
+}
+
+int em2_meta_data_table_sizes(const em2_meta_data_table* table, uint64_t* valueCount0, uint64_t* valueCount1, uint64_t* valueBytes0,
+                              uint64_t* valueBytes1, uint64_t* nonZeroCount, int* path)
+{
+    if (!table) return nullArgument("em2_meta_data_table_sizes");
+    const em2::host::MetaDataTable& t = table->table;
+    uint64_t bytes[2] = {0, 0};
+    for (int f = 0; f < 2; f++) {
+        for (const std::string& value : t.values[f]) bytes[f] += value.size() + 1u;
+    }
+    if (valueCount0) *valueCount0 = t.values[0].size();
+    if (valueCount1) *valueCount1 = t.values[1].size();
+    if (valueBytes0) *valueBytes0 = bytes[0];
+    if (valueBytes1) *valueBytes1 = bytes[1];
+    if (nonZeroCount) *nonZeroCount = t.count.size();
+    if (path) *path = t.path;
+    return EM2_OK;
+}
+
+int em2_meta_data_table_get(const em2_meta_data_table* table, char* values0, uint64_t* counts0, char* values1, uint64_t* counts1,
+                            uint64_t* row, uint64_t* column, uint64_t* count, uint64_t* sums)
+{
+    if (!table) return nullArgument("em2_meta_data_table_get");
+    const em2::host::MetaDataTable& t = table->table;
+    char* values[2] = {values0, values1};
+    uint64_t* counts[2] = {counts0, counts1};
+    for (int f = 0; f < 2; f++) {
+        if (values[f]) {
+            char* at = values[f];
+            for (const std::string& value : t.values[f]) {
+                std::memcpy(at, value.c_str(), value.size() + 1u);
+                at += value.size() + 1u;
+            }
+        }
+        if (counts[f]) std::copy(t.counts[f].begin(), t.counts[f].end(), counts[f]);
+    }
+    if (row) std::copy(t.row.begin(), t.row.end(), row);
+    if (column) std::copy(t.column.begin(), t.column.end(), column);
+    if (count) std::copy(t.count.begin(), t.count.end(), count);
+    if (sums) std::copy(t.sums, t.sums + 4, sums);
+    return EM2_OK;
+}
+
+void em2_meta_data_table_free(em2_meta_data_table* table) { delete table; }
+
+int em2_rand_index(uint64_t sumCells, uint64_t sumRows, uint64_t sumColumns, uint64_t n, double* randIndex, double* adjustedRandIndex)
+{
+    if (!randIndex || !adjustedRandIndex) return nullArgument("em2_rand_index");
+    return guarded([&] {
+        if (n == 0) throw em2::host::Error{EM2_ERROR_RUNTIME, "Assertion failed: rowCount > 0 (computeRandIndex: a table of no element)"};
+        if (!em2::host::randIndexFromSums(sumCells, sumRows, sumColumns, n, *randIndex, *adjustedRandIndex)) {
+            throw em2::host::Error{EM2_ERROR_UNSUPPORTED, "em2_rand_index: n (n - 1) is not below 2^53, where the reference's sums of doubles "
+                                                          "stop being exact; at most 94906266 elements are supported."};
+        }
+    });
+}
+
+int em2_matrix_flush(em2_matrix* matrix)
+{
+    if (!matrix) return nullArgument("em2_matrix_flush");
+    return guarded([&] { matrix->impl->flush(); });
+}
+
+int em2_tool_create_meta_data(const char* directoryName, uint32_t cellCount, uint64_t nameCapacity, uint64_t valueCapacity)
+{
+    if (!directoryName) return nullArgument("em2_tool_create_meta_data");
+    return guarded([&] { em2::host::createMetaDataFiles(directoryName, cellCount, nameCapacity, valueCapacity); });
 }
 
 }  // extern "C"

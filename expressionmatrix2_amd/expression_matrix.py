@@ -65,8 +65,12 @@ class ExpressionMatrix:
         self._signatureGraphs = {}
         self._geneGraphs = {}
         if self._handle:
-            capi.load().em2_matrix_close(self._handle)
-            self._handle = ctypes.c_void_p(None)
+            lib = capi.load()
+            try:
+                capi.check(lib.em2_matrix_flush(self._handle))       # (em2_matrix_close flushes too, but cannot say that it failed)
+            finally:
+                lib.em2_matrix_close(self._handle)
+                self._handle = ctypes.c_void_p(None)
 
     def __del__(self):
         try:
@@ -386,7 +390,7 @@ class ExpressionMatrix:
     def removeSimilarPairs(self, similarPairsName):
         capi.check(capi.load().em2_matrix_remove_similar_pairs(self._handle, _b(similarPairsName)))
 
-    # ---- src/PythonModule.cpp:616-750: cell sets (those made from meta data are not offered: there is no meta data store) ----
+    # ---- src/PythonModule.cpp:616-750: cell sets (createCellSetUsingMetaData is below, with the meta data) ----
     def createCellSet(self, cellSetName, cellIds):
         """ExpressionMatrix::createCellSet (src/ExpressionMatrix.cpp:1626-1633): the cells with these global ids, sorted and
         deduplicated, as CellSet-<cellSetName>, usable by name at once.  "Cell set X already exists."; an id not below the
@@ -446,6 +450,93 @@ class ExpressionMatrix:
         """ExpressionMatrix::removeCellSet (src/CellSets.cpp:88-97): "Cell set X does not exist."; the file goes.  AllCells
         cannot be removed (this package's guard)."""
         capi.check(capi.load().em2_matrix_remove_cell_set(self._handle, _b(cellSetName)))
+
+    # ---- src/PythonModule.cpp:328-400, 622-644, 1122: cell meta data ----
+    def setCellMetaData(self, cellId, name, value):
+        """ExpressionMatrix::setCellMetaData (src/ExpressionMatrix.cpp:942-967): the value of the cell's field `name`, replaced
+        where the cell has one.  The reference binds no Python name for it (its users write meta data through ingest); here it
+        is the way in.  The store lives in memory until close() or flush() write it to the CellMetaData* files."""
+        capi.check(capi.load().em2_matrix_set_cell_meta_data(self._handle, int(cellId), _b(name), _b(value)))
+
+    def _bytes_of(self, entry, *arguments):
+        size = ctypes.c_uint64(0)
+        capi.check(entry(self._handle, *arguments, ctypes.byref(size), None))
+        buffer = ctypes.create_string_buffer(max(int(size.value), 1))
+        capi.check(entry(self._handle, *arguments, ctypes.byref(size), buffer))
+        return buffer.raw[:size.value]
+
+    def getCellMetaDataValue(self, cellId, metaDataName):
+        """getCellMetaData(cellId, name) (src/ExpressionMatrix.cpp:880-907): "" for an unknown name or a cell without it."""
+        raw = self._bytes_of(capi.load().em2_matrix_get_cell_meta_data_value, int(cellId), _b(metaDataName))
+        return raw.decode("utf-8", "surrogateescape")
+
+    def getCellMetaData(self, cellId):
+        """[(name, value)] of a cell, in list order (src/ExpressionMatrix.cpp:913-922)."""
+        raw = self._bytes_of(capi.load().em2_matrix_get_cell_meta_data, int(cellId))
+        parts = [p.decode("utf-8", "surrogateescape") for p in raw.split(b"\0")[:-1]]
+        return list(zip(parts[0::2], parts[1::2]))
+
+    def getCellsMetaData(self, cellIds):
+        """getCellMetaData for every cell of cellIds, in their order (src/ExpressionMatrix.cpp:928-937)."""
+        return [self.getCellMetaData(cellId) for cellId in cellIds]
+
+    def removeCellMetaData(self, cellSetName, metaDataName):
+        """ExpressionMatrix::removeCellMetaData (src/ExpressionMatrix.cpp:998-1029): the field goes from every cell of the
+        cell set; a name no cell ever had does nothing.  "Cell set X not found." """
+        capi.check(capi.load().em2_matrix_remove_cell_meta_data(self._handle, _b(cellSetName), _b(metaDataName)))
+
+    def createCellSetUsingMetaData(self, cellSetName, metaDataFieldName, matchString, useRegex):
+        """ExpressionMatrix::createCellSetUsingMetaData (src/ExpressionMatrix.cpp:1560-1622): the cells, of ALL cells, whose
+        field equals matchString or, with useRegex, matches it as a whole (std::regex, default flags)."""
+        capi.check(capi.load().em2_matrix_create_cell_set_using_meta_data(self._handle, _b(cellSetName), _b(metaDataFieldName),
+                                                                          _b(matchString), 1 if useRegex else 0))
+
+    def createMetaDataFromClusterGraph(self, clusterGraphName, metaDataName):
+        """ExpressionMatrix::createMetaDataFromClusterGraph (src/ExpressionMatrix.cpp:2308-2333): the cluster id of every
+        clustered cell as the field metaDataName, cluster by cluster in the graph's vertex order, then "Unclustered-<cellId>"
+        for every unclustered cell in unclusteredCells order (the order decides the value ids in the files)."""
+        c = self._cluster_graph(clusterGraphName)
+        _b(metaDataName)
+        r = c["result"]
+        for at, clusterId in enumerate(r["clusterIds"].tolist()):
+            value = str(clusterId)
+            for cellId in c["vertexCellIds"][r["cells"][int(r["cellOffsets"][at]):int(r["cellOffsets"][at + 1])]].tolist():
+                self.setCellMetaData(cellId, metaDataName, value)
+        for cellId in self._cluster_graph_unclustered_cells(clusterGraphName):
+            self.setCellMetaData(cellId, metaDataName, "Unclustered-" + str(cellId))
+
+    def computeMetaDataRandIndex(self, cellSetName="AllCells", metaDataName0=_REQUIRED, metaDataName1=_REQUIRED):
+        """ExpressionMatrix::computeMetaDataRandIndex (src/ExpressionMatrix.cpp:1328-1390) -> (randIndex, adjustedRandIndex)
+        of two fields over a cell set, the reference's doubles bit for bit.  The contingency table is counted on the GPU
+        (em2_contingency_create) from one integer per cell and field; the strings are not touched."""
+        if metaDataName0 is _REQUIRED or metaDataName1 is _REQUIRED:
+            raise TypeError("computeMetaDataRandIndex(): metaDataName0 and metaDataName1 are required")
+        ri, ari = ctypes.c_double(0.), ctypes.c_double(0.)
+        capi.check(capi.load().em2_matrix_compute_meta_data_rand_index(self._handle, _b(cellSetName), _b(metaDataName0),
+                                                                       _b(metaDataName1), ctypes.byref(ri), ctypes.byref(ari)))
+        return ri.value, ari.value
+
+    # The reference shows these two through its HTTP pages only (metaDataHistogram, metaDataContingencyTable): no public name.
+    def _meta_data_histogram(self, cellSetName, metaDataName):
+        """histogramMetaData (src/ExpressionMatrix.cpp:1301-1323): [(value, count)], count descending, then value ascending."""
+        handle = ctypes.c_void_p(None)
+        capi.check(capi.load().em2_matrix_meta_data_table(self._handle, _b(cellSetName), _b(metaDataName), None, ctypes.byref(handle)))
+        t = capi.meta_data_table_take(handle)
+        return list(zip(t["values0"], t["counts0"]))
+
+    def _meta_data_contingency_table(self, cellSetName, metaDataName0, metaDataName1):
+        """(triples, histogram0, histogram1, path): the cells of the contingency table (src/ExpressionMatrix.cpp:1369-1381)
+        that are not zero as (row, column, count), rows and columns numbered in the two histograms' order, ascending by (row,
+        column); path is the one em2_contingency_create took (capi.CONTINGENCY_LDS or capi.CONTINGENCY_SORT)."""
+        handle = ctypes.c_void_p(None)
+        capi.check(capi.load().em2_matrix_meta_data_table(self._handle, _b(cellSetName), _b(metaDataName0), _b(metaDataName1),
+                                                          ctypes.byref(handle)))
+        t = capi.meta_data_table_take(handle)
+        return t["triples"], list(zip(t["values0"], t["counts0"])), list(zip(t["values1"], t["counts1"])), t["path"]
+
+    def flush(self):
+        """Writes the meta data store to its files (close() does it too)."""
+        capi.check(capi.load().em2_matrix_flush(self._handle))
 
     # ---- src/PythonModule.cpp:404-478: the stored counts of cells (global ids) ----
     @staticmethod

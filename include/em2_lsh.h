@@ -738,6 +738,42 @@ int em2_gene_graph_get(const em2_gene_graph* graph, uint32_t* vertices, uint32_t
 void em2_gene_graph_free(em2_gene_graph* graph);
 
 /* ------------------------------------------------------------------------------------------------------
+ * The contingency table of two labelings of n items.  csrc/em2_contingency.hip, DESIGN.md 3.16.  Integers only: every output
+ * is exact.
+ * ------------------------------------------------------------------------------------------------------ */
+
+/* What ExpressionMatrix::computeMetaDataRandIndex (src/ExpressionMatrix.cpp:1369-1381) fills with four string copies and two
+ * std::map look-ups per cell, and what computeRandIndex (src/randIndex.hpp:38-85) sums over it: the table whose cell (i, j)
+ * counts the items with id0 == i and id1 == j.  id0[n] with id0[i] < n0, id1[n] with id1[i] < n1, host memory
+ * (em2_dev_contingency: device memory).  An id out of range is EM2_ERROR_INVALID_ARGUMENT: the kernels test an id before they
+ * form an address with it and write nothing for that element.  n0 and n1 positive; n below 2^32 (EM2_ERROR_UNSUPPORTED).
+ * path: 0 chooses -- a private table per workgroup in LDS where n0 * n1 <= 16384, else a radix sort of the (id0, id1) keys --
+ * 1 and 2 force the LDS path (n0 * n1 > 16384: EM2_ERROR_INVALID_ARGUMENT) and the sort path.  Both give the same result.
+ * The table is returned sparse, because a field with many values (createMetaDataFromClusterGraph gives every unclustered cell a
+ * value of its own) makes the reference's dense n0 x n1 vector<vector<size_t>> impossible to allocate.  The result is an
+ * object: em2_contingency_sizes (n0, n1, n, the cells that are not zero, the path that ran: 1 or 2; any may be NULL), then
+ * em2_contingency_get into arrays of those sizes (any may be NULL):
+ *   rowTotals[n0], columnTotals[n1]           the items with id0 == i, with id1 == j;
+ *   i0 / i1 / count[nonZeroCount]             the cells that are not zero, ascending by (i0, i1);
+ *   sums[3]                                   sum of v (v - 1) over the cells, of t (t - 1) over the row totals, over the column
+ *                                             totals: 2 a, 2 (a + b) and 2 (a + c) of src/randIndex.hpp:63-85.
+ * (The host-pointer entry is em2_contingency_create because C has one name space for the type and the functions.) */
+typedef struct em2_contingency em2_contingency;
+int em2_contingency_create(const uint32_t* id0, const uint32_t* id1, uint64_t n, uint32_t n0, uint32_t n1, int path, em2_contingency** table);
+int em2_dev_contingency(const uint32_t* d_id0, const uint32_t* d_id1, uint64_t n, uint32_t n0, uint32_t n1, int path, em2_contingency** table);
+int em2_contingency_sizes(const em2_contingency* table, uint32_t* n0, uint32_t* n1, uint64_t* n, uint64_t* nonZeroCount, int* path);
+int em2_contingency_get(const em2_contingency* table, uint64_t* rowTotals, uint64_t* columnTotals, uint32_t* i0, uint32_t* i1,
+                        uint64_t* count, uint64_t* sums);
+void em2_contingency_free(em2_contingency* table);
+
+/* computeRandIndex (src/randIndex.hpp:58-97) from the three sums of em2_contingency_get and n, on the host, expression by
+ * expression (the library is built without FMA contraction).  While n (n - 1) < 2^53 -- n <= 94906266 -- a, b, c, d, nBinomial2
+ * and every partial sum of the reference's loops are integers a double holds, so the reference's sums are exact in any order and
+ * the two results are the reference's bit for bit (NaN where it divides 0 by 0: n == 1, one value in both fields).  Above that
+ * EM2_ERROR_UNSUPPORTED; n == 0 is the reference's CZI_ASSERT(rowCount > 0), EM2_ERROR_RUNTIME. */
+int em2_rand_index(uint64_t sumCells, uint64_t sumRows, uint64_t sumColumns, uint64_t n, double* randIndex, double* adjustedRandIndex);
+
+/* ------------------------------------------------------------------------------------------------------
  * ExpressionMatrix-level entry points: the methods the reference binds to Python (src/PythonModule.cpp),
  * operating by NAME on a data directory in the reference's memory-mapped formats.  Results are files in
  * that directory (SimilarPairs-<name>-{Info,Pairs,CellInfo}, Lsh-<name>-{Info,Signatures}), byte-compatible
@@ -747,7 +783,8 @@ void em2_gene_graph_free(em2_gene_graph* graph);
 typedef struct em2_matrix em2_matrix;
 
 /* ExpressionMatrix(directoryName, allowReadOnly) for an existing directory (src/ExpressionMatrix.cpp:109-160);
- * opens only what the LSH path reads: CellExpressionCounts.{toc,data}, CellSet-*, GeneSet-*-{GlobalIds,LocalIds}. */
+ * opens only what the entries here read: CellExpressionCounts.{toc,data}, CellSet-*, GeneSet-*-{GlobalIds,LocalIds} and, where
+ * the directory has them, the CellMetaData* files (read into host memory; see the cell meta data entries). */
 int em2_matrix_open(const char* directoryName, em2_matrix** matrix);
 void em2_matrix_close(em2_matrix* matrix);
 
@@ -924,6 +961,63 @@ int em2_matrix_downsample_cell_set(em2_matrix* matrix, const char* inputCellSetN
 int em2_matrix_remove_cell_set(em2_matrix* matrix, const char* cellSetName);
 int em2_matrix_cell_set_names(em2_matrix* matrix, uint64_t* bytes, char* names);
 
+/* Cell meta data: every cell carries (name, value) string pairs.  csrc/em2_meta_data.{h,cpp}, DESIGN.md 3.16.  The store is the
+ * reference's files -- CellMetaData.{toc,data,freeSlots} (MemoryMapped::VectorOfLists<pair<StringId, StringId>>,
+ * src/MemoryMappedVectorOfLists.hpp), CellMetaDataNames-* and CellMetaDataValues-* (MemoryMapped::StringTable<uint32_t>,
+ * src/MemoryMappedStringTable.hpp), CellMetaDataNamesUsageCount (src/ExpressionMatrix.cpp:971-993) -- read by em2_matrix_open,
+ * kept in host memory and written back by em2_matrix_flush and em2_matrix_close.  A directory without them is one where no
+ * cell has a field; the first write creates the store with an empty list per cell and string tables of 1 << 12 slots that
+ * double as the reference's do.  A store whose lists leave the node store or do not close is EM2_ERROR_IO.  A cell id not below
+ * the cell count is EM2_ERROR_INVALID_ARGUMENT (the reference reads out of bounds).
+ *   em2_matrix_set_cell_meta_data          ExpressionMatrix::setCellMetaData (src/ExpressionMatrix.cpp:942-967): the name and
+ *                                          the value enter their tables, in that order; the value of the cell's first node of
+ *                                          that name is replaced, else a node is appended and the name's usage count grows.
+ *   em2_matrix_get_cell_meta_data_value    getCellMetaData(cellId, name) (:880-907): "" for an unknown name or a cell without
+ *                                          it.  value == NULL: *bytes is set; else *bytes is the buffer's size on entry.
+ *   em2_matrix_get_cell_meta_data          getCellMetaData(cellId) (:913-922): name, 0, value, 0, ... in list order; two calls
+ *                                          as above.  (getCellsMetaData, :928-937, is a loop over this.)
+ *   em2_matrix_remove_cell_meta_data       removeCellMetaData (:998-1029): "Cell set X not found."; an unknown name does
+ *                                          nothing; else the first node of that name goes for every cell of the set, its slot
+ *                                          becomes the next one to be reused, the usage count shrinks.
+ *   em2_matrix_create_cell_set_using_meta_data   createCellSetUsingMetaData (:1560-1622): "Cell set X already exists." first;
+ *                                          then the std::regex (default flags; an invalid one is EM2_ERROR_RUNTIME with
+ *                                          std::regex_error's text and no set is made); then ALL cells, each judged by its first
+ *                                          node of that name: std::regex_match of the whole value, or string equality.  The
+ *                                          verdict is formed once per value, not per cell.  The set is stored as
+ *                                          em2_matrix_create_cell_set stores one.
+ *   em2_matrix_compute_meta_data_rand_index      computeMetaDataRandIndex (:1328-1390): "Cell set X not found.", "Meta data
+ *                                          field X not found." for name 0, then name 1; an empty cell set is computeRandIndex's
+ *                                          CZI_ASSERT(rowCount > 0) (EM2_ERROR_RUNTIME).  The host walks the lists of the set
+ *                                          once and writes one compact id per cell and field (the distinct value ids of the
+ *                                          field within the set, ascending; a cell without the field and a stored "" share one,
+ *                                          as the reference hands both out as ""); the table is em2_contingency_create, the
+ *                                          doubles em2_rand_index: above 94906266 cells EM2_ERROR_UNSUPPORTED.
+ *   em2_matrix_meta_data_table             histogramMetaData (:1301-1323) of field 0 and, unless metaDataName1 is NULL, of
+ *                                          field 1 -- count descending, then value ascending as std::string compares -- and the
+ *                                          contingency table of :1369-1381 with rows and columns in that order, sparse.  The
+ *                                          same checks.  em2_meta_data_table_sizes, then em2_meta_data_table_get (any may be
+ *                                          NULL): values0[valueBytes0] (every value followed by a 0 byte), counts0[valueCount0],
+ *                                          the same for field 1, row / column / count[nonZeroCount] ascending by (row, column),
+ *                                          sums[4] = the three of em2_contingency_get and n. */
+typedef struct em2_meta_data_table em2_meta_data_table;
+int em2_matrix_set_cell_meta_data(em2_matrix* matrix, uint32_t cellId, const char* name, const char* value);
+int em2_matrix_get_cell_meta_data_value(em2_matrix* matrix, uint32_t cellId, const char* metaDataName, uint64_t* bytes, char* value);
+int em2_matrix_get_cell_meta_data(em2_matrix* matrix, uint32_t cellId, uint64_t* bytes, char* pairs);
+int em2_matrix_remove_cell_meta_data(em2_matrix* matrix, const char* cellSetName, const char* metaDataName);
+int em2_matrix_create_cell_set_using_meta_data(em2_matrix* matrix, const char* cellSetName, const char* metaDataFieldName,
+                                               const char* matchString, int useRegex);
+int em2_matrix_compute_meta_data_rand_index(em2_matrix* matrix, const char* cellSetName, const char* metaDataName0,
+                                            const char* metaDataName1, double* randIndex, double* adjustedRandIndex);
+int em2_matrix_meta_data_table(em2_matrix* matrix, const char* cellSetName, const char* metaDataName0, const char* metaDataName1,
+                               em2_meta_data_table** table);
+int em2_meta_data_table_sizes(const em2_meta_data_table* table, uint64_t* valueCount0, uint64_t* valueCount1, uint64_t* valueBytes0,
+                              uint64_t* valueBytes1, uint64_t* nonZeroCount, int* path);
+int em2_meta_data_table_get(const em2_meta_data_table* table, char* values0, uint64_t* counts0, char* values1, uint64_t* counts1,
+                            uint64_t* row, uint64_t* column, uint64_t* count, uint64_t* sums);
+void em2_meta_data_table_free(em2_meta_data_table* table);
+/* Writes what the matrix holds in memory and has changed (the meta data store) to its files. */
+int em2_matrix_flush(em2_matrix* matrix);
+
 /* getDenseExpressionMatrix (src/PythonModule.cpp:78-154) for a gene set and a cell set of the directory: the rows
  * [rowBegin, rowEnd) of the cell set into out[(row - rowBegin) * geneSetSize + localGene] (see em2_dev_dense_expression for the
  * arithmetic and elementType).  Only those rows travel to the device, with the gene set applied there.  In the reference's
@@ -993,6 +1087,11 @@ int em2_tool_add_cell_set(const char* directoryName, const char* name, const uin
 /* Writes a Cells file (MemoryMapped::Vector<Cell>, src/Cell.hpp) whose records hold these norm1Inverse / norm2Inverse and
  * zeros elsewhere: one record per global cell. */
 int em2_tool_add_cells(const char* directoryName, const double* norm1Inverse, const double* norm2Inverse, uint32_t cellCount);
+
+/* Writes an empty cell meta data store -- one empty list per cell, string tables of the next powers of two at or above the two
+ * capacities -- as the reference's ExpressionMatrix constructor and its cellMetaData.push_back() per cell leave one
+ * (src/ExpressionMatrix.cpp:81-84, :223). */
+int em2_tool_create_meta_data(const char* directoryName, uint32_t cellCount, uint64_t nameCapacity, uint64_t valueCapacity);
 
 #ifdef __cplusplus
 }
