@@ -252,6 +252,23 @@ SYMBOLS = {
     "em2_meta_data_table_free": (None, [_c.c_void_p]),
     "em2_matrix_flush": (_c.c_int, [_c.c_void_p]),
     "em2_tool_create_meta_data": (_c.c_int, [_c.c_char_p, _c.c_uint32, _c.c_uint64, _c.c_uint64]),
+    "em2_matrix_create": (_c.c_int, [_c.c_char_p, _c.POINTER(_c.c_void_p)]),
+    "em2_matrix_gene_count": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_uint32)]),
+    "em2_matrix_cell_count": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_uint32)]),
+    "em2_matrix_add_gene": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.POINTER(_c.c_int)]),
+    "em2_matrix_gene_name": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.POINTER(_c.c_uint64), _c.c_void_p]),
+    "em2_matrix_gene_id_from_name": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.POINTER(_c.c_uint32)]),
+    "em2_matrix_cell_id_from_string": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.POINTER(_c.c_uint32)]),
+    "em2_matrix_add_cell": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_uint64, _c.c_uint32, _c.c_char_p, _c.c_uint64, _c.c_void_p,
+                                       _c.c_uint32, _c.POINTER(_c.c_uint32)]),
+    "em2_dev_ingest_count": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_uint32,
+                                        _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "em2_dev_ingest_fill": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_uint32,
+                                       _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "em2_set_ingest_lds_row_limit": (None, [_c.c_uint32]),
+    "em2_matrix_add_cells_csr": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_uint64, _c.c_uint32, _c.c_char_p, _c.c_uint64, _c.c_uint32,
+                                            _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_char_p, _c.c_char_p,
+                                            _c.c_uint64, _c.c_uint32, _c.c_uint64, _c.POINTER(_c.c_uint32), _c.POINTER(_c.c_uint32)]),
 }
 
 

@@ -156,10 +156,10 @@ bool isSorted(const uint32_t* p, size_t n) { return std::is_sorted(p, p + n); }
 // MappedFile
 // ---------------------------------------------------------------------------------------------------------
 
-void MappedFile::openExisting(const std::string& path, bool isObject, size_t objectSize)
+void MappedFile::openExisting(const std::string& path, bool isObject, size_t objectSize, bool writable)
 {
     close();
-    const int fd = ::open(path.c_str(), O_RDONLY);
+    const int fd = ::open(path.c_str(), writable ? O_RDWR : O_RDONLY);
     if (fd == -1) {
         fail(EM2_ERROR_IO, "Error accessing " + path + ": Error " + std::to_string(errno) + " opening " + path + ": " +
                                std::string(strerror(errno)));
@@ -173,11 +173,13 @@ void MappedFile::openExisting(const std::string& path, bool isObject, size_t obj
         ::close(fd);
         fail(EM2_ERROR_IO, "Error accessing " + path + ": file is shorter than its header.");
     }
-    void* p = ::mmap(nullptr, size_t(st.st_size), PROT_READ, MAP_SHARED, fd, 0);
+    void* p = ::mmap(nullptr, size_t(st.st_size), writable ? PROT_READ | PROT_WRITE : PROT_READ, MAP_SHARED, fd, 0);
     ::close(fd);
     if (p == MAP_FAILED) fail(EM2_ERROR_IO, "Error accessing " + path + ": Error during mmap.");
     base_ = p;
     size_ = size_t(st.st_size);
+    writable_ = writable;
+    path_ = path;
     const FileHeader* h = static_cast<const FileHeader*>(base_);
     // The checks of accessExisting (src/MemoryMappedVector.hpp:497-499).
     const bool ok = h->magicNumber == (isObject ? kObjectMagic : kVectorMagic) && h->fileSize == size_ &&
@@ -213,7 +215,51 @@ void MappedFile::createNew(const std::string& path, bool isObject, size_t object
     if (p == MAP_FAILED) fail(EM2_ERROR_IO, "Error creating " + path);
     base_ = p;
     size_ = h.fileSize;
+    writable_ = true;
+    path_ = path;
     std::memcpy(base_, &h, sizeof(h));        // data area is already zero = value-initialised objects
+}
+
+void MappedFile::reserve(size_t capacity)
+{
+    FileHeader* h = static_cast<FileHeader*>(base_);
+    if (!base_ || !writable_ || h->magicNumber != kVectorMagic) fail(EM2_ERROR_RUNTIME, "Error growing " + path_ + ": not a writable vector.");
+    if (capacity <= h->capacity) return;
+    const size_t wanted = std::max<size_t>(capacity, 2u * size_t(h->capacity));
+    const size_t pageCount = (sizeof(FileHeader) + size_t(h->objectSize) * wanted - 1) / kPageSize + 1;
+    const size_t fileSize = pageCount * kPageSize;
+    const int fd = ::open(path_.c_str(), O_RDWR);
+    if (fd == -1) fail(EM2_ERROR_IO, "Error growing " + path_ + ": " + std::string(strerror(errno)));
+    const bool truncated = ::ftruncate(fd, off_t(fileSize)) == 0;          // (the new bytes are zero)
+    ::close(fd);
+    if (!truncated) fail(EM2_ERROR_IO, "Error growing " + path_ + ": " + std::string(strerror(errno)));
+    void* p = ::mremap(base_, size_, fileSize, MREMAP_MAYMOVE);
+    if (p == MAP_FAILED) fail(EM2_ERROR_IO, "Error growing " + path_ + ": Error during mremap.");
+    base_ = p;
+    size_ = fileSize;
+    h = static_cast<FileHeader*>(base_);
+    h->pageCount = pageCount;
+    h->fileSize = fileSize;
+    h->capacity = (fileSize - sizeof(FileHeader)) / h->objectSize;
+}
+
+void MappedFile::resize(size_t objectCount)
+{
+    reserve(objectCount);
+    FileHeader* h = static_cast<FileHeader*>(base_);
+    if (objectCount > h->objectCount) {
+        std::memset(static_cast<char*>(data()) + h->objectCount * h->objectSize, 0, (objectCount - h->objectCount) * h->objectSize);
+    }
+    h->objectCount = objectCount;
+}
+
+void MappedFile::append(const void* objects, size_t count)
+{
+    const size_t before = objectCount();
+    reserve(before + count);
+    FileHeader* h = static_cast<FileHeader*>(base_);
+    if (count) std::memcpy(static_cast<char*>(data()) + before * h->objectSize, objects, count * h->objectSize);
+    h->objectCount = before + count;
 }
 
 void MappedFile::close()
@@ -223,6 +269,7 @@ void MappedFile::close()
         ::munmap(base_, size_);
         base_ = nullptr;
         size_ = 0;
+        writable_ = false;
     }
 }
 
@@ -252,7 +299,7 @@ template <class Map> void deleteAll(Map& m)
 }
 }  // namespace
 
-Matrix::Matrix(const std::string& directoryName) : directoryName_(directoryName), metaData_(nullptr)
+Matrix::Matrix(const std::string& directoryName) : directoryName_(directoryName), metaData_(nullptr), ingest_(nullptr)
 {
   try {
     DIR* dir = ::opendir(directoryName.c_str());
@@ -289,7 +336,10 @@ Matrix::Matrix(const std::string& directoryName) : directoryName_(directoryName)
     if (cellSets_.find("AllCells") == cellSets_.end()) fail(EM2_ERROR_RUNTIME, "Cell set \"AllCells\" is missing.");
     if (geneSets_.find("AllGenes") == geneSets_.end()) fail(EM2_ERROR_RUNTIME, "Gene set \"AllGenes\" is missing.");
     openMetaData();                                                                               // ExpressionMatrix.cpp:118-121
+    openIngest(true);                                                                             // ExpressionMatrix.cpp:109-117
   } catch (...) {
+    closeIngest();
+    closeMetaData();
     deleteAll(geneSets_);
     deleteAll(cellSets_);
     throw;
@@ -298,6 +348,7 @@ Matrix::Matrix(const std::string& directoryName) : directoryName_(directoryName)
 
 Matrix::~Matrix()
 {
+    closeIngest();
     closeMetaData();
     deleteAll(geneSets_);
     deleteAll(cellSets_);

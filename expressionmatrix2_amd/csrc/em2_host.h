@@ -32,18 +32,25 @@ struct Error {
 
 class MetaDataStore;       // em2_meta_data.h
 struct MetaDataTable;
+struct IngestState;        // em2_ingest.h
 
 // A read-only or writable mapping of one MemoryMapped file.
 class MappedFile {
 public:
-    MappedFile() : base_(nullptr), size_(0) {}
+    MappedFile() : base_(nullptr), size_(0), writable_(false) {}
     ~MappedFile() { close(); }
     MappedFile(const MappedFile&) = delete;
     MappedFile& operator=(const MappedFile&) = delete;
 
-    void openExisting(const std::string& path, bool isObject, size_t objectSize);
+    void openExisting(const std::string& path, bool isObject, size_t objectSize, bool writable = false);
     void createNew(const std::string& path, bool isObject, size_t objectSize, size_t objectCount);
     void close();
+    // MemoryMapped::Vector::push_back / resize (src/MemoryMappedVector.hpp:575-640) for a vector that was created here or
+    // opened writable: the file grows to at least twice its capacity when it is full (the reference: 1.5 times), new objects
+    // of resize are zero.  data() may move.
+    void append(const void* objects, size_t count);
+    void resize(size_t objectCount);
+    bool isWritable() const { return writable_; }
 
     bool isOpen() const { return base_ != nullptr; }
     size_t objectCount() const;
@@ -51,8 +58,11 @@ public:
     void* data() { return static_cast<char*>(base_) + 256; }
 
 private:
+    void reserve(size_t capacity);
     void* base_;
     size_t size_;
+    bool writable_;
+    std::string path_;
 };
 
 void removeFile(const std::string& path);
@@ -201,6 +211,28 @@ public:
                                   double& randIndex, double& adjustedRandIndex) const;
     void flush();
 
+    // Ingest (em2_ingest_host.cpp; the files are in em2_ingest.h).  create is ExpressionMatrix::createNew
+    // (src/ExpressionMatrix.cpp:56-101): an error if the directory exists; the matrix it returns is open.  The methods that
+    // need the files only create() writes throw EM2_ERROR_RUNTIME with the missing file's name on a directory without them.
+    //   addGene                     src/ExpressionMatrixGenes.cpp:12-39
+    //   geneName, geneIdFromName, cellIdFromString    src/ExpressionMatrix.cpp:822-874 (0xffffffff = not found)
+    //   addCell                     :165-294; a failing call leaves the store as it was
+    //   addCellsFromCsr             the per-barcode loop of addCellsFromHdf5 (src/ExpressionMatrixHdf5.cpp:113-200) on the
+    //                               arrays of the file, the cells' entries on the device; all or nothing, the error of the
+    //                               lowest failing barcode.  skip[i] != 0: the barcode is below the count threshold.
+    static Matrix* create(const std::string& directoryName);
+    uint32_t geneCount() const;
+    bool addGene(const std::string& geneName);
+    std::string geneName(uint32_t geneId) const;
+    uint32_t geneIdFromName(const std::string& geneName) const;
+    uint32_t cellIdFromString(const std::string& s) const;
+    uint32_t addCell(const std::vector<std::pair<std::string, std::string>>& metaData,
+                     const std::vector<std::pair<std::string, float>>& expressionCounts);
+    void addCellsFromCsr(const std::vector<std::string>& geneNames, const std::vector<std::string>& cellNames, const uint64_t* indptr,
+                         const uint32_t* indices, const float* values, uint64_t entryCount, const uint8_t* skip,
+                         const std::string& cellNamePrefix, const std::vector<std::pair<std::string, std::string>>& cellMetaData,
+                         uint64_t chunkBytes, uint32_t& firstCellId, uint32_t& addedCellCount);
+
     const GeneSet& geneSet(const std::string& name) const;                 // throws "Gene set X does not exist."
     const MappedFile& cellSet(const std::string& name) const;              // throws "Cell set X does not exist."
 
@@ -226,6 +258,14 @@ private:
     void checkCellId(const char* who, uint32_t cellId) const;
     const MappedFile& cellSetForMetaData(const std::string& cellSetName) const;    // throws "Cell set X not found."
     MetaDataStore* metaData_;
+    void openIngest(bool writable);
+    void closeIngest();
+    void flushIngest();
+    IngestState& ingest(const char* who) const;               // throws where the directory is no complete store
+    // The writes of addCell after its checks: the name, the meta data list, the entries, the Cell record, AllCells.
+    void commitCell(const std::vector<std::pair<std::string, std::string>>& metaData, const em2_count* entries, uint64_t entryCount,
+                    const void* cellRecord);
+    IngestState* ingest_;
 };
 
 // SimilarPairs files (src/SimilarPairs.cpp:11-42 create, :369-379 copy): -Info, -Pairs, -CellInfo.

@@ -668,4 +668,125 @@ int em2_tool_create_meta_data(const char* directoryName, uint32_t cellCount, uin
     return guarded([&] { em2::host::createMetaDataFiles(directoryName, cellCount, nameCapacity, valueCapacity); });
 }
 
+// ---- ingest (em2_ingest_host.cpp, em2_ingest.hip) ----
+
+}  // extern "C"
+
+namespace {
+
+// `count` strings, each followed by its NUL, in `bytes` bytes.
+std::vector<std::string> splitStrings(const char* who, const char* packed, uint64_t bytes, uint64_t count)
+{
+    std::vector<std::string> result;
+    result.reserve(size_t(count));
+    uint64_t at = 0;
+    while (at < bytes && result.size() < count) {
+        const void* end = std::memchr(packed + at, 0, size_t(bytes - at));
+        if (!end) break;
+        const uint64_t length = uint64_t(static_cast<const char*>(end) - (packed + at));
+        result.emplace_back(packed + at, size_t(length));
+        at += length + 1u;
+    }
+    if (result.size() != count || at != bytes) {
+        throw em2::host::Error{EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": the packed strings are not as many as their count says"};
+    }
+    return result;
+}
+
+std::vector<std::pair<std::string, std::string>> splitPairs(const char* who, const char* packed, uint64_t bytes, uint64_t pairCount)
+{
+    const std::vector<std::string> flat = splitStrings(who, packed, bytes, 2u * pairCount);
+    std::vector<std::pair<std::string, std::string>> pairs;
+    for (size_t i = 0; i < flat.size(); i += 2) pairs.emplace_back(flat[i], flat[i + 1]);
+    return pairs;
+}
+
+}  // namespace
+
+extern "C" {
+
+int em2_matrix_create(const char* directoryName, em2_matrix** matrix)
+{
+    if (!directoryName || !matrix) return nullArgument("em2_matrix_create");
+    *matrix = nullptr;
+    return guarded([&] {
+        std::unique_ptr<em2::host::Matrix> m(em2::host::Matrix::create(directoryName));
+        *matrix = new em2_matrix{m.get()};
+        m.release();
+    });
+}
+
+int em2_matrix_gene_count(em2_matrix* matrix, uint32_t* geneCount)
+{
+    if (!matrix || !geneCount) return nullArgument("em2_matrix_gene_count");
+    return guarded([&] { *geneCount = matrix->impl->geneCount(); });
+}
+
+int em2_matrix_cell_count(em2_matrix* matrix, uint32_t* cellCount)
+{
+    if (!matrix || !cellCount) return nullArgument("em2_matrix_cell_count");
+    return guarded([&] { *cellCount = matrix->impl->cellCount(); });
+}
+
+int em2_matrix_add_gene(em2_matrix* matrix, const char* geneName, int* added)
+{
+    if (!matrix || !geneName || !added) return nullArgument("em2_matrix_add_gene");
+    *added = 0;
+    return guarded([&] { *added = matrix->impl->addGene(geneName) ? 1 : 0; });
+}
+
+int em2_matrix_gene_name(em2_matrix* matrix, uint32_t geneId, uint64_t* bytes, char* value)
+{
+    if (!matrix || !bytes) return nullArgument("em2_matrix_gene_name");
+    return guarded([&] { copyOut("em2_matrix_gene_name", matrix->impl->geneName(geneId), bytes, value); });
+}
+
+int em2_matrix_gene_id_from_name(em2_matrix* matrix, const char* geneName, uint32_t* geneId)
+{
+    if (!matrix || !geneName || !geneId) return nullArgument("em2_matrix_gene_id_from_name");
+    return guarded([&] { *geneId = matrix->impl->geneIdFromName(geneName); });
+}
+
+int em2_matrix_cell_id_from_string(em2_matrix* matrix, const char* s, uint32_t* cellId)
+{
+    if (!matrix || !s || !cellId) return nullArgument("em2_matrix_cell_id_from_string");
+    return guarded([&] { *cellId = matrix->impl->cellIdFromString(s); });
+}
+
+int em2_matrix_add_cell(em2_matrix* matrix, const char* metaData, uint64_t metaDataBytes, uint32_t metaDataPairCount,
+                        const char* geneNames, uint64_t geneNamesBytes, const float* counts, uint32_t countCount, uint32_t* cellId)
+{
+    if (!matrix || !cellId || (!metaData && metaDataBytes) || (!geneNames && geneNamesBytes) || (!counts && countCount)) {
+        return nullArgument("em2_matrix_add_cell");
+    }
+    return guarded([&] {
+        const auto pairs = splitPairs("em2_matrix_add_cell", metaData, metaDataBytes, metaDataPairCount);
+        const std::vector<std::string> names = splitStrings("em2_matrix_add_cell", geneNames, geneNamesBytes, countCount);
+        std::vector<std::pair<std::string, float>> expressionCounts;
+        expressionCounts.reserve(names.size());
+        for (size_t i = 0; i < names.size(); i++) expressionCounts.emplace_back(names[i], counts[i]);
+        *cellId = matrix->impl->addCell(pairs, expressionCounts);
+    });
+}
+
+int em2_matrix_add_cells_csr(em2_matrix* matrix, const char* geneNames, uint64_t geneNamesBytes, uint32_t geneNameCount,
+                             const char* cellNames, uint64_t cellNamesBytes, uint32_t cellCount, const uint64_t* indptr,
+                             const uint32_t* indices, const float* values, uint64_t entryCount, const uint8_t* skip,
+                             const char* cellNamePrefix, const char* cellMetaData, uint64_t cellMetaDataBytes,
+                             uint32_t cellMetaDataPairCount, uint64_t chunkBytes, uint32_t* firstCellId, uint32_t* addedCellCount)
+{
+    if (!matrix || !indptr || !cellNamePrefix || !firstCellId || !addedCellCount || (!geneNames && geneNamesBytes) ||
+        (!cellNames && cellNamesBytes) || (!cellMetaData && cellMetaDataBytes) || ((!indices || !values) && entryCount)) {
+        return nullArgument("em2_matrix_add_cells_csr");
+    }
+    return guarded([&] {
+        const char* who = "em2_matrix_add_cells_csr";
+        const std::vector<std::string> genes = splitStrings(who, geneNames, geneNamesBytes, geneNameCount);
+        const std::vector<std::string> cells = splitStrings(who, cellNames, cellNamesBytes, cellCount);
+        const auto pairs = splitPairs(who, cellMetaData, cellMetaDataBytes, cellMetaDataPairCount);
+        matrix->impl->addCellsFromCsr(genes, cells, indptr, indices, values, entryCount, skip, cellNamePrefix, pairs, chunkBytes,
+                                      *firstCellId, *addedCellCount);
+    });
+}
+
 }  // extern "C"

@@ -143,21 +143,22 @@ std::string StringTable::get(uint32_t id) const
 // MetaDataStore
 // ---------------------------------------------------------------------------------------------------------
 
-void MetaDataStore::load(const std::string& directoryName, uint32_t cellCount)
+void MetaDataStore::load(const std::string& directoryName, uint32_t cellCount, const std::string& prefix)
 {
-    present = fileExists(directoryName + "/CellMetaData.toc");
+    const std::string base = directoryName + "/" + prefix + "MetaData";
+    present = fileExists(base + ".toc");
     dirty = false;
     if (!present) return;
-    readVector(directoryName + "/CellMetaData.toc", toc);
-    readVector(directoryName + "/CellMetaData.data", nodes);
-    readVector(directoryName + "/CellMetaData.freeSlots", freeSlots);
-    readVector(directoryName + "/CellMetaDataNamesUsageCount", usage);
-    names.load(directoryName + "/CellMetaDataNames");
-    values.load(directoryName + "/CellMetaDataValues");
+    readVector(base + ".toc", toc);
+    readVector(base + ".data", nodes);
+    readVector(base + ".freeSlots", freeSlots);
+    readVector(base + "NamesUsageCount", usage);
+    names.load(base + "Names");
+    values.load(base + "Values");
     if (toc.size() != cellCount) {
-        damaged("CellMetaData holds " + std::to_string(toc.size()) + " lists for " + std::to_string(cellCount) + " cells");
+        damaged(prefix + "MetaData holds " + std::to_string(toc.size()) + " lists for " + std::to_string(cellCount) + (prefix == "Cell" ? " cells" : " genes"));
     }
-    if (usage.size() != names.size()) damaged("CellMetaDataNamesUsageCount is not as long as the table of names");
+    if (usage.size() != names.size()) damaged(prefix + "MetaDataNamesUsageCount is not as long as the table of names");
 }
 
 void MetaDataStore::create(uint32_t cellCount, uint64_t nameCapacity, uint64_t valueCapacity)
@@ -175,16 +176,25 @@ void MetaDataStore::create(uint32_t cellCount, uint64_t nameCapacity, uint64_t v
     present = dirty = true;
 }
 
-void MetaDataStore::flush(const std::string& directoryName)
+void MetaDataStore::flush(const std::string& directoryName, const std::string& prefix)
 {
     if (!present || !dirty) return;
-    writeVector(directoryName + "/CellMetaData.toc", toc);
-    writeVector(directoryName + "/CellMetaData.data", nodes);
-    writeVector(directoryName + "/CellMetaData.freeSlots", freeSlots);
-    writeVector(directoryName + "/CellMetaDataNamesUsageCount", usage);
-    names.write(directoryName + "/CellMetaDataNames");
-    values.write(directoryName + "/CellMetaDataValues");
+    const std::string base = directoryName + "/" + prefix + "MetaData";
+    writeVector(base + ".toc", toc);
+    writeVector(base + ".data", nodes);
+    writeVector(base + ".freeSlots", freeSlots);
+    writeVector(base + "NamesUsageCount", usage);
+    names.write(base + "Names");
+    values.write(base + "Values");
     dirty = false;
+}
+
+void MetaDataStore::pushBackList()
+{
+    const uint64_t slot = allocateSlot();
+    toc.push_back(slot);
+    at(slot).previous = at(slot).next = slot;
+    dirty = true;
 }
 
 const MetaDataNode& MetaDataStore::at(uint64_t node) const
@@ -326,7 +336,11 @@ void Matrix::closeMetaData()
     metaData_ = nullptr;
 }
 
-void Matrix::flush() { metaData_->flush(directoryName_); }
+void Matrix::flush()
+{
+    metaData_->flush(directoryName_);
+    flushIngest();
+}
 
 void Matrix::checkCellId(const char* who, uint32_t cellId) const
 {

@@ -60,10 +60,14 @@ public:
     StringTable names, values;
     std::vector<uint32_t> usage;
 
-    void load(const std::string& directoryName, uint32_t cellCount);
+    // prefix: "Cell", or "Gene" for the gene meta data of a complete store (GeneMetaData.*, GeneMetaDataNames-*, ...), which has
+    // the same containers (src/ExpressionMatrix.hpp) with one list per gene.
+    void load(const std::string& directoryName, uint32_t cellCount, const std::string& prefix = "Cell");
     // One empty list per cell: what the reference's cellMetaData.push_back() per cell leaves (src/ExpressionMatrix.cpp:223).
     void create(uint32_t cellCount, uint64_t nameCapacity, uint64_t valueCapacity);
-    void flush(const std::string& directoryName);
+    void flush(const std::string& directoryName, const std::string& prefix = "Cell");
+    // VectorOfLists::push_back() (:195-203): one more, empty list; its end node takes a free slot where there is one.
+    void pushBackList();
 
     static constexpr uint64_t kNoNode = ~uint64_t(0);
     // The first node of the cell's list that carries nameId, kNoNode where there is none.  Every index is checked and the walk

@@ -22,6 +22,12 @@ _REQUIRED = object()
 # device buffer.  Tests set it small to run several chunks.
 DENSE_CHUNK_BYTES = 1 << 30
 
+# addCellsFromCsr hands its barcodes to the GPU in chunks whose arrays take at most this many bytes (one barcode at least).
+# Tests set it small to run several chunks.
+INGEST_CHUNK_BYTES = 1 << 30
+
+INVALID_ID = 0xffffffff        # invalidGeneId, invalidCellId (src/Ids.hpp)
+
 
 class NormalizationMethod(enum.IntEnum):
     """NormalizationMethod (src/NormalizationMethod.hpp:11-16) with the members the reference's module exposes
@@ -51,8 +57,8 @@ def _distributed():
 class ExpressionMatrix:
     def __init__(self, directoryName, allowReadOnly=False):
         # src/PythonModule.cpp:164-176 / src/ExpressionMatrix.cpp:39-52.  The reference creates the directory when it
-        # does not exist; creating an EMPTY expression matrix is ingest (out of scope here), so a missing directory
-        # is an error.  allowReadOnly is accepted for signature compatibility: the path never writes its inputs.
+        # does not exist; here that is the explicit ExpressionMatrix.create(directoryName), and a missing directory
+        # stays an error of the constructor.  allowReadOnly is accepted for signature compatibility.
         self.directoryName = directoryName
         self._handle = ctypes.c_void_p(None)
         self._cellGraphs = {}          # ExpressionMatrix::cellGraphs (src/ExpressionMatrix.hpp): in memory only
@@ -60,6 +66,114 @@ class ExpressionMatrix:
         self._signatureGraphs = {}     # ExpressionMatrix::signatureGraphs, likewise
         self._geneGraphs = {}          # ExpressionMatrix::geneGraphs, likewise
         capi.check(capi.load().em2_matrix_open(_b(directoryName), ctypes.byref(self._handle)))
+
+    @classmethod
+    def create(cls, directoryName):
+        """ExpressionMatrix::createNew (src/ExpressionMatrix.cpp:56-101): a new directory with every file of an empty store,
+        and the open matrix on it.  It is an error if the directory exists.  (The constructor never creates: a missing
+        directory stays its error.)"""
+        self = cls.__new__(cls)
+        self.directoryName = directoryName
+        self._handle = ctypes.c_void_p(None)
+        self._cellGraphs, self._clusterGraphs, self._signatureGraphs, self._geneGraphs = {}, {}, {}, {}
+        capi.check(capi.load().em2_matrix_create(_b(directoryName), ctypes.byref(self._handle)))
+        return self
+
+    # ---- ingest: src/PythonModule.cpp addGene, addCell, addCellsFromHdf5; the lookups of src/ExpressionMatrix.cpp:822-874 ----
+    def geneCount(self):
+        n = ctypes.c_uint32(0)
+        capi.check(capi.load().em2_matrix_gene_count(self._handle, ctypes.byref(n)))
+        return n.value
+
+    def cellCount(self):
+        n = ctypes.c_uint32(0)
+        capi.check(capi.load().em2_matrix_cell_count(self._handle, ctypes.byref(n)))
+        return n.value
+
+    def addGene(self, geneName):
+        """ExpressionMatrix::addGene (src/ExpressionMatrixGenes.cpp:12-39): True if the gene was added, False if the store
+        had it."""
+        added = ctypes.c_int(0)
+        capi.check(capi.load().em2_matrix_add_gene(self._handle, _b(geneName), ctypes.byref(added)))
+        return bool(added.value)
+
+    def geneName(self, geneId):
+        return self._bytes_of(capi.load().em2_matrix_gene_name, int(geneId)).decode("utf-8", "surrogateescape")
+
+    def geneIdFromName(self, geneName):
+        """The gene's id, INVALID_ID (0xffffffff, the reference's invalidGeneId) for a name the store does not have."""
+        found = ctypes.c_uint32(0)
+        capi.check(capi.load().em2_matrix_gene_id_from_name(self._handle, _b(geneName), ctypes.byref(found)))
+        return found.value
+
+    def cellIdFromString(self, s):
+        """ExpressionMatrix::cellIdFromString (src/ExpressionMatrix.cpp:822-836): a decimal number below the cell count is that
+        cell id; anything else is looked up as a cell name; INVALID_ID where there is none."""
+        found = ctypes.c_uint32(0)
+        capi.check(capi.load().em2_matrix_cell_id_from_string(self._handle, _b(s), ctypes.byref(found)))
+        return found.value
+
+    @staticmethod
+    def _pack(strings):
+        return b"".join(_b(s) + b"\0" for s in strings)
+
+    def addCell(self, metaData, expressionCounts):
+        """ExpressionMatrix::addCell (src/ExpressionMatrix.cpp:165-294): metaData is a list of (name, value) with a CellName,
+        expressionCounts a list of (geneName, count); returns the cell id.  Unlike the reference's, a failing call leaves
+        the store unchanged."""
+        pairs = self._pack([s for pair in metaData for s in pair])
+        names = self._pack([name for name, _ in expressionCounts])
+        counts = np.ascontiguousarray([count for _, count in expressionCounts], dtype=np.float32)
+        cell = ctypes.c_uint32(0)
+        capi.check(capi.load().em2_matrix_add_cell(self._handle, pairs, len(pairs), len(metaData), names, len(names), capi._ptr(counts),
+                                                   len(counts), ctypes.byref(cell)))
+        return cell.value
+
+    def addCellsFromCsr(self, geneNames, cellNames, indptr, indices, data, cellNamePrefix="", cellMetaData=(),
+                        totalExpressionCountThreshold=0.):
+        """The arrays of a 10X file as ExpressionMatrix::addCellsFromHdf5 (src/ExpressionMatrixHdf5.cpp:45-218) adds them:
+        every gene of geneNames, then barcode i as the cell cellNamePrefix + "-" + cellNames[i] with the counts
+        float(data[j]) of the genes geneNames[indices[j]], j in [indptr[i], indptr[i + 1]), and the cellMetaData pairs behind
+        its CellName.  A barcode whose counts sum to less than totalExpressionCountThreshold is skipped: neither named nor
+        checked.  data is an integer array (the threshold is decided on the exact row sums) or float32 (the threshold must
+        be 0).  The cells' entries are prepared on the GPU in chunks of at most INGEST_CHUNK_BYTES bytes.  All or nothing:
+        on any error no gene and no cell is added, and the error is that of the lowest failing barcode.  Returns the ids of
+        the added cells as a range."""
+        indptr = np.asarray(indptr)
+        indices = np.asarray(indices)
+        data = np.asarray(data)
+        if indptr.ndim != 1 or indices.ndim != 1 or data.ndim != 1 or len(indptr) != len(cellNames) + 1 or len(indices) != len(data):
+            raise RuntimeError("addCellsFromCsr: indptr must have one entry more than cellNames, indices as many as data")
+        if len(indptr) and (np.any(indptr < 0) or np.any(indices < 0)):
+            raise RuntimeError("addCellsFromCsr: a negative offset or index")
+        if len(indices) and int(indices.max()) >= len(geneNames):
+            raise RuntimeError("addCellsFromCsr: an index is not below the number of gene names")
+        indptr = np.ascontiguousarray(indptr, dtype=np.uint64)
+        indices = np.ascontiguousarray(indices, dtype=np.uint32)
+        threshold = float(totalExpressionCountThreshold)
+        skip = None
+        if data.dtype.kind in "iu":
+            if threshold > 0.:
+                # the reference adds the uint32 counts in double; exact while the sums stay below 2^53, as are these
+                ends = np.concatenate([[0], np.cumsum(data.astype(object) if data.dtype.itemsize == 8 else data.astype(np.int64))])
+                ok = len(indptr) and indptr[0] == 0 and np.all(np.diff(indptr.astype(np.int64)) >= 0) and indptr[-1] == len(data)
+                if ok:
+                    sums = ends[indptr[1:].astype(np.int64)] - ends[indptr[:-1].astype(np.int64)]
+                    skip = np.ascontiguousarray(np.asarray([s < threshold for s in sums], dtype=np.uint8))
+        elif data.dtype == np.float32:
+            if threshold != 0.:
+                raise RuntimeError("addCellsFromCsr: float32 data takes no totalExpressionCountThreshold")
+        else:
+            raise RuntimeError("addCellsFromCsr: data must be an integer array or float32")
+        values = np.ascontiguousarray(data, dtype=np.float32)
+        genes, cells = self._pack(geneNames), self._pack(cellNames)
+        pairs = self._pack([s for pair in cellMetaData for s in pair])
+        first, added = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        capi.check(capi.load().em2_matrix_add_cells_csr(
+            self._handle, genes, len(genes), len(geneNames), cells, len(cells), len(cellNames), capi._ptr(indptr), capi._ptr(indices),
+            capi._ptr(values), len(values), capi._ptr(skip) if skip is not None else None, _b(cellNamePrefix), pairs, len(pairs),
+            len(cellMetaData), int(INGEST_CHUNK_BYTES), ctypes.byref(first), ctypes.byref(added)))
+        return range(first.value, first.value + added.value)
 
     def close(self):
         self._signatureGraphs = {}
@@ -539,10 +653,16 @@ class ExpressionMatrix:
         capi.check(capi.load().em2_matrix_flush(self._handle))
 
     # ---- src/PythonModule.cpp:404-478: the stored counts of cells (global ids) ----
-    @staticmethod
-    def _gene_id(geneId):
+    def _gene_id(self, geneId):
+        """A gene id, or a gene name where the directory has the GeneNames table (a store that create() made): "Gene X does
+        not exist." (src/ExpressionMatrix.cpp:1051-1061, :1096-1106)."""
         if isinstance(geneId, str):
-            raise TypeError("gene names are not offered: this package reads no GeneNames table; pass a gene id")
+            found = ctypes.c_uint32(0)
+            if capi.load().em2_matrix_gene_id_from_name(self._handle, _b(geneId), ctypes.byref(found)) != capi.EM2_OK:
+                raise TypeError("gene names are not offered: this directory has no GeneNames table; pass a gene id")
+            if found.value == INVALID_ID:
+                raise RuntimeError("Gene " + geneId + " does not exist.")
+            return found.value
         return int(geneId)
 
     def _cell_counts(self, cellId):

@@ -1093,6 +1093,96 @@ int em2_tool_add_cells(const char* directoryName, const double* norm1Inverse, co
  * (src/ExpressionMatrix.cpp:81-84, :223). */
 int em2_tool_create_meta_data(const char* directoryName, uint32_t cellCount, uint64_t nameCapacity, uint64_t valueCapacity);
 
+/* ---- Ingest ----
+ *
+ * ExpressionMatrix::createNew (src/ExpressionMatrix.cpp:56-101): a new directory with every file of a store -- GeneNames-*,
+ * GeneMetaData.{toc,data,freeSlots}, GeneMetaDataNames-*, GeneMetaDataValues-*, GeneMetaDataNamesUsageCount, Cells, CellNames-*,
+ * the CellMetaData* family, CellExpressionCounts.{toc,data} (the toc holds the single 0), CellSet-AllCells and
+ * GeneSet-AllGenes-{GlobalIds,LocalIds}, empty -- and the open matrix on it.  It is an error (EM2_ERROR_RUNTIME) if the
+ * directory exists.  New string tables start at 4096 slots (the reference: up to 1 << 24) and double as the reference's do;
+ * vectors grow by doubling (the reference: 1.5 times).  Every file passes the reference's open checks
+ * (src/MemoryMappedVector.hpp:497-499); capacities and file sizes are not the reference's, object counts and objects are.
+ *
+ * em2_matrix_open opens these files where the directory has them.  On a directory without them (em2_tool_create_directory)
+ * every entry below except the two counts fails with EM2_ERROR_RUNTIME and a text that names the missing file.  The string
+ * tables and the gene meta data are kept in host memory and written by em2_matrix_flush and em2_matrix_close, as the cell
+ * meta data is; the vectors (counts, Cells, AllCells, AllGenes) grow in their mapped files.  After any of the calls every
+ * other entry of the same handle sees the new genes and cells. */
+int em2_matrix_create(const char* directoryName, em2_matrix** matrix);
+
+/* geneCount() and cellCount() (src/ExpressionMatrix.hpp).  On a directory without GeneNames the gene count is the length of
+ * GeneSet-AllGenes-LocalIds. */
+int em2_matrix_gene_count(em2_matrix* matrix, uint32_t* geneCount);
+int em2_matrix_cell_count(em2_matrix* matrix, uint32_t* cellCount);
+
+/* ExpressionMatrix::addGene (src/ExpressionMatrixGenes.cpp:12-39): *added = 1 and the gene gets the next id, an empty meta
+ * data list with the field GeneName, and its place in AllGenes; *added = 0 for a name the store has. */
+int em2_matrix_add_gene(em2_matrix* matrix, const char* geneName, int* added);
+
+/* geneName, geneIdFromName and cellIdFromString (src/ExpressionMatrix.cpp:822-874).  The name comes by the two-call protocol
+ * of em2_matrix_get_cell_meta_data_value; a gene id not below the gene count is EM2_ERROR_INVALID_ARGUMENT (the reference
+ * reads out of bounds).  An unknown name gives 0xffffffff.  cellIdFromString takes a text as a cell id where
+ * lexical_cast<CellId> does and the number is below the cell count, and as a cell name otherwise.  Accepted as a number: an
+ * optional '+', then decimal digits only, value at most 0xffffffff.  (Departure: boost also takes a leading '-' and negates
+ * modulo 2^32; here such a text is a name.) */
+int em2_matrix_gene_name(em2_matrix* matrix, uint32_t geneId, uint64_t* bytes, char* value);
+int em2_matrix_gene_id_from_name(em2_matrix* matrix, const char* geneName, uint32_t* geneId);
+int em2_matrix_cell_id_from_string(em2_matrix* matrix, const char* s, uint32_t* cellId);
+
+/* ExpressionMatrix::addCell (src/ExpressionMatrix.cpp:165-294).  metaData: metaDataPairCount (name, value) pairs as
+ * name\0value\0...; geneNames: countCount names, each followed by \0, counts[i] the count of geneNames[i].  CellName is
+ * required ("CellName missing from cell meta data.") and moved to the front; "Cell name X already exists."; genes are added
+ * as met; a negative count is "Negative expression count encountered."; zeros (and -0.0) are dropped, NaN and inf are stored;
+ * sum1 and sum2 are double sums in the caller's order, the square a float product; the kept entries are sorted by gene id;
+ * "Duplicate expression count for cell C gene G" names the smallest gene id that two kept entries share.  The last two
+ * doubles of the 56-byte Cell record are written as 0 (the reference leaves them uninitialised).
+ * Departure: a failing call leaves the store unchanged (the reference leaves a half-added cell). */
+int em2_matrix_add_cell(em2_matrix* matrix, const char* metaData, uint64_t metaDataBytes, uint32_t metaDataPairCount,
+                        const char* geneNames, uint64_t geneNamesBytes, const float* counts, uint32_t countCount, uint32_t* cellId);
+
+/* The storing part of addCell (src/ExpressionMatrix.cpp:241-277) for cellCount rows of a sparse matrix in device memory, in
+ * two passes because the size of the result is not known beforehand.  Row i is d_indices / d_values [d_indptr[i],
+ * d_indptr[i + 1]); d_indptr[0] = 0 and every row is shorter than 2^31.  The gene of an entry is
+ * d_geneIdOfIndex[d_indices[j]], indexCount the length of that map.  d_skip (may be NULL): rows that are not added --
+ * neither counted nor checked.
+ *   _count   d_keptCount[i]: the entries that are not zero; d_status[i]: 0 ok, 1 a negative value, 2 two kept entries of one
+ *            gene -- d_duplicateGene[i] is then the smallest such gene id, 0xffffffff otherwise -- 3 an index not below
+ *            indexCount; a negative value wins over a duplicate.  d_outToc[0..cellCount]: the exclusive sums of d_keptCount.
+ *   _fill    the kept entries of every row that is not skipped, ascending by gene id, at d_outData[d_outToc[i]], and the
+ *            row's Cell record (7 doubles: sum1, sum2, norm2, 1/sum1, 1/norm2, 0, 0) at d_outCells + 56 i; a skipped row's
+ *            record is left as it is.  For rows whose status is 0.  EM2_ERROR_INVALID_ARGUMENT, and nothing written out of
+ *            place, if d_outToc is not the one _count gave.
+ * sum1, sum2 are the sequential double sums in input order bit for bit; sqrt and the divisions are correctly rounded.  Both
+ * calls allocate their own scratch and leave the stream synchronised. */
+int em2_dev_ingest_count(const uint64_t* d_indptr, const uint32_t* d_indices, const float* d_values, const uint8_t* d_skip,
+                         uint32_t cellCount, const uint32_t* d_geneIdOfIndex, uint32_t indexCount, uint32_t* d_keptCount,
+                         uint32_t* d_status, uint32_t* d_duplicateGene, uint64_t* d_outToc, void* stream);
+int em2_dev_ingest_fill(const uint64_t* d_indptr, const uint32_t* d_indices, const float* d_values, const uint8_t* d_skip,
+                        uint32_t cellCount, const uint32_t* d_geneIdOfIndex, uint32_t indexCount, const uint64_t* d_outToc,
+                        em2_count* d_outData, void* d_outCells, void* stream);
+
+/* Rows of at most this many entries are sorted in LDS (a wave up to 512 entries, a workgroup above), longer ones in global
+ * memory.  0 restores the default, 8192; at most 16384.  For tests. */
+void em2_set_ingest_lds_row_limit(uint32_t entries);
+
+/* The per-barcode loop of ExpressionMatrix::addCellsFromHdf5 (src/ExpressionMatrixHdf5.cpp:113-200) on the arrays of the
+ * file: every name of geneNames is added (:116-118; a name twice in geneNames is the error of :72-90, "Duplicate gene name X
+ * in geneNames"), then every barcode i with skip[i] == 0 (skip may be NULL) becomes the cell cellNamePrefix + "-" +
+ * cellNames[i] with the meta data CellName and then the cellMetaData pairs, its counts values[j] of the genes
+ * geneNames[indices[j]], j in [indptr[i], indptr[i + 1]).  Strings are packed as for em2_matrix_add_cell.  The cells' entries
+ * are prepared on the device (em2_dev_ingest_count, em2_dev_ingest_fill) in chunks of barcodes whose arrays take at most
+ * chunkBytes bytes (0: 1 GiB; one barcode at least); names and meta data lists are written on the host, string ids in the
+ * reference's order of first insertion.  *firstCellId is the id of the first added cell, *addedCellCount their number.
+ * Departures: the call is all or nothing, genes included; the error is that of the lowest failing barcode, within a barcode
+ * addCell's order (name exists, negative, duplicate); a skipped barcode is neither named nor checked.  An index not below
+ * geneNameCount, an indptr that does not start at 0, descends or does not end at entryCount is EM2_ERROR_INVALID_ARGUMENT
+ * before any work (the reference asserts). */
+int em2_matrix_add_cells_csr(em2_matrix* matrix, const char* geneNames, uint64_t geneNamesBytes, uint32_t geneNameCount,
+                             const char* cellNames, uint64_t cellNamesBytes, uint32_t cellCount, const uint64_t* indptr,
+                             const uint32_t* indices, const float* values, uint64_t entryCount, const uint8_t* skip,
+                             const char* cellNamePrefix, const char* cellMetaData, uint64_t cellMetaDataBytes,
+                             uint32_t cellMetaDataPairCount, uint64_t chunkBytes, uint32_t* firstCellId, uint32_t* addedCellCount);
+
 #ifdef __cplusplus
 }
 #endif
