@@ -269,6 +269,15 @@ SYMBOLS = {
     "em2_matrix_add_cells_csr": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_uint64, _c.c_uint32, _c.c_char_p, _c.c_uint64, _c.c_uint32,
                                             _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_char_p, _c.c_char_p,
                                             _c.c_uint64, _c.c_uint32, _c.c_uint64, _c.POINTER(_c.c_uint32), _c.POINTER(_c.c_uint32)]),
+    "em2_csv_tokenize": (_c.c_int, [_c.c_char_p, _c.c_char_p, _c.c_uint64, _c.c_int, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64),
+                                    _c.c_void_p]),
+    "em2_dev_csv_parse": (_c.c_int, [_c.c_void_p, _c.c_uint64, _c.c_char_p, _c.c_uint32, _c.c_uint32, _c.c_void_p, _c.c_uint32, _c.c_uint32,
+                                     _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "em2_set_csv_tile_bytes": (None, [_c.c_uint32]),
+    "em2_matrix_add_cells_csv": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_char_p, _c.c_char_p, _c.c_char_p, _c.c_uint64,
+                                            _c.c_uint32, _c.c_uint64, _c.c_int, _c.POINTER(_c.c_uint32), _c.POINTER(_c.c_uint32),
+                                            _c.POINTER(_c.c_uint64)]),
+    "em2_matrix_add_cell_meta_data_csv": (_c.c_int, [_c.c_void_p, _c.c_char_p]),
 }
 
 

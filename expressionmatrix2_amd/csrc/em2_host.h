@@ -232,6 +232,15 @@ public:
                          const uint32_t* indices, const float* values, uint64_t entryCount, const uint8_t* skip,
                          const std::string& cellNamePrefix, const std::vector<std::pair<std::string, std::string>>& cellMetaData,
                          uint64_t chunkBytes, uint32_t& firstCellId, uint32_t& addedCellCount);
+    // The files of the reference's own workflow (em2_csv_host.cpp, em2_csv.hip; the rules are in include/em2_lsh.h).
+    //   addCellsFromCsv             addCells, src/ExpressionMatrix.cpp:380-654; all or nothing.  useDevice == false: the host
+    //                               path.  *deferredFieldCount (may be NULL): the fields the device handed to the host.
+    //   addCellMetaDataFromFile     addCellMetaData, src/ExpressionMatrixBioHub.cpp:337-392; host only, all or nothing.
+    void addCellsFromCsv(const std::string& expressionCountsFileName, const std::string& expressionCountsFileSeparators,
+                         const std::string& cellMetaDataFileName, const std::string& cellMetaDataFileSeparators,
+                         const std::vector<std::pair<std::string, std::string>>& additionalCellMetaData, uint64_t chunkBytes,
+                         bool useDevice, uint32_t& firstCellId, uint32_t& addedCellCount, uint64_t* deferredFieldCount);
+    void addCellMetaDataFromFile(const std::string& cellMetaDataFileName);
 
     const GeneSet& geneSet(const std::string& name) const;                 // throws "Gene set X does not exist."
     const MappedFile& cellSet(const std::string& name) const;              // throws "Cell set X does not exist."
@@ -265,6 +274,12 @@ private:
     // The writes of addCell after its checks: the name, the meta data list, the entries, the Cell record, AllCells.
     void commitCell(const std::vector<std::pair<std::string, std::string>>& metaData, const em2_count* entries, uint64_t entryCount,
                     const void* cellRecord);
+    // The writing half of a bulk add: the new genes in order, then cell i of [0, cellCount) with the list metaDataOf(i) gives
+    // (CellName first; NULL: the cell is skipped), its entries data[toc[i], toc[i + 1]) and its 56-byte record.  String ids
+    // come out in the reference's order of first insertion.  Returns the number of cells written.
+    uint32_t writeCells(const std::vector<std::string>& newGenes, size_t cellCount,
+                        const std::function<const std::vector<std::pair<std::string, std::string>>*(size_t)>& metaDataOf,
+                        const uint64_t* toc, const em2_count* data, const void* cellRecords);
     IngestState* ingest_;
 };
 

@@ -255,6 +255,21 @@ void Matrix::commitCell(const std::vector<std::pair<std::string, std::string>>& 
     s.cells.append(cellRecord, 1);                                            // :283
 }
 
+uint32_t Matrix::writeCells(const std::vector<std::string>& newGenes, size_t cellCount,
+                            const std::function<const std::vector<std::pair<std::string, std::string>>*(size_t)>& metaDataOf,
+                            const uint64_t* toc, const em2_count* data, const void* cellRecords)
+{
+    for (const std::string& name : newGenes) addGene(name);
+    uint32_t added = 0;
+    for (size_t i = 0; i < cellCount; i++) {
+        const std::vector<std::pair<std::string, std::string>>* metaData = metaDataOf(i);
+        if (!metaData) continue;
+        commitCell(*metaData, data + toc[i], toc[i + 1u] - toc[i], static_cast<const CellRecord*>(cellRecords) + i);
+        added++;
+    }
+    return added;
+}
+
 uint32_t Matrix::addCell(const std::vector<std::pair<std::string, std::string>>& metaDataArgument,
                          const std::vector<std::pair<std::string, float>>& expressionCounts)
 {
@@ -405,18 +420,17 @@ void Matrix::addCellsFromCsr(const std::vector<std::string>& geneNames, const st
     if (!kept) allToc.assign(barcodeCount + 1u, 0u);
 
     // Write (:116-118, then addCell per barcode): string-table ids come out in the order of first insertion.
-    for (const std::string& name : newGenes) addGene(name);
     firstCellId = cellCount();
-    addedCellCount = 0;
     std::vector<std::pair<std::string, std::string>> metaData(cellMetaData.size() + 1u);          // :122-124
     metaData.front().first = "CellName";
     std::copy(cellMetaData.begin(), cellMetaData.end(), metaData.begin() + 1);
-    for (size_t i = 0; i < barcodeCount; i++) {
-        if (skip && skip[i]) continue;
-        metaData.front().second = cellNamePrefix + "-" + cellNames[i];
-        commitCell(metaData, allData.data() + allToc[i], allToc[i + 1u] - allToc[i], &allCells[i]);
-        addedCellCount++;
-    }
+    addedCellCount = writeCells(newGenes, barcodeCount,
+                                [&](size_t i) -> const std::vector<std::pair<std::string, std::string>>* {
+                                    if (skip && skip[i]) return nullptr;
+                                    metaData.front().second = cellNamePrefix + "-" + cellNames[i];
+                                    return &metaData;
+                                },
+                                allToc.data(), allData.data(), allCells.data());
 }
 
 }  // namespace host

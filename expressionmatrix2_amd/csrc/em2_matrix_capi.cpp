@@ -2,6 +2,7 @@
 // em2::host::Error into status codes + em2_last_error().
 #include "em2_host.h"
 #include "em2_meta_data.h"
+#include "em2_csv.h"
 
 #include <algorithm>
 #include <cstring>
@@ -786,6 +787,47 @@ int em2_matrix_add_cells_csr(em2_matrix* matrix, const char* geneNames, uint64_t
         const auto pairs = splitPairs(who, cellMetaData, cellMetaDataBytes, cellMetaDataPairCount);
         matrix->impl->addCellsFromCsr(genes, cells, indptr, indices, values, entryCount, skip, cellNamePrefix, pairs, chunkBytes,
                                       *firstCellId, *addedCellCount);
+    });
+}
+
+int em2_matrix_add_cells_csv(em2_matrix* matrix, const char* expressionCountsFileName, const char* expressionCountsFileSeparators,
+                             const char* cellMetaDataFileName, const char* cellMetaDataFileSeparators, const char* additionalCellMetaData,
+                             uint64_t additionalCellMetaDataBytes, uint32_t additionalCellMetaDataPairCount, uint64_t chunkBytes,
+                             int useDevice, uint32_t* firstCellId, uint32_t* addedCellCount, uint64_t* deferredFieldCount)
+{
+    if (!matrix || !expressionCountsFileName || !expressionCountsFileSeparators || !cellMetaDataFileName || !cellMetaDataFileSeparators ||
+        !firstCellId || !addedCellCount || (!additionalCellMetaData && additionalCellMetaDataBytes)) {
+        return nullArgument("em2_matrix_add_cells_csv");
+    }
+    return guarded([&] {
+        const auto pairs = splitPairs("em2_matrix_add_cells_csv", additionalCellMetaData, additionalCellMetaDataBytes,
+                                      additionalCellMetaDataPairCount);
+        matrix->impl->addCellsFromCsv(expressionCountsFileName, expressionCountsFileSeparators, cellMetaDataFileName,
+                                      cellMetaDataFileSeparators, pairs, chunkBytes, useDevice != 0, *firstCellId, *addedCellCount,
+                                      deferredFieldCount);
+    });
+}
+
+int em2_matrix_add_cell_meta_data_csv(em2_matrix* matrix, const char* cellMetaDataFileName)
+{
+    if (!matrix || !cellMetaDataFileName) return nullArgument("em2_matrix_add_cell_meta_data_csv");
+    return guarded([&] { matrix->impl->addCellMetaDataFromFile(cellMetaDataFileName); });
+}
+
+int em2_csv_tokenize(const char* separators, const char* line, uint64_t lineBytes, int removeLeadingAndTrailingBlanks, uint64_t* tokenCount,
+                     uint64_t* bytes, char* packed)
+{
+    if (!separators || (!line && lineBytes) || !tokenCount || !bytes) return nullArgument("em2_csv_tokenize");
+    return guarded([&] {
+        std::vector<std::string> tokens;
+        em2::host::tokenize(separators, line, size_t(lineBytes), tokens, removeLeadingAndTrailingBlanks != 0);
+        std::string all;
+        for (const std::string& t : tokens) {
+            all += t;
+            all += '\0';
+        }
+        *tokenCount = tokens.size();
+        copyOut("em2_csv_tokenize", all, bytes, packed);
     });
 }
 

@@ -26,6 +26,11 @@ DENSE_CHUNK_BYTES = 1 << 30
 # Tests set it small to run several chunks.
 INGEST_CHUNK_BYTES = 1 << 30
 
+# addCells hands the text of the expression counts file to the GPU in chunks of whole lines of at most this many bytes (one
+# line at least).  Tests set it small to run several chunks.  CSV_USE_DEVICE = False parses the file on the host instead.
+CSV_CHUNK_BYTES = 256 << 20
+CSV_USE_DEVICE = True
+
 INVALID_ID = 0xffffffff        # invalidGeneId, invalidCellId (src/Ids.hpp)
 
 
@@ -174,6 +179,34 @@ class ExpressionMatrix:
             capi._ptr(values), len(values), capi._ptr(skip) if skip is not None else None, _b(cellNamePrefix), pairs, len(pairs),
             len(cellMetaData), int(INGEST_CHUNK_BYTES), ctypes.byref(first), ctypes.byref(added)))
         return range(first.value, first.value + added.value)
+
+    def addCells(self, expressionCountsFileName=_REQUIRED, expressionCountsFileSeparators=",", cellMetaDataFileName=_REQUIRED,
+                 cellMetaDataFileSeparators=",", additionalCellMetaData=()):
+        """ExpressionMatrix::addCells (src/ExpressionMatrix.cpp:380-654): the cells named both by the header of the expression
+        counts file (genes x cells, a gene per line) and by the first column of the cell meta data file, in the order of the
+        expression counts file's columns, each with additionalCellMetaData, its CellName and the meta data file's fields.
+        Every gene line adds its gene.  The text of the expression counts file is parsed on the GPU in chunks of whole lines
+        of at most CSV_CHUNK_BYTES bytes; a separator string of more than 8 characters, or one with a quote, a backslash or a
+        line end, and CSV_USE_DEVICE = False send the whole file down the host path, with the same result.  All or nothing;
+        the reference's error texts (include/em2_lsh.h, em2_matrix_add_cells_csv, lists the departures).  Returns None, like
+        the reference; lastCsvDeferredFieldCount is the number of fields the GPU left to the host in this call."""
+        if expressionCountsFileName is _REQUIRED or cellMetaDataFileName is _REQUIRED:
+            raise TypeError("addCells() needs expressionCountsFileName and cellMetaDataFileName")
+        additionalCellMetaData = list(additionalCellMetaData)
+        pairs = self._pack([s for pair in additionalCellMetaData for s in pair])
+        first, added, deferred = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint64(0)
+        capi.check(capi.load().em2_matrix_add_cells_csv(
+            self._handle, _b(expressionCountsFileName), _b(expressionCountsFileSeparators), _b(cellMetaDataFileName),
+            _b(cellMetaDataFileSeparators), pairs, len(pairs), len(additionalCellMetaData), int(CSV_CHUNK_BYTES),
+            1 if CSV_USE_DEVICE else 0, ctypes.byref(first), ctypes.byref(added), ctypes.byref(deferred)))
+        self.lastCsvDeferredFieldCount = deferred.value
+
+    def addCellMetaData(self, cellMetaDataFileName):
+        """ExpressionMatrix::addCellMetaData (src/ExpressionMatrixBioHub.cpp:337-392): a comma separated file whose first
+        column names cells of the store and whose other columns are meta data fields, named by the header (its first token is
+        ignored, a column with an empty name is skipped); setCellMetaData per cell and field, in file order.  Host only.
+        All or nothing, unlike the reference's."""
+        capi.check(capi.load().em2_matrix_add_cell_meta_data_csv(self._handle, _b(cellMetaDataFileName)))
 
     def close(self):
         self._signatureGraphs = {}

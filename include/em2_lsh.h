@@ -1183,6 +1183,71 @@ int em2_matrix_add_cells_csr(em2_matrix* matrix, const char* geneNames, uint64_t
                              const char* cellNamePrefix, const char* cellMetaData, uint64_t cellMetaDataBytes,
                              uint32_t cellMetaDataPairCount, uint64_t chunkBytes, uint32_t* firstCellId, uint32_t* addedCellCount);
 
+/* tokenize (src/tokenize.cpp:16-35, boost::escaped_list_separator<char>("\\", separators, "\"")) restated: a '\\' makes the
+ * next byte literal ('n' a line feed; a quote, a '\\' or a separator itself; nothing after it is "cannot end with escape",
+ * anything else "unknown escape sequence", both EM2_ERROR_RUNTIME); a separator byte outside quotes ends the token; '"'
+ * toggles the quote state and is dropped, an open quote at the end is no error; an empty line has no token, a line ending in
+ * a separator a last empty one.  With removeLeadingAndTrailingBlanks every token is trimmed of space, \t, \n, \v, \f, \r.
+ * The tokens come back each followed by NUL: call with packed == NULL for *bytes, then with a buffer of that size. */
+int em2_csv_tokenize(const char* separators, const char* line, uint64_t lineBytes, int removeLeadingAndTrailingBlanks, uint64_t* tokenCount,
+                     uint64_t* bytes, char* packed);
+
+/* The per-line work of ExpressionMatrix::addCells (src/ExpressionMatrix.cpp:559-626: getline, tokenize, the "0" / "0." test
+ * and strtof of every kept field) for a chunk of whole lines in device memory.  d_text need not be aligned; textBytes is at
+ * most 0xf0000000.  separators: 1 to 8 bytes in host memory, none of them '"', '\\', '\n', '\r' or NUL.  Lines are getline's:
+ * split at '\n' whatever the quotes say, a last line without '\n' counts.
+ *   d_lineTable[6 i ..]   of line i: begin, end (offsets into the text, the '\n' and one '\r' before it excluded), token count,
+ *                         status, begin and end of the first field.  Status 0 ok; 1 the line is empty (before the '\r' is
+ *                         removed); 2 the token count is not expectedTokens; 3 the line holds a '\\': the device reports its
+ *                         begin and end and nothing else, the host tokenizes it whole.
+ *   triples               for every field of a column c < expectedTokens with d_keptCellOfColumn[c] != 0xffffffff, in a line
+ *                         without '\\', that the device decides and that is not skipped: key = kept cell << 32 | (lineBase +
+ *                         i), value = strtof's float.  In no particular order.
+ *   d_deferred[4 j ..]    the fields of such columns the device does not decide: lineBase + i, column, begin, end.  Likewise.
+ * Decided: a field without '"' whose trimmed text is "0" or "0." is skipped, as the reference skips it; one that matches
+ * [+-]?(D+(\.D*)?|\.D+)([eE][+-]?D+)? in at most 32 bytes, with at most 19 digits from the first that is not 0 (an exact
+ * uint64 m), m <= 2^53, at most 4 exponent digits and |q| <= 22 for q = exponent - fraction digits, has the value
+ * float(d), d = double(m) * 10^q or double(m) / 10^-q: one correctly rounded operation on exact operands, so d is the double
+ * nearest the field's value x.  strtof is correctly rounded; if float(d) were not the float nearest x, a float rounding
+ * midpoint M would lie between x and d inclusive, M is a double, so M would be as near to x as d is: M = d.  A d whose low 29
+ * significand bits are exactly 1 << 28 is such a midpoint and is deferred, as is a d != 0 outside the normal float range.
+ * Everything else is deferred: quotes, longer fields, hex, inf, nan, trailing text, empty fields.  Unkept columns are not read.
+ * counts[0..2] (host): the lines, the triples, the deferred fields of the text.  Where counts[0] > lineCapacity nothing else
+ * was written; where counts[1] or counts[2] exceed their capacity the list holds its first `capacity` elements: call again
+ * with room.  Allocates its own scratch and leaves the stream synchronised. */
+int em2_dev_csv_parse(const char* d_text, uint64_t textBytes, const char* separators, uint32_t separatorCount, uint32_t expectedTokens,
+                      const uint32_t* d_keptCellOfColumn, uint32_t lineBase, uint32_t lineCapacity, uint32_t* d_lineTable,
+                      uint64_t tripleCapacity, uint64_t* d_tripleKeys, float* d_tripleValues, uint64_t deferredCapacity,
+                      uint32_t* d_deferred, uint64_t* counts, void* stream);
+
+/* The text is read in tiles of this many bytes (rounded up to 16; at most 1 MiB) when its lines are counted and placed; 0
+ * restores the default, 16384.  For tests: a 2 KB text then spans many tiles. */
+void em2_set_csv_tile_bytes(uint32_t bytes);
+
+/* ExpressionMatrix::addCells (src/ExpressionMatrix.cpp:380-654): the cells that both files name, in the order of the
+ * expression counts file's columns (the loop of :535-543), each with additionalCellMetaData, then CellName, then the fields
+ * of the meta data file (addCell then swaps the first CellName pair to the front, :190-197).  The meta data file is
+ * tokenized without trimming, the expression counts file with; either header may have one token fewer than the second line;
+ * every gene line adds its gene; an unkept column is never parsed.  The reference's order of checks and error texts.  The
+ * expression counts file goes to the device in chunks of whole lines of at most chunkBytes bytes (0: 256 MiB; a line at
+ * least), em2_dev_csv_parse; its counts are sorted by (cell, line) there and stored by em2_dev_ingest_count / _fill.  Lines
+ * with a '\\' and deferred fields are resolved on the host.  useDevice == 0, a separator string the device does not take
+ * (longer than 8 bytes, or with '"', '\\', '\n', '\r'), or a line of 0xf0000000 bytes: the whole file takes the host path,
+ * same result.  *deferredFieldCount (may be NULL): the fields the device deferred.
+ * Departures: all or nothing, genes included; a parse error (file order; within a line token count, duplicate gene, first
+ * invalid count in kept order) comes before any addCell error, which is that of the lowest failing cell; no progress lines;
+ * an empty second line is "Empty line in ... file F" (the reference reads line[-1]). */
+int em2_matrix_add_cells_csv(em2_matrix* matrix, const char* expressionCountsFileName, const char* expressionCountsFileSeparators,
+                             const char* cellMetaDataFileName, const char* cellMetaDataFileSeparators, const char* additionalCellMetaData,
+                             uint64_t additionalCellMetaDataBytes, uint32_t additionalCellMetaDataPairCount, uint64_t chunkBytes,
+                             int useDevice, uint32_t* firstCellId, uint32_t* addedCellCount, uint64_t* deferredFieldCount);
+
+/* ExpressionMatrix::addCellMetaData (src/ExpressionMatrixBioHub.cpp:337-392): separator ",", trimmed tokens, no '\r'
+ * handling; the first header token is ignored, an empty header name skips its column; "Unexpected number of meta data values
+ * in F", "Attempt to add meta data for undefined cell X"; setCellMetaData per (cell, field) in file order.  Host only.
+ * Departure: all or nothing (the reference keeps the lines before the failing one). */
+int em2_matrix_add_cell_meta_data_csv(em2_matrix* matrix, const char* cellMetaDataFileName);
+
 #ifdef __cplusplus
 }
 #endif
