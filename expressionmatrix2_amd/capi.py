@@ -1095,12 +1095,21 @@ def dist_find_similar_pairs4(comm_or_table, local_sig_ptr, cell_count, lsh_count
     return dict(zip(DIST_STAGES, ms)) if timed else None
 
 
+# values[10] of em2_dev_find_similar_pairs5_last_launch (include/em2_lsh.h): the candidate filter that ran
+FSP5_FILTER_FORMS = ("lane", "cooperative", "wide<4,4,true>", "wide<1,16,false>", "wide<1,8,false>", "wide<1,0,false>",
+                     "wide<2,16,true>", "wide<2,16,false>", "wide<2,0,false>")
+
+
 def dev_find_similar_pairs5_last_launch():
-    """dict(gathered_candidates, cells, slice_count, batches, filter_ms, select_ms) of the last findSimilarPairs5 launch."""
-    v = np.zeros(7, dtype=np.float64)
-    check(load().em2_dev_find_similar_pairs5_last_launch(_ptr(v), 7))
+    """dict(gathered_candidates, cells, slice_count, batches, filter_ms, select_ms, distinct_candidates) of the last
+    findSimilarPairs5 launch, and the forms it took: union_form (1 bitmap in LDS, 0 gather + segmented sort), union_passes,
+    union_ids_per_pass, filter_form (one of FSP5_FILTER_FORMS), packed (the selection: 1 packed tiers, 0 whole entries)."""
+    v = np.zeros(12, dtype=np.float64)
+    check(load().em2_dev_find_similar_pairs5_last_launch(_ptr(v), 12))
     return {"gathered_candidates": float(v[0]), "cells": int(v[1]), "slice_count": int(v[2]), "batches": int(v[3]),
-            "filter_ms": float(v[4]), "select_ms": float(v[5]), "distinct_candidates": float(v[6])}
+            "filter_ms": float(v[4]), "select_ms": float(v[5]), "distinct_candidates": float(v[6]),
+            "union_form": int(v[7]), "union_passes": int(v[8]), "union_ids_per_pass": int(v[9]),
+            "filter_form": FSP5_FILTER_FORMS[int(v[10])], "packed": int(v[11])}
 
 
 def dev_release_scratch():

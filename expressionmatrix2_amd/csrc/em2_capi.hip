@@ -574,9 +574,10 @@ int em2_dev_find_similar_pairs5_last_launch(double* values, uint32_t valueCount)
 {
     if (!values && valueCount) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dev_find_similar_pairs5_last_launch: null pointer");
     const em2::Fsp5LaunchInfo info = em2::fsp5LastLaunchInfo();
-    const double all[7] = {info.gatheredCandidates, info.cells, info.sliceCount, info.batches, info.filterMs, info.selectMs,
-                           info.distinctCandidates};
-    for (uint32_t i = 0; i < valueCount; i++) values[i] = i < 7 ? all[i] : 0.0;
+    const double all[12] = {info.gatheredCandidates, info.cells, info.sliceCount, info.batches, info.filterMs, info.selectMs,
+                            info.distinctCandidates, info.unionForm, info.unionPasses, info.unionIdsPerPass, info.filterForm,
+                            info.selectPacked};
+    for (uint32_t i = 0; i < valueCount; i++) values[i] = i < 12 ? all[i] : 0.0;
     return EM2_OK;
 }
 

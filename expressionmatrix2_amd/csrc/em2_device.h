@@ -124,6 +124,24 @@ hipError_t launchProjectionScreened(const uint64_t* toc, const CountIn* data, ui
 struct Fsp5LaunchInfo {
     double gatheredCandidates, cells, sliceCount, batches, filterMs, selectMs;
     double distinctCandidates;      // what the filter read: the sizes of the cells' duplicate-free unions (the cell itself included); -1 in the sort form
+    // which forms ran (host-side facts; tests assert the path they mean to exercise through them)
+    double unionForm;               // 1 = bitmap in LDS (unionKernel), 0 = gatherKernel + segmented sort
+    double unionPasses;             // passes of the bitmap over the id range, ceil(cellCount / unionIdsPerPass); 0 in the sort form
+    double unionIdsPerPass;         // cell ids one pass of the bitmap covers
+    double filterForm;              // Fsp5FilterForm
+    double selectPacked;            // 1 = selectPackedKernel tiers ({key, position} in 4 bytes), 0 = selectKernel tiers of whole entries
+};
+// The candidate filter by shape (runFsp5); the wide forms are filterWideKernel<T, LPC, FULL>.
+enum Fsp5FilterForm {
+    kFsp5FilterLane = 0,            // filterKernel: one lane per candidate
+    kFsp5FilterCooperative = 1,     // filterCooperativeKernel
+    kFsp5FilterWide_4_4_full = 2,
+    kFsp5FilterWide_1_16 = 3,
+    kFsp5FilterWide_1_8 = 4,
+    kFsp5FilterWide_1_0 = 5,
+    kFsp5FilterWide_2_16_full = 6,
+    kFsp5FilterWide_2_16 = 7,
+    kFsp5FilterWide_2_0 = 8
 };
 Fsp5LaunchInfo fsp5LastLaunchInfo();
 void fsp4SetInboxEntriesPerCell(uint32_t entries);       // (this thread's symmetric scans: 0 = the default of 1024; em2_scan_symmetric.hip)

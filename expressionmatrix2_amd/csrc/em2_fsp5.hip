@@ -890,7 +890,7 @@ uint32_t bitsFor(uint64_t maxValue)
 // cellCount cells; candidates are generated and selected for the cells [rowBegin,rowEnd) only (the shard one
 // rank owns).  d_pairs / d_used are device arrays of (rowEnd-rowBegin)*k and (rowEnd-rowBegin) elements.
 namespace {
-thread_local Fsp5LaunchInfo lastFsp5Info = {0., 0., 0., 0., -1., -1., -1.};
+thread_local Fsp5LaunchInfo lastFsp5Info = {0., 0., 0., 0., -1., -1., -1., 0., 0., double(kUnionWords * 32u), 0., 0.};
 }
 
 Fsp5LaunchInfo fsp5LastLaunchInfo() { return lastFsp5Info; }
@@ -1015,6 +1015,34 @@ hipError_t runFsp5(const uint64_t* d_sig, uint32_t cellCount, uint32_t rowBegin,
         batches.push_back(std::move(batch));
         batchBegin = batchEnd;
     }
+    // the forms this call takes, by shape (reported by fsp5LastLaunchInfo):
+    // (more than kUnionSlices slices: gatherKernel + a segmented sort, round 2's form)
+    const bool useUnion = sliceCount <= kUnionSlices;
+    // the filter: 16-byte loads for an even number of words up to 4096 bits, the 8-byte cooperative form for odd word counts and
+    // up to 8192 bits, one lane per candidate beyond
+    const bool cooperative = words <= 8u * 16u;
+    // (signature rows are 16-byte aligned: an even number of words, and the array itself as hipMalloc / the caller's uint64 array
+    // provides it)
+    const bool wide = cooperative && words % 2u == 0u && words <= 64u && reinterpret_cast<uintptr_t>(d_sig) % 16u == 0u;
+    Fsp5FilterForm filterForm = cooperative ? kFsp5FilterCooperative : kFsp5FilterLane;
+    if (wide) {
+        const uint32_t units = words / 2u;
+        const uint32_t unitsPerLane = words <= 32u ? 1u : 2u;
+        uint32_t lanesPerCandidate = 1u;
+        while (lanesPerCandidate < 16u && lanesPerCandidate * unitsPerLane < units) lanesPerCandidate <<= 1;
+        // (2048 bits: FOUR units per lane and four lanes per candidate -- two reduction steps instead of four and a quarter of
+        // the per-candidate bookkeeping per unit: 66.3 -> 62.5 ms at 1M cells, same box; {1, 16} 66.3, {2, 8} 68.1, {8, 2} 77.2,
+        // {16, 1} 196.5; eight loads in flight instead of four change nothing, two cost 10 ms: profiles/r05_fsp5_experiments.md)
+        if (unitsPerLane == 1u && units == 16u) filterForm = kFsp5FilterWide_4_4_full;
+        else if (unitsPerLane == 1u && lanesPerCandidate == 16u) filterForm = kFsp5FilterWide_1_16;
+        else if (unitsPerLane == 1u && lanesPerCandidate == 8u) filterForm = kFsp5FilterWide_1_8;
+        else if (unitsPerLane == 1u) filterForm = kFsp5FilterWide_1_0;
+        else if (units == 32u) filterForm = kFsp5FilterWide_2_16_full;
+        else if (lanesPerCandidate == 16u) filterForm = kFsp5FilterWide_2_16;
+        else filterForm = kFsp5FilterWide_2_0;
+    }
+    // (the packed selection tiers keep a key in 16 bits: lshCount + 1 key classes must fit)
+    const bool packed = k <= kSelectPackedMaxK && lshCount < 65535u;
     {
         double gathered = 0.;
         for (uint32_t c = rowBegin; c < rowEnd; c++) gathered += double(hostCounts[c]);
@@ -1024,6 +1052,11 @@ hipError_t runFsp5(const uint64_t* d_sig, uint32_t cellCount, uint32_t rowBegin,
         lastFsp5Info.batches = double(batches.size());
         lastFsp5Info.filterMs = lastFsp5Info.selectMs = 0.;
         lastFsp5Info.distinctCandidates = -1.;
+        lastFsp5Info.unionForm = useUnion ? 1. : 0.;
+        lastFsp5Info.unionPasses = useUnion ? double((cellCount + kUnionWords * 32u - 1u) / (kUnionWords * 32u)) : 0.;
+        lastFsp5Info.unionIdsPerPass = double(kUnionWords * 32u);
+        lastFsp5Info.filterForm = double(filterForm);
+        lastFsp5Info.selectPacked = packed ? 1. : 0.;
     }
     static thread_local hipEvent_t timing[3] = {nullptr, nullptr, nullptr};
     if (!timing[0]) {
@@ -1031,8 +1064,6 @@ hipError_t runFsp5(const uint64_t* d_sig, uint32_t cellCount, uint32_t rowBegin,
             hipEventCreate(&timing[2]) != hipSuccess) timing[0] = timing[1] = timing[2] = nullptr;
     }
     Buffer segBegin, candA, candB, lists, sortTemp, listCounts, distinctCounts;
-    // (more than kUnionSlices slices: gatherKernel + a segmented sort, round 2's form)
-    const bool useUnion = sliceCount <= kUnionSlices;
     uint32_t unionBlocks = 1;
     if (useUnion) {
         int device = 0, cuCount = 0, perCu = 0;
@@ -1065,10 +1096,6 @@ hipError_t runFsp5(const uint64_t* d_sig, uint32_t cellCount, uint32_t rowBegin,
     size_t sortTempBytes = 0;
     stage("batch plan + scratch allocation");
     const uint32_t idBits = bitsFor(cellCount - 1u);
-    // the filter by shape: 16-byte loads for an even number of words up to 4096 bits, the 8-byte cooperative form for odd word
-    // counts and up to 8192 bits, one lane per candidate beyond
-    const bool cooperative = words <= 8u * 16u;
-    const bool wide = cooperative && words % 2u == 0u && words <= 64u && reinterpret_cast<uintptr_t>(d_sig) % 16u == 0u;
     for (const Batch& batch : batches) {
         const uint32_t batchBegin = batch.begin;
         const uint32_t batchCells = batch.end - batch.begin;
@@ -1120,26 +1147,19 @@ hipError_t runFsp5(const uint64_t* d_sig, uint32_t cellCount, uint32_t rowBegin,
         stage("  batch: order");
         if (timing[0]) (void)hipEventRecord(timing[0], stream);
         if (wide) {
-            // (signature rows are 16-byte aligned: an even number of words, and the array itself as hipMalloc / the caller's
-            // uint64 array provides it -- checked below)
-            const uint32_t units = words / 2u;
-            const uint32_t unitsPerLane = words <= 32u ? 1u : 2u;
-            uint32_t lanesPerCandidate = 1u;
-            while (lanesPerCandidate < 16u && lanesPerCandidate * unitsPerLane < units) lanesPerCandidate <<= 1;
 #define EM2_FILTER_WIDE(TT, LL, FF)                                                                                                     \
             filterWideKernel<TT, LL, FF><<<filterBlocks, 256, 0, stream>>>(d_sig, words, batchBegin, batchCells, segBegin.as<uint32_t>(), sorted,  \
                                                                      lists.as<Entry>(), tables.mGlobal, tables.keyOfMismatch,         \
                                                                      listCounts.as<uint32_t>(), distinct, order, orderChunk)
-            // (2048 bits: FOUR units per lane and four lanes per candidate -- two reduction steps instead of four and a quarter of
-            // the per-candidate bookkeeping per unit: 66.3 -> 62.5 ms at 1M cells, same box; {1, 16} 66.3, {2, 8} 68.1, {8, 2} 77.2,
-            // {16, 1} 196.5; eight loads in flight instead of four change nothing, two cost 10 ms: profiles/r05_fsp5_experiments.md)
-            if (unitsPerLane == 1u && units == 16u) EM2_FILTER_WIDE(4, 4, true);
-            else if (unitsPerLane == 1u && lanesPerCandidate == 16u) EM2_FILTER_WIDE(1, 16, false);
-            else if (unitsPerLane == 1u && lanesPerCandidate == 8u) EM2_FILTER_WIDE(1, 8, false);
-            else if (unitsPerLane == 1u) EM2_FILTER_WIDE(1, 0, false);
-            else if (units == 32u) EM2_FILTER_WIDE(2, 16, true);
-            else if (lanesPerCandidate == 16u) EM2_FILTER_WIDE(2, 16, false);
-            else EM2_FILTER_WIDE(2, 0, false);
+            switch (filterForm) {
+            case kFsp5FilterWide_4_4_full: EM2_FILTER_WIDE(4, 4, true); break;
+            case kFsp5FilterWide_1_16: EM2_FILTER_WIDE(1, 16, false); break;
+            case kFsp5FilterWide_1_8: EM2_FILTER_WIDE(1, 8, false); break;
+            case kFsp5FilterWide_1_0: EM2_FILTER_WIDE(1, 0, false); break;
+            case kFsp5FilterWide_2_16_full: EM2_FILTER_WIDE(2, 16, true); break;
+            case kFsp5FilterWide_2_16: EM2_FILTER_WIDE(2, 16, false); break;
+            default: EM2_FILTER_WIDE(2, 0, false); break;
+            }
 #undef EM2_FILTER_WIDE
         } else if (cooperative) {
             filterCooperativeKernel<<<(batchCells + 3u) / 4u, 256, 0, stream>>>(d_sig, words, batchBegin, batchCells, segBegin.as<uint32_t>(),
@@ -1159,8 +1179,6 @@ hipError_t runFsp5(const uint64_t* d_sig, uint32_t cellCount, uint32_t rowBegin,
         PairOut* outPairs = d_pairs + size_t(batchBegin - rowBegin) * k;
         uint32_t* outUsed = d_used + (batchBegin - rowBegin);
         uint32_t globalAbove = kSelectLdsEntriesBig;
-        // (the packed tiers keep a key in 16 bits: lshCount + 1 key classes must fit)
-        const bool packed = k <= kSelectPackedMaxK && lshCount < 65535u;
         if (packed) {
 #define EM2_SELECT_PACKED(CAPACITY, ABOVE)                                                                                        \
             selectPackedKernel<CAPACITY, ABOVE><<<batchCells, 64, 0, stream>>>(batchCells, segBegin.as<uint32_t>(), lists.as<Entry>(), \

@@ -474,7 +474,13 @@ int em2_dev_find_similar_pairs5(const uint64_t* d_signatures, uint32_t cellCount
  * one look at the sorted list, each distinct one a gather of 8*W signature bytes), [1] cells queried, [2] slices
  * (lshCount / lshSliceLength, src/ExpressionMatrixLsh.cpp:355), [3] batches, [4] / [5] ms of the candidate filter and
  * of the selection, summed over the batches (HIP events on the launch stream), [6] the DISTINCT candidates of all cells
- * (the sizes of the duplicate-free unions, the cell itself included): the signatures the filter actually gathers. */
+ * (the sizes of the duplicate-free unions, the cell itself included): the signatures the filter actually gathers.
+ * Which forms ran (facts the host holds; nothing is measured for them): [7] the candidate union, 1 = bitmap in LDS, 0 = gather +
+ * segmented sort (more than 256 slices); [8] passes of the bitmap over the cell ids, ceil(cellCount / values[9]), 0 in the sort
+ * form; [9] cell ids per pass; [10] the candidate filter: 0 one lane per candidate, 1 cooperative 8-byte loads, 2..8 the
+ * 16-byte forms <T units per lane, LPC lanes per candidate (0 = decided at run time), FULL> = 2 <4,4,true>, 3 <1,16,false>,
+ * 4 <1,8,false>, 5 <1,0,false>, 6 <2,16,true>, 7 <2,16,false>, 8 <2,0,false>; [11] the selection, 1 = packed tiers ({key,
+ * position} in four bytes: k <= 2048), 0 = tiers of whole entries.  Entries beyond the last one defined are 0. */
 int em2_dev_find_similar_pairs5_last_launch(double* values, uint32_t valueCount);
 
 /* findSimilarPairs5 keeps its device scratch (bucket tables, candidate ids, candidate lists: about 10 GB at a million cells x

@@ -398,15 +398,28 @@ int em2o_find_similar_pairs5_cells(
     const size_t sliceCount = size_t(lshCount) / lshSliceLength;
     const size_t valueCount = size_t(1) << lshSliceLength;
     // counting sort per slice: stable, so the cells of a bucket ascend like the reference's push_back order
-    std::vector<std::vector<uint32_t>> start(sliceCount), members(sliceCount);
+    // (slices beyond 24 bits: 2^q offsets per slice are gigabytes, so the offsets are kept for the values that occur only --
+    // start[s][j] for the j-th distinct value of the slice, occurring[s][j], ascending; the buckets are the same)
+    const bool valuesListed = lshSliceLength > 24;
+    std::vector<std::vector<uint32_t>> start(sliceCount), members(sliceCount), occurring(sliceCount);
     std::vector<uint32_t> value(cellCount);
     for (size_t s = 0; s < sliceCount; s++) {
-        start[s].assign(valueCount + 1, 0u);
         for (CellId c = 0; c < cellCount; c++) {
             value[c] = uint32_t(getBitsRange(signatures + size_t(c) * W, s * lshSliceLength, lshSliceLength));
-            ++start[s][value[c] + 1];
         }
-        for (size_t v = 0; v < valueCount; v++) start[s][v + 1] += start[s][v];
+        size_t indexCount = valueCount;
+        if (valuesListed) {
+            occurring[s] = value;
+            std::sort(occurring[s].begin(), occurring[s].end());
+            occurring[s].erase(std::unique(occurring[s].begin(), occurring[s].end()), occurring[s].end());
+            indexCount = occurring[s].size();
+            for (CellId c = 0; c < cellCount; c++) {
+                value[c] = uint32_t(std::lower_bound(occurring[s].begin(), occurring[s].end(), value[c]) - occurring[s].begin());
+            }
+        }
+        start[s].assign(indexCount + 1, 0u);
+        for (CellId c = 0; c < cellCount; c++) ++start[s][value[c] + 1];
+        for (size_t v = 0; v < indexCount; v++) start[s][v + 1] += start[s][v];
         members[s].resize(cellCount);
         std::vector<uint32_t> at(start[s].begin(), start[s].end() - 1);
         for (CellId c = 0; c < cellCount; c++) members[s][at[value[c]]++] = c;
@@ -418,7 +431,8 @@ int em2o_find_similar_pairs5_cells(
         const CellId c0 = cells[i];
         candidates.clear();
         for (size_t s = 0; s < sliceCount; s++) {
-            const uint64_t v = getBitsRange(signatures + size_t(c0) * W, s * lshSliceLength, lshSliceLength);
+            uint64_t v = getBitsRange(signatures + size_t(c0) * W, s * lshSliceLength, lshSliceLength);
+            if (valuesListed) v = uint64_t(std::lower_bound(occurring[s].begin(), occurring[s].end(), uint32_t(v)) - occurring[s].begin());
             const size_t size = start[s][v + 1] - start[s][v];
             if (bucketOverflow == 0 || size <= bucketOverflow) {
                 candidates.insert(candidates.end(), members[s].begin() + start[s][v], members[s].begin() + start[s][v + 1]);

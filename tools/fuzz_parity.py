@@ -5,7 +5,9 @@ FUZZ_ONLY=fsp4 restricts the sweep to one path, FUZZ_WIDTHS=1100,1500,2048 to th
 to one scan form with the matrix cores on.  The fsp6 leg compares with the C++ restatement (tests/fsp6_binding.py); shapes past
 its kernels' limits must answer EM2_ERROR_UNSUPPORTED and are counted apart (fsp6_unsupported), as are runs at the 8192
 clamp and runs over several row chunks.  Half the fsp7 draws go through the device entry on a random row range (fsp7_ranged);
-fsp7 draws the oracle would be slow for are skipped and counted (fsp7_skipped, see fsp7_oracle_is_slow).
+fsp7 draws the oracle would be slow for are skipped and counted (fsp7_skipped, see fsp7_oracle_is_slow).  The fsp5 leg draws its
+width from FSP5_WIDTHS (the common widths and those that leave lanes of the 16-byte filter without a unit), compares a third
+of its draws on a random row range through the device entry (fsp5_ranged), and names the forms that ran in a failure's label.
 
 Six more legs draw from tests/expression_cases.py, the generator tests/test_gpu_expression_sweep.py takes its fixed draws from:
 fsp0, stored_pairs (analyzeSimilarPairs), analyze_lsh, cluster_graph, gene_pairs and gene_information, each against its C++
@@ -30,6 +32,8 @@ import synth  # noqa: E402
 from label_graphs import fast_graph  # noqa: E402
 from expressionmatrix2_amd import capi  # noqa: E402
 
+WIDTHS = [1, 32, 64, 100, 128, 192, 256, 512, 600, 1000, 1024, 1024, 1024, 1100, 2000, 2048, 2048, 4096]
+FSP5_WIDTHS = WIDTHS + [384, 640, 1280, 1920, 2176, 3072, 3968]
 KNOBS = ("EM2_SCAN_MODE", "EM2_MIN_SEGMENT_COLUMNS", "EM2_LOG_CAPACITY", "EM2_FULL_ROW_CELLS",
          "EM2_PREFIX_PERMILLE", "EM2_TILE_SEGMENTS", "EM2_BLOCKS_PER_CU", "EM2_SCAN_MATRIX", "EM2_MATRIX_CONVOY")
 
@@ -41,7 +45,7 @@ def main():
     deadline = time.time() + float(os.environ.get("SECONDS", "120"))
     restatement6 = fsp6_binding.load()
     runs = {"fsp4": 0, "fsp5": 0, "fsp6": 0, "fsp7": 0, "signatures": 0, "graph": 0, "labels": 0, "fsp6_unsupported": 0,
-            "fsp6_clamp8192": 0, "fsp6_chunks": 0, "fsp7_ranged": 0, "fsp7_skipped": 0}
+            "fsp6_clamp8192": 0, "fsp6_chunks": 0, "fsp7_ranged": 0, "fsp7_skipped": 0, "fsp5_ranged": 0}
     for name in expression_cases.ENTRIES:
         runs.update({name: 0, name + "_skipped": 0, name + "_discarded": 0})
     references = {}
@@ -77,7 +81,7 @@ def main():
             runs["labels"] += 1
             continue
         n = int(rng.choice([1, 2, 63, 64, 65, 200, 500, 1000, 1500, 2500, 4000]))
-        L = int(rng.choice([1, 32, 64, 100, 128, 192, 256, 512, 600, 1000, 1024, 1024, 1024, 1100, 2000, 2048, 2048, 4096]))
+        L = int(rng.choice(WIDTHS))
         if os.environ.get("FUZZ_WIDTHS"):
             L = int(rng.choice([int(x) for x in os.environ["FUZZ_WIDTHS"].split(",")]))
         k = int(rng.choice([1, 2, 5, 10, 33, 100, 300]))
@@ -108,13 +112,28 @@ def main():
             cell, sim, used = oracle.find_similar_pairs4(sig, L, k, thr)
             pairs, gused = capi.find_similar_pairs4(sig, L, k, thr)
         elif what == "fsp5":
+            if not os.environ.get("FUZZ_WIDTHS"):
+                L = int(rng.choice(FSP5_WIDTHS))
+                sig = synth.clustered_signatures(n, L, cluster_count=clusters, flip=flip, seed=sig_seed)
             q = int(rng.choice([1, 3, 8, 13, 20]))
             overflow = int(rng.choice([0, 5, 1000]))
+            ranged = bool(rng.random() < 0.33)
+            begin, end = sorted(int(x) for x in rng.integers(0, n + 1, size=2)) if ranged else (0, n)
             knobs = {"EM2_FSP5_BATCH_LOG2": str(int(rng.choice([20, 22, 29]))), "EM2_SCRATCH_CACHE_MB": str(int(rng.choice([0, 1, 4096])))}
             os.environ.update(knobs)
-            label.update(q=q, overflow=overflow, **knobs)
-            cell, sim, used = oracle.find_similar_pairs5(sig, L, k, thr, q, overflow)
-            pairs, gused = capi.find_similar_pairs5(sig, L, k, thr, q, overflow)
+            label.update(L=L, q=q, overflow=overflow, rows=[begin, end] if ranged else None, **knobs)
+            if ranged:
+                # the device entry on a row range, against the oracle's rows of that range
+                cell, sim, used = oracle.find_similar_pairs5_rows(sig, L, k, thr, q, overflow, begin, end)
+                pairs, gused = fsp5_rows(sig, L, k, thr, q, overflow, begin, end)
+                runs["fsp5_ranged"] += 1
+            else:
+                cell, sim, used = oracle.find_similar_pairs5(sig, L, k, thr, q, overflow)
+                pairs, gused = capi.find_similar_pairs5(sig, L, k, thr, q, overflow)
+            if begin < end:
+                info = capi.dev_find_similar_pairs5_last_launch()
+                label.update(filter_form=info["filter_form"], union_form=info["union_form"], union_passes=info["union_passes"],
+                             packed=info["packed"], batches=info["batches"])
             for key in knobs:
                 os.environ.pop(key, None)
         elif what == "fsp6":
@@ -229,6 +248,20 @@ def fsp7_oracle_is_slow(n, L, k, lengths, max_check, log2b):
     walked = sum((L // length) * max(1.0, n / 2.0 ** min(length, log2b)) for length in lengths) if candidates == n else candidates
     return (n * k > 4300 * 4096 or tables * n > 3 * 10 ** 7 or n * candidates * ((L - 1) // 64 + 1) > 2 * 10 ** 9 or
             n * walked > 2 * 10 ** 9)
+
+
+def fsp5_rows(sig, L, k, thr, q, overflow, begin, end):
+    """capi.dev_find_similar_pairs5 for rows [begin, end), as fsp7_rows."""
+    import torch
+    rows = end - begin
+    d_sig = torch.from_numpy(sig.view(np.int64)).cuda()
+    d_pairs = torch.full((max(rows, 1), k, 2), 0x5a5a5a5a, dtype=torch.int32, device="cuda")
+    d_used = torch.full((max(rows, 1),), 0x5a5a5a5a, dtype=torch.int32, device="cuda")
+    capi.dev_find_similar_pairs5(d_sig.data_ptr(), len(sig), begin, end, L, k, thr, q, overflow, d_pairs.data_ptr(),
+                                 d_used.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    pairs = d_pairs.cpu().numpy().view(capi.PAIR_DTYPE)[:rows, :, 0]
+    return pairs, d_used.cpu().numpy().view(np.uint32)[:rows]
 
 
 def fsp7_rows(sig, L, k, thr, lengths, max_check, log2b, begin, end):
