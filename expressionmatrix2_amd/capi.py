@@ -150,6 +150,11 @@ SYMBOLS = {
     "em2_gene_graph_sizes": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_uint32), _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint32)]),
     "em2_gene_graph_get": (_c.c_int, [_c.c_void_p] * 8),
     "em2_gene_graph_free": (None, [_c.c_void_p]),
+    "em2_graph_layout": (_c.c_int, [_c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "em2_dev_graph_layout": (_c.c_int, [_c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                        _c.c_void_p]),
+    "em2_graph_layout_forces": (_c.c_int, [_c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_double, _c.c_void_p, _c.c_void_p,
+                                           _c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_double)]),
     "em2_matrix_create_gene_graph": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_int64, _c.c_double, _c.POINTER(_c.c_void_p)]),
     "em2_matrix_create_gene_set_intersection": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.POINTER(_c.c_int)]),
     "em2_matrix_create_gene_set_union": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.POINTER(_c.c_int)]),
@@ -707,6 +712,71 @@ def dev_gene_graph_create(pairs, used_count, pairs_gene_set, graph_gene_set, sim
                                            len(pairs_genes), pairs.shape[1], _ptr(pairs_genes), _ptr(graph_genes), len(graph_genes),
                                            similarity_threshold, int(max_connectivity) % 2 ** 64, ctypes.byref(handle)))
     return gene_graph_take(handle)
+
+
+class LayoutParameters(_c.Structure):
+    """em2_layout_parameters, with the defaults of include/em2_lsh.h."""
+    _fields_ = [("seed", _c.c_uint32), ("maxIterationCount", _c.c_uint32), ("tolerance", _c.c_double), ("gravity", _c.c_double),
+                ("initialStep", _c.c_double)]
+
+    def __init__(self, seed=231, maxIterationCount=300, tolerance=0.01, gravity=0.02, initialStep=1.0):
+        super().__init__(seed, maxIterationCount, tolerance, gravity, initialStep)
+
+
+class LayoutResult(_c.Structure):
+    """em2_layout_result."""
+    _fields_ = [("iterationCount", _c.c_uint32), ("reserved", _c.c_uint32), ("step", _c.c_double), ("energy", _c.c_double)]
+
+
+def _layout_edges(vertex_count, edge_vertex0, edge_vertex1):
+    v0 = np.ascontiguousarray(edge_vertex0, dtype=np.uint32)
+    v1 = np.ascontiguousarray(edge_vertex1, dtype=np.uint32)
+    if v0.ndim != 1 or v0.shape != v1.shape:
+        raise ValueError("edge_vertex0 and edge_vertex1 must be one-dimensional and of one length")
+    return int(vertex_count), v0, v1
+
+
+def graph_layout(vertex_count, edge_vertex0, edge_vertex1, parameters=None):
+    """em2_graph_layout -> (x float32 [V], y float32 [V], iterations, final step, final energy).  parameters: a
+    LayoutParameters (None: the defaults)."""
+    n, v0, v1 = _layout_edges(vertex_count, edge_vertex0, edge_vertex1)
+    parameters = parameters if parameters is not None else LayoutParameters()
+    x, y = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.float32)
+    result = LayoutResult()
+    check(load().em2_graph_layout(n, _ptr(v0), _ptr(v1), len(v0), ctypes.byref(parameters), _ptr(x), _ptr(y), ctypes.byref(result)))
+    return x, y, result.iterationCount, result.step, result.energy
+
+
+def dev_graph_layout(vertex_count, edge_vertex0, edge_vertex1, parameters=None):
+    """The same through em2_dev_graph_layout: the edges go to torch device buffers first, the positions come back from two."""
+    import torch
+    n, v0, v1 = _layout_edges(vertex_count, edge_vertex0, edge_vertex1)
+    parameters = parameters if parameters is not None else LayoutParameters()
+    device = torch.device("cuda")
+    d_v0 = torch.from_numpy(v0.view(np.int32).copy()).to(device)
+    d_v1 = torch.from_numpy(v1.view(np.int32).copy()).to(device)
+    d_x = torch.zeros(n, dtype=torch.float32, device=device)
+    d_y = torch.zeros(n, dtype=torch.float32, device=device)
+    torch.cuda.synchronize()
+    result = LayoutResult()
+    check(load().em2_dev_graph_layout(n, d_v0.data_ptr() if len(v0) else None, d_v1.data_ptr() if len(v0) else None, len(v0),
+                                      ctypes.byref(parameters), d_x.data_ptr() if n else None, d_y.data_ptr() if n else None,
+                                      ctypes.byref(result)))
+    return d_x.cpu().numpy(), d_y.cpu().numpy(), result.iterationCount, result.step, result.energy
+
+
+def graph_layout_forces(vertex_count, edge_vertex0, edge_vertex1, gravity, x, y):
+    """em2_graph_layout_forces (for tests): one evaluation at the positions x / y -> (fx float32 [V], fy float32 [V], energy)."""
+    n, v0, v1 = _layout_edges(vertex_count, edge_vertex0, edge_vertex1)
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    if x.shape != (n,) or y.shape != (n,):
+        raise ValueError("x and y must hold one position per vertex")
+    fx, fy = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.float32)
+    energy = ctypes.c_double(0.)
+    check(load().em2_graph_layout_forces(n, _ptr(v0), _ptr(v1), len(v0), float(gravity), _ptr(x), _ptr(y), _ptr(fx), _ptr(fy),
+                                         ctypes.byref(energy)))
+    return fx, fy, energy.value
 
 
 CONTINGENCY_AUTOMATIC, CONTINGENCY_LDS, CONTINGENCY_SORT = 0, 1, 2

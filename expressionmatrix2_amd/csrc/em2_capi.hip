@@ -12,6 +12,7 @@
 #include "em2_cluster_graph.h"
 #include "em2_signature_graph.h"
 #include "em2_gene_graph.h"
+#include "em2_layout.h"
 #include "em2_contingency.h"
 #include "em2_tables.h"
 
@@ -22,6 +23,7 @@
 #include <condition_variable>
 #include <fstream>
 #include <functional>
+#include <limits>
 #include <map>
 #include <thread>
 #include <cstdio>
@@ -2374,6 +2376,104 @@ int em2_gene_graph_get(const em2_gene_graph* graph, uint32_t* vertices, uint32_t
 }
 
 void em2_gene_graph_free(em2_gene_graph* graph) { delete graph; }
+
+// ---- the layout of a graph (em2_layout.hip) ----
+
+// The edge arrays of a host-pointer entry in device memory.
+static int uploadEdges(const uint32_t* edgeVertex0, const uint32_t* edgeVertex1, uint64_t edgeCount, DeviceBuffer& d0, DeviceBuffer& d1)
+{
+    EM2_HIP(d0.allocate(size_t(edgeCount) * sizeof(uint32_t)));
+    EM2_HIP(d1.allocate(size_t(edgeCount) * sizeof(uint32_t)));
+    if (edgeCount) {
+        EM2_HIP(hipMemcpy(d0.p, edgeVertex0, size_t(edgeCount) * sizeof(uint32_t), hipMemcpyHostToDevice));
+        EM2_HIP(hipMemcpy(d1.p, edgeVertex1, size_t(edgeCount) * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    return EM2_OK;
+}
+
+static int graphLayout(const char* who, bool onDevice, uint32_t vertexCount, const uint32_t* edgeVertex0, const uint32_t* edgeVertex1,
+                       uint64_t edgeCount, const em2_layout_parameters* parameters, float* x, float* y, em2_layout_result* result)
+{
+    if (!parameters || (vertexCount && (!x || !y)) || (edgeCount && (!edgeVertex0 || !edgeVertex1))) return failArgument(who, "null pointer");
+    if (!(parameters->tolerance >= 0.)) return failArgument(who, "tolerance must not be negative");
+    if (!(parameters->gravity >= 0.)) return failArgument(who, "gravity must not be negative");
+    if (!(parameters->initialStep >= 0.)) return failArgument(who, "initialStep must not be negative");
+    if (vertexCount > em2::kLayoutMaxVertexCount) return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": vertexCount is above 2^30");
+    if (result) {
+        result->iterationCount = result->reserved = 0u;
+        result->step = parameters->initialStep;
+        result->energy = std::numeric_limits<double>::infinity();
+    }
+    if (vertexCount == 0) {
+        // (no vertex, so every edge end is out of range)
+        return edgeCount ? failArgument(who, "an edge names a vertex outside the graph") : EM2_OK;
+    }
+    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
+    DeviceBuffer d0, d1, dx, dy;
+    if (!onDevice) {
+        const int status = uploadEdges(edgeVertex0, edgeVertex1, edgeCount, d0, d1);
+        if (status != EM2_OK) return status;
+        EM2_HIP(dx.allocate(size_t(vertexCount) * sizeof(float)));
+        EM2_HIP(dy.allocate(size_t(vertexCount) * sizeof(float)));
+    }
+    const em2::LayoutParameters p = {parameters->seed, parameters->maxIterationCount, parameters->tolerance, parameters->gravity,
+                                     parameters->initialStep};
+    em2::LayoutResult r;
+    uint32_t inputError = 0;
+    EM2_HIP(em2::runGraphLayout(vertexCount, onDevice ? edgeVertex0 : d0.as<uint32_t>(), onDevice ? edgeVertex1 : d1.as<uint32_t>(), edgeCount,
+                                p, onDevice ? x : dx.as<float>(), onDevice ? y : dy.as<float>(), r, &inputError, nullptr));
+    if (inputError) return failArgument(who, "an edge names a vertex outside the graph");
+    if (!onDevice) {
+        EM2_HIP(hipMemcpy(x, dx.p, size_t(vertexCount) * sizeof(float), hipMemcpyDeviceToHost));
+        EM2_HIP(hipMemcpy(y, dy.p, size_t(vertexCount) * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    if (result) {
+        result->iterationCount = r.iterationCount;
+        result->step = r.step;
+        result->energy = r.energy;
+    }
+    return EM2_OK;
+}
+
+int em2_graph_layout(uint32_t vertexCount, const uint32_t* edgeVertex0, const uint32_t* edgeVertex1, uint64_t edgeCount,
+                     const em2_layout_parameters* parameters, float* x, float* y, em2_layout_result* result)
+{
+    return graphLayout("em2_graph_layout", false, vertexCount, edgeVertex0, edgeVertex1, edgeCount, parameters, x, y, result);
+}
+
+int em2_dev_graph_layout(uint32_t vertexCount, const uint32_t* d_edgeVertex0, const uint32_t* d_edgeVertex1, uint64_t edgeCount,
+                         const em2_layout_parameters* parameters, float* d_x, float* d_y, em2_layout_result* result)
+{
+    return graphLayout("em2_dev_graph_layout", true, vertexCount, d_edgeVertex0, d_edgeVertex1, edgeCount, parameters, d_x, d_y, result);
+}
+
+int em2_graph_layout_forces(uint32_t vertexCount, const uint32_t* edgeVertex0, const uint32_t* edgeVertex1, uint64_t edgeCount,
+                            double gravity, const float* x, const float* y, float* fx, float* fy, double* energy)
+{
+    const char* who = "em2_graph_layout_forces";
+    if ((vertexCount && (!x || !y || !fx || !fy)) || (edgeCount && (!edgeVertex0 || !edgeVertex1))) return failArgument(who, "null pointer");
+    if (!(gravity >= 0.)) return failArgument(who, "gravity must not be negative");
+    if (vertexCount > em2::kLayoutMaxVertexCount) return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": vertexCount is above 2^30");
+    if (energy) *energy = 0.;
+    if (vertexCount == 0) return edgeCount ? failArgument(who, "an edge names a vertex outside the graph") : EM2_OK;
+    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
+    DeviceBuffer d0, d1, d[4];
+    const int status = uploadEdges(edgeVertex0, edgeVertex1, edgeCount, d0, d1);
+    if (status != EM2_OK) return status;
+    const size_t bytes = size_t(vertexCount) * sizeof(float);
+    for (DeviceBuffer& buffer : d) EM2_HIP(buffer.allocate(bytes));
+    EM2_HIP(hipMemcpy(d[0].p, x, bytes, hipMemcpyHostToDevice));
+    EM2_HIP(hipMemcpy(d[1].p, y, bytes, hipMemcpyHostToDevice));
+    uint32_t inputError = 0;
+    double e = 0.;
+    EM2_HIP(em2::runGraphLayoutForces(vertexCount, d0.as<uint32_t>(), d1.as<uint32_t>(), edgeCount, gravity, d[0].as<float>(), d[1].as<float>(),
+                                      d[2].as<float>(), d[3].as<float>(), &e, &inputError, nullptr));
+    if (inputError) return failArgument(who, "an edge names a vertex outside the graph");
+    EM2_HIP(hipMemcpy(fx, d[2].p, bytes, hipMemcpyDeviceToHost));
+    EM2_HIP(hipMemcpy(fy, d[3].p, bytes, hipMemcpyDeviceToHost));
+    if (energy) *energy = e;
+    return EM2_OK;
+}
 
 // ---- the contingency table of two labelings (em2_contingency.hip) ----
 

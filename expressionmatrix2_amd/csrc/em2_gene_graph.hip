@@ -22,6 +22,7 @@
 //     neighbour half of every sorted key.
 
 #include "em2_gene_graph.h"
+#include "em2_adjacency.h"
 #include "em2_hip_util.h"
 #include "em2_scratch.h"
 
@@ -67,18 +68,6 @@ edgeRecordsKernel(const uint32_t* __restrict__ edge0, const uint32_t* __restrict
         values[2u * e] = bits;
         values[2u * e + 1u] = bits;
     }
-}
-
-// The first of the ascending keys[0, n) that is not below `key`, n where there is none.
-__device__ __forceinline__ uint64_t lowerBound(const uint64_t* __restrict__ keys, uint64_t n, uint64_t key)
-{
-    uint64_t low = 0, high = n;
-    while (low < high) {
-        const uint64_t middle = low + (high - low) / 2u;
-        if (keys[middle] < key) low = middle + 1u;
-        else high = middle;
-    }
-    return low;
 }
 
 // offsets[v] = where the records of vertex v begin, v in [0, geneCount]; alive[v] = 1 where v has one, alive[geneCount] = 0

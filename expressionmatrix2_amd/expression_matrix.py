@@ -42,6 +42,32 @@ class NormalizationMethod(enum.IntEnum):
     L2 = 2
 
 
+class CellGraphVertexInfo:
+    """CellGraphVertexInfo (src/CellGraph.hpp:127-155) as the reference's module exposes it: cellId, x(), y(), and an
+    equality that compares the cell id and the position."""
+    __slots__ = ("cellId", "position")
+
+    def __init__(self, cellId=INVALID_ID, position=(0., 0.)):
+        self.cellId = cellId
+        self.position = (float(position[0]), float(position[1]))
+
+    def x(self):
+        return self.position[0]
+
+    def y(self):
+        return self.position[1]
+
+    def __eq__(self, that):
+        if not isinstance(that, CellGraphVertexInfo):
+            return NotImplemented
+        return self.cellId == that.cellId and self.position == that.position
+
+    __hash__ = None
+
+    def __repr__(self):
+        return "CellGraphVertexInfo(cellId=%d, x=%r, y=%r)" % (self.cellId, self.position[0], self.position[1])
+
+
 def _b(s):
     if not isinstance(s, str):
         raise TypeError("expected a string, got %r" % (s,))
@@ -831,6 +857,27 @@ class ExpressionMatrix:
         """[(cellId0, cellId1)] per edge, in edge-list order (src/ExpressionMatrix.cpp:1892-1913)."""
         c0, c1 = self._cell_graph(graphName)["edgeCellIds"]
         return list(zip(c0.tolist(), c1.tolist()))
+
+    def computeCellGraphLayout(self, graphName, seed=231, maxIterationCount=300, tolerance=0.01, gravity=0.02):
+        """ExpressionMatrix::computeCellGraphLayout (src/ExpressionMatrix.cpp:1850-1864).  The reference runs Graphviz's sfdp
+        on the graph; here the model sfdp minimises is iterated on the GPU at a single level (em2_graph_layout, DESIGN.md
+        3.19), in units of the natural edge length.  The keyword arguments are this project's (the reference has none).
+        Computed once per graph, like the reference's layoutWasComputed: a second call does nothing."""
+        g = self._cell_graph(graphName)
+        if "layout" in g:
+            return
+        v0, v1 = g["edgeVertices"]
+        parameters = capi.LayoutParameters(seed=seed, maxIterationCount=maxIterationCount, tolerance=tolerance, gravity=gravity)
+        x, y, _, _, _ = capi.graph_layout(g["vertexCount"], v0, v1, parameters)
+        g["layout"] = (x.astype(np.float64), y.astype(np.float64))
+
+    def getCellGraphVertices(self, graphName):
+        """[CellGraphVertexInfo] per vertex, in vertex order (src/ExpressionMatrix.cpp:1869-1888)."""
+        g = self._cell_graph(graphName)
+        if "layout" not in g:
+            raise RuntimeError("Layout for graph " + graphName + " is not available.")
+        x, y = g["layout"]
+        return [CellGraphVertexInfo(cellId, (px, py)) for cellId, px, py in zip(g["vertexCellIds"].tolist(), x.tolist(), y.tolist())]
 
     def labelPropagationClustering(self, graphName, seed=231, stableIterationCountThreshold=3, maxIterationCount=100):
         """CellGraph::labelPropagationClustering (src/CellGraph.cpp:443-612), the first step of

@@ -744,6 +744,65 @@ int em2_gene_graph_get(const em2_gene_graph* graph, uint32_t* vertices, uint32_t
 void em2_gene_graph_free(em2_gene_graph* graph);
 
 /* ------------------------------------------------------------------------------------------------------
+ * The layout of a graph in the plane.  csrc/em2_layout.hip, DESIGN.md 3.19.
+ * The reference writes Graph.dot and runs Graphviz's sfdp (src/CellGraph.cpp:210-264).  This is the model sfdp minimises --
+ * Hu's spring-electrical model -- at a single level with the exact N-body repulsion: no multilevel coarsening, no
+ * approximation of the far field, no overlap removal, no edge smoothing.  The positions are not sfdp's; they are a function
+ * of the input alone, bit for bit (every rounding and the shape of every sum are fixed).
+ * ------------------------------------------------------------------------------------------------------ */
+
+/* The graph: vertexCount vertices, edgeCount undirected, unweighted edges (edgeVertex0[e], edgeVertex1[e]).  A self-loop
+ * contributes nothing, a repeated edge attracts twice.  With d = |p_i - p_j|, natural length K = 1 and C = 0.2 the force on
+ * vertex i is
+ *     sum over every j of (p_i - p_j) * C K^2 / max(d^2, 1e-30)  -  sum over the neighbours j of (p_i - p_j) * d / K  -  gravity * p_i
+ * The start positions are a hash of (seed, vertex index), uniform on a square of side sqrt(vertexCount) * K about the origin
+ * (those of a vertex differ between two vertex counts by that factor only).  An iteration moves every vertex by
+ * step * f / |f| (not at all where |f| = 0) and then adapts the step from the energy, the sum of |f|^2 in double: times 0.9
+ * when it did not fall, divided by 0.9 after five falls in a row.  The run ends after maxIterationCount iterations or as soon as
+ * step < tolerance * K; with maxIterationCount 0 the start positions come back.
+ * The defaults (DESIGN.md 3.19 says on which graphs they were chosen; nothing is promised about the picture they give): */
+#define EM2_LAYOUT_DEFAULT_SEED 231u
+#define EM2_LAYOUT_DEFAULT_MAX_ITERATION_COUNT 300u
+#define EM2_LAYOUT_DEFAULT_TOLERANCE 0.01
+#define EM2_LAYOUT_DEFAULT_GRAVITY 0.02
+#define EM2_LAYOUT_DEFAULT_INITIAL_STEP 1.0
+typedef struct em2_layout_parameters {
+    uint32_t seed;
+    uint32_t maxIterationCount;
+    double tolerance;   /* >= 0 */
+    double gravity;     /* >= 0; 0 is allowed: nothing then holds the components of a disconnected graph together */
+    double initialStep; /* >= 0, in units of K */
+} em2_layout_parameters;
+#define EM2_LAYOUT_PARAMETERS_DEFAULT                                                                                          \
+    {EM2_LAYOUT_DEFAULT_SEED, EM2_LAYOUT_DEFAULT_MAX_ITERATION_COUNT, EM2_LAYOUT_DEFAULT_TOLERANCE, EM2_LAYOUT_DEFAULT_GRAVITY, \
+     EM2_LAYOUT_DEFAULT_INITIAL_STEP}
+
+/* iterationCount: the iterations done; step: the step after the last update; energy: the sum of |f|^2 of the last evaluation
+ * (the positions before the last move), +infinity where there was no iteration. */
+typedef struct em2_layout_result {
+    uint32_t iterationCount;
+    uint32_t reserved;
+    double step;
+    double energy;
+} em2_layout_result;
+
+/* x / y [vertexCount] receive the positions; result may be NULL.  em2_graph_layout: host pointers; em2_dev_graph_layout:
+ * edgeVertex0 / edgeVertex1 / x / y in device memory (it takes its scratch from the library's cache and returns when the
+ * positions are written).  vertexCount 0 is EM2_OK and writes nothing.  EM2_ERROR_INVALID_ARGUMENT: a null pointer (the edge
+ * arrays may be NULL where edgeCount is 0), an edge end >= vertexCount (checked on the device before anything indexes with
+ * it), a negative or NaN tolerance, gravity or initialStep.  EM2_ERROR_UNSUPPORTED: vertexCount above 2^30.
+ * Not tied to cells: any graph given as two index arrays can be laid out. */
+int em2_graph_layout(uint32_t vertexCount, const uint32_t* edgeVertex0, const uint32_t* edgeVertex1, uint64_t edgeCount,
+                     const em2_layout_parameters* parameters, float* x, float* y, em2_layout_result* result);
+int em2_dev_graph_layout(uint32_t vertexCount, const uint32_t* d_edgeVertex0, const uint32_t* d_edgeVertex1, uint64_t edgeCount,
+                         const em2_layout_parameters* parameters, float* d_x, float* d_y, em2_layout_result* result);
+
+/* For tests: one evaluation of f at the given positions x / y [vertexCount], no move.  fx / fy [vertexCount] and *energy (may
+ * be NULL) receive the forces and the sum of |f|^2.  Host pointers; the same checks. */
+int em2_graph_layout_forces(uint32_t vertexCount, const uint32_t* edgeVertex0, const uint32_t* edgeVertex1, uint64_t edgeCount,
+                            double gravity, const float* x, const float* y, float* fx, float* fy, double* energy);
+
+/* ------------------------------------------------------------------------------------------------------
  * The contingency table of two labelings of n items.  csrc/em2_contingency.hip, DESIGN.md 3.16.  Integers only: every output
  * is exact.
  * ------------------------------------------------------------------------------------------------------ */
