@@ -18,7 +18,7 @@ SOURCE = os.path.join(NATIVE_DIR, "em2_ingest_restatement.cpp")
 FILL = 0x5a
 GUARD = 64
 NO_GENE = 0xffffffff
-OK, NEGATIVE, DUPLICATE = 0, 1, 2
+OK, NEGATIVE, DUPLICATE, BAD_INDEX = 0, 1, 2, 3
 
 c = ctypes
 P = c.c_void_p
@@ -58,6 +58,20 @@ class Csr:
         self.cells = len(rows)
         self.skip = None if skip is None else np.ascontiguousarray(skip, dtype=np.uint8)
 
+    @classmethod
+    def from_arrays(cls, indptr, indices, values, skip=None):
+        """The same from the arrays themselves (a million rows as lists of pairs would take minutes)."""
+        self = cls.__new__(cls)
+        self.indptr = np.ascontiguousarray(indptr, dtype=np.uint64)
+        self.indices = np.ascontiguousarray(indices, dtype=np.uint32)
+        self.values = np.ascontiguousarray(values, dtype=np.float32)
+        self.cells = len(self.indptr) - 1
+        assert self.indptr[0] == 0 and int(self.indptr[-1]) == len(self.indices) == len(self.values)
+        assert (self.indptr[1:] >= self.indptr[:-1]).all()
+        self.skip = None if skip is None else np.ascontiguousarray(skip, dtype=np.uint8)
+        assert self.skip is None or len(self.skip) == self.cells
+        return self
+
 
 def restate(csr, gene_map):
     """-> dict(kept, status, duplicate, toc, data (bytes, 0x5a where nothing is stored), cells (bytes, likewise))."""
@@ -78,41 +92,56 @@ def _device(torch, array):
     return torch.from_numpy(array.view(np.uint8).reshape(-1).copy()).cuda()
 
 
-def device_count(torch, csr, gene_map):
-    """em2_dev_ingest_count -> (dict(kept, status, duplicate, toc), the device arrays for the fill)."""
+def device_count(torch, csr, gene_map, index_count=None):
+    """em2_dev_ingest_count -> (dict(kept, status, duplicate, toc), the device arrays for the fill).  The map's buffer holds
+    exactly the map, with a guard behind it; `index_count` is what the entry is told (default: the map's length)."""
     gene_map = np.ascontiguousarray(gene_map, dtype=np.uint32)
+    index_count = len(gene_map) if index_count is None else index_count
+    assert index_count <= len(gene_map)
     n = csr.cells
+    genes = torch.full((4 * len(gene_map) + GUARD,), FILL, dtype=torch.uint8, device="cuda")
+    genes[:4 * len(gene_map)] = _device(torch, gene_map)
     d = {"indptr": _device(torch, csr.indptr), "indices": _device(torch, csr.indices), "values": _device(torch, csr.values),
-         "skip": _device(torch, csr.skip) if csr.skip is not None else None, "genes": _device(torch, gene_map)}
+         "skip": _device(torch, csr.skip) if csr.skip is not None else None, "genes": genes}
     out = {key: torch.full((4 * n + GUARD,), FILL, dtype=torch.uint8, device="cuda") for key in ("kept", "status", "duplicate")}
     out["toc"] = torch.full((8 * (n + 1) + GUARD,), FILL, dtype=torch.uint8, device="cuda")
     capi.check(capi.load().em2_dev_ingest_count(
         d["indptr"].data_ptr(), d["indices"].data_ptr(), d["values"].data_ptr(), d["skip"].data_ptr() if d["skip"] is not None else None,
-        n, d["genes"].data_ptr(), len(gene_map), out["kept"].data_ptr(), out["status"].data_ptr(), out["duplicate"].data_ptr(),
+        n, d["genes"].data_ptr(), index_count, out["kept"].data_ptr(), out["status"].data_ptr(), out["duplicate"].data_ptr(),
         out["toc"].data_ptr(), None))
     torch.cuda.synchronize()
+    assert (genes[4 * len(gene_map):].cpu().numpy() == FILL).all(), "the guard behind the gene map was written"
     result = {}
     for key, item, count in (("kept", 4, n), ("status", 4, n), ("duplicate", 4, n), ("toc", 8, n + 1)):
         host = out[key].cpu().numpy()
         assert (host[item * count:] == FILL).all(), "the guard behind %s was written" % key
         result[key] = host[:item * count].view(np.uint32 if item == 4 else np.uint64).copy()
     d["toc"] = out["toc"]
-    d["map_length"] = len(gene_map)
+    d["map_length"] = index_count
     return result, d
 
 
-def device_fill(torch, csr, d, entry_count):
-    """em2_dev_ingest_fill into buffers pre-filled with 0x5a with a guard behind each -> (data bytes, cells bytes)."""
+def device_fill(torch, csr, d, entry_count, index_count=None, toc=None):
+    """em2_dev_ingest_fill into buffers pre-filled with 0x5a with a guard behind each -> (data bytes, cells bytes).
+    `index_count` defaults to what the count pass was told; `toc` (cells + 1 offsets) stands in for the count pass's own.
+    The guards are looked at before the entry's answer is: a call that fails must have kept to its buffers too."""
     n = csr.cells
     data = torch.full((8 * entry_count + GUARD,), FILL, dtype=torch.uint8, device="cuda")
     cells = torch.full((56 * n + GUARD,), FILL, dtype=torch.uint8, device="cuda")
-    capi.check(capi.load().em2_dev_ingest_fill(
+    d_toc = d["toc"]
+    if toc is not None:
+        toc = np.ascontiguousarray(toc, dtype=np.uint64)
+        assert len(toc) == n + 1
+        d_toc = _device(torch, toc)
+    rc = capi.load().em2_dev_ingest_fill(
         d["indptr"].data_ptr(), d["indices"].data_ptr(), d["values"].data_ptr(), d["skip"].data_ptr() if d["skip"] is not None else None,
-        n, d["genes"].data_ptr(), d["map_length"], d["toc"].data_ptr(), data.data_ptr(), cells.data_ptr(), None))
+        n, d["genes"].data_ptr(), d["map_length"] if index_count is None else index_count, d_toc.data_ptr(), data.data_ptr(),
+        cells.data_ptr(), None)
     torch.cuda.synchronize()
     data, cells = data.cpu().numpy(), cells.cpu().numpy()
     assert (data[8 * entry_count:] == FILL).all(), "the guard behind the entries was written"
     assert (cells[56 * n:] == FILL).all(), "the guard behind the Cell records was written"
+    capi.check(rc)
     return data[:8 * entry_count].copy(), cells[:56 * n].copy()
 
 

@@ -15,7 +15,13 @@ restatement (analyze_lsh: the oracle) with the comparison of its own test file. 
 the cost cap of its leg is counted as <leg>_skipped; one that reaches a place the reference leaves open or asserts in (a makeKnn
 tie or a NaN similarity of the cluster graph, bin < binCount of the two analyses -- the device entry must then answer with the
 reference's text) as <leg>_discarded.  On a difference the case dict is printed: expression_cases.ENTRIES[leg].check(case,
-reference) reproduces it."""
+reference) reproduces it.
+
+Two legs draw from tests/ingest_limit_cases.py: csv_parse (random structure and numeric fields, tile size, misalignment and kept
+subset through csv_binding.assert_parse, against the model of em2_dev_csv_parse) and ingest (row lengths around 512 and the LDS
+row limit, value kinds, orders, duplicates, zeros and skip flags through ingest_binding.assert_same, against the restatement of
+addCell's storing part).  FUZZ_ONLY=csv_parse / ingest selects them; a difference prints the draw's dict (its seed rebuilds it:
+ingest_limit_cases.draw_csv_parse(None, seed) / draw_ingest(None, seed))."""
 import os
 import sys
 import time
@@ -48,10 +54,14 @@ def main():
             "fsp6_clamp8192": 0, "fsp6_chunks": 0, "fsp7_ranged": 0, "fsp7_skipped": 0, "fsp5_ranged": 0}
     for name in expression_cases.ENTRIES:
         runs.update({name: 0, name + "_skipped": 0, name + "_discarded": 0})
+    runs.update({name: 0 for name in WRITE_LEGS})
     references = {}
     while time.time() < deadline:
         for key in KNOBS:
             os.environ.pop(key, None)
+        if os.environ.get("FUZZ_ONLY") in WRITE_LEGS or (rng.random() < 0.1 and not os.environ.get("FUZZ_ONLY")):
+            write_leg(rng, os.environ.get("FUZZ_ONLY") or str(rng.choice(WRITE_LEGS)), runs)
+            continue
         if os.environ.get("FUZZ_ONLY") in expression_cases.ENTRIES or (rng.random() < 0.35 and not os.environ.get("FUZZ_ONLY")):
             name = os.environ.get("FUZZ_ONLY") or str(rng.choice(list(expression_cases.ENTRIES)))
             expression_leg(rng, name, references, runs)
@@ -232,6 +242,41 @@ def expression_leg(rng, name, references, runs):
     if difference:
         print(difference)
         raise SystemExit("PARITY FAILURE %s %r" % (name, case))
+    runs[name] += 1
+
+
+WRITE_LEGS = ("csv_parse", "ingest")
+
+
+def write_leg(rng, name, runs):
+    """One draw of tests/ingest_limit_cases.py for the write path: em2_dev_csv_parse against its model, or the two ingest passes
+    against their restatement.  Nothing is skipped or discarded."""
+    import torch
+    import csv_binding
+    import ingest_binding
+    import ingest_limit_cases
+    lib = capi.load()
+    if name == "csv_parse":
+        case = ingest_limit_cases.draw_csv_parse(rng)
+        lib.em2_set_csv_tile_bytes(case["tile"])
+        try:
+            csv_binding.assert_parse(torch, case["text"], case["separators"], case["columns"], case["kept"], "fuzz",
+                                     misalign=case["misalign"])
+        except AssertionError as e:
+            raise SystemExit("PARITY FAILURE csv_parse %r: %s" % (case, e))
+        finally:
+            lib.em2_set_csv_tile_bytes(0)
+    else:
+        case = ingest_limit_cases.draw_ingest(rng)
+        lib.em2_set_ingest_lds_row_limit(case["lds_limit"])
+        try:
+            csr = ingest_binding.Csr.from_arrays(case["indptr"], case["indices"], case["values"], case["skip"])
+            ingest_binding.assert_same(torch, csr, ingest_limit_cases.gene_map(), "fuzz")
+        except AssertionError as e:
+            label = {key: case[key] for key in ("lds_limit", "seed", "kind", "order")}
+            raise SystemExit("PARITY FAILURE ingest %r, row lengths %r: %s" % (label, np.diff(case["indptr"].astype(np.int64)).tolist(), e))
+        finally:
+            lib.em2_set_ingest_lds_row_limit(0)
     runs[name] += 1
 
 
