@@ -19,6 +19,8 @@
 
 #include "em2_device.h"
 #include "em2_expression.h"
+#include "em2_entry.h"
+#include "em2_csr.h"
 
 #include <cmath>
 #include <cstdio>
@@ -28,6 +30,8 @@
 #include <vector>
 
 #include "em2_tables.h"
+
+#include <algorithm>
 
 namespace em2 {
 namespace {
@@ -245,3 +249,170 @@ bool analysisEnd(AnalysisState* s, uint32_t lshCount, const char* statisticsCsvP
 }
 
 }  // namespace em2
+
+
+// ---- the C entry points (include/em2_lsh.h) ----
+
+using namespace em2::entry;
+using em2::DeviceBuffer;
+using em2::wordCountOf;
+
+namespace {
+
+// Ends an analysis that does not reach its end (an error return): closes the csv, frees the state.
+struct AnalysisCloser {
+    em2::AnalysisState*& state;
+    ~AnalysisCloser() { if (state) em2::analysisEnd(state, 0, nullptr, nullptr, nullptr, nullptr); }
+};
+
+}  // namespace
+
+extern "C" {
+
+int em2_analyze_lsh(const uint64_t* toc, const em2_count* data, uint32_t cellCount, uint32_t geneCount,
+                    const uint64_t* signatures, uint32_t lshCount, const uint32_t* globalCellIds, uint32_t seed,
+                    double csvDownsample, const char* pairsCsvPath, const char* statisticsCsvPath,
+                    uint64_t* sum0, double* sum1, double* sum2, double* exactSimilarity, double* lshSimilarity)
+{
+    if (lshCount == 0 || geneCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_analyze_lsh: lshCount and geneCount must be positive");
+    if (cellCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_analyze_lsh: the cell set is empty");
+    if (!toc || !signatures || !globalCellIds || !pairsCsvPath) return failNull("em2_analyze_lsh");
+    if (!haveDevice()) return failNoDevice("em2_analyze_lsh");
+    const uint64_t nnz = toc[cellCount];
+    if (nnz && !data) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_analyze_lsh: null data");
+    for (uint64_t i = 0; i < nnz; ++i) {
+        if (data[i].gene >= geneCount) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_analyze_lsh: a local gene id is not below geneCount");
+    }
+    const uint32_t words = wordCountOf(lshCount);
+
+    // ExpressionMatrixSubset::computeSums (src/ExpressionMatrixSubset.cpp:47-58)
+    std::vector<double> sums(2 * size_t(cellCount), 0.);
+    for (uint32_t c = 0; c < cellCount; ++c) {
+        double s1 = 0., s2 = 0.;
+        for (uint64_t i = toc[c]; i < toc[c + 1]; ++i) {
+            const float count = data[i].count;
+            s1 += count;
+            s2 += count * count;
+        }
+        sums[2 * size_t(c)] = s1;
+        sums[2 * size_t(c) + 1] = s2;
+    }
+
+    em2::AnalysisState* state = em2::analyzeLshBegin(lshCount, seed, pairsCsvPath);
+    if (!state) return fail(EM2_ERROR_RUNTIME, std::string("em2_analyze_lsh: cannot open ") + pairsCsvPath);
+    AnalysisCloser closer{state};
+
+    // rows in chunks of about 16M pairs: 192 MB of device output per chunk, walked by the host in order
+    const uint64_t chunkPairs = 1ull << 24;
+    const auto chunkEnd = [&](uint32_t begin, uint64_t& pairs) {
+        uint32_t end = begin;
+        for (pairs = 0; end + 1 < cellCount && (end == begin || pairs + (cellCount - 1 - end) <= chunkPairs);) pairs += cellCount - 1 - end++;
+        return end;
+    };
+    uint32_t maxRows = 0;
+    uint64_t maxPairs = 0, pairs = 0;
+    for (uint32_t begin = 0; begin + 1 < cellCount;) {
+        const uint32_t end = chunkEnd(begin, pairs);
+        if (end - begin > maxRows) maxRows = end - begin;
+        if (pairs > maxPairs) maxPairs = pairs;
+        begin = end;
+    }
+    em2::UploadedCsr csr;
+    (void)csr.check(toc, reinterpret_cast<const em2::CountIn*>(data), cellCount, false);      // (null data was refused above)
+    EM2_HIP(csr.upload());
+    DeviceBuffer dSig, dProducts, dMismatches, dScratch;
+    EM2_HIP(dSig.upload(signatures, size_t(cellCount) * words));
+    EM2_HIP(dProducts.allocateFor<double>(maxPairs));
+    EM2_HIP(dMismatches.allocateFor<uint32_t>(maxPairs));
+    EM2_HIP(dScratch.allocate(em2::analyzeScratchBytes(geneCount, maxRows)));
+    std::vector<double> products(maxPairs);
+    std::vector<uint32_t> mismatches(maxPairs);
+    uint64_t done = 0;
+    for (uint32_t begin = 0; begin + 1 < cellCount;) {
+        const uint32_t end = chunkEnd(begin, pairs);
+        EM2_HIP(em2::launchAnalyzePairs(csr.toc.as<uint64_t>(), csr.data.as<em2::CountIn>(), cellCount, geneCount, dSig.as<uint64_t>(), words,
+                                        begin, end, dScratch.p, dProducts.as<double>(), dMismatches.as<uint32_t>(), nullptr));
+        EM2_HIP(hipStreamSynchronize(nullptr));
+        EM2_HIP(dProducts.download(products.data(), pairs));
+        EM2_HIP(dMismatches.download(mismatches.data(), pairs));
+        if (!em2::analyzeLshRows(state, sums.data(), cellCount, geneCount, globalCellIds, begin, end, products.data(), mismatches.data(),
+                                 csvDownsample, exactSimilarity ? exactSimilarity + done : nullptr,
+                                 lshSimilarity ? lshSimilarity + done : nullptr)) {
+            return fail(EM2_ERROR_RUNTIME, "em2_analyze_lsh: Assertion failed: bin < binCount (a pair of cells with exact similarity 1, or a "
+                                           "cell without variance; src/ExpressionMatrixLsh.cpp:1322)");
+        }
+        done += pairs;
+        begin = end;
+    }
+    em2::AnalysisState* finished = state;
+    state = nullptr;
+    if (!em2::analysisEnd(finished, lshCount, statisticsCsvPath, sum0, sum1, sum2)) {
+        return fail(EM2_ERROR_RUNTIME, std::string("em2_analyze_lsh: cannot write ") + (statisticsCsvPath ? statisticsCsvPath : ""));
+    }
+    return EM2_OK;
+}
+
+
+// ExpressionMatrix::analyzeSimilarPairs (src/ExpressionMatrixLsh.cpp:55-150) after its lookups: the exact similarity of every
+// stored pair on the device, chunk of rows by chunk of rows; bins, the seeded draw and the csv lines on the host in the
+// reference's order (cell 0 ascending, stored order).
+int em2_analyze_similar_pairs(const uint64_t* toc, const em2_count* data, uint32_t cellCount, uint32_t geneCount,
+                              const em2_pair* pairs, const uint32_t* usedCount, uint32_t k, const uint32_t* globalCellIds,
+                              double csvDownsample, const char* pairsCsvPath, const char* statisticsCsvPath,
+                              uint64_t* sum0, double* sum1, double* sum2)
+{
+    const char* who = "em2_analyze_similar_pairs";
+    if (geneCount == 0) return failArgument(who, "geneCount must be positive");
+    if (!toc || !usedCount || !globalCellIds || !pairsCsvPath || !statisticsCsvPath || (!pairs && k && cellCount)) return failNull(who);
+    em2::UploadedCsr csr;
+    if (const char* error = csr.check(toc, reinterpret_cast<const em2::CountIn*>(data), cellCount)) return failArgument(who, error);
+    if (cellCount && toc[0] != 0) return failArgument(who, "toc must start at 0");
+    uint64_t stored = 0;
+    for (uint32_t c = 0; c < cellCount; ++c) {
+        if (usedCount[c] > k) return failArgument(who, "a cell stores more than k pairs");
+        for (uint32_t t = 0; t < usedCount[c]; ++t) {
+            if (pairs[size_t(c) * k + t].cell >= cellCount) return failArgument(who, "a stored pair names a cell that does not exist");
+        }
+        stored += usedCount[c];
+    }
+    if (stored && !haveDevice()) return failNoDevice(who);
+
+    em2::AnalysisState* state = em2::analyzeStoredBegin(pairsCsvPath);
+    if (!state) return fail(EM2_ERROR_RUNTIME, std::string(who) + ": cannot open " + pairsCsvPath);
+    AnalysisCloser closer{state};
+
+    if (stored) {
+        // rows in chunks of at most 2^24 slots (128 MB of doubles), one row at least
+        const uint32_t chunkRows = std::max<uint32_t>(1u, uint32_t(std::min<uint64_t>(cellCount, (1ull << 24) / k)));
+        const em2::PairOut* hostPairs = reinterpret_cast<const em2::PairOut*>(pairs);
+        DeviceBuffer dPairs, dUsed, dWorkspace, dExact;
+        EM2_HIP(csr.upload());
+        EM2_HIP(dPairs.upload(pairs, size_t(cellCount) * k));
+        EM2_HIP(dUsed.upload(usedCount, cellCount));
+        EM2_HIP(dWorkspace.allocate(em2::storedPairsWorkspaceBytes(cellCount, chunkRows, geneCount)));
+        EM2_HIP(dExact.allocateFor<double>(size_t(chunkRows) * k));
+        uint32_t inputError = 0;
+        EM2_HIP(em2::prepareStoredPairs(csr.toc.as<uint64_t>(), csr.data.as<em2::CountIn>(), cellCount, geneCount, dWorkspace.p, &inputError, nullptr));
+        if (inputError) return failArgument(who, em2::inputErrorText(inputError));
+        std::vector<double> exact(size_t(chunkRows) * k);
+        for (uint32_t begin = 0; begin < cellCount; begin += chunkRows) {
+            const uint32_t end = uint32_t(std::min<uint64_t>(cellCount, uint64_t(begin) + chunkRows));
+            EM2_HIP(em2::launchStoredPairs(csr.toc.as<uint64_t>(), csr.data.as<em2::CountIn>(), cellCount, geneCount, begin, end,
+                                           dPairs.as<em2::PairOut>(), dUsed.as<uint32_t>(), k, dWorkspace.p, dExact.as<double>(), nullptr));
+            EM2_HIP(hipStreamSynchronize(nullptr));
+            EM2_HIP(dExact.download(exact.data(), size_t(end - begin) * k));
+            if (!em2::analyzeStoredRows(state, hostPairs, usedCount, k, globalCellIds, begin, end, exact.data(), csvDownsample)) {
+                return fail(EM2_ERROR_RUNTIME, std::string(who) + ": Assertion failed: bin < binCount (a stored pair with exact "
+                                               "similarity 1 or not finite; src/ExpressionMatrixLsh.cpp:111)");
+            }
+        }
+    }
+    em2::AnalysisState* finished = state;
+    state = nullptr;
+    if (!em2::analysisEnd(finished, 0, statisticsCsvPath, sum0, sum1, sum2)) {
+        return fail(EM2_ERROR_RUNTIME, std::string(who) + ": cannot open " + statisticsCsvPath);
+    }
+    return EM2_OK;
+}
+
+}  // extern "C"

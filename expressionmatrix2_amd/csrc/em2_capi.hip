@@ -1,19 +1,13 @@
-// em2_capi.hip -- the C ABI of include/em2_lsh.h: argument checking, device memory, kernel launches.
+// em2_capi.hip -- the entry points of include/em2_lsh.h that belong to no topic file or to several: the em2_last_error slot,
+// the version, the hyperplanes, the tables, device selection, the signatures, findSimilarPairs4 to 7 with the sharded phases,
+// the subset call, the cell-graph edges and the label propagation.  (Every other entry point is defined at the end of the
+// file of its topic -- em2_fsp0.hip, em2_gene_graph.hip, em2_ingest.hip, ... -- and all of them report through em2_entry.h.)
 // No algorithmic work happens on the host here except the O(geneCount*lshCount) hyperplane generator and the
 // O(lshCount) lookup tables; there is no CPU fallback for the device paths.
 
-#include "../../include/em2_lsh.h"
-
+#include "em2_entry.h"
 #include "em2_device.h"
-#include "em2_hip_util.h"
-#include "em2_csr.h"
-#include "em2_expression.h"
 #include "em2_scratch.h"
-#include "em2_cluster_graph.h"
-#include "em2_signature_graph.h"
-#include "em2_gene_graph.h"
-#include "em2_layout.h"
-#include "em2_contingency.h"
 #include "em2_tables.h"
 
 #include <algorithm>
@@ -21,58 +15,24 @@
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
-#include <fstream>
 #include <functional>
-#include <limits>
-#include <map>
 #include <thread>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
-#include <random>
 #include <string>
 #include <vector>
 
+using namespace em2::entry;
+
 namespace {
 
-thread_local std::string lastError;
-
-int fail(int code, const std::string& message)
-{
-    lastError = message;
-    return code;
-}
-
-int failHip(hipError_t e, const char* what)
-{
-    return fail(EM2_ERROR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
-
-#define EM2_HIP(call)                                   \
-    do {                                                \
-        hipError_t em2HipError_ = (call);               \
-        if (em2HipError_ != hipSuccess) return failHip(em2HipError_, #call); \
-    } while (0)
+thread_local std::string lastError;          // what em2_last_error returns; em2_entry.h's reporters set it
 
 using em2::alignUp;
 using em2::DeviceBuffer;
 using em2::wordCountOf;
-
-// An argument error under the caller's name: what UploadedCsr::check or em2::inputErrorText says.
-int failArgument(const char* who, const char* text) { return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": " + text); }
-
-// Ends an analysis that does not reach its end (an error return): closes the csv, frees the state.
-struct AnalysisCloser {
-    em2::AnalysisState*& state;
-    ~AnalysisCloser() { if (state) em2::analysisEnd(state, 0, nullptr, nullptr, nullptr, nullptr); }
-};
-
-bool haveDevice()
-{
-    int n = 0;
-    return hipGetDeviceCount(&n) == hipSuccess && n > 0;
-}
 
 // Per-device cache of the lookup tables of em2_tables.h.
 struct CachedTables {
@@ -216,18 +176,16 @@ int hostFindSimilarPairs(const char* who, const uint64_t* signatures, uint32_t c
                          em2_pair* pairs, uint32_t* usedCount, Run run)
 {
     if (cellCount == 0) return EM2_OK;
-    if (!signatures || !usedCount || (!pairs && k)) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
-    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
-    const uint32_t words = wordCountOf(lshCount);
+    if (!signatures || !usedCount || (!pairs && k)) return failNull(who);
+    if (!haveDevice()) return failNoDevice(who);
     DeviceBuffer dSig, dPairs, dUsed;
-    EM2_HIP(dSig.allocate(size_t(cellCount) * words * sizeof(uint64_t)));
-    EM2_HIP(dPairs.allocate(size_t(cellCount) * k * sizeof(em2_pair)));
-    EM2_HIP(dUsed.allocate(size_t(cellCount) * sizeof(uint32_t)));
-    EM2_HIP(hipMemcpy(dSig.p, signatures, size_t(cellCount) * words * sizeof(uint64_t), hipMemcpyHostToDevice));
+    EM2_HIP(dSig.upload(signatures, size_t(cellCount) * wordCountOf(lshCount)));
+    EM2_HIP(dPairs.allocateFor<em2_pair>(size_t(cellCount) * k));
+    EM2_HIP(dUsed.allocateFor<uint32_t>(cellCount));
     const int rc = run(dSig.as<uint64_t>(), dPairs.as<em2_pair>(), dUsed.as<uint32_t>());
     if (rc != EM2_OK) return rc;
-    if (k) EM2_HIP(hipMemcpy(pairs, dPairs.p, size_t(cellCount) * k * sizeof(em2_pair), hipMemcpyDeviceToHost));
-    EM2_HIP(hipMemcpy(usedCount, dUsed.p, size_t(cellCount) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    EM2_HIP(dPairs.download(pairs, size_t(cellCount) * k));
+    EM2_HIP(dUsed.download(usedCount, cellCount));
     return EM2_OK;
 }
 
@@ -484,7 +442,7 @@ int em2_dev_compute_signatures(const uint64_t* d_toc, const em2_count* d_data, u
 {
     if (lshCount == 0 || geneCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dev_compute_signatures: lshCount and geneCount must be positive");
     if (cellCount == 0) return EM2_OK;
-    if (!d_toc || !d_vectors || !d_signatures || !d_workspace) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dev_compute_signatures: null pointer");
+    if (!d_toc || !d_vectors || !d_signatures || !d_workspace) return failNull("em2_dev_compute_signatures");
     if (workspaceBytes < em2_dev_compute_signatures_workspace(cellCount, lshCount)) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dev_compute_signatures: workspace too small");
     hipStream_t s = static_cast<hipStream_t>(stream);
     void* ws = reinterpret_cast<void*>(alignUp(reinterpret_cast<size_t>(d_workspace)));
@@ -561,7 +519,7 @@ int em2_dev_find_similar_pairs4_form_for(uint32_t cellCount, uint32_t rowCount, 
 
 int em2_dev_find_similar_pairs4_last_launch(double* values, uint32_t valueCount)
 {
-    if (!values && valueCount) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dev_find_similar_pairs4_last_launch: null pointer");
+    if (!values && valueCount) return failNull("em2_dev_find_similar_pairs4_last_launch");
     const em2::Fsp4LaunchInfo info = em2::fsp4LastLaunchInfo();
     const double all[9] = {double(info.form), info.scanKernelMs, info.waveColumnSteps, info.inboxEntries, info.segments, info.fullRowCells,
                            info.matrixPairs, info.matrixKernelMs, info.matrixClockGHz};
@@ -574,7 +532,7 @@ void em2_dev_release_scratch(void) { em2::releaseScratch(); }
 
 int em2_dev_find_similar_pairs5_last_launch(double* values, uint32_t valueCount)
 {
-    if (!values && valueCount) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dev_find_similar_pairs5_last_launch: null pointer");
+    if (!values && valueCount) return failNull("em2_dev_find_similar_pairs5_last_launch");
     const em2::Fsp5LaunchInfo info = em2::fsp5LastLaunchInfo();
     const double all[12] = {info.gatheredCandidates, info.cells, info.sliceCount, info.batches, info.filterMs, info.selectMs,
                             info.distinctCandidates, info.unionForm, info.unionPasses, info.unionIdsPerPass, info.filterForm,
@@ -591,7 +549,7 @@ int em2_dev_find_similar_pairs4(const uint64_t* d_signatures, uint32_t cellCount
     if (lshCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dev_find_similar_pairs4: lshCount must be positive");
     if (rowBegin > rowEnd || rowEnd > cellCount) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dev_find_similar_pairs4: bad row range");
     if (rowBegin == rowEnd) return EM2_OK;
-    if (!d_signatures || !d_usedCount || (!d_pairs && k) || !d_workspace) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dev_find_similar_pairs4: null pointer");
+    if (!d_signatures || !d_usedCount || (!d_pairs && k) || !d_workspace) return failNull("em2_dev_find_similar_pairs4");
     const uint32_t rows = rowEnd - rowBegin;
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (k == 0) {       // keepBest(v, 0) empties every list (src/heap.hpp:116-126)
@@ -638,7 +596,7 @@ static size_t shardedRepackBytes(uint32_t cellCount, uint32_t lshCount)
 int em2_dev_fsp4_sharded_plan(uint32_t cellCount, uint32_t lshCount, uint32_t k, uint32_t rank, uint32_t world,
                               uint64_t* values, uint32_t valueCount)
 {
-    if (!values && valueCount) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dev_fsp4_sharded_plan: null pointer");
+    if (!values && valueCount) return failNull("em2_dev_fsp4_sharded_plan");
     uint64_t all[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     const uint32_t padded = lshCount ? em2::paddedDwords(lshCount) : 0;
     if (padded != 0 && k != 0 && k <= em2::fsp4MaxK() && world >= 1 && rank < world) {
@@ -669,7 +627,7 @@ int em2_dev_fsp4_sharded_phase(int phase, const uint64_t* d_signatures, uint32_t
                                uint32_t* d_usedCount, void* d_workspace, size_t workspaceBytes, uint64_t gatheredCount,
                                void* stream)
 {
-    if (!d_signatures || !d_pairs || !d_usedCount || !d_workspace) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dev_fsp4_sharded_phase: null pointer");
+    if (!d_signatures || !d_pairs || !d_usedCount || !d_workspace) return failNull("em2_dev_fsp4_sharded_phase");
     if (phase < 0 || phase > 4) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dev_fsp4_sharded_phase: phase must be 0..4");
     uint64_t values[2] = {0, 0};
     em2_dev_fsp4_sharded_plan(cellCount, lshCount, k, rank, world, values, 2);
@@ -698,7 +656,7 @@ int em2_dev_fsp4_sharded_phase(int phase, const uint64_t* d_signatures, uint32_t
 int em2_dev_fsp4_sharded_status(uint32_t cellCount, uint32_t k, uint32_t rank, uint32_t world, const void* d_workspace,
                                 void* stream, uint64_t* usedEntries, uint32_t* overflow)
 {
-    if (!d_workspace || !usedEntries || !overflow) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dev_fsp4_sharded_status: null pointer");
+    if (!d_workspace || !usedEntries || !overflow) return failNull("em2_dev_fsp4_sharded_status");
     const em2::Fsp4ShardPlan plan = em2::fsp4ShardPlan(cellCount, k, rank, world);
     if (!plan.eligible) return fail(EM2_ERROR_UNSUPPORTED, "em2_dev_fsp4_sharded_status: this shape is not eligible for the sharded symmetric scan");
     uint32_t error = 0;
@@ -728,12 +686,12 @@ static int prepareRows(const char* who, const uint64_t* d_signatures, uint32_t c
                        const uint32_t* d_usedCount, em2::DeviceTables& tables, bool& empty)
 {
     empty = false;
-    if (rowBegin > rowEnd || rowEnd > cellCount) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": bad row range");
+    if (rowBegin > rowEnd || rowEnd > cellCount) return failArgument(who, "bad row range");
     if (rowBegin == rowEnd) {
         empty = true;
         return EM2_OK;
     }
-    if (!d_signatures || !d_usedCount || (!d_pairs && k)) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+    if (!d_signatures || !d_usedCount || (!d_pairs && k)) return failNull(who);
     return getDeviceTables(lshCount, similarityThreshold, tables);
 }
 
@@ -760,13 +718,13 @@ int em2_dev_find_similar_pairs5(const uint64_t* d_signatures, uint32_t cellCount
 static int prepareFsp6(const char* who, uint32_t cellCount, uint32_t lshCount, uint32_t permutationCount, uint32_t searchCount,
                        uint32_t permutedBitCount)
 {
-    if (lshCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": lshCount must be positive");
+    if (lshCount == 0) return failArgument(who, "lshCount must be positive");
     if (permutedBitCount > lshCount) {
         return fail(EM2_ERROR_RUNTIME, "Argument permutationStoreBitCount " + std::to_string(permutedBitCount) +
                                            " exceeds number of signature bits " + std::to_string(lshCount));
     }
     // the reference computes ((0-1) >> 6) + 1 = 2^58 words here (:920) and dies allocating them
-    if (permutedBitCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": permutedBitCount must be positive");
+    if (permutedBitCount == 0) return failArgument(who, "permutedBitCount must be positive");
     if (permutationCount > em2::fsp6MaxPermutations()) {
         return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": permutationCount above " + std::to_string(em2::fsp6MaxPermutations()) +
                                                " is not supported");
@@ -805,8 +763,8 @@ int em2_dev_find_similar_pairs6(const uint64_t* d_signatures, uint32_t cellCount
 static int prepareFsp7(const char* who, uint32_t lshCount, double similarityThreshold, const int32_t* sliceLengths,
                        uint32_t sliceLengthCount, uint32_t k, uint32_t log2BucketCount, uint64_t& mismatchThreshold)
 {
-    if (lshCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": lshCount must be positive");
-    if (sliceLengthCount && !sliceLengths) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null sliceLengths");
+    if (lshCount == 0) return failArgument(who, "lshCount must be positive");
+    if (sliceLengthCount && !sliceLengths) return failArgument(who, "null sliceLengths");
     for (uint32_t i = 1; i < sliceLengthCount; i++) {
         if (sliceLengths[i] >= sliceLengths[i - 1]) return fail(EM2_ERROR_RUNTIME, "The slice lengths are not in decreasing order.");
     }
@@ -815,7 +773,7 @@ static int prepareFsp7(const char* who, uint32_t lshCount, double similarityThre
     }
     for (uint32_t i = 0; i < sliceLengthCount; i++) {
         // the reference divides lshBitCount by the slice length (:760): zero is a crash there, negatives nonsense
-        if (sliceLengths[i] < 1) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": slice lengths must be positive");
+        if (sliceLengths[i] < 1) return failArgument(who, "slice lengths must be positive");
     }
     if (log2BucketCount > 40) return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": log2BucketCount above 40 is not supported");
     for (uint32_t i = 0; i < sliceLengthCount; i++) {
@@ -901,7 +859,7 @@ int em2_dev_subset_count(const uint64_t* d_globalToc, const em2_count* d_globalD
                          uint32_t cellCount, const uint32_t* d_geneLocalIds, uint32_t globalGeneCount, uint64_t* d_toc,
                          void* d_workspace, size_t workspaceBytes, void* stream)
 {
-    if (!d_globalToc || !d_geneLocalIds || !d_toc || !d_workspace) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dev_subset_count: null pointer");
+    if (!d_globalToc || !d_geneLocalIds || !d_toc || !d_workspace) return failNull("em2_dev_subset_count");
     if (workspaceBytes < em2::subsetWorkspaceBytes(cellCount)) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dev_subset_count: workspace too small");
     EM2_HIP(em2::launchSubsetCount(d_globalToc, reinterpret_cast<const em2::CountIn*>(d_globalData), d_cellIds, cellCount,
                                    d_geneLocalIds, globalGeneCount, d_toc, d_workspace, workspaceBytes,
@@ -913,7 +871,7 @@ int em2_dev_subset_fill(const uint64_t* d_globalToc, const em2_count* d_globalDa
                         uint32_t cellCount, const uint32_t* d_geneLocalIds, uint32_t globalGeneCount, const uint64_t* d_toc,
                         em2_count* d_data, void* stream)
 {
-    if (!d_globalToc || !d_geneLocalIds || !d_toc) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dev_subset_fill: null pointer");
+    if (!d_globalToc || !d_geneLocalIds || !d_toc) return failNull("em2_dev_subset_fill");
     EM2_HIP(em2::launchSubsetFill(d_globalToc, reinterpret_cast<const em2::CountIn*>(d_globalData), d_cellIds, cellCount,
                                   d_geneLocalIds, globalGeneCount, d_toc, reinterpret_cast<em2::CountIn*>(d_data),
                                   static_cast<hipStream_t>(stream)));
@@ -934,7 +892,7 @@ int em2_subset_find_similar_pairs4(const uint64_t* globalToc, const em2_count* g
                                    uint64_t* signatures, uint32_t k, double similarityThreshold, em2_pair* pairs,
                                    uint32_t* usedCount)
 {
-    if (!vectors && cellCount && lshCount && geneCount) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_subset_find_similar_pairs4: null pointer");
+    if (!vectors && cellCount && lshCount && geneCount) return failNull("em2_subset_find_similar_pairs4");
     return subsetFindSimilarPairs4(globalToc, globalData, globalCellCount, cellIds, cellCount, geneLocalIds, globalGeneCount, geneCount,
                                    vectors, nullptr, nullptr, lshCount, signatures, k, similarityThreshold, pairs, usedCount);
 }
@@ -949,7 +907,7 @@ int em2_internal_subset_find_similar_pairs4(const uint64_t* globalToc, const em2
                                             uint64_t* signatures, uint32_t k, double similarityThreshold, em2_pair* pairs,
                                             uint32_t* usedCount)
 {
-    if (!vectorsWhenNeeded) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_internal_subset_find_similar_pairs4: null pointer");
+    if (!vectorsWhenNeeded) return failNull("em2_internal_subset_find_similar_pairs4");
     return subsetFindSimilarPairs4(globalToc, globalData, globalCellCount, cellIds, cellCount, geneLocalIds, globalGeneCount, geneCount,
                                    nullptr, vectorsWhenNeeded, vectorsContext, lshCount, signatures, k, similarityThreshold, pairs, usedCount);
 }
@@ -963,11 +921,11 @@ static int subsetFindSimilarPairs4(const uint64_t* globalToc, const em2_count* g
 {
     if (lshCount == 0 || geneCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_subset_find_similar_pairs4: lshCount and geneCount must be positive");
     if (cellCount == 0) return EM2_OK;
-    if (!globalToc || !geneLocalIds) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_subset_find_similar_pairs4: null pointer");
+    if (!globalToc || !geneLocalIds) return failNull("em2_subset_find_similar_pairs4");
     const bool wantPairs = usedCount != nullptr;
     if (wantPairs && !pairs && k) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_subset_find_similar_pairs4: null pairs");
     if (!wantPairs && !signatures) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_subset_find_similar_pairs4: nothing to compute");
-    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, "em2_subset_find_similar_pairs4: no HIP device is visible (this library has no CPU path)");
+    if (!haveDevice()) return failNoDevice("em2_subset_find_similar_pairs4");
     const uint32_t padded = em2::paddedDwords(lshCount);
     if (wantPairs && k) {
         if (padded == 0) return fail(EM2_ERROR_UNSUPPORTED, "em2_subset_find_similar_pairs4: lshCount above 4096 is not supported");
@@ -1136,21 +1094,18 @@ int em2_compute_signatures(const uint64_t* toc, const em2_count* data, uint32_t 
 {
     if (lshCount == 0 || geneCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_compute_signatures: lshCount and geneCount must be positive");
     if (cellCount == 0) return EM2_OK;
-    if (!toc || !vectors || !signatures) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_compute_signatures: null pointer");
-    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, "em2_compute_signatures: no HIP device is visible (this library has no CPU path)");
+    if (!toc || !vectors || !signatures) return failNull("em2_compute_signatures");
+    if (!haveDevice()) return failNoDevice("em2_compute_signatures");
     const uint64_t nnz = toc[cellCount];
     if (nnz && !data) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_compute_signatures: null data");
-    const uint32_t words = wordCountOf(lshCount);
+    const size_t signatureWords = size_t(cellCount) * wordCountOf(lshCount);
     DeviceBuffer dToc, dData, dVectors, dSig, dWs, dAux;
     const size_t wsBytes = em2_dev_compute_signatures_workspace(cellCount, lshCount);
-    EM2_HIP(dToc.allocate((size_t(cellCount) + 1) * sizeof(uint64_t)));
-    EM2_HIP(dData.allocate(nnz * sizeof(em2_count)));
-    EM2_HIP(dVectors.allocate(size_t(geneCount) * lshCount * sizeof(double)));
-    EM2_HIP(dSig.allocate(size_t(cellCount) * words * sizeof(uint64_t)));
+    EM2_HIP(dToc.upload(toc, size_t(cellCount) + 1));
+    EM2_HIP(dData.upload(data, nnz));
+    EM2_HIP(dVectors.upload(vectors, size_t(geneCount) * lshCount));
+    EM2_HIP(dSig.allocateFor<uint64_t>(signatureWords));
     EM2_HIP(dWs.allocate(wsBytes));
-    EM2_HIP(hipMemcpy(dToc.p, toc, (size_t(cellCount) + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
-    if (nnz) EM2_HIP(hipMemcpy(dData.p, data, nnz * sizeof(em2_count), hipMemcpyHostToDevice));
-    EM2_HIP(hipMemcpy(dVectors.p, vectors, size_t(geneCount) * lshCount * sizeof(double), hipMemcpyHostToDevice));
     void* aux = nullptr;
     if (lshCount % 4u == 0u) {          // (other widths: the exact arithmetic only)
         EM2_HIP(dAux.allocate(em2_dev_vector_aux_bytes(geneCount, lshCount)));
@@ -1163,7 +1118,7 @@ int em2_compute_signatures(const uint64_t* toc, const em2_count* data, uint32_t 
                                               dWs.p, wsBytes, nullptr);
     if (rc != EM2_OK) return rc;
     EM2_HIP(hipStreamSynchronize(nullptr));
-    EM2_HIP(hipMemcpy(signatures, dSig.p, size_t(cellCount) * words * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    EM2_HIP(dSig.download(signatures, signatureWords));
     return EM2_OK;
 }
 
@@ -1210,16 +1165,16 @@ static int cellGraphEdges(const char* what, bool pairsOnDevice, const em2_pair* 
                           uint32_t maxConnectivity, uint32_t* edgeVertex0, uint32_t* edgeVertex1, float* edgeSimilarity,
                           uint64_t* edgeCount)
 {
-    if (!edgeCount) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(what) + ": null edgeCount");
+    if (!edgeCount) return failArgument(what, "null edgeCount");
     *edgeCount = 0;
     // CellGraph.cpp:101 tests pairs.size() == maxConnectivity after a push_back, so 0 never matches and means
     // "no limit"; a vertex never selects more than the k stored pairs either way.
     if (maxConnectivity == 0 || maxConnectivity > k) maxConnectivity = k;
     if (graphCellCount == 0 || maxConnectivity == 0) return EM2_OK;
     if (!usedCount || !similarPairsCellSet || !graphCellSet || (!pairs && k && similarPairsCellCount) || !edgeVertex0 || !edgeVertex1 || !edgeSimilarity) {
-        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(what) + ": null pointer");
+        return failNull(what);
     }
-    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, std::string(what) + ": no HIP device is visible (this library has no CPU path)");
+    if (!haveDevice()) return failNoDevice(what);
     for (uint32_t i = 1; i < similarPairsCellCount; i++) {
         if (similarPairsCellSet[i - 1] > similarPairsCellSet[i]) return fail(EM2_ERROR_RUNTIME, std::string(what) + ": the SimilarPairs cell set is not sorted.");
     }
@@ -1234,13 +1189,13 @@ static int cellGraphEdges(const char* what, bool pairsOnDevice, const em2_pair* 
     std::vector<uint32_t> sortedIds(graphCellCount);
     for (uint32_t i = 0; i < graphCellCount; i++) sortedIds[i] = graphCellSet[order[i]];
     for (uint32_t i = 1; i < graphCellCount; i++) {
-        if (sortedIds[i] == sortedIds[i - 1]) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(what) + ": duplicate cell id in the graph cell set");
+        if (sortedIds[i] == sortedIds[i - 1]) return failArgument(what, "duplicate cell id in the graph cell set");
     }
     const size_t slots = size_t(graphCellCount) * maxConnectivity;
     DeviceBuffer dPairs, dUsed, dSp, dGraph, dSorted, dOrder, dE0, dE1, dEs;
     if (!pairsOnDevice) {
-        EM2_HIP(dPairs.allocate(size_t(similarPairsCellCount) * k * sizeof(em2_pair)));
-        EM2_HIP(dUsed.allocate(size_t(similarPairsCellCount) * sizeof(uint32_t)));
+        EM2_HIP(dPairs.upload(pairs, size_t(similarPairsCellCount) * k));
+        EM2_HIP(dUsed.upload(usedCount, similarPairsCellCount));
     }
     // The three output arrays may be host or device memory (documented capacity graphCellCount * maxConnectivity): device
     // arrays are written in place, host arrays through device buffers.
@@ -1254,9 +1209,9 @@ static int cellGraphEdges(const char* what, bool pairsOnDevice, const em2_pair* 
     };
     const bool outputsOnDevice = onDevice(edgeVertex0) && onDevice(edgeVertex1) && onDevice(edgeSimilarity);
     if (!outputsOnDevice) {
-        EM2_HIP(dE0.allocate(slots * sizeof(uint32_t)));
-        EM2_HIP(dE1.allocate(slots * sizeof(uint32_t)));
-        EM2_HIP(dEs.allocate(slots * sizeof(float)));
+        EM2_HIP(dE0.allocateFor<uint32_t>(slots));
+        EM2_HIP(dE1.allocateFor<uint32_t>(slots));
+        EM2_HIP(dEs.allocateFor<float>(slots));
     }
     uint32_t* out0 = outputsOnDevice ? edgeVertex0 : dE0.as<uint32_t>();
     uint32_t* out1 = outputsOnDevice ? edgeVertex1 : dE1.as<uint32_t>();
@@ -1265,42 +1220,28 @@ static int cellGraphEdges(const char* what, bool pairsOnDevice, const em2_pair* 
     const bool spConsecutive = similarPairsCellCount && similarPairsCellSet[similarPairsCellCount - 1] - similarPairsCellSet[0] == similarPairsCellCount - 1 &&
                                std::adjacent_find(similarPairsCellSet, similarPairsCellSet + similarPairsCellCount) == similarPairsCellSet + similarPairsCellCount;
     const bool graphConsecutive = sortedIds[graphCellCount - 1] - sortedIds[0] == graphCellCount - 1;
-    if (similarPairsCellCount) {
-        if (!pairsOnDevice) {
-            if (k) EM2_HIP(hipMemcpy(dPairs.p, pairs, size_t(similarPairsCellCount) * k * sizeof(em2_pair), hipMemcpyHostToDevice));
-            EM2_HIP(hipMemcpy(dUsed.p, usedCount, size_t(similarPairsCellCount) * sizeof(uint32_t), hipMemcpyHostToDevice));
-        }
-    }
     const em2::PairOut* devicePairs = pairsOnDevice ? reinterpret_cast<const em2::PairOut*>(pairs) : dPairs.as<em2::PairOut>();
     const uint32_t* deviceUsed = pairsOnDevice ? usedCount : dUsed.as<uint32_t>();
     // The cell sets go to the device unless they are arithmetic there: consecutive ids (the SimilarPairs set), consecutive ids in
     // ascending order (the graph's: AllCells and every stored set without gaps) -- three 4 MB uploads and four allocations less
     // at a million cells.
     const bool graphArithmetic = graphConsecutive && graphWasSorted;
-    if (!spConsecutive && similarPairsCellCount) {
-        EM2_HIP(dSp.allocate(size_t(similarPairsCellCount) * sizeof(uint32_t)));
-        EM2_HIP(hipMemcpy(dSp.p, similarPairsCellSet, size_t(similarPairsCellCount) * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
+    if (!spConsecutive && similarPairsCellCount) EM2_HIP(dSp.upload(similarPairsCellSet, similarPairsCellCount));
     if (!graphArithmetic) {
-        EM2_HIP(dGraph.allocate(size_t(graphCellCount) * sizeof(uint32_t)));
-        EM2_HIP(dOrder.allocate(size_t(graphCellCount) * sizeof(uint32_t)));
-        EM2_HIP(hipMemcpy(dGraph.p, graphCellSet, size_t(graphCellCount) * sizeof(uint32_t), hipMemcpyHostToDevice));
-        EM2_HIP(hipMemcpy(dOrder.p, order.data(), size_t(graphCellCount) * sizeof(uint32_t), hipMemcpyHostToDevice));
+        EM2_HIP(dGraph.upload(graphCellSet, graphCellCount));
+        EM2_HIP(dOrder.upload(order.data(), graphCellCount));
     }
-    if (!graphConsecutive) {
-        EM2_HIP(dSorted.allocate(size_t(graphCellCount) * sizeof(uint32_t)));
-        EM2_HIP(hipMemcpy(dSorted.p, sortedIds.data(), size_t(graphCellCount) * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
+    if (!graphConsecutive) EM2_HIP(dSorted.upload(sortedIds.data(), graphCellCount));
     uint64_t count = 0;
     EM2_HIP(em2::runCellGraphEdges(devicePairs, deviceUsed, similarPairsCellCount, k, spConsecutive ? nullptr : dSp.as<uint32_t>(),
                                    graphArithmetic ? nullptr : dGraph.as<uint32_t>(), graphConsecutive ? nullptr : dSorted.as<uint32_t>(),
                                    graphArithmetic ? nullptr : dOrder.as<uint32_t>(), graphCellCount,
                                    similarityThreshold, maxConnectivity, out0, out1, outSimilarity, &count, nullptr, spConsecutive,
                                    similarPairsCellCount ? similarPairsCellSet[0] : 0u, graphConsecutive, sortedIds[0]));
-    if (count && !outputsOnDevice) {
-        EM2_HIP(hipMemcpy(edgeVertex0, dE0.p, count * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        EM2_HIP(hipMemcpy(edgeVertex1, dE1.p, count * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        EM2_HIP(hipMemcpy(edgeSimilarity, dEs.p, count * sizeof(float), hipMemcpyDeviceToHost));
+    if (!outputsOnDevice) {
+        EM2_HIP(dE0.download(edgeVertex0, count));
+        EM2_HIP(dE1.download(edgeVertex1, count));
+        EM2_HIP(dEs.download(edgeSimilarity, count));
     }
     *edgeCount = count;
     return EM2_OK;
@@ -1325,557 +1266,6 @@ int em2_dev_cell_graph_edges(const em2_pair* d_pairs, const uint32_t* d_usedCoun
                           edgeCount);
 }
 
-int em2_analyze_lsh(const uint64_t* toc, const em2_count* data, uint32_t cellCount, uint32_t geneCount,
-                    const uint64_t* signatures, uint32_t lshCount, const uint32_t* globalCellIds, uint32_t seed,
-                    double csvDownsample, const char* pairsCsvPath, const char* statisticsCsvPath,
-                    uint64_t* sum0, double* sum1, double* sum2, double* exactSimilarity, double* lshSimilarity)
-{
-    if (lshCount == 0 || geneCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_analyze_lsh: lshCount and geneCount must be positive");
-    if (cellCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_analyze_lsh: the cell set is empty");
-    if (!toc || !signatures || !globalCellIds || !pairsCsvPath) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_analyze_lsh: null pointer");
-    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, "em2_analyze_lsh: no HIP device is visible (this library has no CPU path)");
-    const uint64_t nnz = toc[cellCount];
-    if (nnz && !data) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_analyze_lsh: null data");
-    for (uint64_t i = 0; i < nnz; ++i) {
-        if (data[i].gene >= geneCount) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_analyze_lsh: a local gene id is not below geneCount");
-    }
-    const uint32_t words = wordCountOf(lshCount);
-
-    // ExpressionMatrixSubset::computeSums (src/ExpressionMatrixSubset.cpp:47-58)
-    std::vector<double> sums(2 * size_t(cellCount), 0.);
-    for (uint32_t c = 0; c < cellCount; ++c) {
-        double s1 = 0., s2 = 0.;
-        for (uint64_t i = toc[c]; i < toc[c + 1]; ++i) {
-            const float count = data[i].count;
-            s1 += count;
-            s2 += count * count;
-        }
-        sums[2 * size_t(c)] = s1;
-        sums[2 * size_t(c) + 1] = s2;
-    }
-
-    em2::AnalysisState* state = em2::analyzeLshBegin(lshCount, seed, pairsCsvPath);
-    if (!state) return fail(EM2_ERROR_RUNTIME, std::string("em2_analyze_lsh: cannot open ") + pairsCsvPath);
-    AnalysisCloser closer{state};
-
-    // rows in chunks of about 16M pairs: 192 MB of device output per chunk, walked by the host in order
-    const uint64_t chunkPairs = 1ull << 24;
-    const auto chunkEnd = [&](uint32_t begin, uint64_t& pairs) {
-        uint32_t end = begin;
-        for (pairs = 0; end + 1 < cellCount && (end == begin || pairs + (cellCount - 1 - end) <= chunkPairs);) pairs += cellCount - 1 - end++;
-        return end;
-    };
-    uint32_t maxRows = 0;
-    uint64_t maxPairs = 0, pairs = 0;
-    for (uint32_t begin = 0; begin + 1 < cellCount;) {
-        const uint32_t end = chunkEnd(begin, pairs);
-        if (end - begin > maxRows) maxRows = end - begin;
-        if (pairs > maxPairs) maxPairs = pairs;
-        begin = end;
-    }
-    em2::UploadedCsr csr;
-    (void)csr.check(toc, reinterpret_cast<const em2::CountIn*>(data), cellCount, false);      // (null data was refused above)
-    EM2_HIP(csr.upload());
-    DeviceBuffer dSig, dProducts, dMismatches, dScratch;
-    EM2_HIP(dSig.allocate(size_t(cellCount) * words * sizeof(uint64_t)));
-    EM2_HIP(dProducts.allocate(maxPairs * sizeof(double)));
-    EM2_HIP(dMismatches.allocate(maxPairs * sizeof(uint32_t)));
-    EM2_HIP(dScratch.allocate(em2::analyzeScratchBytes(geneCount, maxRows)));
-    EM2_HIP(hipMemcpy(dSig.p, signatures, size_t(cellCount) * words * sizeof(uint64_t), hipMemcpyHostToDevice));
-    std::vector<double> products(maxPairs);
-    std::vector<uint32_t> mismatches(maxPairs);
-    uint64_t done = 0;
-    for (uint32_t begin = 0; begin + 1 < cellCount;) {
-        const uint32_t end = chunkEnd(begin, pairs);
-        EM2_HIP(em2::launchAnalyzePairs(csr.toc.as<uint64_t>(), csr.data.as<em2::CountIn>(), cellCount, geneCount, dSig.as<uint64_t>(), words,
-                                        begin, end, dScratch.p, dProducts.as<double>(), dMismatches.as<uint32_t>(), nullptr));
-        EM2_HIP(hipStreamSynchronize(nullptr));
-        EM2_HIP(hipMemcpy(products.data(), dProducts.p, pairs * sizeof(double), hipMemcpyDeviceToHost));
-        EM2_HIP(hipMemcpy(mismatches.data(), dMismatches.p, pairs * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        if (!em2::analyzeLshRows(state, sums.data(), cellCount, geneCount, globalCellIds, begin, end, products.data(), mismatches.data(),
-                                 csvDownsample, exactSimilarity ? exactSimilarity + done : nullptr,
-                                 lshSimilarity ? lshSimilarity + done : nullptr)) {
-            return fail(EM2_ERROR_RUNTIME, "em2_analyze_lsh: Assertion failed: bin < binCount (a pair of cells with exact similarity 1, or a "
-                                           "cell without variance; src/ExpressionMatrixLsh.cpp:1322)");
-        }
-        done += pairs;
-        begin = end;
-    }
-    em2::AnalysisState* finished = state;
-    state = nullptr;
-    if (!em2::analysisEnd(finished, lshCount, statisticsCsvPath, sum0, sum1, sum2)) {
-        return fail(EM2_ERROR_RUNTIME, std::string("em2_analyze_lsh: cannot write ") + (statisticsCsvPath ? statisticsCsvPath : ""));
-    }
-    return EM2_OK;
-}
-
-
-
-// ---- findSimilarPairs0 (em2_fsp0.hip) ----
-
-// The checks of findSimilarPairs0 that need no device.  CZI_ASSERT(similarityThreshold <= 1.)
-// (src/ExpressionMatrixFindSimilarPairs.cpp:26) comes first in the reference.
-static int prepareFsp0(const char* who, uint32_t cellCount, uint32_t geneCount, uint32_t k, double similarityThreshold)
-{
-    if (!(similarityThreshold <= 1.)) return fail(EM2_ERROR_RUNTIME, std::string(who) + ": Assertion failed: similarityThreshold <= 1.");
-    if (geneCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": geneCount must be positive");
-    if (!em2::fsp0Supported(cellCount, k)) {
-        return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": more than " + std::to_string(em2::fsp0MaxSlots()) +
-                                               " stored pairs per cell (min(k, cellCount-1)) is not supported");
-    }
-    return EM2_OK;
-}
-
-size_t em2_dev_find_similar_pairs0_workspace(uint32_t cellCount, uint32_t rowCount, uint32_t geneCount, uint32_t k)
-{
-    return em2::fsp0WorkspaceBytes(cellCount, rowCount, geneCount, k);
-}
-
-int em2_dev_find_similar_pairs0(const uint64_t* d_toc, const em2_count* d_data, uint32_t cellCount, uint32_t geneCount,
-                                uint32_t rowBegin, uint32_t rowEnd, uint32_t k, double similarityThreshold, em2_pair* d_pairs,
-                                uint32_t* d_usedCount, uint32_t* d_lowestSimilarityIndex, float* d_lowestSimilarity,
-                                void* d_workspace, size_t workspaceBytes, void* stream)
-{
-    const char* who = "em2_dev_find_similar_pairs0";
-    const int prc = prepareFsp0(who, cellCount, geneCount, k, similarityThreshold);
-    if (prc != EM2_OK) return prc;
-    if (rowBegin > rowEnd || rowEnd > cellCount) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": bad row range");
-    if (rowBegin == rowEnd) return EM2_OK;
-    if (!d_toc || !d_usedCount || !d_lowestSimilarityIndex || !d_lowestSimilarity || (!d_pairs && k) || !d_workspace) {
-        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
-    }
-    if (workspaceBytes < em2::fsp0WorkspaceBytes(cellCount, rowEnd - rowBegin, geneCount, k)) {
-        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": workspace too small");
-    }
-    uint32_t inputError = 0;
-    EM2_HIP(em2::runFsp0(d_toc, reinterpret_cast<const em2::CountIn*>(d_data), cellCount, geneCount, rowBegin, rowEnd, k,
-                         similarityThreshold, reinterpret_cast<em2::PairOut*>(d_pairs), d_usedCount, d_lowestSimilarityIndex,
-                         d_lowestSimilarity, d_workspace, &inputError, static_cast<hipStream_t>(stream)));
-    if (inputError) return failArgument(who, em2::inputErrorText(inputError));
-    return EM2_OK;
-}
-
-int em2_find_similar_pairs0(const uint64_t* toc, const em2_count* data, uint32_t cellCount, uint32_t geneCount, uint32_t k,
-                            double similarityThreshold, em2_pair* pairs, uint32_t* usedCount, uint32_t* lowestSimilarityIndex,
-                            float* lowestSimilarity)
-{
-    const char* who = "em2_find_similar_pairs0";
-    const int prc = prepareFsp0(who, cellCount, geneCount, k, similarityThreshold);
-    if (prc != EM2_OK) return prc;
-    if (cellCount == 0) return EM2_OK;
-    if (!toc || !usedCount || !lowestSimilarityIndex || !lowestSimilarity || (!pairs && k)) {
-        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
-    }
-    em2::UploadedCsr csr;
-    if (const char* error = csr.check(toc, reinterpret_cast<const em2::CountIn*>(data), cellCount)) return failArgument(who, error);
-    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
-    EM2_HIP(csr.upload());                     // (the device checks the gene ids before any kernel indexes with them)
-    DeviceBuffer dPairs, dUsed, dIndex, dLowest, dWorkspace;
-    const size_t workspaceBytes = em2::fsp0WorkspaceBytes(cellCount, cellCount, geneCount, k);
-    EM2_HIP(dPairs.allocate(size_t(cellCount) * k * sizeof(em2_pair)));
-    EM2_HIP(dUsed.allocate(size_t(cellCount) * sizeof(uint32_t)));
-    EM2_HIP(dIndex.allocate(size_t(cellCount) * sizeof(uint32_t)));
-    EM2_HIP(dLowest.allocate(size_t(cellCount) * sizeof(float)));
-    EM2_HIP(dWorkspace.allocate(workspaceBytes));
-    const int rc = em2_dev_find_similar_pairs0(csr.toc.as<uint64_t>(), csr.data.as<em2_count>(), cellCount, geneCount, 0, cellCount, k,
-                                               similarityThreshold, dPairs.as<em2_pair>(), dUsed.as<uint32_t>(), dIndex.as<uint32_t>(),
-                                               dLowest.as<float>(), dWorkspace.p, workspaceBytes, nullptr);
-    if (rc != EM2_OK) return rc;
-    if (k) EM2_HIP(hipMemcpy(pairs, dPairs.p, size_t(cellCount) * k * sizeof(em2_pair), hipMemcpyDeviceToHost));
-    EM2_HIP(hipMemcpy(usedCount, dUsed.p, size_t(cellCount) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    EM2_HIP(hipMemcpy(lowestSimilarityIndex, dIndex.p, size_t(cellCount) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    EM2_HIP(hipMemcpy(lowestSimilarity, dLowest.p, size_t(cellCount) * sizeof(float), hipMemcpyDeviceToHost));
-    return EM2_OK;
-}
-
-
-// ---- findSimilarGenePairs0 (em2_gene_pairs.hip) ----
-
-// std::sort by similarity alone, per gene (em2_host.cpp).
-extern "C" void em2_internal_sort_gene_pairs(em2_pair* pairs, const uint32_t* usedCount, uint32_t geneCount, uint32_t k);
-
-static const uint32_t kAllSimilaritiesMaxGenes = 8192;          // allSimilarities: 256 MB of floats at most
-
-void em2_set_gene_pairs_buffer_mb(uint64_t megabytes) { em2::setGenePairsBudgetMegabytes(megabytes); }
-
-int em2_find_similar_gene_pairs0(const uint64_t* toc, const em2_count* data, uint32_t cellCount, uint32_t geneCount,
-                                 int normalizationMethod, uint32_t k, double similarityThreshold, em2_pair* pairs,
-                                 uint32_t* usedCount, float* allSimilarities)
-{
-    const char* who = "em2_find_similar_gene_pairs0";
-    if (normalizationMethod < 0 || normalizationMethod > 2) {
-        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": invalid normalization method (0 none, 1 L1, 2 L2)");
-    }
-    if (geneCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": geneCount must be positive");
-    if (cellCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": cellCount must be positive");
-    if (!toc || !usedCount || (!pairs && k)) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
-    if (allSimilarities && geneCount > kAllSimilaritiesMaxGenes) {
-        return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": allSimilarities is an aid for at most " +
-                                               std::to_string(kAllSimilaritiesMaxGenes) + " genes");
-    }
-    em2::UploadedCsr csr;
-    if (const char* error = csr.check(toc, reinterpret_cast<const em2::CountIn*>(data), cellCount)) return failArgument(who, error);
-    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
-    EM2_HIP(csr.upload());                     // (the device checks the gene ids before any kernel indexes with them)
-    const size_t allBytes = allSimilarities ? size_t(geneCount) * geneCount * sizeof(float) : 0;
-    DeviceBuffer dPairs, dUsed, dAll;
-    EM2_HIP(dPairs.allocate(size_t(geneCount) * k * sizeof(em2_pair)));
-    EM2_HIP(dUsed.allocate(size_t(geneCount) * sizeof(uint32_t)));
-    if (allSimilarities) {
-        EM2_HIP(dAll.allocate(allBytes));
-        EM2_HIP(hipMemset(dAll.p, 0, allBytes));                                   // (the diagonal: the reference computes none)
-    }
-    em2::GenePairsStatus status;
-    EM2_HIP(em2::runGenePairs(csr.toc.as<uint64_t>(), csr.data.as<em2::CountIn>(), cellCount, geneCount, normalizationMethod, k,
-                              similarityThreshold, dPairs.as<em2::PairOut>(), dUsed.as<uint32_t>(), dAll.as<float>(), &status, nullptr));
-    if (status.inputError) return failArgument(who, em2::inputErrorText(status.inputError));
-    if (status.overflow) {
-        return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": " + std::to_string(status.records) + " candidate records (" +
-                                               std::to_string(status.records * em2::kGenePairsBytesPerRecord >> 20) +
-                                               " MB with the sort's second buffer) fit neither the candidate buffer (" +
-                                               std::to_string(em2::genePairsBudgetRecords() * em2::kGenePairsBytesPerRecord >> 20) +
-                                               " MB, em2_set_gene_pairs_buffer_mb; the Python binding sets it from its environment variable) nor "
-                                               "the free device memory (" + std::to_string(status.freeBytes >> 20) +
-                                               " MB), so a larger buffer cannot help: raise the similarity threshold");
-    }
-    if (k) EM2_HIP(hipMemcpy(pairs, dPairs.p, size_t(geneCount) * k * sizeof(em2_pair), hipMemcpyDeviceToHost));
-    EM2_HIP(hipMemcpy(usedCount, dUsed.p, size_t(geneCount) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (allSimilarities) EM2_HIP(hipMemcpy(allSimilarities, dAll.p, allBytes, hipMemcpyDeviceToHost));
-    if (k) em2_internal_sort_gene_pairs(pairs, usedCount, geneCount, k);          // :186, the library's own std::sort
-    return EM2_OK;
-}
-
-
-// ---- gene information content and expressing cells (em2_gene_information.hip) ----
-
-static const char* geneInformationErrorText(uint32_t inputError)
-{
-    return (inputError & 4u) ? "toc does not start at 0, does not end at entryCount or is not ascending" : em2::inputErrorText(inputError);
-}
-
-// Cell::norm1Inverse / norm2Inverse as ExpressionMatrix::addCell defines them (src/ExpressionMatrix.cpp:241-263), on the host:
-// walkCell's arithmetic (em2_expression.h) and its checks.
-int em2_cell_norm_inverses(const uint64_t* toc, const em2_count* data, uint32_t cellCount, uint32_t geneCount, double* norm1Inverse,
-                           double* norm2Inverse)
-{
-    const char* who = "em2_cell_norm_inverses";
-    if (cellCount == 0) return EM2_OK;
-    if (!toc || !norm1Inverse || !norm2Inverse) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
-    em2::UploadedCsr csr;
-    if (const char* error = csr.check(toc, reinterpret_cast<const em2::CountIn*>(data), cellCount)) return failArgument(who, error);
-    uint32_t bad = 0;
-    for (uint32_t cell = 0; cell < cellCount; ++cell) {
-        double sum1 = 0., sum2 = 0.;
-        for (uint64_t p = toc[cell]; p < toc[cell + 1]; ++p) {
-            if (data[p].gene >= geneCount) bad |= 1u;
-            if (p != toc[cell] && data[p].gene <= data[p - 1].gene) bad |= 2u;
-            const float value = data[p].count;
-            sum1 += double(value);
-            sum2 += double(value * value);                  // a float product (:258)
-        }
-        norm1Inverse[cell] = 1. / sum1;
-        norm2Inverse[cell] = 1. / std::sqrt(sum2);
-    }
-    if (bad) return failArgument(who, em2::inputErrorText(bad));
-    return EM2_OK;
-}
-
-void em2_set_gene_information_max_blocks(uint32_t blocks) { em2::setGeneInformationMaxBlocks(blocks); }
-
-size_t em2_dev_gene_information_content_workspace(uint32_t cellCount, uint32_t geneCount, uint64_t entryCount)
-{
-    (void)cellCount;
-    return em2::geneInformationWorkspaceBytes(entryCount, geneCount);
-}
-
-// The device call under the name of the entry point that makes it.
-static int devGeneInformation(const char* who, const uint64_t* d_toc, const em2_count* d_data, uint32_t cellCount, uint32_t geneCount,
-                              uint64_t entryCount, const double* d_normInverse, float* d_informationContent,
-                              double* d_informationContentDouble, uint32_t* d_expressingCellCount, void* d_workspace,
-                              size_t workspaceBytes, void* stream)
-{
-    if (geneCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": geneCount must be positive");
-    if (cellCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": cellCount must be positive");
-    if (!d_toc || !d_informationContent || !d_workspace || (!d_data && entryCount)) {
-        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
-    }
-    if (workspaceBytes < em2::geneInformationWorkspaceBytes(entryCount, geneCount)) {
-        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": workspace too small");
-    }
-    uint32_t inputError = 0;
-    // :2004 and :2015 with the host's log, so that a gene without a positive entry gets the reference's float exactly
-    EM2_HIP(em2::runGeneInformation(d_toc, reinterpret_cast<const em2::CountIn*>(d_data), cellCount, geneCount, entryCount, d_normInverse,
-                                    std::log(double(cellCount)), std::log(2.), d_informationContent, d_informationContentDouble,
-                                    d_expressingCellCount, d_workspace, workspaceBytes, &inputError, static_cast<hipStream_t>(stream)));
-    if (inputError) return failArgument(who, geneInformationErrorText(inputError));
-    return EM2_OK;
-}
-
-int em2_dev_gene_information_content(const uint64_t* d_toc, const em2_count* d_data, uint32_t cellCount, uint32_t geneCount,
-                                     uint64_t entryCount, const double* d_normInverse, float* d_informationContent,
-                                     double* d_informationContentDouble, uint32_t* d_expressingCellCount, void* d_workspace,
-                                     size_t workspaceBytes, void* stream)
-{
-    return devGeneInformation("em2_dev_gene_information_content", d_toc, d_data, cellCount, geneCount, entryCount, d_normInverse,
-                              d_informationContent, d_informationContentDouble, d_expressingCellCount, d_workspace, workspaceBytes, stream);
-}
-
-// The device call on a CSR that is on the device already; the results to the host.
-static int geneInformationToHost(const char* who, const uint64_t* d_toc, const em2_count* d_data, uint32_t cellCount, uint32_t geneCount,
-                                 uint64_t entryCount, const double* d_normInverse, float* informationContent,
-                                 double* informationContentDouble, uint32_t* expressingCellCount)
-{
-    DeviceBuffer dFloat, dDouble, dExpressing, dWorkspace;
-    const size_t workspaceBytes = em2::geneInformationWorkspaceBytes(entryCount, geneCount);
-    EM2_HIP(dFloat.allocate(size_t(geneCount) * sizeof(float)));
-    if (informationContentDouble) EM2_HIP(dDouble.allocate(size_t(geneCount) * sizeof(double)));
-    if (expressingCellCount) EM2_HIP(dExpressing.allocate(size_t(geneCount) * sizeof(uint32_t)));
-    EM2_HIP(dWorkspace.allocate(workspaceBytes));
-    const int rc = devGeneInformation(who, d_toc, d_data, cellCount, geneCount, entryCount, d_normInverse, dFloat.as<float>(),
-                                      dDouble.as<double>(), dExpressing.as<uint32_t>(), dWorkspace.p, workspaceBytes, nullptr);
-    if (rc != EM2_OK) return rc;
-    if (informationContent) EM2_HIP(hipMemcpy(informationContent, dFloat.p, size_t(geneCount) * sizeof(float), hipMemcpyDeviceToHost));
-    if (informationContentDouble) EM2_HIP(hipMemcpy(informationContentDouble, dDouble.p, size_t(geneCount) * sizeof(double), hipMemcpyDeviceToHost));
-    if (expressingCellCount) EM2_HIP(hipMemcpy(expressingCellCount, dExpressing.p, size_t(geneCount) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return EM2_OK;
-}
-
-int em2_gene_information_content(const uint64_t* toc, const em2_count* data, uint32_t cellCount, uint32_t geneCount,
-                                 const double* normInverse, float* informationContent, double* informationContentDouble,
-                                 uint32_t* expressingCellCount)
-{
-    const char* who = "em2_gene_information_content";
-    if (geneCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": geneCount must be positive");
-    if (cellCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": cellCount must be positive");
-    if (!toc || !informationContent) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
-    em2::UploadedCsr csr;
-    if (const char* error = csr.check(toc, reinterpret_cast<const em2::CountIn*>(data), cellCount)) return failArgument(who, error);
-    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
-    EM2_HIP(csr.upload());                     // (the device checks the gene ids before any kernel indexes with them)
-    DeviceBuffer dNorm;
-    if (normInverse) {
-        EM2_HIP(dNorm.allocate(size_t(cellCount) * sizeof(double)));
-        EM2_HIP(hipMemcpy(dNorm.p, normInverse, size_t(cellCount) * sizeof(double), hipMemcpyHostToDevice));
-    }
-    return geneInformationToHost(who, csr.toc.as<uint64_t>(), csr.data.as<em2_count>(), cellCount, geneCount, csr.nnz,
-                                 normInverse ? dNorm.as<double>() : nullptr, informationContent, informationContentDouble, expressingCellCount);
-}
-
-// The matrix-level call (em2_host.cpp): the rows of the cell set go to the device with their global gene ids; the cells' norm
-// inverses are taken over those WHOLE rows there (or come from the Cells file: normInverseOfRows, one per row), the gene set
-// is applied by the device subset, and the rest is em2_dev_gene_information_content.  rowToc from 0.  Internal to the library.
-int em2_internal_gene_information(const uint64_t* rowToc, const em2_count* rowData, uint32_t cellCount, const uint32_t* geneLocalIds,
-                                  uint32_t globalGeneCount, uint32_t geneCount, int normalizationMethod, const double* normInverseOfRows,
-                                  float* informationContent, uint32_t* expressingCellCount)
-{
-    const char* who = "em2_matrix_gene_information_content";
-    if (normalizationMethod < 0 || normalizationMethod > 2) {
-        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": invalid normalization method (0 none, 1 L1, 2 L2)");
-    }
-    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
-    em2::UploadedCsr rows;
-    if (const char* error = rows.check(rowToc, reinterpret_cast<const em2::CountIn*>(rowData), cellCount)) return failArgument(who, error);
-    EM2_HIP(rows.upload());
-    DeviceBuffer dNorm, dLocalIds, dToc, dData, dSubsetWorkspace;
-    if (normalizationMethod != 0) {
-        EM2_HIP(dNorm.allocate(size_t(cellCount) * sizeof(double)));
-        if (normInverseOfRows) {
-            EM2_HIP(hipMemcpy(dNorm.p, normInverseOfRows, size_t(cellCount) * sizeof(double), hipMemcpyHostToDevice));
-        } else {
-            // (a global gene id is checked by nothing here: the subset below drops what the gene set does not know)
-            EM2_HIP(em2::launchCellNormInverses(rows.toc.as<uint64_t>(), rows.data.as<em2::CountIn>(), cellCount, 0xffffffffu,
-                                                normalizationMethod, dNorm.as<double>(), nullptr));
-        }
-    }
-    const size_t subsetBytes = em2::subsetWorkspaceBytes(cellCount);
-    EM2_HIP(dLocalIds.allocate(size_t(globalGeneCount) * sizeof(uint32_t)));
-    if (globalGeneCount) EM2_HIP(hipMemcpy(dLocalIds.p, geneLocalIds, size_t(globalGeneCount) * sizeof(uint32_t), hipMemcpyHostToDevice));
-    EM2_HIP(dToc.allocate((size_t(cellCount) + 1) * sizeof(uint64_t)));
-    EM2_HIP(dSubsetWorkspace.allocate(subsetBytes));
-    EM2_HIP(em2::launchSubsetCount(rows.toc.as<uint64_t>(), rows.data.as<em2::CountIn>(), nullptr, cellCount, dLocalIds.as<uint32_t>(),
-                                   globalGeneCount, dToc.as<uint64_t>(), dSubsetWorkspace.p, subsetBytes, nullptr));
-    uint64_t entryCount = 0;
-    EM2_HIP(hipMemcpy(&entryCount, dToc.as<uint64_t>() + cellCount, sizeof(uint64_t), hipMemcpyDeviceToHost));
-    EM2_HIP(dData.allocate(entryCount * sizeof(em2_count)));
-    EM2_HIP(em2::launchSubsetFill(rows.toc.as<uint64_t>(), rows.data.as<em2::CountIn>(), nullptr, cellCount, dLocalIds.as<uint32_t>(),
-                                  globalGeneCount, dToc.as<uint64_t>(), dData.as<em2::CountIn>(), nullptr));
-    return geneInformationToHost(who, dToc.as<uint64_t>(), dData.as<em2_count>(), cellCount, geneCount, entryCount,
-                                 normalizationMethod != 0 ? dNorm.as<double>() : nullptr, informationContent, nullptr, expressingCellCount);
-}
-
-
-// ---- getDenseExpressionMatrix (em2_dense.hip) ----
-
-size_t em2_dev_dense_expression_workspace(uint32_t rowCount) { return em2::denseExpressionWorkspaceBytes(rowCount); }
-
-// The device call under the name of the entry point that makes it.
-static int devDenseExpression(const char* who, const uint64_t* d_toc, const em2_count* d_data, const uint32_t* d_cellIds, uint32_t cellCount,
-                              const uint32_t* d_geneLocalIds, uint32_t globalGeneCount, uint32_t geneCount, int normalizationMethod,
-                              uint32_t rowBegin, uint32_t rowEnd, int elementType, void* d_out, uint64_t pitchElements, void* d_workspace,
-                              size_t workspaceBytes, void* stream)
-{
-    if (normalizationMethod < 0 || normalizationMethod > 2) {
-        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": invalid normalization method (0 none, 1 L1, 2 L2)");
-    }
-    if (elementType != EM2_DENSE_FLOAT64 && elementType != EM2_DENSE_FLOAT32) {
-        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": elementType must be 0 (float64) or 1 (float32)");
-    }
-    if (geneCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": geneCount must be positive");
-    if (rowBegin > rowEnd || rowEnd > cellCount) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": rowBegin <= rowEnd <= cellCount is required");
-    if (pitchElements < geneCount) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": pitchElements is below geneCount");
-    if (rowBegin == rowEnd) return EM2_OK;
-    if (!d_toc || !d_out || !d_workspace) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
-    const size_t elementBytes = elementType == EM2_DENSE_FLOAT64 ? sizeof(double) : sizeof(float);
-    if (reinterpret_cast<uintptr_t>(d_out) % elementBytes) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": d_out is not aligned to its element");
-    if (workspaceBytes < em2::denseExpressionWorkspaceBytes(rowEnd - rowBegin)) {
-        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": workspace too small");
-    }
-    uint32_t inputError = 0;
-    static_assert(EM2_DENSE_FLOAT64 == 0 && EM2_DENSE_FLOAT32 == 1, "the element types as numbers");
-    const bool elementsAreDouble = elementType == 0;          // (not by name: EM2_HIP keeps the call's text)
-    EM2_HIP(em2::runDenseExpression(d_toc, reinterpret_cast<const em2::CountIn*>(d_data), d_cellIds, d_geneLocalIds, globalGeneCount, geneCount,
-                                    normalizationMethod, rowBegin, rowEnd, elementsAreDouble, d_out, size_t(pitchElements),
-                                    d_workspace, workspaceBytes, &inputError, static_cast<hipStream_t>(stream)));
-    if (inputError) return failArgument(who, em2::inputErrorText(inputError));
-    return EM2_OK;
-}
-
-int em2_dev_dense_expression(const uint64_t* d_toc, const em2_count* d_data, const uint32_t* d_cellIds, uint32_t cellCount,
-                             const uint32_t* d_geneLocalIds, uint32_t globalGeneCount, uint32_t geneCount, int normalizationMethod,
-                             uint32_t rowBegin, uint32_t rowEnd, int elementType, void* d_out, uint64_t pitchElements,
-                             void* d_workspace, size_t workspaceBytes, void* stream)
-{
-    return devDenseExpression("em2_dev_dense_expression", d_toc, d_data, d_cellIds, cellCount, d_geneLocalIds, globalGeneCount, geneCount,
-                              normalizationMethod, rowBegin, rowEnd, elementType, d_out, pitchElements, d_workspace, workspaceBytes, stream);
-}
-
-static const size_t kDenseDeviceBufferBytes = size_t(1) << 30;          // em2_dense_expression's device buffer at most
-
-int em2_dense_expression(const uint64_t* toc, const em2_count* data, uint32_t csrCellCount, const uint32_t* cellIds, uint32_t cellCount,
-                         const uint32_t* geneLocalIds, uint32_t globalGeneCount, uint32_t geneCount, int normalizationMethod,
-                         int elementType, void* out, uint64_t pitchElements)
-{
-    const char* who = "em2_dense_expression";
-    if (normalizationMethod < 0 || normalizationMethod > 2) {
-        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": invalid normalization method (0 none, 1 L1, 2 L2)");
-    }
-    if (elementType != EM2_DENSE_FLOAT64 && elementType != EM2_DENSE_FLOAT32) {
-        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": elementType must be 0 (float64) or 1 (float32)");
-    }
-    if (geneCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": geneCount must be positive");
-    if (pitchElements < geneCount) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": pitchElements is below geneCount");
-    if (!cellIds && cellCount != csrCellCount) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": without cellIds cellCount must be csrCellCount");
-    if (cellCount == 0) return EM2_OK;
-    if (!toc || !out || (!geneLocalIds && globalGeneCount)) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
-    for (uint32_t i = 0; cellIds && i < cellCount; ++i) {
-        if (cellIds[i] >= csrCellCount) return failArgument(who, "a cell id is not below the cell count of the CSR");
-    }
-    em2::UploadedCsr csr;
-    if (const char* error = csr.check(toc, reinterpret_cast<const em2::CountIn*>(data), csrCellCount)) return failArgument(who, error);
-    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
-    EM2_HIP(csr.upload());                     // (the device checks the gene ids before any kernel indexes with them)
-    DeviceBuffer dCellIds, dLocalIds, dOut, dWorkspace;
-    if (cellIds) {
-        EM2_HIP(dCellIds.allocate(size_t(cellCount) * sizeof(uint32_t)));
-        EM2_HIP(hipMemcpy(dCellIds.p, cellIds, size_t(cellCount) * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    if (geneLocalIds) {
-        EM2_HIP(dLocalIds.allocate(size_t(globalGeneCount) * sizeof(uint32_t)));
-        EM2_HIP(hipMemcpy(dLocalIds.p, geneLocalIds, size_t(globalGeneCount) * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    const size_t elementBytes = elementType == EM2_DENSE_FLOAT64 ? sizeof(double) : sizeof(float);
-    const size_t rowBytes = size_t(geneCount) * elementBytes;
-    const uint64_t rowsThatFit = kDenseDeviceBufferBytes / rowBytes;
-    const uint32_t chunkRows = uint32_t(rowsThatFit < 1 ? 1 : (rowsThatFit > cellCount ? cellCount : rowsThatFit));
-    const size_t workspaceBytes = em2::denseExpressionWorkspaceBytes(chunkRows);
-    EM2_HIP(dOut.allocate(size_t(chunkRows) * rowBytes));
-    EM2_HIP(dWorkspace.allocate(workspaceBytes));
-    for (uint32_t rowBegin = 0; rowBegin < cellCount; rowBegin += chunkRows) {
-        const uint32_t rowEnd = cellCount - rowBegin < chunkRows ? cellCount : rowBegin + chunkRows;
-        const int rc = devDenseExpression(who, csr.toc.as<uint64_t>(), csr.data.as<em2_count>(), cellIds ? dCellIds.as<uint32_t>() : nullptr,
-                                          cellCount, geneLocalIds ? dLocalIds.as<uint32_t>() : nullptr, globalGeneCount, geneCount,
-                                          normalizationMethod, rowBegin, rowEnd, elementType, dOut.p, geneCount, dWorkspace.p, workspaceBytes,
-                                          nullptr);
-        if (rc != EM2_OK) return rc;
-        // the geneCount elements of every row; the caller's padding stays as it is
-        char* const to = static_cast<char*>(out) + size_t(rowBegin) * size_t(pitchElements) * elementBytes;
-        if (pitchElements == geneCount) {
-            EM2_HIP(hipMemcpy(to, dOut.p, size_t(rowEnd - rowBegin) * rowBytes, hipMemcpyDeviceToHost));
-        } else {
-            EM2_HIP(hipMemcpy2D(to, size_t(pitchElements) * elementBytes, dOut.p, rowBytes, rowBytes, rowEnd - rowBegin, hipMemcpyDeviceToHost));
-        }
-    }
-    return EM2_OK;
-}
-
-
-// ExpressionMatrix::analyzeSimilarPairs (src/ExpressionMatrixLsh.cpp:55-150) after its lookups: the exact similarity of every
-// stored pair on the device, chunk of rows by chunk of rows; bins, the seeded draw and the csv lines on the host in the
-// reference's order (cell 0 ascending, stored order).
-int em2_analyze_similar_pairs(const uint64_t* toc, const em2_count* data, uint32_t cellCount, uint32_t geneCount,
-                              const em2_pair* pairs, const uint32_t* usedCount, uint32_t k, const uint32_t* globalCellIds,
-                              double csvDownsample, const char* pairsCsvPath, const char* statisticsCsvPath,
-                              uint64_t* sum0, double* sum1, double* sum2)
-{
-    const char* who = "em2_analyze_similar_pairs";
-    if (geneCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": geneCount must be positive");
-    if (!toc || !usedCount || !globalCellIds || !pairsCsvPath || !statisticsCsvPath || (!pairs && k && cellCount)) {
-        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
-    }
-    em2::UploadedCsr csr;
-    if (const char* error = csr.check(toc, reinterpret_cast<const em2::CountIn*>(data), cellCount)) return failArgument(who, error);
-    if (cellCount && toc[0] != 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": toc must start at 0");
-    uint64_t stored = 0;
-    for (uint32_t c = 0; c < cellCount; ++c) {
-        if (usedCount[c] > k) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": a cell stores more than k pairs");
-        for (uint32_t t = 0; t < usedCount[c]; ++t) {
-            if (pairs[size_t(c) * k + t].cell >= cellCount) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": a stored pair names a cell that does not exist");
-        }
-        stored += usedCount[c];
-    }
-    if (stored && !haveDevice()) return fail(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
-
-    em2::AnalysisState* state = em2::analyzeStoredBegin(pairsCsvPath);
-    if (!state) return fail(EM2_ERROR_RUNTIME, std::string(who) + ": cannot open " + pairsCsvPath);
-    AnalysisCloser closer{state};
-
-    if (stored) {
-        // rows in chunks of at most 2^24 slots (128 MB of doubles), one row at least
-        const uint32_t chunkRows = std::max<uint32_t>(1u, uint32_t(std::min<uint64_t>(cellCount, (1ull << 24) / k)));
-        const em2::PairOut* hostPairs = reinterpret_cast<const em2::PairOut*>(pairs);
-        DeviceBuffer dPairs, dUsed, dWorkspace, dExact;
-        EM2_HIP(csr.upload());
-        EM2_HIP(dPairs.allocate(size_t(cellCount) * k * sizeof(em2_pair)));
-        EM2_HIP(dUsed.allocate(size_t(cellCount) * sizeof(uint32_t)));
-        EM2_HIP(dWorkspace.allocate(em2::storedPairsWorkspaceBytes(cellCount, chunkRows, geneCount)));
-        EM2_HIP(dExact.allocate(size_t(chunkRows) * k * sizeof(double)));
-        EM2_HIP(hipMemcpy(dPairs.p, pairs, size_t(cellCount) * k * sizeof(em2_pair), hipMemcpyHostToDevice));
-        EM2_HIP(hipMemcpy(dUsed.p, usedCount, size_t(cellCount) * sizeof(uint32_t), hipMemcpyHostToDevice));
-        uint32_t inputError = 0;
-        EM2_HIP(em2::prepareStoredPairs(csr.toc.as<uint64_t>(), csr.data.as<em2::CountIn>(), cellCount, geneCount, dWorkspace.p, &inputError, nullptr));
-        if (inputError) return failArgument(who, em2::inputErrorText(inputError));
-        std::vector<double> exact(size_t(chunkRows) * k);
-        for (uint32_t begin = 0; begin < cellCount; begin += chunkRows) {
-            const uint32_t end = uint32_t(std::min<uint64_t>(cellCount, uint64_t(begin) + chunkRows));
-            EM2_HIP(em2::launchStoredPairs(csr.toc.as<uint64_t>(), csr.data.as<em2::CountIn>(), cellCount, geneCount, begin, end,
-                                           dPairs.as<em2::PairOut>(), dUsed.as<uint32_t>(), k, dWorkspace.p, dExact.as<double>(), nullptr));
-            EM2_HIP(hipStreamSynchronize(nullptr));
-            EM2_HIP(hipMemcpy(exact.data(), dExact.p, size_t(end - begin) * k * sizeof(double), hipMemcpyDeviceToHost));
-            if (!em2::analyzeStoredRows(state, hostPairs, usedCount, k, globalCellIds, begin, end, exact.data(), csvDownsample)) {
-                return fail(EM2_ERROR_RUNTIME, std::string(who) + ": Assertion failed: bin < binCount (a stored pair with exact "
-                                               "similarity 1 or not finite; src/ExpressionMatrixLsh.cpp:111)");
-            }
-        }
-    }
-    em2::AnalysisState* finished = state;
-    state = nullptr;
-    if (!em2::analysisEnd(finished, 0, statisticsCsvPath, sum0, sum1, sum2)) {
-        return fail(EM2_ERROR_RUNTIME, std::string(who) + ": cannot open " + statisticsCsvPath);
-    }
-    return EM2_OK;
-}
-
-
 static int labelPropagation(bool edgesOnDevice, const uint32_t* vertexCellIds, uint32_t vertexCount, const uint32_t* edgeVertex0,
                             const uint32_t* edgeVertex1, const float* edgeSimilarity, uint64_t edgeCount, uint64_t seed,
                             uint64_t stableIterationCountThreshold, uint64_t maxIterationCount, uint32_t* clusterIds,
@@ -1884,7 +1274,7 @@ static int labelPropagation(bool edgesOnDevice, const uint32_t* vertexCellIds, u
     if (iterationCount) *iterationCount = 0;
     if (vertexCount == 0) return EM2_OK;
     if (!vertexCellIds || !clusterIds || (edgeCount && (!edgeVertex0 || !edgeVertex1 || !edgeSimilarity))) {
-        return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_cell_graph_label_propagation: null pointer");
+        return failNull("em2_cell_graph_label_propagation");
     }
     // (edges on the device are what em2_dev_cell_graph_edges wrote there: valid by construction, not read here)
     for (uint64_t e = 0; e < (edgesOnDevice ? 0 : edgeCount); e++) {
@@ -1906,7 +1296,7 @@ static int labelPropagation(bool edgesOnDevice, const uint32_t* vertexCellIds, u
             return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_cell_graph_label_propagation: duplicate cell id among the vertices");
         }
     }
-    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, "em2_cell_graph_label_propagation: no HIP device is visible (this library has no CPU path)");
+    if (!haveDevice()) return failNoDevice("em2_cell_graph_label_propagation");
     uint64_t iterations = 0;
     uint32_t error = 0;
     CallTimer timer;
@@ -1974,590 +1364,5 @@ int em2_dev_cell_graph_label_propagation(const uint32_t* vertexCellIds, uint32_t
     return labelPropagation(true, vertexCellIds, vertexCount, d_edgeVertex0, d_edgeVertex1, d_edgeSimilarity, edgeCount, seed,
                             stableIterationCountThreshold, maxIterationCount, clusterIds, iterationCount);
 }
-
-// ---- the rest of createClusterGraph (em2_cluster_graph.hip) ----
-
-struct em2_cluster_graph {
-    em2::ClusterGraphResult result;
-};
-
-static int clusterStatus(const em2::ClusterStatus& status) { return status.code == EM2_OK ? EM2_OK : fail(status.code, status.message); }
-
-int em2_cluster_average_expression(const uint64_t* toc, const em2_count* data, uint32_t cellCount, uint32_t geneCount,
-                                   const uint32_t* clusterCells, const uint64_t* clusterOffsets, uint32_t clusterCount,
-                                   double* averages)
-{
-    const char* who = "em2_cluster_average_expression";
-    if (geneCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": geneCount must be positive");
-    if (clusterCount == 0) return EM2_OK;
-    if (!toc || !clusterOffsets || !averages || (clusterOffsets[clusterCount] && !clusterCells)) {
-        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
-    }
-    if (clusterOffsets[0] != 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": clusterOffsets must start at 0");
-    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
-    em2::ClusterDevice device;
-    int rc = clusterStatus(device.upload(who, toc, reinterpret_cast<const em2::CountIn*>(data), cellCount, geneCount));
-    if (rc != EM2_OK) return rc;
-    return clusterStatus(device.averages(who, clusterCells, clusterOffsets, clusterCount, averages));
-}
-
-int em2_cluster_similarities(const double* averages, uint32_t clusterCount, uint32_t geneCount, const uint32_t* edgeCluster0,
-                             const uint32_t* edgeCluster1, uint64_t edgeCount, double* similarity)
-{
-    const char* who = "em2_cluster_similarities";
-    if (geneCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": geneCount must be positive");
-    if (edgeCount == 0) return EM2_OK;
-    if (!averages || !edgeCluster0 || !edgeCluster1 || !similarity) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
-    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
-    em2::ClusterDevice device;
-    const int rc = clusterStatus(device.setAverages(averages, clusterCount, geneCount));
-    if (rc != EM2_OK) return rc;
-    return clusterStatus(device.similarities(who, edgeCluster0, edgeCluster1, edgeCount, similarity));
-}
-
-int em2_cluster_graph_create(const uint64_t* toc, const em2_count* data, uint32_t rowCount, uint32_t geneCount,
-                             const uint32_t* vertexRows, uint32_t vertexCount, const uint32_t* edgeVertex0,
-                             const uint32_t* edgeVertex1, uint64_t edgeCount, const uint32_t* labels, uint64_t minClusterSize,
-                             uint64_t k, double similarityThreshold, double similarityThresholdForMerge, em2_cluster_graph** graph)
-{
-    const char* who = "em2_cluster_graph_create";
-    if (!graph) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
-    *graph = nullptr;
-    if (geneCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": geneCount must be positive");
-    if (!toc || (vertexCount && !labels) || (edgeCount && (!edgeVertex0 || !edgeVertex1))) {
-        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
-    }
-    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
-    em2_cluster_graph* g = new em2_cluster_graph;
-    const int rc = clusterStatus(em2::createClusterGraph(toc, reinterpret_cast<const em2::CountIn*>(data), rowCount, geneCount, vertexRows,
-                                                         vertexCount, edgeVertex0, edgeVertex1, edgeCount, labels, minClusterSize, k,
-                                                         similarityThreshold, similarityThresholdForMerge, g->result));
-    if (rc != EM2_OK) {
-        delete g;
-        return rc;
-    }
-    *graph = g;
-    return EM2_OK;
-}
-
-int em2_cluster_graph_sizes(const em2_cluster_graph* graph, uint32_t* clusterCount, uint32_t* geneCount, uint64_t* clusteredCellCount,
-                            uint64_t* unclusteredCellCount, uint64_t* edgeCount)
-{
-    if (!graph) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_cluster_graph_sizes: null pointer");
-    const em2::ClusterGraphResult& r = graph->result;
-    if (clusterCount) *clusterCount = uint32_t(r.clusterIds.size());
-    if (geneCount) *geneCount = r.geneCount;
-    if (clusteredCellCount) *clusteredCellCount = r.cells.size();
-    if (unclusteredCellCount) *unclusteredCellCount = r.unclusteredCells.size();
-    if (edgeCount) *edgeCount = r.edgeSimilarity.size();
-    return EM2_OK;
-}
-
-int em2_cluster_graph_get(const em2_cluster_graph* graph, uint32_t* clusterIds, uint64_t* cellOffsets, uint32_t* cells,
-                          uint32_t* unclusteredCells, double* averages, uint32_t* edgeCluster0, uint32_t* edgeCluster1,
-                          double* edgeSimilarity)
-{
-    if (!graph) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_cluster_graph_get: null pointer");
-    const em2::ClusterGraphResult& r = graph->result;
-    if (clusterIds) std::copy(r.clusterIds.begin(), r.clusterIds.end(), clusterIds);
-    if (cellOffsets) std::copy(r.cellOffsets.begin(), r.cellOffsets.end(), cellOffsets);
-    if (cells) std::copy(r.cells.begin(), r.cells.end(), cells);
-    if (unclusteredCells) std::copy(r.unclusteredCells.begin(), r.unclusteredCells.end(), unclusteredCells);
-    if (averages) std::copy(r.averages.begin(), r.averages.end(), averages);
-    if (edgeCluster0) std::copy(r.edgeCluster0.begin(), r.edgeCluster0.end(), edgeCluster0);
-    if (edgeCluster1) std::copy(r.edgeCluster1.begin(), r.edgeCluster1.end(), edgeCluster1);
-    if (edgeSimilarity) std::copy(r.edgeSimilarity.begin(), r.edgeSimilarity.end(), edgeSimilarity);
-    return EM2_OK;
-}
-
-int em2_cluster_graph_facts(const em2_cluster_graph* graph, double* values, uint32_t valueCount)
-{
-    if (!graph || (valueCount && !values)) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_cluster_graph_facts: null pointer");
-    const em2::ClusterGraphResult& r = graph->result;
-    const double facts[5] = {r.totalSeconds, r.averagesSeconds, r.similaritiesSeconds, double(r.initialClusterCount),
-                             double(r.initialEdgeCount)};
-    for (uint32_t i = 0; i < valueCount; ++i) values[i] = i < 5u ? facts[i] : 0.;
-    return EM2_OK;
-}
-
-void em2_cluster_graph_free(em2_cluster_graph* graph) { delete graph; }
-
-// ---- the signature graph and the signature diagnostics (em2_signature_graph.hip) ----
-
-struct em2_signature_graph {
-    em2::SignatureGraphResult result;
-};
-
-// lshCount, then cellCount, then the pointer, then the device: none of them reaches a launch.
-static int checkSignatureArguments(const char* who, const void* signatures, uint32_t cellCount, uint32_t lshCount)
-{
-    if (lshCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": lshCount must be positive");
-    if (lshCount > em2::kSignatureGraphMaxLshCount) {
-        return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": lshCount above " + std::to_string(em2::kSignatureGraphMaxLshCount) + " is not supported");
-    }
-    if (cellCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": cellCount must be positive");
-    if (!signatures) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
-    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
-    return EM2_OK;
-}
-
-static int signatureGroups(const char* who, const uint64_t* d_signatures, uint32_t cellCount, uint32_t lshCount, uint64_t minCellCount,
-                           bool withEdges, em2::SignatureGraphResult& result)
-{
-    uint32_t inputError = 0;
-    EM2_HIP(em2::runSignatureGraph(d_signatures, cellCount, lshCount, minCellCount, withEdges, result, &inputError, nullptr));
-    if (inputError) return failArgument(who, "a signature has a bit set at or beyond lshCount");
-    return EM2_OK;
-}
-
-static int signatureGraphCreate(const char* who, bool onDevice, const uint64_t* signatures, uint32_t cellCount, uint32_t lshCount,
-                                uint64_t minCellCount, em2_signature_graph** graph)
-{
-    if (!graph) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
-    *graph = nullptr;
-    int rc = checkSignatureArguments(who, signatures, cellCount, lshCount);
-    if (rc != EM2_OK) return rc;
-    DeviceBuffer dSig;
-    if (!onDevice) {
-        const size_t bytes = size_t(cellCount) * wordCountOf(lshCount) * sizeof(uint64_t);
-        EM2_HIP(dSig.allocate(bytes));
-        EM2_HIP(hipMemcpy(dSig.p, signatures, bytes, hipMemcpyHostToDevice));
-    }
-    em2_signature_graph* g = new em2_signature_graph;
-    rc = signatureGroups(who, onDevice ? signatures : dSig.as<uint64_t>(), cellCount, lshCount, minCellCount, true, g->result);
-    if (rc != EM2_OK) {
-        delete g;
-        return rc;
-    }
-    *graph = g;
-    return EM2_OK;
-}
-
-int em2_signature_graph_create(const uint64_t* signatures, uint32_t cellCount, uint32_t lshCount, uint64_t minCellCount,
-                               em2_signature_graph** graph)
-{
-    return signatureGraphCreate("em2_signature_graph_create", false, signatures, cellCount, lshCount, minCellCount, graph);
-}
-
-int em2_dev_signature_graph_create(const uint64_t* d_signatures, uint32_t cellCount, uint32_t lshCount, uint64_t minCellCount,
-                                   em2_signature_graph** graph)
-{
-    return signatureGraphCreate("em2_dev_signature_graph_create", true, d_signatures, cellCount, lshCount, minCellCount, graph);
-}
-
-int em2_signature_graph_sizes(const em2_signature_graph* graph, uint64_t* distinctCount, uint32_t* vertexCount, uint32_t* wordCount,
-                              uint64_t* cellCount, uint64_t* edgeCount)
-{
-    if (!graph) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_signature_graph_sizes: null pointer");
-    const em2::SignatureGraphResult& r = graph->result;
-    if (distinctCount) *distinctCount = r.distinctCount;
-    if (vertexCount) *vertexCount = uint32_t(r.cellOffsets.size() - 1u);
-    if (wordCount) *wordCount = r.wordCount;
-    if (cellCount) *cellCount = r.cells.size();
-    if (edgeCount) *edgeCount = r.edgeVertex0.size();
-    return EM2_OK;
-}
-
-int em2_signature_graph_get(const em2_signature_graph* graph, uint64_t* vertexSignatures, uint64_t* cellOffsets, uint32_t* cells,
-                            uint32_t* edgeVertex0, uint32_t* edgeVertex1)
-{
-    if (!graph) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_signature_graph_get: null pointer");
-    const em2::SignatureGraphResult& r = graph->result;
-    if (vertexSignatures) std::copy(r.vertexSignatures.begin(), r.vertexSignatures.end(), vertexSignatures);
-    if (cellOffsets) std::copy(r.cellOffsets.begin(), r.cellOffsets.end(), cellOffsets);
-    if (cells) std::copy(r.cells.begin(), r.cells.end(), cells);
-    if (edgeVertex0) std::copy(r.edgeVertex0.begin(), r.edgeVertex0.end(), edgeVertex0);
-    if (edgeVertex1) std::copy(r.edgeVertex1.begin(), r.edgeVertex1.end(), edgeVertex1);
-    return EM2_OK;
-}
-
-void em2_signature_graph_free(em2_signature_graph* graph) { delete graph; }
-
-// setCount[lshCount] on the host from signatures that are on the device.
-static int signatureStatisticsToHost(const uint64_t* d_signatures, uint32_t cellCount, uint32_t lshCount, uint64_t* setCount)
-{
-    DeviceBuffer dCounts;
-    EM2_HIP(dCounts.allocate(size_t(lshCount) * sizeof(unsigned long long)));
-    EM2_HIP(em2::launchSignatureStatistics(d_signatures, cellCount, lshCount, dCounts.as<unsigned long long>(), nullptr));
-    EM2_HIP(hipMemcpy(setCount, dCounts.p, size_t(lshCount) * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return EM2_OK;
-}
-
-static int signatureStatistics(const char* who, bool onDevice, const uint64_t* signatures, uint32_t cellCount, uint32_t lshCount,
-                               uint64_t* setCount)
-{
-    const int rc = checkSignatureArguments(who, setCount ? static_cast<const void*>(signatures) : nullptr, cellCount, lshCount);
-    if (rc != EM2_OK) return rc;
-    DeviceBuffer dSig;
-    if (!onDevice) {
-        const size_t bytes = size_t(cellCount) * wordCountOf(lshCount) * sizeof(uint64_t);
-        EM2_HIP(dSig.allocate(bytes));
-        EM2_HIP(hipMemcpy(dSig.p, signatures, bytes, hipMemcpyHostToDevice));
-    }
-    return signatureStatisticsToHost(onDevice ? signatures : dSig.as<uint64_t>(), cellCount, lshCount, setCount);
-}
-
-int em2_lsh_signature_statistics(const uint64_t* signatures, uint32_t cellCount, uint32_t lshCount, uint64_t* setCount)
-{
-    return signatureStatistics("em2_lsh_signature_statistics", false, signatures, cellCount, lshCount, setCount);
-}
-
-int em2_dev_lsh_signature_statistics(const uint64_t* d_signatures, uint32_t cellCount, uint32_t lshCount, uint64_t* setCount)
-{
-    return signatureStatistics("em2_dev_lsh_signature_statistics", true, d_signatures, cellCount, lshCount, setCount);
-}
-
-int em2_analyze_lsh_signatures(const uint64_t* signatures, uint32_t cellCount, uint32_t lshCount, const char* directory)
-{
-    const char* who = "em2_analyze_lsh_signatures";
-    int rc = checkSignatureArguments(who, signatures, cellCount, lshCount);
-    if (rc != EM2_OK) return rc;
-    const uint32_t words = wordCountOf(lshCount);
-    DeviceBuffer dSig;
-    EM2_HIP(dSig.allocate(size_t(cellCount) * words * sizeof(uint64_t)));
-    EM2_HIP(hipMemcpy(dSig.p, signatures, size_t(cellCount) * words * sizeof(uint64_t), hipMemcpyHostToDevice));
-    em2::SignatureGraphResult groups;                           // src/ExpressionMatrixLsh.cpp:1421-1424: the map, nothing filtered
-    rc = signatureGroups(who, dSig.as<uint64_t>(), cellCount, lshCount, 0u, false, groups);
-    if (rc != EM2_OK) return rc;
-    std::vector<uint64_t> setCount(lshCount);
-    rc = signatureStatisticsToHost(dSig.as<uint64_t>(), cellCount, lshCount, setCount.data());
-    if (rc != EM2_OK) return rc;
-    dSig.release();
-
-    const std::string prefix = directory && directory[0] ? std::string(directory) + "/" : std::string();
-    const size_t groupCount = groups.cellOffsets.size() - 1u;
-    // :1428-1435: (signature, size) in map order, std::sort by size descending -- not stable: the host's own std::sort
-    std::vector<std::pair<uint64_t, uint64_t>> table(groupCount);
-    for (size_t g = 0; g < groupCount; ++g) table[g] = std::make_pair(uint64_t(g), groups.cellOffsets[g + 1u] - groups.cellOffsets[g]);
-    std::sort(table.begin(), table.end(),
-              [](const std::pair<uint64_t, uint64_t>& x, const std::pair<uint64_t, uint64_t>& y) { return x.second > y.second; });
-    {
-        const std::string path = prefix + "Signatures.csv";                                  // :1440-1447
-        std::ofstream csv(path);
-        if (!csv) return fail(EM2_ERROR_RUNTIME, std::string(who) + ": cannot open " + path);
-        std::string line(size_t(lshCount), '_');
-        for (const std::pair<uint64_t, uint64_t>& p : table) {
-            const uint64_t* signature = groups.vertexSignatures.data() + size_t(p.first) * words;
-            for (uint32_t i = 0; i < lshCount; ++i) line[i] = (signature[i >> 6] >> (63u - (i & 63u))) & 1u ? 'x' : '_';
-            csv << line << "," << p.second << "\n";
-        }
-    }
-    {
-        const std::string path = prefix + "Histogram.csv";                                   // :1451-1467
-        std::ofstream csv(path);
-        if (!csv) return fail(EM2_ERROR_RUNTIME, std::string(who) + ": cannot open " + path);
-        std::map<uint64_t, uint64_t> groupsOfSize;               // the sizes that occur, ascending
-        for (size_t g = 0; g < groupCount; ++g) groupsOfSize[groups.cellOffsets[g + 1u] - groups.cellOffsets[g]] += 1u;
-        uint64_t cellsSoFar = 0;
-        for (const std::pair<const uint64_t, uint64_t>& entry : groupsOfSize) {
-            cellsSoFar += entry.first * entry.second;
-            csv << entry.first << "," << entry.second << "," << entry.first * entry.second << "," << cellsSoFar << "\n";
-        }
-    }
-    {
-        const std::string path = prefix + "LshSignatureStatistics.csv";                      // src/Lsh.cpp:284-301
-        std::ofstream csv(path);
-        if (!csv) return fail(EM2_ERROR_RUNTIME, std::string(who) + ": cannot open " + path);
-        csv << "Bit,Set,Unset,Total\n";
-        for (uint32_t i = 0; i < lshCount; ++i) {
-            csv << i << "," << setCount[i] << "," << uint64_t(cellCount) - setCount[i] << "," << cellCount << "\n";
-        }
-    }
-    return EM2_OK;
-}
-
-// ---- the gene graph (em2_gene_graph.hip) ----
-
-struct em2_gene_graph {
-    em2::GeneGraphResult result;
-};
-
-// Strictly ascending: what a stored GeneSet is once sorted (src/GeneSet.cpp), and what both id look-ups rely on.
-static bool strictlyAscending(const uint32_t* ids, uint32_t count)
-{
-    for (uint32_t i = 1; i < count; i++) {
-        if (ids[i - 1] >= ids[i]) return false;
-    }
-    return true;
-}
-
-static int geneGraphCreate(const char* who, bool pairsOnDevice, const em2_pair* pairs, const uint32_t* usedCount, uint32_t pairsGeneCount,
-                           uint32_t k, const uint32_t* pairsGeneSet, const uint32_t* graphGeneSet, uint32_t graphGeneCount,
-                           double similarityThreshold, uint64_t maxConnectivity, em2_gene_graph** graph)
-{
-    if (!graph) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
-    *graph = nullptr;
-    if (graphGeneCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": graphGeneCount must be positive");
-    if (!graphGeneSet || (pairsGeneCount && (!pairsGeneSet || !usedCount || (!pairs && k)))) {
-        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
-    }
-    if (!strictlyAscending(pairsGeneSet, pairsGeneCount) || !strictlyAscending(graphGeneSet, graphGeneCount)) {
-        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": a gene set is not in strictly ascending order");
-    }
-    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
-    // src/GeneGraph.cpp:80-83 increments and then tests for equality, so 0 -- and a negative Python int, converted to size_t --
-    // never matches: no limit.  A gene never selects more than its k stored pairs either way.
-    const uint32_t effective = (maxConnectivity == 0 || maxConnectivity > k) ? k : uint32_t(maxConnectivity);
-    // (sets of consecutive ids need no search on the device and are not sent there)
-    const bool pairsConsecutive = pairsGeneCount && pairsGeneSet[pairsGeneCount - 1] - pairsGeneSet[0] == pairsGeneCount - 1;
-    const bool graphConsecutive = graphGeneSet[graphGeneCount - 1] - graphGeneSet[0] == graphGeneCount - 1;
-    DeviceBuffer dPairs, dUsed, dPairsSet, dGraphSet;
-    if (!pairsOnDevice) {
-        EM2_HIP(dPairs.allocate(size_t(pairsGeneCount) * k * sizeof(em2_pair)));
-        EM2_HIP(dUsed.allocate(size_t(pairsGeneCount) * sizeof(uint32_t)));
-        if (pairsGeneCount && k) EM2_HIP(hipMemcpy(dPairs.p, pairs, size_t(pairsGeneCount) * k * sizeof(em2_pair), hipMemcpyHostToDevice));
-        if (pairsGeneCount) EM2_HIP(hipMemcpy(dUsed.p, usedCount, size_t(pairsGeneCount) * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    if (!pairsConsecutive) {
-        EM2_HIP(dPairsSet.allocate(size_t(pairsGeneCount) * sizeof(uint32_t)));
-        if (pairsGeneCount) EM2_HIP(hipMemcpy(dPairsSet.p, pairsGeneSet, size_t(pairsGeneCount) * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    if (!graphConsecutive) {
-        EM2_HIP(dGraphSet.allocate(size_t(graphGeneCount) * sizeof(uint32_t)));
-        EM2_HIP(hipMemcpy(dGraphSet.p, graphGeneSet, size_t(graphGeneCount) * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    em2_gene_graph* g = new em2_gene_graph;
-    uint32_t inputError = 0;
-    const hipError_t status = em2::runGeneGraph(
-        pairsOnDevice ? reinterpret_cast<const em2::PairOut*>(pairs) : dPairs.as<em2::PairOut>(), pairsOnDevice ? usedCount : dUsed.as<uint32_t>(),
-        pairsGeneCount, k, pairsConsecutive ? nullptr : dPairsSet.as<uint32_t>(), pairsConsecutive, pairsGeneCount ? pairsGeneSet[0] : 0u,
-        graphConsecutive ? nullptr : dGraphSet.as<uint32_t>(), graphConsecutive, graphGeneSet[0], graphGeneCount, similarityThreshold,
-        effective, g->result, &inputError, nullptr);
-    if (status != hipSuccess || inputError) {
-        delete g;
-        EM2_HIP(status);
-        if (inputError & em2::kGeneGraphUsedCount) return failArgument(who, "a usedCount is above k");
-        if (inputError & em2::kGeneGraphPartnerRange) return failArgument(who, "a stored pair names a gene outside the pairs' gene set");
-        return failArgument(who, "a stored pair names its own gene");
-    }
-    *graph = g;
-    return EM2_OK;
-}
-
-int em2_gene_graph_create(const em2_pair* pairs, const uint32_t* usedCount, uint32_t pairsGeneCount, uint32_t k,
-                          const uint32_t* pairsGeneSet, const uint32_t* graphGeneSet, uint32_t graphGeneCount,
-                          double similarityThreshold, uint64_t maxConnectivity, em2_gene_graph** graph)
-{
-    return geneGraphCreate("em2_gene_graph_create", false, pairs, usedCount, pairsGeneCount, k, pairsGeneSet, graphGeneSet, graphGeneCount,
-                           similarityThreshold, maxConnectivity, graph);
-}
-
-int em2_dev_gene_graph_create(const em2_pair* d_pairs, const uint32_t* d_usedCount, uint32_t pairsGeneCount, uint32_t k,
-                              const uint32_t* pairsGeneSet, const uint32_t* graphGeneSet, uint32_t graphGeneCount,
-                              double similarityThreshold, uint64_t maxConnectivity, em2_gene_graph** graph)
-{
-    return geneGraphCreate("em2_dev_gene_graph_create", true, d_pairs, d_usedCount, pairsGeneCount, k, pairsGeneSet, graphGeneSet,
-                           graphGeneCount, similarityThreshold, maxConnectivity, graph);
-}
-
-int em2_gene_graph_sizes(const em2_gene_graph* graph, uint32_t* vertexCount, uint64_t* edgeCount, uint32_t* removedCount)
-{
-    if (!graph) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_gene_graph_sizes: null pointer");
-    const em2::GeneGraphResult& r = graph->result;
-    if (vertexCount) *vertexCount = uint32_t(r.vertices.size());
-    if (edgeCount) *edgeCount = r.edge0.size();
-    if (removedCount) *removedCount = r.geneCount - uint32_t(r.vertices.size());
-    return EM2_OK;
-}
-
-int em2_gene_graph_get(const em2_gene_graph* graph, uint32_t* vertices, uint32_t* edgeGene0, uint32_t* edgeGene1, float* edgeSimilarity,
-                       uint64_t* connectivityOffsets, uint32_t* connectivityGenes, float* connectivitySimilarities)
-{
-    if (!graph) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_gene_graph_get: null pointer");
-    const em2::GeneGraphResult& r = graph->result;
-    if (vertices) std::copy(r.vertices.begin(), r.vertices.end(), vertices);
-    if (edgeGene0) std::copy(r.edge0.begin(), r.edge0.end(), edgeGene0);
-    if (edgeGene1) std::copy(r.edge1.begin(), r.edge1.end(), edgeGene1);
-    if (edgeSimilarity) std::copy(r.edgeSimilarity.begin(), r.edgeSimilarity.end(), edgeSimilarity);
-    if (connectivityOffsets) std::copy(r.connectivityOffsets.begin(), r.connectivityOffsets.end(), connectivityOffsets);
-    if (connectivityGenes) std::copy(r.connectivityGenes.begin(), r.connectivityGenes.end(), connectivityGenes);
-    if (connectivitySimilarities) std::copy(r.connectivitySimilarities.begin(), r.connectivitySimilarities.end(), connectivitySimilarities);
-    return EM2_OK;
-}
-
-void em2_gene_graph_free(em2_gene_graph* graph) { delete graph; }
-
-// ---- the layout of a graph (em2_layout.hip) ----
-
-// The edge arrays of a host-pointer entry in device memory.
-static int uploadEdges(const uint32_t* edgeVertex0, const uint32_t* edgeVertex1, uint64_t edgeCount, DeviceBuffer& d0, DeviceBuffer& d1)
-{
-    EM2_HIP(d0.allocate(size_t(edgeCount) * sizeof(uint32_t)));
-    EM2_HIP(d1.allocate(size_t(edgeCount) * sizeof(uint32_t)));
-    if (edgeCount) {
-        EM2_HIP(hipMemcpy(d0.p, edgeVertex0, size_t(edgeCount) * sizeof(uint32_t), hipMemcpyHostToDevice));
-        EM2_HIP(hipMemcpy(d1.p, edgeVertex1, size_t(edgeCount) * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    return EM2_OK;
-}
-
-static int graphLayout(const char* who, bool onDevice, uint32_t vertexCount, const uint32_t* edgeVertex0, const uint32_t* edgeVertex1,
-                       uint64_t edgeCount, const em2_layout_parameters* parameters, float* x, float* y, em2_layout_result* result)
-{
-    if (!parameters || (vertexCount && (!x || !y)) || (edgeCount && (!edgeVertex0 || !edgeVertex1))) return failArgument(who, "null pointer");
-    if (!(parameters->tolerance >= 0.)) return failArgument(who, "tolerance must not be negative");
-    if (!(parameters->gravity >= 0.)) return failArgument(who, "gravity must not be negative");
-    if (!(parameters->initialStep >= 0.)) return failArgument(who, "initialStep must not be negative");
-    if (vertexCount > em2::kLayoutMaxVertexCount) return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": vertexCount is above 2^30");
-    if (result) {
-        result->iterationCount = result->reserved = 0u;
-        result->step = parameters->initialStep;
-        result->energy = std::numeric_limits<double>::infinity();
-    }
-    if (vertexCount == 0) {
-        // (no vertex, so every edge end is out of range)
-        return edgeCount ? failArgument(who, "an edge names a vertex outside the graph") : EM2_OK;
-    }
-    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
-    DeviceBuffer d0, d1, dx, dy;
-    if (!onDevice) {
-        const int status = uploadEdges(edgeVertex0, edgeVertex1, edgeCount, d0, d1);
-        if (status != EM2_OK) return status;
-        EM2_HIP(dx.allocate(size_t(vertexCount) * sizeof(float)));
-        EM2_HIP(dy.allocate(size_t(vertexCount) * sizeof(float)));
-    }
-    const em2::LayoutParameters p = {parameters->seed, parameters->maxIterationCount, parameters->tolerance, parameters->gravity,
-                                     parameters->initialStep};
-    em2::LayoutResult r;
-    uint32_t inputError = 0;
-    EM2_HIP(em2::runGraphLayout(vertexCount, onDevice ? edgeVertex0 : d0.as<uint32_t>(), onDevice ? edgeVertex1 : d1.as<uint32_t>(), edgeCount,
-                                p, onDevice ? x : dx.as<float>(), onDevice ? y : dy.as<float>(), r, &inputError, nullptr));
-    if (inputError) return failArgument(who, "an edge names a vertex outside the graph");
-    if (!onDevice) {
-        EM2_HIP(hipMemcpy(x, dx.p, size_t(vertexCount) * sizeof(float), hipMemcpyDeviceToHost));
-        EM2_HIP(hipMemcpy(y, dy.p, size_t(vertexCount) * sizeof(float), hipMemcpyDeviceToHost));
-    }
-    if (result) {
-        result->iterationCount = r.iterationCount;
-        result->step = r.step;
-        result->energy = r.energy;
-    }
-    return EM2_OK;
-}
-
-int em2_graph_layout(uint32_t vertexCount, const uint32_t* edgeVertex0, const uint32_t* edgeVertex1, uint64_t edgeCount,
-                     const em2_layout_parameters* parameters, float* x, float* y, em2_layout_result* result)
-{
-    return graphLayout("em2_graph_layout", false, vertexCount, edgeVertex0, edgeVertex1, edgeCount, parameters, x, y, result);
-}
-
-int em2_dev_graph_layout(uint32_t vertexCount, const uint32_t* d_edgeVertex0, const uint32_t* d_edgeVertex1, uint64_t edgeCount,
-                         const em2_layout_parameters* parameters, float* d_x, float* d_y, em2_layout_result* result)
-{
-    return graphLayout("em2_dev_graph_layout", true, vertexCount, d_edgeVertex0, d_edgeVertex1, edgeCount, parameters, d_x, d_y, result);
-}
-
-int em2_graph_layout_forces(uint32_t vertexCount, const uint32_t* edgeVertex0, const uint32_t* edgeVertex1, uint64_t edgeCount,
-                            double gravity, const float* x, const float* y, float* fx, float* fy, double* energy)
-{
-    const char* who = "em2_graph_layout_forces";
-    if ((vertexCount && (!x || !y || !fx || !fy)) || (edgeCount && (!edgeVertex0 || !edgeVertex1))) return failArgument(who, "null pointer");
-    if (!(gravity >= 0.)) return failArgument(who, "gravity must not be negative");
-    if (vertexCount > em2::kLayoutMaxVertexCount) return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": vertexCount is above 2^30");
-    if (energy) *energy = 0.;
-    if (vertexCount == 0) return edgeCount ? failArgument(who, "an edge names a vertex outside the graph") : EM2_OK;
-    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
-    DeviceBuffer d0, d1, d[4];
-    const int status = uploadEdges(edgeVertex0, edgeVertex1, edgeCount, d0, d1);
-    if (status != EM2_OK) return status;
-    const size_t bytes = size_t(vertexCount) * sizeof(float);
-    for (DeviceBuffer& buffer : d) EM2_HIP(buffer.allocate(bytes));
-    EM2_HIP(hipMemcpy(d[0].p, x, bytes, hipMemcpyHostToDevice));
-    EM2_HIP(hipMemcpy(d[1].p, y, bytes, hipMemcpyHostToDevice));
-    uint32_t inputError = 0;
-    double e = 0.;
-    EM2_HIP(em2::runGraphLayoutForces(vertexCount, d0.as<uint32_t>(), d1.as<uint32_t>(), edgeCount, gravity, d[0].as<float>(), d[1].as<float>(),
-                                      d[2].as<float>(), d[3].as<float>(), &e, &inputError, nullptr));
-    if (inputError) return failArgument(who, "an edge names a vertex outside the graph");
-    EM2_HIP(hipMemcpy(fx, d[2].p, bytes, hipMemcpyDeviceToHost));
-    EM2_HIP(hipMemcpy(fy, d[3].p, bytes, hipMemcpyDeviceToHost));
-    if (energy) *energy = e;
-    return EM2_OK;
-}
-
-// ---- the contingency table of two labelings (em2_contingency.hip) ----
-
-struct em2_contingency {
-    em2::ContingencyResult result;
-};
-
-static int contingencyCreate(const char* who, bool idsOnDevice, const uint32_t* id0, const uint32_t* id1, uint64_t n, uint32_t n0,
-                             uint32_t n1, int path, em2_contingency** out)
-{
-    if (!out) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
-    *out = nullptr;
-    if (n && (!id0 || !id1)) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
-    if (n0 == 0 || n1 == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": n0 and n1 must be positive");
-    if (path != em2::kContingencyAutomatic && path != em2::kContingencyLds && path != em2::kContingencySort) {
-        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": path must be 0 (automatic), 1 (LDS) or 2 (sort)");
-    }
-    if (path == em2::kContingencyLds && uint64_t(n0) * n1 > em2::kContingencyLdsCells) {
-        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": the LDS path holds a table of at most " +
-                                                    std::to_string(em2::kContingencyLdsCells) + " cells");
-    }
-    // (the three sums are at most n (n - 1), and a run's first element is kept in 32 bits)
-    if (n > 0xffffffffull) return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 1 elements are not supported");
-    if (!haveDevice()) return fail(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
-    DeviceBuffer d0, d1;
-    if (!idsOnDevice && n) {
-        EM2_HIP(d0.allocate(size_t(n) * sizeof(uint32_t)));
-        EM2_HIP(d1.allocate(size_t(n) * sizeof(uint32_t)));
-        EM2_HIP(hipMemcpy(d0.p, id0, size_t(n) * sizeof(uint32_t), hipMemcpyHostToDevice));
-        EM2_HIP(hipMemcpy(d1.p, id1, size_t(n) * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    em2_contingency* c = new em2_contingency;
-    uint32_t inputError = 0;
-    const hipError_t status = em2::runContingency(idsOnDevice || !n ? id0 : d0.as<uint32_t>(), idsOnDevice || !n ? id1 : d1.as<uint32_t>(), n,
-                                                  n0, n1, path, c->result, &inputError, nullptr);
-    if (status != hipSuccess || inputError) {
-        delete c;
-        EM2_HIP(status);
-        return failArgument(who, "an id is not below its count (id0 < n0, id1 < n1)");
-    }
-    *out = c;
-    return EM2_OK;
-}
-
-int em2_contingency_create(const uint32_t* id0, const uint32_t* id1, uint64_t n, uint32_t n0, uint32_t n1, int path, em2_contingency** out)
-{
-    return contingencyCreate("em2_contingency", false, id0, id1, n, n0, n1, path, out);
-}
-
-int em2_dev_contingency(const uint32_t* d_id0, const uint32_t* d_id1, uint64_t n, uint32_t n0, uint32_t n1, int path, em2_contingency** out)
-{
-    return contingencyCreate("em2_dev_contingency", true, d_id0, d_id1, n, n0, n1, path, out);
-}
-
-int em2_contingency_sizes(const em2_contingency* table, uint32_t* n0, uint32_t* n1, uint64_t* n, uint64_t* nonZeroCount, int* path)
-{
-    if (!table) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_contingency_sizes: null pointer");
-    const em2::ContingencyResult& r = table->result;
-    if (n0) *n0 = r.n0;
-    if (n1) *n1 = r.n1;
-    if (n) *n = r.n;
-    if (nonZeroCount) *nonZeroCount = r.count.size();
-    if (path) *path = r.path;
-    return EM2_OK;
-}
-
-int em2_contingency_get(const em2_contingency* table, uint64_t* rowTotals, uint64_t* columnTotals, uint32_t* i0, uint32_t* i1,
-                        uint64_t* count, uint64_t* sums)
-{
-    if (!table) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_contingency_get: null pointer");
-    const em2::ContingencyResult& r = table->result;
-    if (rowTotals) std::copy(r.rowTotals.begin(), r.rowTotals.end(), rowTotals);
-    if (columnTotals) std::copy(r.columnTotals.begin(), r.columnTotals.end(), columnTotals);
-    if (i0) std::copy(r.i0.begin(), r.i0.end(), i0);
-    if (i1) std::copy(r.i1.begin(), r.i1.end(), i1);
-    if (count) std::copy(r.count.begin(), r.count.end(), count);
-    if (sums) {
-        sums[0] = r.sumCells;
-        sums[1] = r.sumRows;
-        sums[2] = r.sumColumns;
-    }
-    return EM2_OK;
-}
-
-void em2_contingency_free(em2_contingency* table) { delete table; }
 
 }  // extern "C"

@@ -32,9 +32,8 @@
 
 #include "em2_device.h"
 #include "em2_expression.h"
-#include "em2_hip_util.h"
+#include "em2_entry.h"
 #include "em2_csr.h"
-#include "em2_cluster_graph.h"
 #include "../../include/em2_lsh.h"
 
 #include <cstring>
@@ -48,7 +47,56 @@
 #include <unordered_map>
 #include <unordered_set>
 
+#include <memory>
+#include <string>
+#include <vector>
+
+// What the device code and the C entry points at the end of this file share.
 namespace em2 {
+
+struct ClusterStatus {
+    int code;                   // EM2_OK or an EM2_ERROR_* of include/em2_lsh.h
+    std::string message;
+};
+
+// The device side of ClusterGraph::computeAverageGeneExpression / computeSimilarities (src/ClusterGraph.cpp:125-169):
+// holds the expression counts and the table of averages [cluster][gene] in device memory between the calls.
+class ClusterDevice {
+public:
+    ClusterDevice();
+    ~ClusterDevice();
+    ClusterDevice(const ClusterDevice&) = delete;
+    ClusterDevice& operator=(const ClusterDevice&) = delete;
+    ClusterStatus upload(const char* who, const uint64_t* toc, const CountIn* data, uint32_t rowCount, uint32_t geneCount);
+    ClusterStatus setAverages(const double* averages, uint32_t clusterCount, uint32_t geneCount);
+    ClusterStatus averages(const char* who, const uint32_t* cellRows, const uint64_t* offsets, uint32_t clusterCount, double* hostAverages);
+    ClusterStatus similarities(const char* who, const uint32_t* edge0, const uint32_t* edge1, uint64_t edgeCount, double* similarity);
+
+private:
+    struct State;
+    State* state;
+};
+
+// What ExpressionMatrix::createClusterGraph (src/ExpressionMatrix.cpp:2153-2181) leaves in the ClusterGraph.  Clusters in
+// vertex order; cells and unclusteredCells are cell-graph vertex indices; edges in the order of their creation.
+struct ClusterGraphResult {
+    uint32_t geneCount = 0;
+    std::vector<uint32_t> clusterIds;
+    std::vector<uint64_t> cellOffsets;
+    std::vector<uint32_t> cells, unclusteredCells;
+    std::vector<double> averages;
+    std::vector<uint32_t> edgeCluster0, edgeCluster1;
+    std::vector<double> edgeSimilarity;
+    uint32_t initialClusterCount = 0;       // vertices and edges of the constructor, before the merge
+    uint64_t initialEdgeCount = 0;
+    double averagesSeconds = 0., similaritiesSeconds = 0., totalSeconds = 0.;
+};
+
+static ClusterStatus createClusterGraph(const uint64_t* toc, const CountIn* data, uint32_t rowCount, uint32_t geneCount,
+                                        const uint32_t* vertexRows, uint32_t vertexCount, const uint32_t* edgeVertex0,
+                                        const uint32_t* edgeVertex1, uint64_t edgeCount, const uint32_t* labels, uint64_t minClusterSize,
+                                        uint64_t k, double similarityThreshold, double similarityThresholdForMerge, ClusterGraphResult& out);
+
 namespace {
 
 constexpr uint32_t kChunk = 1024;                   // doubles of LDS per wave in the sequential-sum kernels
@@ -627,3 +675,110 @@ ClusterStatus createClusterGraph(const uint64_t* toc, const CountIn* data, uint3
 }
 
 }  // namespace em2
+
+
+// ---- the C entry points (include/em2_lsh.h) ----
+
+using namespace em2::entry;
+
+extern "C" {
+
+struct em2_cluster_graph {
+    em2::ClusterGraphResult result;
+};
+
+static int clusterStatus(const em2::ClusterStatus& status) { return status.code == EM2_OK ? EM2_OK : fail(status.code, status.message); }
+
+int em2_cluster_average_expression(const uint64_t* toc, const em2_count* data, uint32_t cellCount, uint32_t geneCount,
+                                   const uint32_t* clusterCells, const uint64_t* clusterOffsets, uint32_t clusterCount,
+                                   double* averages)
+{
+    const char* who = "em2_cluster_average_expression";
+    if (geneCount == 0) return failArgument(who, "geneCount must be positive");
+    if (clusterCount == 0) return EM2_OK;
+    if (!toc || !clusterOffsets || !averages || (clusterOffsets[clusterCount] && !clusterCells)) return failNull(who);
+    if (clusterOffsets[0] != 0) return failArgument(who, "clusterOffsets must start at 0");
+    if (!haveDevice()) return failNoDevice(who);
+    em2::ClusterDevice device;
+    int rc = clusterStatus(device.upload(who, toc, reinterpret_cast<const em2::CountIn*>(data), cellCount, geneCount));
+    if (rc != EM2_OK) return rc;
+    return clusterStatus(device.averages(who, clusterCells, clusterOffsets, clusterCount, averages));
+}
+
+int em2_cluster_similarities(const double* averages, uint32_t clusterCount, uint32_t geneCount, const uint32_t* edgeCluster0,
+                             const uint32_t* edgeCluster1, uint64_t edgeCount, double* similarity)
+{
+    const char* who = "em2_cluster_similarities";
+    if (geneCount == 0) return failArgument(who, "geneCount must be positive");
+    if (edgeCount == 0) return EM2_OK;
+    if (!averages || !edgeCluster0 || !edgeCluster1 || !similarity) return failNull(who);
+    if (!haveDevice()) return failNoDevice(who);
+    em2::ClusterDevice device;
+    const int rc = clusterStatus(device.setAverages(averages, clusterCount, geneCount));
+    if (rc != EM2_OK) return rc;
+    return clusterStatus(device.similarities(who, edgeCluster0, edgeCluster1, edgeCount, similarity));
+}
+
+int em2_cluster_graph_create(const uint64_t* toc, const em2_count* data, uint32_t rowCount, uint32_t geneCount,
+                             const uint32_t* vertexRows, uint32_t vertexCount, const uint32_t* edgeVertex0,
+                             const uint32_t* edgeVertex1, uint64_t edgeCount, const uint32_t* labels, uint64_t minClusterSize,
+                             uint64_t k, double similarityThreshold, double similarityThresholdForMerge, em2_cluster_graph** graph)
+{
+    const char* who = "em2_cluster_graph_create";
+    if (!graph) return failNull(who);
+    *graph = nullptr;
+    if (geneCount == 0) return failArgument(who, "geneCount must be positive");
+    if (!toc || (vertexCount && !labels) || (edgeCount && (!edgeVertex0 || !edgeVertex1))) return failNull(who);
+    if (!haveDevice()) return failNoDevice(who);
+    std::unique_ptr<em2_cluster_graph> g(new em2_cluster_graph);
+    const int rc = clusterStatus(em2::createClusterGraph(toc, reinterpret_cast<const em2::CountIn*>(data), rowCount, geneCount, vertexRows,
+                                                         vertexCount, edgeVertex0, edgeVertex1, edgeCount, labels, minClusterSize, k,
+                                                         similarityThreshold, similarityThresholdForMerge, g->result));
+    if (rc != EM2_OK) return rc;
+    *graph = g.release();
+    return EM2_OK;
+}
+
+int em2_cluster_graph_sizes(const em2_cluster_graph* graph, uint32_t* clusterCount, uint32_t* geneCount, uint64_t* clusteredCellCount,
+                            uint64_t* unclusteredCellCount, uint64_t* edgeCount)
+{
+    if (!graph) return failNull("em2_cluster_graph_sizes");
+    const em2::ClusterGraphResult& r = graph->result;
+    if (clusterCount) *clusterCount = uint32_t(r.clusterIds.size());
+    if (geneCount) *geneCount = r.geneCount;
+    if (clusteredCellCount) *clusteredCellCount = r.cells.size();
+    if (unclusteredCellCount) *unclusteredCellCount = r.unclusteredCells.size();
+    if (edgeCount) *edgeCount = r.edgeSimilarity.size();
+    return EM2_OK;
+}
+
+int em2_cluster_graph_get(const em2_cluster_graph* graph, uint32_t* clusterIds, uint64_t* cellOffsets, uint32_t* cells,
+                          uint32_t* unclusteredCells, double* averages, uint32_t* edgeCluster0, uint32_t* edgeCluster1,
+                          double* edgeSimilarity)
+{
+    if (!graph) return failNull("em2_cluster_graph_get");
+    const em2::ClusterGraphResult& r = graph->result;
+    if (clusterIds) std::copy(r.clusterIds.begin(), r.clusterIds.end(), clusterIds);
+    if (cellOffsets) std::copy(r.cellOffsets.begin(), r.cellOffsets.end(), cellOffsets);
+    if (cells) std::copy(r.cells.begin(), r.cells.end(), cells);
+    if (unclusteredCells) std::copy(r.unclusteredCells.begin(), r.unclusteredCells.end(), unclusteredCells);
+    if (averages) std::copy(r.averages.begin(), r.averages.end(), averages);
+    if (edgeCluster0) std::copy(r.edgeCluster0.begin(), r.edgeCluster0.end(), edgeCluster0);
+    if (edgeCluster1) std::copy(r.edgeCluster1.begin(), r.edgeCluster1.end(), edgeCluster1);
+    if (edgeSimilarity) std::copy(r.edgeSimilarity.begin(), r.edgeSimilarity.end(), edgeSimilarity);
+    return EM2_OK;
+}
+
+int em2_cluster_graph_facts(const em2_cluster_graph* graph, double* values, uint32_t valueCount)
+{
+    if (!graph || (valueCount && !values)) return failNull("em2_cluster_graph_facts");
+    const em2::ClusterGraphResult& r = graph->result;
+    const double facts[5] = {r.totalSeconds, r.averagesSeconds, r.similaritiesSeconds, double(r.initialClusterCount),
+                             double(r.initialEdgeCount)};
+    for (uint32_t i = 0; i < valueCount; ++i) values[i] = i < 5u ? facts[i] : 0.;
+    return EM2_OK;
+}
+
+void em2_cluster_graph_free(em2_cluster_graph* graph) { delete graph; }
+
+}  // extern "C"

@@ -19,15 +19,49 @@
 // Every kernel that reads an id tests it against n0 / n1 before an address is formed with it, writes nothing for an element
 // that fails and raises the error word; the host reads that word before anything derived from the ids is used.
 
-#include "em2_contingency.h"
-#include "em2_hip_util.h"
+#include "em2_entry.h"
 #include "em2_scratch.h"
 #include "em2_wave.h"
 
 #include <cstring>            // (rocPRIM calls memset without including it)
 #include <rocprim/rocprim.hpp>
 
+#include <algorithm>
+#include <memory>
+#include <string>
+#include <vector>
+
+// What the device code and the C entry points at the end of this file share.
 namespace em2 {
+
+// The contingency table of two labelings of n items (the `matrix` of ExpressionMatrix::computeMetaDataRandIndex,
+// src/ExpressionMatrix.cpp:1369-1381, and what computeRandIndex, src/randIndex.hpp:38-85, sums over it), in host memory.
+//   rowTotals [n0], columnTotals [n1]       the items with id0 == i / id1 == j;
+//   i0 / i1 / count                         the table cells that are not zero, ascending by (i0, i1);
+//   sumCells, sumRows, sumColumns           the sums of v (v - 1) over the cells, of t (t - 1) over the row totals and over
+//                                           the column totals.  All three are at most n (n - 1) < 2^64 (n < 2^32).
+struct ContingencyResult {
+    uint32_t n0 = 0, n1 = 0;
+    uint64_t n = 0;
+    int path = 0;                                  // the path that ran: kContingencyLds or kContingencySort
+    std::vector<uint64_t> rowTotals, columnTotals;
+    std::vector<uint32_t> i0, i1;
+    std::vector<uint64_t> count;
+    uint64_t sumCells = 0, sumRows = 0, sumColumns = 0;
+};
+
+constexpr int kContingencyAutomatic = 0;
+constexpr int kContingencyLds = 1;                 // a private 32-bit table per workgroup in LDS
+constexpr int kContingencySort = 2;                // radix sort of the (id0, id1) keys, then the runs
+constexpr uint64_t kContingencyLdsCells = 16384;   // n0 * n1 at most, for the LDS path: 64 KiB of counters
+
+// d_id0 / d_id1 [n] in device memory, n < 2^32, n0 and n1 positive; path: one of the three constants, the LDS path only where
+// n0 * n1 <= kContingencyLdsCells (the caller checks all of this).  *inputError is set to 1 and nothing is computed where an
+// id0 is not below n0 or an id1 is not below n1: the kernels test an id before they form an address with it.
+// Takes its scratch from the cache of em2_scratch.h; synchronises the stream.
+static hipError_t runContingency(const uint32_t* d_id0, const uint32_t* d_id1, uint64_t n, uint32_t n0, uint32_t n1, int path,
+                                 ContingencyResult& out, uint32_t* inputError, hipStream_t stream);
+
 namespace {
 
 typedef unsigned long long u64;      // (the type HIP's 64-bit atomicAdd takes)
@@ -361,3 +395,93 @@ hipError_t runContingency(const uint32_t* d_id0, const uint32_t* d_id1, uint64_t
 }
 
 }  // namespace em2
+
+
+// ---- the C entry points (include/em2_lsh.h) ----
+
+using namespace em2::entry;
+using em2::DeviceBuffer;
+
+extern "C" {
+
+struct em2_contingency {
+    em2::ContingencyResult result;
+};
+
+static int contingencyCreate(const char* who, bool idsOnDevice, const uint32_t* id0, const uint32_t* id1, uint64_t n, uint32_t n0,
+                             uint32_t n1, int path, em2_contingency** out)
+{
+    if (!out) return failNull(who);
+    *out = nullptr;
+    if (n && (!id0 || !id1)) return failNull(who);
+    if (n0 == 0 || n1 == 0) return failArgument(who, "n0 and n1 must be positive");
+    if (path != em2::kContingencyAutomatic && path != em2::kContingencyLds && path != em2::kContingencySort) {
+        return failArgument(who, "path must be 0 (automatic), 1 (LDS) or 2 (sort)");
+    }
+    if (path == em2::kContingencyLds && uint64_t(n0) * n1 > em2::kContingencyLdsCells) {
+        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": the LDS path holds a table of at most " +
+                                                    std::to_string(em2::kContingencyLdsCells) + " cells");
+    }
+    // (the three sums are at most n (n - 1), and a run's first element is kept in 32 bits)
+    if (n > 0xffffffffull) return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": more than 2^32 - 1 elements are not supported");
+    if (!haveDevice()) return failNoDevice(who);
+    DeviceBuffer d0, d1;
+    if (!idsOnDevice && n) {
+        EM2_HIP(d0.upload(id0, size_t(n)));
+        EM2_HIP(d1.upload(id1, size_t(n)));
+    }
+    std::unique_ptr<em2_contingency> c(new em2_contingency);
+    uint32_t inputError = 0;
+    const hipError_t status = em2::runContingency(idsOnDevice || !n ? id0 : d0.as<uint32_t>(), idsOnDevice || !n ? id1 : d1.as<uint32_t>(), n,
+                                                  n0, n1, path, c->result, &inputError, nullptr);
+    if (status != hipSuccess || inputError) {
+        EM2_HIP(status);
+        return failArgument(who, "an id is not below its count (id0 < n0, id1 < n1)");
+    }
+    *out = c.release();
+    return EM2_OK;
+}
+
+int em2_contingency_create(const uint32_t* id0, const uint32_t* id1, uint64_t n, uint32_t n0, uint32_t n1, int path, em2_contingency** out)
+{
+    return contingencyCreate("em2_contingency", false, id0, id1, n, n0, n1, path, out);
+}
+
+int em2_dev_contingency(const uint32_t* d_id0, const uint32_t* d_id1, uint64_t n, uint32_t n0, uint32_t n1, int path, em2_contingency** out)
+{
+    return contingencyCreate("em2_dev_contingency", true, d_id0, d_id1, n, n0, n1, path, out);
+}
+
+int em2_contingency_sizes(const em2_contingency* table, uint32_t* n0, uint32_t* n1, uint64_t* n, uint64_t* nonZeroCount, int* path)
+{
+    if (!table) return failNull("em2_contingency_sizes");
+    const em2::ContingencyResult& r = table->result;
+    if (n0) *n0 = r.n0;
+    if (n1) *n1 = r.n1;
+    if (n) *n = r.n;
+    if (nonZeroCount) *nonZeroCount = r.count.size();
+    if (path) *path = r.path;
+    return EM2_OK;
+}
+
+int em2_contingency_get(const em2_contingency* table, uint64_t* rowTotals, uint64_t* columnTotals, uint32_t* i0, uint32_t* i1,
+                        uint64_t* count, uint64_t* sums)
+{
+    if (!table) return failNull("em2_contingency_get");
+    const em2::ContingencyResult& r = table->result;
+    if (rowTotals) std::copy(r.rowTotals.begin(), r.rowTotals.end(), rowTotals);
+    if (columnTotals) std::copy(r.columnTotals.begin(), r.columnTotals.end(), columnTotals);
+    if (i0) std::copy(r.i0.begin(), r.i0.end(), i0);
+    if (i1) std::copy(r.i1.begin(), r.i1.end(), i1);
+    if (count) std::copy(r.count.begin(), r.count.end(), count);
+    if (sums) {
+        sums[0] = r.sumCells;
+        sums[1] = r.sumRows;
+        sums[2] = r.sumColumns;
+    }
+    return EM2_OK;
+}
+
+void em2_contingency_free(em2_contingency* table) { delete table; }
+
+}  // extern "C"

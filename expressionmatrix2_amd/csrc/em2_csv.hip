@@ -18,7 +18,7 @@
 // A field is decided only where strtof's bits are proven (include/em2_lsh.h, em2_dev_csv_parse); everything else is deferred
 // to the host, which has the box's strtof.
 #include "em2_csv.h"
-#include "em2_hip_util.h"
+#include "em2_entry.h"
 #include "em2_scratch.h"
 #include "em2_wave.h"
 
@@ -30,7 +30,7 @@
 #include <memory>
 #include <string>
 
-extern "C" void em2_internal_set_last_error(const char* message);
+using namespace em2::entry;
 
 namespace em2 {
 
@@ -357,20 +357,6 @@ __global__ __launch_bounds__(256) void csvFieldsKernel(const FieldArguments a)
     if (staged) flushStaged(a, myKeys, myValues, staged, lane);
 }
 
-int failWith(int code, const std::string& message)
-{
-    em2_internal_set_last_error(message.c_str());
-    return code;
-}
-
-int failHip(const char* who, hipError_t e) { return failWith(EM2_ERROR_HIP, std::string(who) + ": " + hipGetErrorString(e)); }
-
-bool haveDevice()
-{
-    int n = 0;
-    return hipGetDeviceCount(&n) == hipSuccess && n > 0;
-}
-
 uint32_t tileBytesNow()
 {
     const uint32_t setting = tileBytesSetting.load();
@@ -457,20 +443,20 @@ int devCsvParse(const char* who, const char* d_text, uint64_t textBytes, const c
 {
     if (!counts || !separators || (textBytes && !d_text) || (expectedTokens && !d_keptCellOfColumn) || (lineCapacity && !d_lineTable) ||
         (tripleCapacity && (!d_tripleKeys || !d_tripleValues)) || (deferredCapacity && !d_deferred)) {
-        return failWith(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
+        return failNull(who);
     }
     if (!host::csvSeparatorsRunOnDevice(std::string(separators, separatorCount))) {
-        return failWith(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": the device takes 1 to 8 separator bytes, none of them '\"', '\\', "
+        return fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": the device takes 1 to 8 separator bytes, none of them '\"', '\\', "
                                                                        "a line feed, a carriage return or NUL");
     }
-    if (textBytes > kMaxTextBytes) return failWith(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": a chunk is at most 0xf0000000 bytes");
-    if (!haveDevice()) return failWith(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
+    if (textBytes > kMaxTextBytes) return failArgument(who, "a chunk is at most 0xf0000000 bytes");
+    if (!haveDevice()) return failNoDevice(who);
     uint64_t packed = 0;
     for (uint32_t k = 0; k < separatorCount; k++) packed |= uint64_t(uint8_t(separators[k])) << (8u * k);
-    const hipError_t e = runParse(reinterpret_cast<const uint8_t*>(d_text), uint32_t(textBytes), packed, separatorCount, expectedTokens,
-                                  d_keptCellOfColumn, lineBase, lineCapacity, d_lineTable, tripleCapacity, d_tripleKeys, d_tripleValues,
-                                  deferredCapacity, d_deferred, counts, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? EM2_OK : failHip(who, e);
+    EM2_HIP_FOR(who, runParse(reinterpret_cast<const uint8_t*>(d_text), uint32_t(textBytes), packed, separatorCount, expectedTokens,
+                              d_keptCellOfColumn, lineBase, lineCapacity, d_lineTable, tripleCapacity, d_tripleKeys, d_tripleValues,
+                              deferredCapacity, d_deferred, counts, static_cast<hipStream_t>(stream)));
+    return EM2_OK;
 }
 
 // key in: cell << 32 | line; out: cell << lineBits | line.
@@ -530,12 +516,6 @@ struct CsvSession {
 CsvSession* csvSessionCreate() { return new CsvSession; }
 void csvSessionDestroy(CsvSession* session) { delete session; }
 
-#define EM2_CSV_HIP(call)                                           \
-    do {                                                            \
-        const hipError_t csvError_ = (call);                        \
-        if (csvError_ != hipSuccess) return failHip(who, csvError_); \
-    } while (0)
-
 int csvSessionChunk(CsvSession* session, const char* text, uint64_t bytes, const std::string& separators, uint32_t expectedTokens,
                     const std::vector<uint32_t>& keptCellOfColumn, uint32_t lineBase, std::vector<CsvLine>& lines,
                     std::vector<CsvDeferred>& deferred)
@@ -543,14 +523,13 @@ int csvSessionChunk(CsvSession* session, const char* text, uint64_t bytes, const
     const char* who = "em2_matrix_add_cells_csv";
     lines.clear();
     deferred.clear();
-    if (!haveDevice()) return failWith(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
+    if (!haveDevice()) return failNoDevice(who);
     if (bytes == 0) return EM2_OK;
     Scratch dText;
     DeviceBuffer dKept, dLines, dDeferred;
-    EM2_CSV_HIP(dText.allocate(size_t(bytes)));
-    EM2_CSV_HIP(hipMemcpy(dText.p, text, size_t(bytes), hipMemcpyHostToDevice));
-    EM2_CSV_HIP(dKept.allocate(keptCellOfColumn.size() * sizeof(uint32_t)));
-    EM2_CSV_HIP(hipMemcpy(dKept.p, keptCellOfColumn.data(), keptCellOfColumn.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    EM2_HIP_FOR(who, dText.allocate(size_t(bytes)));
+    EM2_HIP_FOR(who, hipMemcpy(dText.p, text, size_t(bytes), hipMemcpyHostToDevice));
+    EM2_HIP_FOR(who, dKept.upload(keptCellOfColumn.data(), keptCellOfColumn.size()));
     // A line that passes has at least expectedTokens bytes with its '\n'; shorter ones, a first guess for the counts of a
     // file that is mostly "0", and a first guess for the deferred fields are put right by a second run with what the first
     // one counted.
@@ -560,17 +539,17 @@ int csvSessionChunk(CsvSession* session, const char* text, uint64_t bytes, const
     for (int attempt = 0;; attempt++) {
         part.keys.reset(new Scratch);
         part.values.reset(new Scratch);
-        EM2_CSV_HIP(part.keys->allocate(size_t(tripleCapacity) * sizeof(uint64_t)));
-        EM2_CSV_HIP(part.values->allocate(size_t(tripleCapacity) * sizeof(float)));
-        EM2_CSV_HIP(dLines.allocate(size_t(lineCapacity) * sizeof(CsvLine)));
-        EM2_CSV_HIP(dDeferred.allocate(size_t(deferredCapacity) * sizeof(CsvDeferred)));
+        EM2_HIP_FOR(who, part.keys->allocate(size_t(tripleCapacity) * sizeof(uint64_t)));
+        EM2_HIP_FOR(who, part.values->allocate(size_t(tripleCapacity) * sizeof(float)));
+        EM2_HIP_FOR(who, dLines.allocateFor<CsvLine>(size_t(lineCapacity)));
+        EM2_HIP_FOR(who, dDeferred.allocateFor<CsvDeferred>(size_t(deferredCapacity)));
         const int rc = devCsvParse(who, static_cast<const char*>(dText.p), bytes, separators.data(), uint32_t(separators.size()),
                                    expectedTokens, dKept.as<uint32_t>(), lineBase, uint32_t(lineCapacity), dLines.as<uint32_t>(),
                                    tripleCapacity, part.keys->as<uint64_t>(), part.values->as<float>(), deferredCapacity,
                                    dDeferred.as<uint32_t>(), counts, nullptr);
         if (rc != EM2_OK) return rc;
         if (counts[0] <= lineCapacity && counts[1] <= tripleCapacity && counts[2] <= deferredCapacity) break;
-        if (attempt == 2) return failWith(EM2_ERROR_RUNTIME, std::string(who) + ": the device pass does not settle on its counts");
+        if (attempt == 2) return fail(EM2_ERROR_RUNTIME, std::string(who) + ": the device pass does not settle on its counts");
         if (counts[0] > lineCapacity) {                                       // (the fields were not read yet)
             lineCapacity = counts[0];
         } else {
@@ -578,11 +557,11 @@ int csvSessionChunk(CsvSession* session, const char* text, uint64_t bytes, const
             deferredCapacity = counts[2] > deferredCapacity ? counts[2] : deferredCapacity;
         }
     }
-    if (uint64_t(lineBase) + counts[0] >= kNone) return failWith(EM2_ERROR_UNSUPPORTED, std::string(who) + ": too many lines");
+    if (uint64_t(lineBase) + counts[0] >= kNone) return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": too many lines");
     lines.resize(size_t(counts[0]));
     deferred.resize(size_t(counts[2]));
-    if (counts[0]) EM2_CSV_HIP(hipMemcpy(lines.data(), dLines.p, lines.size() * sizeof(CsvLine), hipMemcpyDeviceToHost));
-    if (counts[2]) EM2_CSV_HIP(hipMemcpy(deferred.data(), dDeferred.p, deferred.size() * sizeof(CsvDeferred), hipMemcpyDeviceToHost));
+    EM2_HIP_FOR(who, dLines.download(lines.data(), lines.size()));
+    EM2_HIP_FOR(who, dDeferred.download(deferred.data(), deferred.size()));
     part.count = counts[1];
     session->parts.push_back(std::move(part));
     return EM2_OK;
@@ -599,7 +578,7 @@ int csvSessionFinish(CsvSession* session, const std::vector<CsvTriple>& extra, u
     data.clear();
     cells.assign(keptCellCount, CellRecord());
     if (keptCellCount == 0) return EM2_OK;
-    if (!haveDevice()) return failWith(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
+    if (!haveDevice()) return failNoDevice(who);
     uint64_t total = extra.size();
     for (const CsvSession::Part& part : session->parts) total += part.count;
 
@@ -608,16 +587,16 @@ int csvSessionFinish(CsvSession* session, const std::vector<CsvTriple>& extra, u
     const uint32_t lineBits = bitsFor(lineCount), cellBits = bitsFor(keptCellCount);
     Scratch keysIn, keysOut, valuesIn, valuesOut, sortTemp, dIndices;
     DeviceBuffer dIndptr, dGenes, dKept, dStatus, dDuplicate, dToc, dData, dCells;
-    EM2_CSV_HIP(keysIn.allocate(size_t(total) * sizeof(uint64_t)));
-    EM2_CSV_HIP(keysOut.allocate(size_t(total) * sizeof(uint64_t)));
-    EM2_CSV_HIP(valuesIn.allocate(size_t(total) * sizeof(float)));
-    EM2_CSV_HIP(valuesOut.allocate(size_t(total) * sizeof(float)));
-    EM2_CSV_HIP(dIndices.allocate(size_t(total) * sizeof(uint32_t)));
+    EM2_HIP_FOR(who, keysIn.allocate(size_t(total) * sizeof(uint64_t)));
+    EM2_HIP_FOR(who, keysOut.allocate(size_t(total) * sizeof(uint64_t)));
+    EM2_HIP_FOR(who, valuesIn.allocate(size_t(total) * sizeof(float)));
+    EM2_HIP_FOR(who, valuesOut.allocate(size_t(total) * sizeof(float)));
+    EM2_HIP_FOR(who, dIndices.allocate(size_t(total) * sizeof(uint32_t)));
     uint64_t at = 0;
     for (CsvSession::Part& part : session->parts) {
         if (part.count) {
-            EM2_CSV_HIP(hipMemcpy(keysIn.as<uint64_t>() + at, part.keys->p, size_t(part.count) * sizeof(uint64_t), hipMemcpyDeviceToDevice));
-            EM2_CSV_HIP(hipMemcpy(valuesIn.as<float>() + at, part.values->p, size_t(part.count) * sizeof(float), hipMemcpyDeviceToDevice));
+            EM2_HIP_FOR(who, hipMemcpy(keysIn.as<uint64_t>() + at, part.keys->p, size_t(part.count) * sizeof(uint64_t), hipMemcpyDeviceToDevice));
+            EM2_HIP_FOR(who, hipMemcpy(valuesIn.as<float>() + at, part.values->p, size_t(part.count) * sizeof(float), hipMemcpyDeviceToDevice));
         }
         at += part.count;
         part.keys.reset();
@@ -629,66 +608,63 @@ int csvSessionFinish(CsvSession* session, const std::vector<CsvTriple>& extra, u
         std::vector<float> values(extra.size());
         for (size_t i = 0; i < extra.size(); i++) {
             if (extra[i].cell >= keptCellCount || extra[i].line >= lineCount) {
-                return failWith(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": a count of the host names no kept cell or no line");
+                return failArgument(who, "a count of the host names no kept cell or no line");
             }
             keys[i] = (uint64_t(extra[i].cell) << 32) | extra[i].line;
             values[i] = extra[i].value;
         }
-        EM2_CSV_HIP(hipMemcpy(keysIn.as<uint64_t>() + at, keys.data(), keys.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-        EM2_CSV_HIP(hipMemcpy(valuesIn.as<float>() + at, values.data(), values.size() * sizeof(float), hipMemcpyHostToDevice));
+        EM2_HIP_FOR(who, hipMemcpy(keysIn.as<uint64_t>() + at, keys.data(), keys.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+        EM2_HIP_FOR(who, hipMemcpy(valuesIn.as<float>() + at, values.data(), values.size() * sizeof(float), hipMemcpyHostToDevice));
     }
-    EM2_CSV_HIP(dIndptr.allocate((size_t(keptCellCount) + 1u) * sizeof(uint64_t)));
+    EM2_HIP_FOR(who, dIndptr.allocateFor<uint64_t>(size_t(keptCellCount) + 1u));
     const uint64_t* sortedKeys = keysIn.as<uint64_t>();
     const float* sortedValues = valuesIn.as<float>();
     if (total) {
         csvPackKeysKernel<<<dim3(gridFor(total)), dim3(256)>>>(keysIn.as<uint64_t>(), total, lineBits);
-        EM2_CSV_HIP(hipGetLastError());
+        EM2_HIP_FOR(who, hipGetLastError());
         size_t tempBytes = 0;
-        EM2_CSV_HIP(rocprim::radix_sort_pairs(nullptr, tempBytes, keysIn.as<uint64_t>(), keysOut.as<uint64_t>(), valuesIn.as<float>(),
+        EM2_HIP_FOR(who, rocprim::radix_sort_pairs(nullptr, tempBytes, keysIn.as<uint64_t>(), keysOut.as<uint64_t>(), valuesIn.as<float>(),
                                               valuesOut.as<float>(), size_t(total), 0u, lineBits + cellBits));
-        EM2_CSV_HIP(sortTemp.allocate(tempBytes));
-        EM2_CSV_HIP(rocprim::radix_sort_pairs(sortTemp.p, tempBytes, keysIn.as<uint64_t>(), keysOut.as<uint64_t>(), valuesIn.as<float>(),
+        EM2_HIP_FOR(who, sortTemp.allocate(tempBytes));
+        EM2_HIP_FOR(who, rocprim::radix_sort_pairs(sortTemp.p, tempBytes, keysIn.as<uint64_t>(), keysOut.as<uint64_t>(), valuesIn.as<float>(),
                                               valuesOut.as<float>(), size_t(total), 0u, lineBits + cellBits));
         sortedKeys = keysOut.as<uint64_t>();
         sortedValues = valuesOut.as<float>();
         csvIndicesKernel<<<dim3(gridFor(total)), dim3(256)>>>(sortedKeys, total, lineBits, dIndices.as<uint32_t>());
-        EM2_CSV_HIP(hipGetLastError());
+        EM2_HIP_FOR(who, hipGetLastError());
     }
     csvIndptrKernel<<<dim3(gridFor(uint64_t(keptCellCount) + 1u)), dim3(256)>>>(sortedKeys, total, lineBits, keptCellCount, dIndptr.as<uint64_t>());
-    EM2_CSV_HIP(hipGetLastError());
-    EM2_CSV_HIP(hipDeviceSynchronize());
+    EM2_HIP_FOR(who, hipGetLastError());
+    EM2_HIP_FOR(who, hipDeviceSynchronize());
 
     // addCell's storing part: the rows are the cells, the indices the lines, the map the ids the file's genes get.
-    EM2_CSV_HIP(dGenes.allocate(size_t(lineCount) * sizeof(uint32_t)));
-    if (lineCount) EM2_CSV_HIP(hipMemcpy(dGenes.p, geneIdOfLine.data(), size_t(lineCount) * sizeof(uint32_t), hipMemcpyHostToDevice));
-    EM2_CSV_HIP(dKept.allocate(size_t(keptCellCount) * sizeof(uint32_t)));
-    EM2_CSV_HIP(dStatus.allocate(size_t(keptCellCount) * sizeof(uint32_t)));
-    EM2_CSV_HIP(dDuplicate.allocate(size_t(keptCellCount) * sizeof(uint32_t)));
-    EM2_CSV_HIP(dToc.allocate((size_t(keptCellCount) + 1u) * sizeof(uint64_t)));
+    EM2_HIP_FOR(who, dGenes.upload(geneIdOfLine.data(), lineCount));
+    EM2_HIP_FOR(who, dKept.allocateFor<uint32_t>(keptCellCount));
+    EM2_HIP_FOR(who, dStatus.allocateFor<uint32_t>(keptCellCount));
+    EM2_HIP_FOR(who, dDuplicate.allocateFor<uint32_t>(keptCellCount));
+    EM2_HIP_FOR(who, dToc.allocateFor<uint64_t>(size_t(keptCellCount) + 1u));
     int rc = em2_dev_ingest_count(dIndptr.as<uint64_t>(), dIndices.as<uint32_t>(), sortedValues, nullptr, keptCellCount, dGenes.as<uint32_t>(),
                                   lineCount, dKept.as<uint32_t>(), dStatus.as<uint32_t>(), dDuplicate.as<uint32_t>(), dToc.as<uint64_t>(),
                                   nullptr);
     if (rc != EM2_OK) return rc;
-    EM2_CSV_HIP(hipMemcpy(status.data(), dStatus.p, size_t(keptCellCount) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    EM2_CSV_HIP(hipMemcpy(toc.data(), dToc.p, (size_t(keptCellCount) + 1u) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    EM2_HIP_FOR(who, dStatus.download(status.data(), keptCellCount));
+    EM2_HIP_FOR(who, dToc.download(toc.data(), size_t(keptCellCount) + 1u));
     for (uint32_t s : status) {
         if (s != 0u) *failed = true;
     }
     if (*failed) return EM2_OK;
     const uint64_t outCount = toc[keptCellCount];
-    EM2_CSV_HIP(dData.allocate(size_t(outCount) * sizeof(em2_count)));
-    EM2_CSV_HIP(dCells.allocate(size_t(keptCellCount) * sizeof(CellRecord)));
-    EM2_CSV_HIP(hipMemset(dCells.p, 0, size_t(keptCellCount) * sizeof(CellRecord)));
+    EM2_HIP_FOR(who, dData.allocateFor<em2_count>(size_t(outCount)));
+    EM2_HIP_FOR(who, dCells.allocateFor<CellRecord>(keptCellCount));
+    EM2_HIP_FOR(who, hipMemset(dCells.p, 0, size_t(keptCellCount) * sizeof(CellRecord)));
     rc = em2_dev_ingest_fill(dIndptr.as<uint64_t>(), dIndices.as<uint32_t>(), sortedValues, nullptr, keptCellCount, dGenes.as<uint32_t>(),
                              lineCount, dToc.as<uint64_t>(), dData.as<em2_count>(), dCells.p, nullptr);
     if (rc != EM2_OK) return rc;
     data.resize(size_t(outCount));
-    if (outCount) EM2_CSV_HIP(hipMemcpy(data.data(), dData.p, size_t(outCount) * sizeof(em2_count), hipMemcpyDeviceToHost));
-    EM2_CSV_HIP(hipMemcpy(cells.data(), dCells.p, size_t(keptCellCount) * sizeof(CellRecord), hipMemcpyDeviceToHost));
+    EM2_HIP_FOR(who, dData.download(data.data(), size_t(outCount)));
+    EM2_HIP_FOR(who, dCells.download(cells.data(), keptCellCount));
     return EM2_OK;
 }
-
-#undef EM2_CSV_HIP
 
 }  // namespace host
 }  // namespace em2

@@ -20,7 +20,10 @@
 
 #include "em2_device.h"
 #include "em2_expression.h"
-#include "em2_hip_util.h"
+#include "em2_entry.h"
+#include "em2_csr.h"
+
+#include <string>
 
 namespace em2 {
 namespace {
@@ -160,3 +163,103 @@ hipError_t runDenseExpression(const uint64_t* d_toc, const CountIn* d_data, cons
 }
 
 }  // namespace em2
+
+
+// ---- the C entry points (include/em2_lsh.h) ----
+
+using namespace em2::entry;
+using em2::DeviceBuffer;
+
+extern "C" {
+
+size_t em2_dev_dense_expression_workspace(uint32_t rowCount) { return em2::denseExpressionWorkspaceBytes(rowCount); }
+
+// The device call under the name of the entry point that makes it.
+static int devDenseExpression(const char* who, const uint64_t* d_toc, const em2_count* d_data, const uint32_t* d_cellIds, uint32_t cellCount,
+                              const uint32_t* d_geneLocalIds, uint32_t globalGeneCount, uint32_t geneCount, int normalizationMethod,
+                              uint32_t rowBegin, uint32_t rowEnd, int elementType, void* d_out, uint64_t pitchElements, void* d_workspace,
+                              size_t workspaceBytes, void* stream)
+{
+    if (normalizationMethod < 0 || normalizationMethod > 2) return failArgument(who, "invalid normalization method (0 none, 1 L1, 2 L2)");
+    if (elementType != EM2_DENSE_FLOAT64 && elementType != EM2_DENSE_FLOAT32) {
+        return failArgument(who, "elementType must be 0 (float64) or 1 (float32)");
+    }
+    if (geneCount == 0) return failArgument(who, "geneCount must be positive");
+    if (rowBegin > rowEnd || rowEnd > cellCount) return failArgument(who, "rowBegin <= rowEnd <= cellCount is required");
+    if (pitchElements < geneCount) return failArgument(who, "pitchElements is below geneCount");
+    if (rowBegin == rowEnd) return EM2_OK;
+    if (!d_toc || !d_out || !d_workspace) return failNull(who);
+    const size_t elementBytes = elementType == EM2_DENSE_FLOAT64 ? sizeof(double) : sizeof(float);
+    if (reinterpret_cast<uintptr_t>(d_out) % elementBytes) return failArgument(who, "d_out is not aligned to its element");
+    if (workspaceBytes < em2::denseExpressionWorkspaceBytes(rowEnd - rowBegin)) return failArgument(who, "workspace too small");
+    uint32_t inputError = 0;
+    static_assert(EM2_DENSE_FLOAT64 == 0 && EM2_DENSE_FLOAT32 == 1, "the element types as numbers");
+    const bool elementsAreDouble = elementType == 0;          // (not by name: EM2_HIP keeps the call's text)
+    EM2_HIP(em2::runDenseExpression(d_toc, reinterpret_cast<const em2::CountIn*>(d_data), d_cellIds, d_geneLocalIds, globalGeneCount, geneCount,
+                                    normalizationMethod, rowBegin, rowEnd, elementsAreDouble, d_out, size_t(pitchElements),
+                                    d_workspace, workspaceBytes, &inputError, static_cast<hipStream_t>(stream)));
+    if (inputError) return failArgument(who, em2::inputErrorText(inputError));
+    return EM2_OK;
+}
+
+int em2_dev_dense_expression(const uint64_t* d_toc, const em2_count* d_data, const uint32_t* d_cellIds, uint32_t cellCount,
+                             const uint32_t* d_geneLocalIds, uint32_t globalGeneCount, uint32_t geneCount, int normalizationMethod,
+                             uint32_t rowBegin, uint32_t rowEnd, int elementType, void* d_out, uint64_t pitchElements,
+                             void* d_workspace, size_t workspaceBytes, void* stream)
+{
+    return devDenseExpression("em2_dev_dense_expression", d_toc, d_data, d_cellIds, cellCount, d_geneLocalIds, globalGeneCount, geneCount,
+                              normalizationMethod, rowBegin, rowEnd, elementType, d_out, pitchElements, d_workspace, workspaceBytes, stream);
+}
+
+static const size_t kDenseDeviceBufferBytes = size_t(1) << 30;          // em2_dense_expression's device buffer at most
+
+int em2_dense_expression(const uint64_t* toc, const em2_count* data, uint32_t csrCellCount, const uint32_t* cellIds, uint32_t cellCount,
+                         const uint32_t* geneLocalIds, uint32_t globalGeneCount, uint32_t geneCount, int normalizationMethod,
+                         int elementType, void* out, uint64_t pitchElements)
+{
+    const char* who = "em2_dense_expression";
+    if (normalizationMethod < 0 || normalizationMethod > 2) return failArgument(who, "invalid normalization method (0 none, 1 L1, 2 L2)");
+    if (elementType != EM2_DENSE_FLOAT64 && elementType != EM2_DENSE_FLOAT32) {
+        return failArgument(who, "elementType must be 0 (float64) or 1 (float32)");
+    }
+    if (geneCount == 0) return failArgument(who, "geneCount must be positive");
+    if (pitchElements < geneCount) return failArgument(who, "pitchElements is below geneCount");
+    if (!cellIds && cellCount != csrCellCount) return failArgument(who, "without cellIds cellCount must be csrCellCount");
+    if (cellCount == 0) return EM2_OK;
+    if (!toc || !out || (!geneLocalIds && globalGeneCount)) return failNull(who);
+    for (uint32_t i = 0; cellIds && i < cellCount; ++i) {
+        if (cellIds[i] >= csrCellCount) return failArgument(who, "a cell id is not below the cell count of the CSR");
+    }
+    em2::UploadedCsr csr;
+    if (const char* error = csr.check(toc, reinterpret_cast<const em2::CountIn*>(data), csrCellCount)) return failArgument(who, error);
+    if (!haveDevice()) return failNoDevice(who);
+    EM2_HIP(csr.upload());                     // (the device checks the gene ids before any kernel indexes with them)
+    DeviceBuffer dCellIds, dLocalIds, dOut, dWorkspace;
+    if (cellIds) EM2_HIP(dCellIds.upload(cellIds, cellCount));
+    if (geneLocalIds) EM2_HIP(dLocalIds.upload(geneLocalIds, globalGeneCount));
+    const size_t elementBytes = elementType == EM2_DENSE_FLOAT64 ? sizeof(double) : sizeof(float);
+    const size_t rowBytes = size_t(geneCount) * elementBytes;
+    const uint64_t rowsThatFit = kDenseDeviceBufferBytes / rowBytes;
+    const uint32_t chunkRows = uint32_t(rowsThatFit < 1 ? 1 : (rowsThatFit > cellCount ? cellCount : rowsThatFit));
+    const size_t workspaceBytes = em2::denseExpressionWorkspaceBytes(chunkRows);
+    EM2_HIP(dOut.allocate(size_t(chunkRows) * rowBytes));
+    EM2_HIP(dWorkspace.allocate(workspaceBytes));
+    for (uint32_t rowBegin = 0; rowBegin < cellCount; rowBegin += chunkRows) {
+        const uint32_t rowEnd = cellCount - rowBegin < chunkRows ? cellCount : rowBegin + chunkRows;
+        const int rc = devDenseExpression(who, csr.toc.as<uint64_t>(), csr.data.as<em2_count>(), cellIds ? dCellIds.as<uint32_t>() : nullptr,
+                                          cellCount, geneLocalIds ? dLocalIds.as<uint32_t>() : nullptr, globalGeneCount, geneCount,
+                                          normalizationMethod, rowBegin, rowEnd, elementType, dOut.p, geneCount, dWorkspace.p, workspaceBytes,
+                                          nullptr);
+        if (rc != EM2_OK) return rc;
+        // the geneCount elements of every row; the caller's padding stays as it is
+        char* const to = static_cast<char*>(out) + size_t(rowBegin) * size_t(pitchElements) * elementBytes;
+        if (pitchElements == geneCount) {
+            EM2_HIP(hipMemcpy(to, dOut.p, size_t(rowEnd - rowBegin) * rowBytes, hipMemcpyDeviceToHost));
+        } else {
+            EM2_HIP(hipMemcpy2D(to, size_t(pitchElements) * elementBytes, dOut.p, rowBytes, rowBytes, rowEnd - rowBegin, hipMemcpyDeviceToHost));
+        }
+    }
+    return EM2_OK;
+}
+
+}  // extern "C"

@@ -20,9 +20,7 @@
 // RCCL is bound at run time: the nccl* entry points are looked up in the process first (the library the caller created
 // the communicator with), then in librccl.so.1 / librccl.so -- libem2lsh.so itself has no link-time dependency on it.
 
-#include "../../include/em2_lsh.h"
-
-#include "em2_hip_util.h"
+#include "em2_entry.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -36,21 +34,9 @@
 #include <string>
 #include <vector>
 
-extern "C" void em2_internal_set_last_error(const char* message);
+using namespace em2::entry;
 
 namespace {
-
-int fail(int code, const std::string& message)
-{
-    em2_internal_set_last_error(message.c_str());
-    return code;
-}
-
-#define EM2_DIST_HIP(call)                                                                                  \
-    do {                                                                                                    \
-        hipError_t em2HipError_ = (call);                                                                   \
-        if (em2HipError_ != hipSuccess) return fail(EM2_ERROR_HIP, std::string(#call) + ": " + hipGetErrorString(em2HipError_)); \
-    } while (0)
 
 #define EM2_DIST_OK(call)                      \
     do {                                       \
@@ -227,7 +213,7 @@ int em2_dist_find_similar_pairs4_with(const em2_collectives* c, const uint64_t* 
     if (c->world < 1 || c->rank < 0 || c->rank >= c->world) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dist_find_similar_pairs4: rank / world out of range");
     if (lshCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dist_find_similar_pairs4: lshCount must be positive");
     if (cellCount == 0) return EM2_OK;
-    if (!d_localSignatures || !d_allSignatures || !d_usedCount || (!d_pairs && k) || !d_workspace) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dist_find_similar_pairs4: null pointer");
+    if (!d_localSignatures || !d_allSignatures || !d_usedCount || (!d_pairs && k) || !d_workspace) return failNull("em2_dist_find_similar_pairs4");
     const uint32_t world = uint32_t(c->world), rank = uint32_t(c->rank);
     const Layout l = layoutOf(cellCount, lshCount, k, rank, world);
     char* ws = reinterpret_cast<char*>(alignUp(reinterpret_cast<size_t>(d_workspace)));
@@ -341,10 +327,10 @@ int em2_dist_find_similar_pairs4_with(const em2_collectives* c, const uint64_t* 
     // (a failed copy of this rank's own row would send stale counts: the row is staged through a pinned-size host vector and
     // the flag travels in it, so a HIP error here is the one place where this rank cannot tell the others -- the transport
     // call below then fails or the others time out; such an error means the device is lost)
-    EM2_DIST_HIP(hipMemcpyAsync(counts + size_t(rank) * stride, mine.data(), stride * 8u, hipMemcpyHostToDevice, stream));
+    EM2_HIP(hipMemcpyAsync(counts + size_t(rank) * stride, mine.data(), stride * 8u, hipMemcpyHostToDevice, stream));
     if (c->all_gather(c->context, counts + size_t(rank) * stride, counts, stride * 8u, stream) != 0) return fail(EM2_ERROR_RUNTIME, "em2_dist_find_similar_pairs4: all_gather of the counts failed");
-    EM2_DIST_HIP(hipMemcpyAsync(all.data(), counts, all.size() * 8u, hipMemcpyDeviceToHost, stream));
-    EM2_DIST_HIP(hipStreamSynchronize(stream));
+    EM2_HIP(hipMemcpyAsync(all.data(), counts, all.size() * 8u, hipMemcpyDeviceToHost, stream));
+    EM2_HIP(hipStreamSynchronize(stream));
     // ---- the agreement: every rank evaluates the same matrix the same way ----
     bool fallBack = false;
     uint64_t maxUsed = 0;

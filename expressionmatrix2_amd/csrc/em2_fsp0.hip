@@ -23,9 +23,12 @@
 
 #include "em2_device.h"
 #include "em2_expression.h"
-#include "em2_hip_util.h"
+#include "em2_entry.h"
+#include "em2_csr.h"
 
 #include <cfloat>
+
+#include <string>
 
 namespace em2 {
 namespace {
@@ -331,3 +334,82 @@ hipError_t launchStoredPairs(const uint64_t* toc, const CountIn* data, uint32_t 
 }
 
 }  // namespace em2
+
+
+// ---- the C entry points (include/em2_lsh.h) ----
+
+using namespace em2::entry;
+using em2::DeviceBuffer;
+
+extern "C" {
+
+// The checks of findSimilarPairs0 that need no device.  CZI_ASSERT(similarityThreshold <= 1.)
+// (src/ExpressionMatrixFindSimilarPairs.cpp:26) comes first in the reference.
+static int prepareFsp0(const char* who, uint32_t cellCount, uint32_t geneCount, uint32_t k, double similarityThreshold)
+{
+    if (!(similarityThreshold <= 1.)) return fail(EM2_ERROR_RUNTIME, std::string(who) + ": Assertion failed: similarityThreshold <= 1.");
+    if (geneCount == 0) return failArgument(who, "geneCount must be positive");
+    if (!em2::fsp0Supported(cellCount, k)) {
+        return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": more than " + std::to_string(em2::fsp0MaxSlots()) +
+                                               " stored pairs per cell (min(k, cellCount-1)) is not supported");
+    }
+    return EM2_OK;
+}
+
+size_t em2_dev_find_similar_pairs0_workspace(uint32_t cellCount, uint32_t rowCount, uint32_t geneCount, uint32_t k)
+{
+    return em2::fsp0WorkspaceBytes(cellCount, rowCount, geneCount, k);
+}
+
+int em2_dev_find_similar_pairs0(const uint64_t* d_toc, const em2_count* d_data, uint32_t cellCount, uint32_t geneCount,
+                                uint32_t rowBegin, uint32_t rowEnd, uint32_t k, double similarityThreshold, em2_pair* d_pairs,
+                                uint32_t* d_usedCount, uint32_t* d_lowestSimilarityIndex, float* d_lowestSimilarity,
+                                void* d_workspace, size_t workspaceBytes, void* stream)
+{
+    const char* who = "em2_dev_find_similar_pairs0";
+    const int prc = prepareFsp0(who, cellCount, geneCount, k, similarityThreshold);
+    if (prc != EM2_OK) return prc;
+    if (rowBegin > rowEnd || rowEnd > cellCount) return failArgument(who, "bad row range");
+    if (rowBegin == rowEnd) return EM2_OK;
+    if (!d_toc || !d_usedCount || !d_lowestSimilarityIndex || !d_lowestSimilarity || (!d_pairs && k) || !d_workspace) return failNull(who);
+    if (workspaceBytes < em2::fsp0WorkspaceBytes(cellCount, rowEnd - rowBegin, geneCount, k)) return failArgument(who, "workspace too small");
+    uint32_t inputError = 0;
+    EM2_HIP(em2::runFsp0(d_toc, reinterpret_cast<const em2::CountIn*>(d_data), cellCount, geneCount, rowBegin, rowEnd, k,
+                         similarityThreshold, reinterpret_cast<em2::PairOut*>(d_pairs), d_usedCount, d_lowestSimilarityIndex,
+                         d_lowestSimilarity, d_workspace, &inputError, static_cast<hipStream_t>(stream)));
+    if (inputError) return failArgument(who, em2::inputErrorText(inputError));
+    return EM2_OK;
+}
+
+int em2_find_similar_pairs0(const uint64_t* toc, const em2_count* data, uint32_t cellCount, uint32_t geneCount, uint32_t k,
+                            double similarityThreshold, em2_pair* pairs, uint32_t* usedCount, uint32_t* lowestSimilarityIndex,
+                            float* lowestSimilarity)
+{
+    const char* who = "em2_find_similar_pairs0";
+    const int prc = prepareFsp0(who, cellCount, geneCount, k, similarityThreshold);
+    if (prc != EM2_OK) return prc;
+    if (cellCount == 0) return EM2_OK;
+    if (!toc || !usedCount || !lowestSimilarityIndex || !lowestSimilarity || (!pairs && k)) return failNull(who);
+    em2::UploadedCsr csr;
+    if (const char* error = csr.check(toc, reinterpret_cast<const em2::CountIn*>(data), cellCount)) return failArgument(who, error);
+    if (!haveDevice()) return failNoDevice(who);
+    EM2_HIP(csr.upload());                     // (the device checks the gene ids before any kernel indexes with them)
+    DeviceBuffer dPairs, dUsed, dIndex, dLowest, dWorkspace;
+    const size_t workspaceBytes = em2::fsp0WorkspaceBytes(cellCount, cellCount, geneCount, k);
+    EM2_HIP(dPairs.allocateFor<em2_pair>(size_t(cellCount) * k));
+    EM2_HIP(dUsed.allocateFor<uint32_t>(cellCount));
+    EM2_HIP(dIndex.allocateFor<uint32_t>(cellCount));
+    EM2_HIP(dLowest.allocateFor<float>(cellCount));
+    EM2_HIP(dWorkspace.allocate(workspaceBytes));
+    const int rc = em2_dev_find_similar_pairs0(csr.toc.as<uint64_t>(), csr.data.as<em2_count>(), cellCount, geneCount, 0, cellCount, k,
+                                               similarityThreshold, dPairs.as<em2_pair>(), dUsed.as<uint32_t>(), dIndex.as<uint32_t>(),
+                                               dLowest.as<float>(), dWorkspace.p, workspaceBytes, nullptr);
+    if (rc != EM2_OK) return rc;
+    EM2_HIP(dPairs.download(pairs, size_t(cellCount) * k));
+    EM2_HIP(dUsed.download(usedCount, cellCount));
+    EM2_HIP(dIndex.download(lowestSimilarityIndex, cellCount));
+    EM2_HIP(dLowest.download(lowestSimilarity, cellCount));
+    return EM2_OK;
+}
+
+}  // extern "C"

@@ -21,15 +21,54 @@
 //   * an exclusive scan of the alive flags, then geneGraphCompactKernel: the surviving genes in ascending order, and the
 //     neighbour half of every sorted key.
 
-#include "em2_gene_graph.h"
+#include "em2_device.h"
 #include "em2_adjacency.h"
-#include "em2_hip_util.h"
+#include "em2_entry.h"
 #include "em2_scratch.h"
 
 #include <cstring>            // (rocPRIM calls memset without including it)
 #include <rocprim/rocprim.hpp>
 
+#include <algorithm>
+#include <memory>
+#include <vector>
+
+// What the device code and the C entry points at the end of this file share.
 namespace em2 {
+
+// What the GeneGraph constructor (src/GeneGraph.cpp:22-104) leaves in the graph and what GeneGraph::getConnectivity
+// (:108-143) reads from it, in host memory.  Every id is local to the graph's gene set S.
+//   vertices                  the genes that keep a vertex (degree > 0), ascending;
+//   edge0 / edge1 / edgeSimilarity   the edges in the order add_edge created them; the similarity is that of the first insertion;
+//   connectivityOffsets       [|S| + 1]; the neighbours of gene v are connectivityGenes / connectivitySimilarities
+//                             [offsets[v], offsets[v + 1]), none for a removed gene.  ORDER WITHIN A LIST: ascending neighbour id.
+//                             The reference iterates a std::set of listS vertex descriptors -- heap pointers: its order is
+//                             whatever malloc gave, i.e. undefined; this is the project's definition.
+struct GeneGraphResult {
+    uint32_t geneCount = 0;                        // |S|
+    std::vector<uint32_t> vertices;
+    std::vector<uint32_t> edge0, edge1;
+    std::vector<float> edgeSimilarity;
+    std::vector<uint64_t> connectivityOffsets;
+    std::vector<uint32_t> connectivityGenes;
+    std::vector<float> connectivitySimilarities;
+};
+
+// Bits of *inputError (nothing was computed where it is not 0).
+constexpr uint32_t kGeneGraphSelfPair = 1u;        // a stored pair names its own gene
+constexpr uint32_t kGeneGraphPartnerRange = 2u;    // a stored pair names a local id >= pairsGeneCount
+constexpr uint32_t kGeneGraphUsedCount = 4u;       // a usedCount above k
+
+// d_pairs [pairsGeneCount][k] and d_usedCount [pairsGeneCount] in device memory: the SimilarGenePairs object over the gene set
+// P.  d_pairsGeneSet / d_graphGeneSet: the ascending global ids of P and of S in device memory, or NULL for a set of
+// consecutive ids (then *Consecutive is true and *First is its first id).  graphGeneCount > 0.  maxConnectivity is the
+// effective one: 0 (nothing is selected: k == 0) .. k.  Every stored pair of P is checked, also those of genes outside S.
+// Takes its scratch from the cache of em2_scratch.h; synchronises the stream.
+static hipError_t runGeneGraph(const PairOut* d_pairs, const uint32_t* d_usedCount, uint32_t pairsGeneCount, uint32_t k,
+                               const uint32_t* d_pairsGeneSet, bool pairsConsecutive, uint32_t pairsFirst, const uint32_t* d_graphGeneSet,
+                               bool graphConsecutive, uint32_t graphFirst, uint32_t graphGeneCount, double similarityThreshold,
+                               uint32_t maxConnectivity, GeneGraphResult& out, uint32_t* inputError, hipStream_t stream);
+
 namespace {
 
 // Slot i = g * k + j of the pairs, for j < usedCount[g]: the partner is a local id of P other than g (findSimilarGenePairs0
@@ -240,3 +279,111 @@ hipError_t runGeneGraph(const PairOut* d_pairs, const uint32_t* d_usedCount, uin
 }
 
 }  // namespace em2
+
+
+// ---- the C entry points (include/em2_lsh.h) ----
+
+using namespace em2::entry;
+using em2::DeviceBuffer;
+
+extern "C" {
+
+struct em2_gene_graph {
+    em2::GeneGraphResult result;
+};
+
+// Strictly ascending: what a stored GeneSet is once sorted (src/GeneSet.cpp), and what both id look-ups rely on.
+static bool strictlyAscending(const uint32_t* ids, uint32_t count)
+{
+    for (uint32_t i = 1; i < count; i++) {
+        if (ids[i - 1] >= ids[i]) return false;
+    }
+    return true;
+}
+
+static int geneGraphCreate(const char* who, bool pairsOnDevice, const em2_pair* pairs, const uint32_t* usedCount, uint32_t pairsGeneCount,
+                           uint32_t k, const uint32_t* pairsGeneSet, const uint32_t* graphGeneSet, uint32_t graphGeneCount,
+                           double similarityThreshold, uint64_t maxConnectivity, em2_gene_graph** graph)
+{
+    if (!graph) return failNull(who);
+    *graph = nullptr;
+    if (graphGeneCount == 0) return failArgument(who, "graphGeneCount must be positive");
+    if (!graphGeneSet || (pairsGeneCount && (!pairsGeneSet || !usedCount || (!pairs && k)))) return failNull(who);
+    if (!strictlyAscending(pairsGeneSet, pairsGeneCount) || !strictlyAscending(graphGeneSet, graphGeneCount)) {
+        return failArgument(who, "a gene set is not in strictly ascending order");
+    }
+    if (!haveDevice()) return failNoDevice(who);
+    // src/GeneGraph.cpp:80-83 increments and then tests for equality, so 0 -- and a negative Python int, converted to size_t --
+    // never matches: no limit.  A gene never selects more than its k stored pairs either way.
+    const uint32_t effective = (maxConnectivity == 0 || maxConnectivity > k) ? k : uint32_t(maxConnectivity);
+    // (sets of consecutive ids need no search on the device and are not sent there)
+    const bool pairsConsecutive = pairsGeneCount && pairsGeneSet[pairsGeneCount - 1] - pairsGeneSet[0] == pairsGeneCount - 1;
+    const bool graphConsecutive = graphGeneSet[graphGeneCount - 1] - graphGeneSet[0] == graphGeneCount - 1;
+    DeviceBuffer dPairs, dUsed, dPairsSet, dGraphSet;
+    if (!pairsOnDevice) {
+        EM2_HIP(dPairs.upload(pairs, size_t(pairsGeneCount) * k));
+        EM2_HIP(dUsed.upload(usedCount, pairsGeneCount));
+    }
+    if (!pairsConsecutive) EM2_HIP(dPairsSet.upload(pairsGeneSet, pairsGeneCount));
+    if (!graphConsecutive) EM2_HIP(dGraphSet.upload(graphGeneSet, graphGeneCount));
+    std::unique_ptr<em2_gene_graph> g(new em2_gene_graph);
+    uint32_t inputError = 0;
+    const hipError_t status = em2::runGeneGraph(
+        pairsOnDevice ? reinterpret_cast<const em2::PairOut*>(pairs) : dPairs.as<em2::PairOut>(), pairsOnDevice ? usedCount : dUsed.as<uint32_t>(),
+        pairsGeneCount, k, pairsConsecutive ? nullptr : dPairsSet.as<uint32_t>(), pairsConsecutive, pairsGeneCount ? pairsGeneSet[0] : 0u,
+        graphConsecutive ? nullptr : dGraphSet.as<uint32_t>(), graphConsecutive, graphGeneSet[0], graphGeneCount, similarityThreshold,
+        effective, g->result, &inputError, nullptr);
+    if (status != hipSuccess || inputError) {
+        EM2_HIP(status);
+        if (inputError & em2::kGeneGraphUsedCount) return failArgument(who, "a usedCount is above k");
+        if (inputError & em2::kGeneGraphPartnerRange) return failArgument(who, "a stored pair names a gene outside the pairs' gene set");
+        return failArgument(who, "a stored pair names its own gene");
+    }
+    *graph = g.release();
+    return EM2_OK;
+}
+
+int em2_gene_graph_create(const em2_pair* pairs, const uint32_t* usedCount, uint32_t pairsGeneCount, uint32_t k,
+                          const uint32_t* pairsGeneSet, const uint32_t* graphGeneSet, uint32_t graphGeneCount,
+                          double similarityThreshold, uint64_t maxConnectivity, em2_gene_graph** graph)
+{
+    return geneGraphCreate("em2_gene_graph_create", false, pairs, usedCount, pairsGeneCount, k, pairsGeneSet, graphGeneSet, graphGeneCount,
+                           similarityThreshold, maxConnectivity, graph);
+}
+
+int em2_dev_gene_graph_create(const em2_pair* d_pairs, const uint32_t* d_usedCount, uint32_t pairsGeneCount, uint32_t k,
+                              const uint32_t* pairsGeneSet, const uint32_t* graphGeneSet, uint32_t graphGeneCount,
+                              double similarityThreshold, uint64_t maxConnectivity, em2_gene_graph** graph)
+{
+    return geneGraphCreate("em2_dev_gene_graph_create", true, d_pairs, d_usedCount, pairsGeneCount, k, pairsGeneSet, graphGeneSet,
+                           graphGeneCount, similarityThreshold, maxConnectivity, graph);
+}
+
+int em2_gene_graph_sizes(const em2_gene_graph* graph, uint32_t* vertexCount, uint64_t* edgeCount, uint32_t* removedCount)
+{
+    if (!graph) return failNull("em2_gene_graph_sizes");
+    const em2::GeneGraphResult& r = graph->result;
+    if (vertexCount) *vertexCount = uint32_t(r.vertices.size());
+    if (edgeCount) *edgeCount = r.edge0.size();
+    if (removedCount) *removedCount = r.geneCount - uint32_t(r.vertices.size());
+    return EM2_OK;
+}
+
+int em2_gene_graph_get(const em2_gene_graph* graph, uint32_t* vertices, uint32_t* edgeGene0, uint32_t* edgeGene1, float* edgeSimilarity,
+                       uint64_t* connectivityOffsets, uint32_t* connectivityGenes, float* connectivitySimilarities)
+{
+    if (!graph) return failNull("em2_gene_graph_get");
+    const em2::GeneGraphResult& r = graph->result;
+    if (vertices) std::copy(r.vertices.begin(), r.vertices.end(), vertices);
+    if (edgeGene0) std::copy(r.edge0.begin(), r.edge0.end(), edgeGene0);
+    if (edgeGene1) std::copy(r.edge1.begin(), r.edge1.end(), edgeGene1);
+    if (edgeSimilarity) std::copy(r.edgeSimilarity.begin(), r.edgeSimilarity.end(), edgeSimilarity);
+    if (connectivityOffsets) std::copy(r.connectivityOffsets.begin(), r.connectivityOffsets.end(), connectivityOffsets);
+    if (connectivityGenes) std::copy(r.connectivityGenes.begin(), r.connectivityGenes.end(), connectivityGenes);
+    if (connectivitySimilarities) std::copy(r.connectivitySimilarities.begin(), r.connectivitySimilarities.end(), connectivitySimilarities);
+    return EM2_OK;
+}
+
+void em2_gene_graph_free(em2_gene_graph* graph) { delete graph; }
+
+}  // extern "C"

@@ -31,7 +31,8 @@
 
 #include "em2_device.h"
 #include "em2_expression.h"
-#include "em2_hip_util.h"
+#include "em2_entry.h"
+#include "em2_csr.h"
 #include "em2_wave.h"
 
 #include <cstring>            // (rocPRIM calls memset without including it)
@@ -42,6 +43,8 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+
+#include <string>
 
 namespace em2 {
 namespace {
@@ -363,3 +366,158 @@ hipError_t runGeneInformation(const uint64_t* d_toc, const CountIn* d_data, uint
 }
 
 }  // namespace em2
+
+
+// ---- the C entry points (include/em2_lsh.h) ----
+
+using namespace em2::entry;
+using em2::DeviceBuffer;
+
+extern "C" {
+
+static const char* geneInformationErrorText(uint32_t inputError)
+{
+    return (inputError & 4u) ? "toc does not start at 0, does not end at entryCount or is not ascending" : em2::inputErrorText(inputError);
+}
+
+// Cell::norm1Inverse / norm2Inverse as ExpressionMatrix::addCell defines them (src/ExpressionMatrix.cpp:241-263), on the host:
+// walkCell's arithmetic (em2_expression.h) and its checks.
+int em2_cell_norm_inverses(const uint64_t* toc, const em2_count* data, uint32_t cellCount, uint32_t geneCount, double* norm1Inverse,
+                           double* norm2Inverse)
+{
+    const char* who = "em2_cell_norm_inverses";
+    if (cellCount == 0) return EM2_OK;
+    if (!toc || !norm1Inverse || !norm2Inverse) return failNull(who);
+    em2::UploadedCsr csr;
+    if (const char* error = csr.check(toc, reinterpret_cast<const em2::CountIn*>(data), cellCount)) return failArgument(who, error);
+    uint32_t bad = 0;
+    for (uint32_t cell = 0; cell < cellCount; ++cell) {
+        double sum1 = 0., sum2 = 0.;
+        for (uint64_t p = toc[cell]; p < toc[cell + 1]; ++p) {
+            if (data[p].gene >= geneCount) bad |= 1u;
+            if (p != toc[cell] && data[p].gene <= data[p - 1].gene) bad |= 2u;
+            const float value = data[p].count;
+            sum1 += double(value);
+            sum2 += double(value * value);                  // a float product (:258)
+        }
+        norm1Inverse[cell] = 1. / sum1;
+        norm2Inverse[cell] = 1. / std::sqrt(sum2);
+    }
+    if (bad) return failArgument(who, em2::inputErrorText(bad));
+    return EM2_OK;
+}
+
+void em2_set_gene_information_max_blocks(uint32_t blocks) { em2::setGeneInformationMaxBlocks(blocks); }
+
+size_t em2_dev_gene_information_content_workspace(uint32_t cellCount, uint32_t geneCount, uint64_t entryCount)
+{
+    (void)cellCount;
+    return em2::geneInformationWorkspaceBytes(entryCount, geneCount);
+}
+
+// The device call under the name of the entry point that makes it.
+static int devGeneInformation(const char* who, const uint64_t* d_toc, const em2_count* d_data, uint32_t cellCount, uint32_t geneCount,
+                              uint64_t entryCount, const double* d_normInverse, float* d_informationContent,
+                              double* d_informationContentDouble, uint32_t* d_expressingCellCount, void* d_workspace,
+                              size_t workspaceBytes, void* stream)
+{
+    if (geneCount == 0) return failArgument(who, "geneCount must be positive");
+    if (cellCount == 0) return failArgument(who, "cellCount must be positive");
+    if (!d_toc || !d_informationContent || !d_workspace || (!d_data && entryCount)) return failNull(who);
+    if (workspaceBytes < em2::geneInformationWorkspaceBytes(entryCount, geneCount)) return failArgument(who, "workspace too small");
+    uint32_t inputError = 0;
+    // :2004 and :2015 with the host's log, so that a gene without a positive entry gets the reference's float exactly
+    EM2_HIP(em2::runGeneInformation(d_toc, reinterpret_cast<const em2::CountIn*>(d_data), cellCount, geneCount, entryCount, d_normInverse,
+                                    std::log(double(cellCount)), std::log(2.), d_informationContent, d_informationContentDouble,
+                                    d_expressingCellCount, d_workspace, workspaceBytes, &inputError, static_cast<hipStream_t>(stream)));
+    if (inputError) return failArgument(who, geneInformationErrorText(inputError));
+    return EM2_OK;
+}
+
+int em2_dev_gene_information_content(const uint64_t* d_toc, const em2_count* d_data, uint32_t cellCount, uint32_t geneCount,
+                                     uint64_t entryCount, const double* d_normInverse, float* d_informationContent,
+                                     double* d_informationContentDouble, uint32_t* d_expressingCellCount, void* d_workspace,
+                                     size_t workspaceBytes, void* stream)
+{
+    return devGeneInformation("em2_dev_gene_information_content", d_toc, d_data, cellCount, geneCount, entryCount, d_normInverse,
+                              d_informationContent, d_informationContentDouble, d_expressingCellCount, d_workspace, workspaceBytes, stream);
+}
+
+// The device call on a CSR that is on the device already; the results to the host.
+static int geneInformationToHost(const char* who, const uint64_t* d_toc, const em2_count* d_data, uint32_t cellCount, uint32_t geneCount,
+                                 uint64_t entryCount, const double* d_normInverse, float* informationContent,
+                                 double* informationContentDouble, uint32_t* expressingCellCount)
+{
+    DeviceBuffer dFloat, dDouble, dExpressing, dWorkspace;
+    const size_t workspaceBytes = em2::geneInformationWorkspaceBytes(entryCount, geneCount);
+    EM2_HIP(dFloat.allocateFor<float>(geneCount));
+    if (informationContentDouble) EM2_HIP(dDouble.allocateFor<double>(geneCount));
+    if (expressingCellCount) EM2_HIP(dExpressing.allocateFor<uint32_t>(geneCount));
+    EM2_HIP(dWorkspace.allocate(workspaceBytes));
+    const int rc = devGeneInformation(who, d_toc, d_data, cellCount, geneCount, entryCount, d_normInverse, dFloat.as<float>(),
+                                      dDouble.as<double>(), dExpressing.as<uint32_t>(), dWorkspace.p, workspaceBytes, nullptr);
+    if (rc != EM2_OK) return rc;
+    if (informationContent) EM2_HIP(dFloat.download(informationContent, geneCount));
+    if (informationContentDouble) EM2_HIP(dDouble.download(informationContentDouble, geneCount));
+    if (expressingCellCount) EM2_HIP(dExpressing.download(expressingCellCount, geneCount));
+    return EM2_OK;
+}
+
+int em2_gene_information_content(const uint64_t* toc, const em2_count* data, uint32_t cellCount, uint32_t geneCount,
+                                 const double* normInverse, float* informationContent, double* informationContentDouble,
+                                 uint32_t* expressingCellCount)
+{
+    const char* who = "em2_gene_information_content";
+    if (geneCount == 0) return failArgument(who, "geneCount must be positive");
+    if (cellCount == 0) return failArgument(who, "cellCount must be positive");
+    if (!toc || !informationContent) return failNull(who);
+    em2::UploadedCsr csr;
+    if (const char* error = csr.check(toc, reinterpret_cast<const em2::CountIn*>(data), cellCount)) return failArgument(who, error);
+    if (!haveDevice()) return failNoDevice(who);
+    EM2_HIP(csr.upload());                     // (the device checks the gene ids before any kernel indexes with them)
+    DeviceBuffer dNorm;
+    if (normInverse) EM2_HIP(dNorm.upload(normInverse, cellCount));
+    return geneInformationToHost(who, csr.toc.as<uint64_t>(), csr.data.as<em2_count>(), cellCount, geneCount, csr.nnz,
+                                 normInverse ? dNorm.as<double>() : nullptr, informationContent, informationContentDouble, expressingCellCount);
+}
+
+// The matrix-level call (em2_host.cpp): the rows of the cell set go to the device with their global gene ids; the cells' norm
+// inverses are taken over those WHOLE rows there (or come from the Cells file: normInverseOfRows, one per row), the gene set
+// is applied by the device subset, and the rest is em2_dev_gene_information_content.  rowToc from 0.  Internal to the library.
+int em2_internal_gene_information(const uint64_t* rowToc, const em2_count* rowData, uint32_t cellCount, const uint32_t* geneLocalIds,
+                                  uint32_t globalGeneCount, uint32_t geneCount, int normalizationMethod, const double* normInverseOfRows,
+                                  float* informationContent, uint32_t* expressingCellCount)
+{
+    const char* who = "em2_matrix_gene_information_content";
+    if (normalizationMethod < 0 || normalizationMethod > 2) return failArgument(who, "invalid normalization method (0 none, 1 L1, 2 L2)");
+    if (!haveDevice()) return failNoDevice(who);
+    em2::UploadedCsr rows;
+    if (const char* error = rows.check(rowToc, reinterpret_cast<const em2::CountIn*>(rowData), cellCount)) return failArgument(who, error);
+    EM2_HIP(rows.upload());
+    DeviceBuffer dNorm, dLocalIds, dToc, dData, dSubsetWorkspace;
+    if (normalizationMethod != 0) {
+        if (normInverseOfRows) {
+            EM2_HIP(dNorm.upload(normInverseOfRows, cellCount));
+        } else {
+            EM2_HIP(dNorm.allocateFor<double>(cellCount));
+            // (a global gene id is checked by nothing here: the subset below drops what the gene set does not know)
+            EM2_HIP(em2::launchCellNormInverses(rows.toc.as<uint64_t>(), rows.data.as<em2::CountIn>(), cellCount, 0xffffffffu,
+                                                normalizationMethod, dNorm.as<double>(), nullptr));
+        }
+    }
+    const size_t subsetBytes = em2::subsetWorkspaceBytes(cellCount);
+    EM2_HIP(dLocalIds.upload(geneLocalIds, globalGeneCount));
+    EM2_HIP(dToc.allocateFor<uint64_t>(size_t(cellCount) + 1));
+    EM2_HIP(dSubsetWorkspace.allocate(subsetBytes));
+    EM2_HIP(em2::launchSubsetCount(rows.toc.as<uint64_t>(), rows.data.as<em2::CountIn>(), nullptr, cellCount, dLocalIds.as<uint32_t>(),
+                                   globalGeneCount, dToc.as<uint64_t>(), dSubsetWorkspace.p, subsetBytes, nullptr));
+    uint64_t entryCount = 0;
+    EM2_HIP(hipMemcpy(&entryCount, dToc.as<uint64_t>() + cellCount, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    EM2_HIP(dData.allocateFor<em2_count>(entryCount));
+    EM2_HIP(em2::launchSubsetFill(rows.toc.as<uint64_t>(), rows.data.as<em2::CountIn>(), nullptr, cellCount, dLocalIds.as<uint32_t>(),
+                                  globalGeneCount, dToc.as<uint64_t>(), dData.as<em2::CountIn>(), nullptr));
+    return geneInformationToHost(who, dToc.as<uint64_t>(), dData.as<em2_count>(), cellCount, geneCount, entryCount,
+                                 normalizationMethod != 0 ? dNorm.as<double>() : nullptr, informationContent, nullptr, expressingCellCount);
+}
+
+}  // extern "C"

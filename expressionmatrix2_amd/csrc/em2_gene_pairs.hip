@@ -28,7 +28,8 @@
 
 #include "em2_device.h"
 #include "em2_expression.h"
-#include "em2_hip_util.h"
+#include "em2_entry.h"
+#include "em2_csr.h"
 #include "em2_wave.h"
 
 #include <cstring>            // (rocPRIM calls memset without including it)
@@ -38,6 +39,8 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+
+#include <string>
 
 namespace em2 {
 namespace {
@@ -466,3 +469,65 @@ hipError_t runGenePairs(const uint64_t* d_toc, const CountIn* d_data, uint32_t c
 }
 
 }  // namespace em2
+
+
+// ---- the C entry points (include/em2_lsh.h) ----
+
+using namespace em2::entry;
+using em2::DeviceBuffer;
+
+extern "C" {
+
+// std::sort by similarity alone, per gene (em2_host.cpp).
+extern "C" void em2_internal_sort_gene_pairs(em2_pair* pairs, const uint32_t* usedCount, uint32_t geneCount, uint32_t k);
+
+static const uint32_t kAllSimilaritiesMaxGenes = 8192;          // allSimilarities: 256 MB of floats at most
+
+void em2_set_gene_pairs_buffer_mb(uint64_t megabytes) { em2::setGenePairsBudgetMegabytes(megabytes); }
+
+int em2_find_similar_gene_pairs0(const uint64_t* toc, const em2_count* data, uint32_t cellCount, uint32_t geneCount,
+                                 int normalizationMethod, uint32_t k, double similarityThreshold, em2_pair* pairs,
+                                 uint32_t* usedCount, float* allSimilarities)
+{
+    const char* who = "em2_find_similar_gene_pairs0";
+    if (normalizationMethod < 0 || normalizationMethod > 2) return failArgument(who, "invalid normalization method (0 none, 1 L1, 2 L2)");
+    if (geneCount == 0) return failArgument(who, "geneCount must be positive");
+    if (cellCount == 0) return failArgument(who, "cellCount must be positive");
+    if (!toc || !usedCount || (!pairs && k)) return failNull(who);
+    if (allSimilarities && geneCount > kAllSimilaritiesMaxGenes) {
+        return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": allSimilarities is an aid for at most " +
+                                               std::to_string(kAllSimilaritiesMaxGenes) + " genes");
+    }
+    em2::UploadedCsr csr;
+    if (const char* error = csr.check(toc, reinterpret_cast<const em2::CountIn*>(data), cellCount)) return failArgument(who, error);
+    if (!haveDevice()) return failNoDevice(who);
+    EM2_HIP(csr.upload());                     // (the device checks the gene ids before any kernel indexes with them)
+    const size_t allCount = allSimilarities ? size_t(geneCount) * geneCount : 0;
+    DeviceBuffer dPairs, dUsed, dAll;
+    EM2_HIP(dPairs.allocateFor<em2_pair>(size_t(geneCount) * k));
+    EM2_HIP(dUsed.allocateFor<uint32_t>(geneCount));
+    if (allSimilarities) {
+        EM2_HIP(dAll.allocateFor<float>(allCount));
+        EM2_HIP(hipMemset(dAll.p, 0, allCount * sizeof(float)));                   // (the diagonal: the reference computes none)
+    }
+    em2::GenePairsStatus status;
+    EM2_HIP(em2::runGenePairs(csr.toc.as<uint64_t>(), csr.data.as<em2::CountIn>(), cellCount, geneCount, normalizationMethod, k,
+                              similarityThreshold, dPairs.as<em2::PairOut>(), dUsed.as<uint32_t>(), dAll.as<float>(), &status, nullptr));
+    if (status.inputError) return failArgument(who, em2::inputErrorText(status.inputError));
+    if (status.overflow) {
+        return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": " + std::to_string(status.records) + " candidate records (" +
+                                               std::to_string(status.records * em2::kGenePairsBytesPerRecord >> 20) +
+                                               " MB with the sort's second buffer) fit neither the candidate buffer (" +
+                                               std::to_string(em2::genePairsBudgetRecords() * em2::kGenePairsBytesPerRecord >> 20) +
+                                               " MB, em2_set_gene_pairs_buffer_mb; the Python binding sets it from its environment variable) nor "
+                                               "the free device memory (" + std::to_string(status.freeBytes >> 20) +
+                                               " MB), so a larger buffer cannot help: raise the similarity threshold");
+    }
+    EM2_HIP(dPairs.download(pairs, size_t(geneCount) * k));
+    EM2_HIP(dUsed.download(usedCount, geneCount));
+    EM2_HIP(dAll.download(allSimilarities, allCount));
+    if (k) em2_internal_sort_gene_pairs(pairs, usedCount, geneCount, k);          // :186, the library's own std::sort
+    return EM2_OK;
+}
+
+}  // extern "C"

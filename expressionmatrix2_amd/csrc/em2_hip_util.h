@@ -1,6 +1,7 @@
 // em2_hip_util.h -- the host-side plumbing every driver needs: bail out on a HIP error, a device allocation that frees
-// itself, the 1-D grid of a 256-thread kernel, blocks per items, 256-byte alignment, signature words, the stage timer.  (The device-side counterpart is
-// em2_wave.h; device scratch that outlives a call is em2_scratch.h.)
+// itself and copies typed arrays in and out, the 1-D grid of a 256-thread kernel, blocks per items, 256-byte alignment,
+// signature words, the stage timer.  (The device-side counterpart is em2_wave.h; device scratch that outlives a call is
+// em2_scratch.h; what a C entry point reports its errors with is em2_entry.h.)
 #ifndef EM2_HIP_UTIL_H
 #define EM2_HIP_UTIL_H
 
@@ -13,7 +14,7 @@
 #include <cstdlib>
 
 // Returns the hipError_t of a failed call from the enclosing function.  (The call's text is not kept: the entry points
-// that report one, em2_capi.hip's EM2_HIP and em2_cluster_graph.hip's EM2_TRYC, have macros of their own.)
+// report one with em2_entry.h's EM2_HIP and EM2_HIP_FOR, createClusterGraph with em2_cluster_graph.hip's EM2_TRYC.)
 #define EM2_TRY(call)                        \
     do {                                     \
         hipError_t em2Err_ = (call);         \
@@ -40,6 +41,18 @@ struct DeviceBuffer {
         return hipMalloc(&p, bytes ? bytes : 1);
     }
     template <class T> T* as() const { return static_cast<T*>(p); }
+    // Room for count elements of T; upload() also fills it from the host.  The copies are synchronous hipMemcpy calls (callers
+    // rely on them to wait for the null stream); count == 0 copies nothing, and host may then be null.
+    template <class T> hipError_t allocateFor(size_t count) { return allocate(count * sizeof(T)); }
+    template <class T> hipError_t upload(const T* host, size_t count)
+    {
+        EM2_TRY(allocateFor<T>(count));
+        return count ? hipMemcpy(p, host, count * sizeof(T), hipMemcpyHostToDevice) : hipSuccess;
+    }
+    template <class T> hipError_t download(T* host, size_t count) const
+    {
+        return count ? hipMemcpy(host, p, count * sizeof(T), hipMemcpyDeviceToHost) : hipSuccess;
+    }
 };
 
 // Blocks of 256 threads for n items, at least 1 and at most 16384 (the kernels launched with it stride over the grid).

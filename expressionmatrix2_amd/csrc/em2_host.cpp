@@ -1505,7 +1505,7 @@ void createDirectoryFromCsr(const std::string& directoryName, uint32_t geneCount
 }  // namespace host
 }  // namespace em2
 
-// internal to the library (em2_capi.hip: the last step of em2_find_similar_gene_pairs0)
+// internal to the library (em2_gene_pairs.hip: the last step of em2_find_similar_gene_pairs0)
 extern "C" void em2_internal_sort_gene_pairs(em2_pair* pairs, const uint32_t* usedCount, uint32_t geneCount, uint32_t k)
 {
     em2::host::sortGenePairs(pairs, usedCount, geneCount, k);

@@ -18,7 +18,7 @@
 // order is an integer below 2^53, nothing is ever rounded, and the lanes add in parallel.  The square is a float product
 // (__fmul_rn: never contracted), sqrt and the divisions are __dsqrt_rn and __ddiv_rn.
 #include "em2_ingest.h"
-#include "em2_hip_util.h"
+#include "em2_entry.h"
 #include "em2_wave.h"
 
 #include <cstring>
@@ -28,7 +28,7 @@
 #include <atomic>
 #include <string>
 
-extern "C" void em2_internal_set_last_error(const char* message);
+using namespace em2::entry;
 
 namespace em2 {
 
@@ -360,31 +360,15 @@ hipError_t runIngest(IngestArguments a, uint64_t* outTocOfCount, uint32_t* error
     return hipStreamSynchronize(stream);                                      // (the lists and the scratch end with this call)
 }
 
-int failWith(int code, const std::string& message)
-{
-    em2_internal_set_last_error(message.c_str());
-    return code;
-}
-
-int failHip(const char* who, hipError_t e) { return failWith(EM2_ERROR_HIP, std::string(who) + ": " + hipGetErrorString(e)); }
-
-bool haveDevice()
-{
-    int n = 0;
-    return hipGetDeviceCount(&n) == hipSuccess && n > 0;
-}
-
 int devIngestCount(const char* who, const uint64_t* d_indptr, const uint32_t* d_indices, const float* d_values, const uint8_t* d_skip,
                    uint32_t cellCount, const uint32_t* d_geneIdOfIndex, uint32_t indexCount, uint32_t* d_keptCount, uint32_t* d_status,
                    uint32_t* d_duplicateGene, uint64_t* d_outToc, void* stream)
 {
-    if (!d_indptr || !d_outToc || (cellCount && (!d_keptCount || !d_status || !d_duplicateGene))) {
-        return failWith(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
-    }
-    if (!haveDevice()) return failWith(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
+    if (!d_indptr || !d_outToc || (cellCount && (!d_keptCount || !d_status || !d_duplicateGene))) return failNull(who);
+    if (!haveDevice()) return failNoDevice(who);
     if (cellCount == 0) {
-        const hipError_t e = hipMemsetAsync(d_outToc, 0, sizeof(uint64_t), static_cast<hipStream_t>(stream));
-        return e == hipSuccess ? EM2_OK : failHip(who, e);
+        EM2_HIP_FOR(who, hipMemsetAsync(d_outToc, 0, sizeof(uint64_t), static_cast<hipStream_t>(stream)));
+        return EM2_OK;
     }
     IngestArguments a{};
     a.indptr = d_indptr;
@@ -398,8 +382,8 @@ int devIngestCount(const char* who, const uint64_t* d_indptr, const uint32_t* d_
     a.status = d_status;
     a.duplicateGene = d_duplicateGene;
     uint32_t error = 0;
-    const hipError_t e = runIngest<false>(a, d_outToc, &error, static_cast<hipStream_t>(stream));
-    return e == hipSuccess ? EM2_OK : failHip(who, e);
+    EM2_HIP_FOR(who, runIngest<false>(a, d_outToc, &error, static_cast<hipStream_t>(stream)));
+    return EM2_OK;
 }
 
 int devIngestFill(const char* who, const uint64_t* d_indptr, const uint32_t* d_indices, const float* d_values, const uint8_t* d_skip,
@@ -407,11 +391,9 @@ int devIngestFill(const char* who, const uint64_t* d_indptr, const uint32_t* d_i
                   void* d_outCells, void* stream)
 {
     if (cellCount == 0) return EM2_OK;
-    if (!d_indptr || !d_outToc || !d_outData || !d_outCells) return failWith(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null pointer");
-    if (reinterpret_cast<uintptr_t>(d_outCells) % sizeof(double)) {
-        return failWith(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": d_outCells is not aligned to a double");
-    }
-    if (!haveDevice()) return failWith(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
+    if (!d_indptr || !d_outToc || !d_outData || !d_outCells) return failNull(who);
+    if (reinterpret_cast<uintptr_t>(d_outCells) % sizeof(double)) return failArgument(who, "d_outCells is not aligned to a double");
+    if (!haveDevice()) return failNoDevice(who);
     IngestArguments a{};
     a.indptr = d_indptr;
     a.indices = d_indices;
@@ -424,9 +406,8 @@ int devIngestFill(const char* who, const uint64_t* d_indptr, const uint32_t* d_i
     a.outData = reinterpret_cast<Entry*>(d_outData);
     a.outCells = static_cast<double*>(d_outCells);
     uint32_t error = 0;
-    const hipError_t e = runIngest<true>(a, nullptr, &error, static_cast<hipStream_t>(stream));
-    if (e != hipSuccess) return failHip(who, e);
-    if (error) return failWith(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": d_outToc is not what the count pass gives for these rows");
+    EM2_HIP_FOR(who, runIngest<true>(a, nullptr, &error, static_cast<hipStream_t>(stream)));
+    if (error) return failArgument(who, "d_outToc is not what the count pass gives for these rows");
     return EM2_OK;
 }
 
@@ -441,30 +422,18 @@ int ingestChunkOnDevice(const uint64_t* indptr, const uint32_t* indices, const f
 {
     const char* who = "em2_matrix_add_cells_csr";
     *failed = false;
-    if (!haveDevice()) return failWith(EM2_ERROR_NO_DEVICE, std::string(who) + ": no HIP device is visible (this library has no CPU path)");
+    if (!haveDevice()) return failNoDevice(who);
     const uint64_t entryCount = indptr[cellCount];
     DeviceBuffer dIndptr, dIndices, dValues, dSkip, dGenes, dKept, dStatus, dDuplicate, dToc, dData, dCells;
-#define EM2_INGEST_HIP(call)                                              \
-    do {                                                                  \
-        const hipError_t ingestError_ = (call);                           \
-        if (ingestError_ != hipSuccess) return failHip(who, ingestError_); \
-    } while (0)
-    EM2_INGEST_HIP(dIndptr.allocate((size_t(cellCount) + 1u) * sizeof(uint64_t)));
-    EM2_INGEST_HIP(dIndices.allocate(size_t(entryCount) * sizeof(uint32_t)));
-    EM2_INGEST_HIP(dValues.allocate(size_t(entryCount) * sizeof(float)));
-    EM2_INGEST_HIP(dSkip.allocate(cellCount));
-    EM2_INGEST_HIP(dGenes.allocate(size_t(indexCount) * sizeof(uint32_t)));
-    EM2_INGEST_HIP(dKept.allocate(size_t(cellCount) * sizeof(uint32_t)));
-    EM2_INGEST_HIP(dStatus.allocate(size_t(cellCount) * sizeof(uint32_t)));
-    EM2_INGEST_HIP(dDuplicate.allocate(size_t(cellCount) * sizeof(uint32_t)));
-    EM2_INGEST_HIP(dToc.allocate((size_t(cellCount) + 1u) * sizeof(uint64_t)));
-    EM2_INGEST_HIP(hipMemcpy(dIndptr.p, indptr, (size_t(cellCount) + 1u) * sizeof(uint64_t), hipMemcpyHostToDevice));
-    if (entryCount) {
-        EM2_INGEST_HIP(hipMemcpy(dIndices.p, indices, size_t(entryCount) * sizeof(uint32_t), hipMemcpyHostToDevice));
-        EM2_INGEST_HIP(hipMemcpy(dValues.p, values, size_t(entryCount) * sizeof(float), hipMemcpyHostToDevice));
-    }
-    if (cellCount) EM2_INGEST_HIP(hipMemcpy(dSkip.p, skip, cellCount, hipMemcpyHostToDevice));
-    if (indexCount) EM2_INGEST_HIP(hipMemcpy(dGenes.p, geneIdOfIndex, size_t(indexCount) * sizeof(uint32_t), hipMemcpyHostToDevice));
+    EM2_HIP_FOR(who, dIndptr.upload(indptr, size_t(cellCount) + 1u));
+    EM2_HIP_FOR(who, dIndices.upload(indices, size_t(entryCount)));
+    EM2_HIP_FOR(who, dValues.upload(values, size_t(entryCount)));
+    EM2_HIP_FOR(who, dSkip.upload(skip, cellCount));
+    EM2_HIP_FOR(who, dGenes.upload(geneIdOfIndex, indexCount));
+    EM2_HIP_FOR(who, dKept.allocateFor<uint32_t>(cellCount));
+    EM2_HIP_FOR(who, dStatus.allocateFor<uint32_t>(cellCount));
+    EM2_HIP_FOR(who, dDuplicate.allocateFor<uint32_t>(cellCount));
+    EM2_HIP_FOR(who, dToc.allocateFor<uint64_t>(size_t(cellCount) + 1u));
     int rc = devIngestCount(who, dIndptr.as<uint64_t>(), dIndices.as<uint32_t>(), dValues.as<float>(), dSkip.as<uint8_t>(), cellCount,
                             dGenes.as<uint32_t>(), indexCount, dKept.as<uint32_t>(), dStatus.as<uint32_t>(), dDuplicate.as<uint32_t>(),
                             dToc.as<uint64_t>(), nullptr);
@@ -473,12 +442,10 @@ int ingestChunkOnDevice(const uint64_t* indptr, const uint32_t* indices, const f
     status.resize(cellCount);
     duplicateGene.resize(cellCount);
     toc.resize(size_t(cellCount) + 1u);
-    if (cellCount) {
-        EM2_INGEST_HIP(hipMemcpy(keptCount.data(), dKept.p, size_t(cellCount) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        EM2_INGEST_HIP(hipMemcpy(status.data(), dStatus.p, size_t(cellCount) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        EM2_INGEST_HIP(hipMemcpy(duplicateGene.data(), dDuplicate.p, size_t(cellCount) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    }
-    EM2_INGEST_HIP(hipMemcpy(toc.data(), dToc.p, (size_t(cellCount) + 1u) * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    EM2_HIP_FOR(who, dKept.download(keptCount.data(), cellCount));
+    EM2_HIP_FOR(who, dStatus.download(status.data(), cellCount));
+    EM2_HIP_FOR(who, dDuplicate.download(duplicateGene.data(), cellCount));
+    EM2_HIP_FOR(who, dToc.download(toc.data(), size_t(cellCount) + 1u));
     for (uint32_t i = 0; i < cellCount; i++) {
         if (status[i] != 0u) *failed = true;
     }
@@ -486,16 +453,15 @@ int ingestChunkOnDevice(const uint64_t* indptr, const uint32_t* indices, const f
     cells.assign(cellCount, CellRecord());
     if (*failed) return EM2_OK;
     const uint64_t outCount = toc[cellCount];
-    EM2_INGEST_HIP(dData.allocate(size_t(outCount) * sizeof(em2_count)));
-    EM2_INGEST_HIP(dCells.allocate(size_t(cellCount) * sizeof(CellRecord)));
-    EM2_INGEST_HIP(hipMemset(dCells.p, 0, size_t(cellCount) * sizeof(CellRecord)));
+    EM2_HIP_FOR(who, dData.allocateFor<em2_count>(size_t(outCount)));
+    EM2_HIP_FOR(who, dCells.allocateFor<CellRecord>(cellCount));
+    EM2_HIP_FOR(who, hipMemset(dCells.p, 0, size_t(cellCount) * sizeof(CellRecord)));
     rc = devIngestFill(who, dIndptr.as<uint64_t>(), dIndices.as<uint32_t>(), dValues.as<float>(), dSkip.as<uint8_t>(), cellCount,
                        dGenes.as<uint32_t>(), indexCount, dToc.as<uint64_t>(), dData.as<em2_count>(), dCells.p, nullptr);
     if (rc != EM2_OK) return rc;
     data.resize(size_t(outCount));
-    if (outCount) EM2_INGEST_HIP(hipMemcpy(data.data(), dData.p, size_t(outCount) * sizeof(em2_count), hipMemcpyDeviceToHost));
-    if (cellCount) EM2_INGEST_HIP(hipMemcpy(cells.data(), dCells.p, size_t(cellCount) * sizeof(CellRecord), hipMemcpyDeviceToHost));
-#undef EM2_INGEST_HIP
+    EM2_HIP_FOR(who, dData.download(data.data(), size_t(outCount)));
+    EM2_HIP_FOR(who, dCells.download(cells.data(), cellCount));
     return EM2_OK;
 }
 

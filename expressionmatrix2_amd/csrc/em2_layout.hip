@@ -17,17 +17,60 @@
 //   * energyStepKernel     one workgroup: the chunk energies by a fixed tree, then one thread updates the step (Hu's adaptive
 //                          scheme) in device memory.  The host reads the new step, one double per iteration, to decide the end.
 
-#include "em2_layout.h"
 #include "em2_adjacency.h"
-#include "em2_hip_util.h"
+#include "em2_entry.h"
 #include "em2_scratch.h"
 
 #include <cmath>
 #include <cstring>            // (rocPRIM calls memset without including it)
 #include <limits>
 #include <rocprim/rocprim.hpp>
+#include <string>
 
+// What the device code and the C entry points at the end of this file share.
 namespace em2 {
+
+// The constants of the model (Hu 2005) and of the summation shapes.  The shapes are part of the contract: they are functions
+// of the vertex count alone, never of the device or the grid.
+constexpr float kLayoutC = 0.2f;                    // C * K^2, with the natural length K = 1
+constexpr float kLayoutFloor = 1e-30f;              // delta: d^2 is raised to it, so j = i and coincident vertices add an exact 0
+constexpr double kLayoutT = 0.9;                    // the step is multiplied by t when the energy did not fall
+constexpr uint32_t kLayoutProgress = 5;             // ... and divided by t after this many falls in a row
+constexpr uint32_t kLayoutSliceCount = 16;          // slices of the j range of a repulsion sum: ceil(N / 16) consecutive vertices each
+constexpr uint32_t kLayoutTile = 128;               // j positions staged in LDS at a time (no effect on any sum)
+constexpr uint32_t kLayoutBlockVertices = 256;      // vertices of a workgroup, and the leaves of one chunk of the energy tree
+constexpr uint32_t kLayoutMaxVertexCount = 1u << 30;
+
+struct LayoutParameters {
+    uint32_t seed;
+    uint32_t maxIterationCount;
+    double tolerance;
+    double gravity;
+    double initialStep;
+};
+
+struct LayoutResult {
+    uint32_t iterationCount = 0;
+    double step = 0.;
+    double energy = 0.;
+};
+
+// Bit of *inputError (nothing was computed where it is not 0).
+constexpr uint32_t kLayoutEdgeRange = 1u;           // an edge end >= vertexCount
+
+// The layout of the graph of vertexCount > 0 vertices and the edges (d_edge0[e], d_edge1[e]) in device memory: initial
+// positions from (seed, vertex), then Hu's adaptive iteration until maxIterationCount or step < tolerance.  d_x / d_y
+// [vertexCount] in device memory receive the positions.  Every edge end is checked before anything indexes with it.
+// Takes its scratch from the cache of em2_scratch.h; synchronises the stream.
+static hipError_t runGraphLayout(uint32_t vertexCount, const uint32_t* d_edge0, const uint32_t* d_edge1, uint64_t edgeCount,
+                                 const LayoutParameters& parameters, float* d_x, float* d_y, LayoutResult& result, uint32_t* inputError,
+                                 hipStream_t stream);
+
+// One evaluation of the forces at the positions d_x / d_y, no move: d_fx / d_fy [vertexCount], *energy = the sum of |f|^2.
+static hipError_t runGraphLayoutForces(uint32_t vertexCount, const uint32_t* d_edge0, const uint32_t* d_edge1, uint64_t edgeCount, double gravity,
+                                       const float* d_x, const float* d_y, float* d_fx, float* d_fy, double* energy, uint32_t* inputError,
+                                       hipStream_t stream);
+
 namespace {
 
 struct LayoutState {
@@ -410,3 +453,105 @@ hipError_t runGraphLayoutForces(uint32_t vertexCount, const uint32_t* d_edge0, c
 }
 
 }  // namespace em2
+
+
+// ---- the C entry points (include/em2_lsh.h) ----
+
+using namespace em2::entry;
+using em2::DeviceBuffer;
+
+extern "C" {
+
+// The edge arrays of a host-pointer entry in device memory.
+static int uploadEdges(const uint32_t* edgeVertex0, const uint32_t* edgeVertex1, uint64_t edgeCount, DeviceBuffer& d0, DeviceBuffer& d1)
+{
+    EM2_HIP(d0.upload(edgeVertex0, size_t(edgeCount)));
+    EM2_HIP(d1.upload(edgeVertex1, size_t(edgeCount)));
+    return EM2_OK;
+}
+
+static int graphLayout(const char* who, bool onDevice, uint32_t vertexCount, const uint32_t* edgeVertex0, const uint32_t* edgeVertex1,
+                       uint64_t edgeCount, const em2_layout_parameters* parameters, float* x, float* y, em2_layout_result* result)
+{
+    if (!parameters || (vertexCount && (!x || !y)) || (edgeCount && (!edgeVertex0 || !edgeVertex1))) return failNull(who);
+    if (!(parameters->tolerance >= 0.)) return failArgument(who, "tolerance must not be negative");
+    if (!(parameters->gravity >= 0.)) return failArgument(who, "gravity must not be negative");
+    if (!(parameters->initialStep >= 0.)) return failArgument(who, "initialStep must not be negative");
+    if (vertexCount > em2::kLayoutMaxVertexCount) return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": vertexCount is above 2^30");
+    if (result) {
+        result->iterationCount = result->reserved = 0u;
+        result->step = parameters->initialStep;
+        result->energy = std::numeric_limits<double>::infinity();
+    }
+    if (vertexCount == 0) {
+        // (no vertex, so every edge end is out of range)
+        return edgeCount ? failArgument(who, "an edge names a vertex outside the graph") : EM2_OK;
+    }
+    if (!haveDevice()) return failNoDevice(who);
+    DeviceBuffer d0, d1, dx, dy;
+    if (!onDevice) {
+        const int status = uploadEdges(edgeVertex0, edgeVertex1, edgeCount, d0, d1);
+        if (status != EM2_OK) return status;
+        EM2_HIP(dx.allocateFor<float>(vertexCount));
+        EM2_HIP(dy.allocateFor<float>(vertexCount));
+    }
+    const em2::LayoutParameters p = {parameters->seed, parameters->maxIterationCount, parameters->tolerance, parameters->gravity,
+                                     parameters->initialStep};
+    em2::LayoutResult r;
+    uint32_t inputError = 0;
+    EM2_HIP(em2::runGraphLayout(vertexCount, onDevice ? edgeVertex0 : d0.as<uint32_t>(), onDevice ? edgeVertex1 : d1.as<uint32_t>(), edgeCount,
+                                p, onDevice ? x : dx.as<float>(), onDevice ? y : dy.as<float>(), r, &inputError, nullptr));
+    if (inputError) return failArgument(who, "an edge names a vertex outside the graph");
+    if (!onDevice) {
+        EM2_HIP(dx.download(x, vertexCount));
+        EM2_HIP(dy.download(y, vertexCount));
+    }
+    if (result) {
+        result->iterationCount = r.iterationCount;
+        result->step = r.step;
+        result->energy = r.energy;
+    }
+    return EM2_OK;
+}
+
+int em2_graph_layout(uint32_t vertexCount, const uint32_t* edgeVertex0, const uint32_t* edgeVertex1, uint64_t edgeCount,
+                     const em2_layout_parameters* parameters, float* x, float* y, em2_layout_result* result)
+{
+    return graphLayout("em2_graph_layout", false, vertexCount, edgeVertex0, edgeVertex1, edgeCount, parameters, x, y, result);
+}
+
+int em2_dev_graph_layout(uint32_t vertexCount, const uint32_t* d_edgeVertex0, const uint32_t* d_edgeVertex1, uint64_t edgeCount,
+                         const em2_layout_parameters* parameters, float* d_x, float* d_y, em2_layout_result* result)
+{
+    return graphLayout("em2_dev_graph_layout", true, vertexCount, d_edgeVertex0, d_edgeVertex1, edgeCount, parameters, d_x, d_y, result);
+}
+
+int em2_graph_layout_forces(uint32_t vertexCount, const uint32_t* edgeVertex0, const uint32_t* edgeVertex1, uint64_t edgeCount,
+                            double gravity, const float* x, const float* y, float* fx, float* fy, double* energy)
+{
+    const char* who = "em2_graph_layout_forces";
+    if ((vertexCount && (!x || !y || !fx || !fy)) || (edgeCount && (!edgeVertex0 || !edgeVertex1))) return failNull(who);
+    if (!(gravity >= 0.)) return failArgument(who, "gravity must not be negative");
+    if (vertexCount > em2::kLayoutMaxVertexCount) return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": vertexCount is above 2^30");
+    if (energy) *energy = 0.;
+    if (vertexCount == 0) return edgeCount ? failArgument(who, "an edge names a vertex outside the graph") : EM2_OK;
+    if (!haveDevice()) return failNoDevice(who);
+    DeviceBuffer d0, d1, dx, dy, dfx, dfy;
+    const int status = uploadEdges(edgeVertex0, edgeVertex1, edgeCount, d0, d1);
+    if (status != EM2_OK) return status;
+    EM2_HIP(dx.upload(x, vertexCount));
+    EM2_HIP(dy.upload(y, vertexCount));
+    EM2_HIP(dfx.allocateFor<float>(vertexCount));
+    EM2_HIP(dfy.allocateFor<float>(vertexCount));
+    uint32_t inputError = 0;
+    double e = 0.;
+    EM2_HIP(em2::runGraphLayoutForces(vertexCount, d0.as<uint32_t>(), d1.as<uint32_t>(), edgeCount, gravity, dx.as<float>(), dy.as<float>(),
+                                      dfx.as<float>(), dfy.as<float>(), &e, &inputError, nullptr));
+    if (inputError) return failArgument(who, "an edge names a vertex outside the graph");
+    EM2_HIP(dfx.download(fx, vertexCount));
+    EM2_HIP(dfy.download(fy, vertexCount));
+    if (energy) *energy = e;
+    return EM2_OK;
+}
+
+}  // extern "C"

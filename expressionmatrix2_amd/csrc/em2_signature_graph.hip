@@ -29,15 +29,49 @@
 // them.
 
 #include "em2_device.h"
-#include "em2_hip_util.h"
+#include "em2_entry.h"
 #include "em2_scratch.h"
-#include "em2_signature_graph.h"
 #include "em2_wave.h"
 
 #include <cstring>            // (rocPRIM calls memset without including it)
 #include <rocprim/rocprim.hpp>
+#include <algorithm>
+#include <fstream>
+#include <map>
+#include <memory>
+#include <string>
+#include <vector>
 
+// What the device code and the C entry points at the end of this file share.
 namespace em2 {
+
+// The longest signature the grouping takes (1024 words of 64 bits).
+constexpr uint32_t kSignatureGraphMaxLshCount = 65536;
+
+// What ExpressionMatrix::createSignatureGraph (src/ExpressionMatrixSignatureGraph.cpp:42-150) leaves in the SignatureGraph,
+// in host memory.  Vertices in the order of the reference's std::map (ascending by word 0, then word 1, ...); cells are ids
+// local to the cell set, ascending within a vertex; edges in the order of SignatureGraph::createEdges (src/SignatureGraph.cpp:
+// 23-48): vertex 0 ascending, then bit ascending.
+struct SignatureGraphResult {
+    uint32_t wordCount = 0;
+    uint64_t distinctCount = 0;                  // groups before the minCellCount filter
+    std::vector<uint64_t> vertexSignatures;      // [vertexCount][wordCount]
+    std::vector<uint64_t> cellOffsets;           // [vertexCount + 1]
+    std::vector<uint32_t> cells;                 // [cellOffsets[vertexCount]]
+    std::vector<uint32_t> edgeVertex0, edgeVertex1;
+};
+
+// d_signatures [cellCount][wordCount] in device memory, cellCount > 0, 0 < lshCount <= kSignatureGraphMaxLshCount.
+// withEdges false: the groups only (analyzeLshSignatures).  *inputError != 0: a signature has a bit set at or beyond lshCount,
+// nothing was computed.  Takes its scratch from the cache of em2_scratch.h; synchronises the stream.
+static hipError_t runSignatureGraph(const uint64_t* d_signatures, uint32_t cellCount, uint32_t lshCount, uint64_t minCellCount, bool withEdges,
+                                    SignatureGraphResult& out, uint32_t* inputError, hipStream_t stream);
+
+// Lsh::writeSignatureStatistics (src/Lsh.cpp:279-303) without its text: d_setCount[i] = the cells with bit i set, i < lshCount.
+// d_setCount is zeroed here.  Asynchronous on the stream.
+static hipError_t launchSignatureStatistics(const uint64_t* d_signatures, uint32_t cellCount, uint32_t lshCount,
+                                            unsigned long long* d_setCount, hipStream_t stream);
+
 namespace {
 
 // keys[i] = word w of the signature of the i-th cell in the current order (order NULL: cell i, and ids[i] = i), shifted right
@@ -436,3 +470,185 @@ hipError_t launchSignatureStatistics(const uint64_t* d_signatures, uint32_t cell
 }
 
 }  // namespace em2
+
+
+// ---- the C entry points (include/em2_lsh.h) ----
+
+using namespace em2::entry;
+using em2::DeviceBuffer;
+using em2::wordCountOf;
+
+extern "C" {
+
+struct em2_signature_graph {
+    em2::SignatureGraphResult result;
+};
+
+// lshCount, then cellCount, then the pointer, then the device: none of them reaches a launch.
+static int checkSignatureArguments(const char* who, const void* signatures, uint32_t cellCount, uint32_t lshCount)
+{
+    if (lshCount == 0) return failArgument(who, "lshCount must be positive");
+    if (lshCount > em2::kSignatureGraphMaxLshCount) {
+        return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": lshCount above " + std::to_string(em2::kSignatureGraphMaxLshCount) + " is not supported");
+    }
+    if (cellCount == 0) return failArgument(who, "cellCount must be positive");
+    if (!signatures) return failNull(who);
+    if (!haveDevice()) return failNoDevice(who);
+    return EM2_OK;
+}
+
+static int signatureGroups(const char* who, const uint64_t* d_signatures, uint32_t cellCount, uint32_t lshCount, uint64_t minCellCount,
+                           bool withEdges, em2::SignatureGraphResult& result)
+{
+    uint32_t inputError = 0;
+    EM2_HIP(em2::runSignatureGraph(d_signatures, cellCount, lshCount, minCellCount, withEdges, result, &inputError, nullptr));
+    if (inputError) return failArgument(who, "a signature has a bit set at or beyond lshCount");
+    return EM2_OK;
+}
+
+static int signatureGraphCreate(const char* who, bool onDevice, const uint64_t* signatures, uint32_t cellCount, uint32_t lshCount,
+                                uint64_t minCellCount, em2_signature_graph** graph)
+{
+    if (!graph) return failNull(who);
+    *graph = nullptr;
+    int rc = checkSignatureArguments(who, signatures, cellCount, lshCount);
+    if (rc != EM2_OK) return rc;
+    DeviceBuffer dSig;
+    if (!onDevice) EM2_HIP(dSig.upload(signatures, size_t(cellCount) * wordCountOf(lshCount)));
+    std::unique_ptr<em2_signature_graph> g(new em2_signature_graph);
+    rc = signatureGroups(who, onDevice ? signatures : dSig.as<uint64_t>(), cellCount, lshCount, minCellCount, true, g->result);
+    if (rc != EM2_OK) return rc;
+    *graph = g.release();
+    return EM2_OK;
+}
+
+int em2_signature_graph_create(const uint64_t* signatures, uint32_t cellCount, uint32_t lshCount, uint64_t minCellCount,
+                               em2_signature_graph** graph)
+{
+    return signatureGraphCreate("em2_signature_graph_create", false, signatures, cellCount, lshCount, minCellCount, graph);
+}
+
+int em2_dev_signature_graph_create(const uint64_t* d_signatures, uint32_t cellCount, uint32_t lshCount, uint64_t minCellCount,
+                                   em2_signature_graph** graph)
+{
+    return signatureGraphCreate("em2_dev_signature_graph_create", true, d_signatures, cellCount, lshCount, minCellCount, graph);
+}
+
+int em2_signature_graph_sizes(const em2_signature_graph* graph, uint64_t* distinctCount, uint32_t* vertexCount, uint32_t* wordCount,
+                              uint64_t* cellCount, uint64_t* edgeCount)
+{
+    if (!graph) return failNull("em2_signature_graph_sizes");
+    const em2::SignatureGraphResult& r = graph->result;
+    if (distinctCount) *distinctCount = r.distinctCount;
+    if (vertexCount) *vertexCount = uint32_t(r.cellOffsets.size() - 1u);
+    if (wordCount) *wordCount = r.wordCount;
+    if (cellCount) *cellCount = r.cells.size();
+    if (edgeCount) *edgeCount = r.edgeVertex0.size();
+    return EM2_OK;
+}
+
+int em2_signature_graph_get(const em2_signature_graph* graph, uint64_t* vertexSignatures, uint64_t* cellOffsets, uint32_t* cells,
+                            uint32_t* edgeVertex0, uint32_t* edgeVertex1)
+{
+    if (!graph) return failNull("em2_signature_graph_get");
+    const em2::SignatureGraphResult& r = graph->result;
+    if (vertexSignatures) std::copy(r.vertexSignatures.begin(), r.vertexSignatures.end(), vertexSignatures);
+    if (cellOffsets) std::copy(r.cellOffsets.begin(), r.cellOffsets.end(), cellOffsets);
+    if (cells) std::copy(r.cells.begin(), r.cells.end(), cells);
+    if (edgeVertex0) std::copy(r.edgeVertex0.begin(), r.edgeVertex0.end(), edgeVertex0);
+    if (edgeVertex1) std::copy(r.edgeVertex1.begin(), r.edgeVertex1.end(), edgeVertex1);
+    return EM2_OK;
+}
+
+void em2_signature_graph_free(em2_signature_graph* graph) { delete graph; }
+
+// setCount[lshCount] on the host from signatures that are on the device.
+static int signatureStatisticsToHost(const uint64_t* d_signatures, uint32_t cellCount, uint32_t lshCount, uint64_t* setCount)
+{
+    DeviceBuffer dCounts;
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the kernel's counters are the caller's uint64_t");
+    EM2_HIP(dCounts.allocateFor<uint64_t>(lshCount));
+    EM2_HIP(em2::launchSignatureStatistics(d_signatures, cellCount, lshCount, dCounts.as<unsigned long long>(), nullptr));
+    EM2_HIP(dCounts.download(setCount, lshCount));
+    return EM2_OK;
+}
+
+static int signatureStatistics(const char* who, bool onDevice, const uint64_t* signatures, uint32_t cellCount, uint32_t lshCount,
+                               uint64_t* setCount)
+{
+    const int rc = checkSignatureArguments(who, setCount ? static_cast<const void*>(signatures) : nullptr, cellCount, lshCount);
+    if (rc != EM2_OK) return rc;
+    DeviceBuffer dSig;
+    if (!onDevice) EM2_HIP(dSig.upload(signatures, size_t(cellCount) * wordCountOf(lshCount)));
+    return signatureStatisticsToHost(onDevice ? signatures : dSig.as<uint64_t>(), cellCount, lshCount, setCount);
+}
+
+int em2_lsh_signature_statistics(const uint64_t* signatures, uint32_t cellCount, uint32_t lshCount, uint64_t* setCount)
+{
+    return signatureStatistics("em2_lsh_signature_statistics", false, signatures, cellCount, lshCount, setCount);
+}
+
+int em2_dev_lsh_signature_statistics(const uint64_t* d_signatures, uint32_t cellCount, uint32_t lshCount, uint64_t* setCount)
+{
+    return signatureStatistics("em2_dev_lsh_signature_statistics", true, d_signatures, cellCount, lshCount, setCount);
+}
+
+int em2_analyze_lsh_signatures(const uint64_t* signatures, uint32_t cellCount, uint32_t lshCount, const char* directory)
+{
+    const char* who = "em2_analyze_lsh_signatures";
+    int rc = checkSignatureArguments(who, signatures, cellCount, lshCount);
+    if (rc != EM2_OK) return rc;
+    const uint32_t words = wordCountOf(lshCount);
+    DeviceBuffer dSig;
+    EM2_HIP(dSig.upload(signatures, size_t(cellCount) * words));
+    em2::SignatureGraphResult groups;                           // src/ExpressionMatrixLsh.cpp:1421-1424: the map, nothing filtered
+    rc = signatureGroups(who, dSig.as<uint64_t>(), cellCount, lshCount, 0u, false, groups);
+    if (rc != EM2_OK) return rc;
+    std::vector<uint64_t> setCount(lshCount);
+    rc = signatureStatisticsToHost(dSig.as<uint64_t>(), cellCount, lshCount, setCount.data());
+    if (rc != EM2_OK) return rc;
+    dSig.release();
+
+    const std::string prefix = directory && directory[0] ? std::string(directory) + "/" : std::string();
+    const size_t groupCount = groups.cellOffsets.size() - 1u;
+    // :1428-1435: (signature, size) in map order, std::sort by size descending -- not stable: the host's own std::sort
+    std::vector<std::pair<uint64_t, uint64_t>> table(groupCount);
+    for (size_t g = 0; g < groupCount; ++g) table[g] = std::make_pair(uint64_t(g), groups.cellOffsets[g + 1u] - groups.cellOffsets[g]);
+    std::sort(table.begin(), table.end(),
+              [](const std::pair<uint64_t, uint64_t>& x, const std::pair<uint64_t, uint64_t>& y) { return x.second > y.second; });
+    {
+        const std::string path = prefix + "Signatures.csv";                                  // :1440-1447
+        std::ofstream csv(path);
+        if (!csv) return fail(EM2_ERROR_RUNTIME, std::string(who) + ": cannot open " + path);
+        std::string line(size_t(lshCount), '_');
+        for (const std::pair<uint64_t, uint64_t>& p : table) {
+            const uint64_t* signature = groups.vertexSignatures.data() + size_t(p.first) * words;
+            for (uint32_t i = 0; i < lshCount; ++i) line[i] = (signature[i >> 6] >> (63u - (i & 63u))) & 1u ? 'x' : '_';
+            csv << line << "," << p.second << "\n";
+        }
+    }
+    {
+        const std::string path = prefix + "Histogram.csv";                                   // :1451-1467
+        std::ofstream csv(path);
+        if (!csv) return fail(EM2_ERROR_RUNTIME, std::string(who) + ": cannot open " + path);
+        std::map<uint64_t, uint64_t> groupsOfSize;               // the sizes that occur, ascending
+        for (size_t g = 0; g < groupCount; ++g) groupsOfSize[groups.cellOffsets[g + 1u] - groups.cellOffsets[g]] += 1u;
+        uint64_t cellsSoFar = 0;
+        for (const std::pair<const uint64_t, uint64_t>& entry : groupsOfSize) {
+            cellsSoFar += entry.first * entry.second;
+            csv << entry.first << "," << entry.second << "," << entry.first * entry.second << "," << cellsSoFar << "\n";
+        }
+    }
+    {
+        const std::string path = prefix + "LshSignatureStatistics.csv";                      // src/Lsh.cpp:284-301
+        std::ofstream csv(path);
+        if (!csv) return fail(EM2_ERROR_RUNTIME, std::string(who) + ": cannot open " + path);
+        csv << "Bit,Set,Unset,Total\n";
+        for (uint32_t i = 0; i < lshCount; ++i) {
+            csv << i << "," << setCount[i] << "," << uint64_t(cellCount) - setCount[i] << "," << cellCount << "\n";
+        }
+    }
+    return EM2_OK;
+}
+
+}  // extern "C"

@@ -18,7 +18,7 @@ K = 1.0
 FLOOR = 1e-30
 T = 0.9
 DEFAULTS = dict(seed=231, maxIterationCount=300, tolerance=0.01, gravity=0.02, initialStep=1.0)
-# the shapes of csrc/em2_layout.h
+# the shapes of csrc/em2_layout.hip
 SLICE_COUNT = 16
 TILE = 128
 BLOCK_VERTICES = 256
