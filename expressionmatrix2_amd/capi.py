@@ -155,6 +155,12 @@ SYMBOLS = {
                                         _c.c_void_p]),
     "em2_graph_layout_forces": (_c.c_int, [_c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_double, _c.c_void_p, _c.c_void_p,
                                            _c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_double)]),
+    "em2_graph_layout_pyramid": (_c.c_int, [_c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint32, _c.c_void_p,
+                                            _c.c_void_p, _c.c_void_p]),
+    "em2_dev_graph_layout_pyramid": (_c.c_int, [_c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint32, _c.c_void_p,
+                                                _c.c_void_p, _c.c_void_p]),
+    "em2_graph_layout_forces_pyramid": (_c.c_int, [_c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_double, _c.c_uint32, _c.c_void_p,
+                                                   _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_double)]),
     "em2_matrix_create_gene_graph": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_int64, _c.c_double, _c.POINTER(_c.c_void_p)]),
     "em2_matrix_create_gene_set_intersection": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.POINTER(_c.c_int)]),
     "em2_matrix_create_gene_set_union": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.POINTER(_c.c_int)]),
@@ -736,18 +742,40 @@ def _layout_edges(vertex_count, edge_vertex0, edge_vertex1):
     return int(vertex_count), v0, v1
 
 
-def graph_layout(vertex_count, edge_vertex0, edge_vertex1, parameters=None):
+LAYOUT_DEPTH_AUTO = 0xffffffff                                # EM2_LAYOUT_DEPTH_AUTO
+LAYOUT_MAX_DEPTH = 10                                         # EM2_LAYOUT_MAX_DEPTH
+LAYOUT_LEAF_TARGET = 8                                        # EM2_LAYOUT_LEAF_TARGET
+
+
+def _depth(depth):
+    """The depth argument of a pyramid entry as a tuple to splice into the call; none for an exact entry (depth None)."""
+    return () if depth is None else (int(depth) % 2 ** 32,)
+
+
+def graph_layout(vertex_count, edge_vertex0, edge_vertex1, parameters=None, _depth_argument=None):
     """em2_graph_layout -> (x float32 [V], y float32 [V], iterations, final step, final energy).  parameters: a
     LayoutParameters (None: the defaults)."""
     n, v0, v1 = _layout_edges(vertex_count, edge_vertex0, edge_vertex1)
     parameters = parameters if parameters is not None else LayoutParameters()
     x, y = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.float32)
     result = LayoutResult()
-    check(load().em2_graph_layout(n, _ptr(v0), _ptr(v1), len(v0), ctypes.byref(parameters), _ptr(x), _ptr(y), ctypes.byref(result)))
+    entry = load().em2_graph_layout if _depth_argument is None else load().em2_graph_layout_pyramid
+    check(entry(n, _ptr(v0), _ptr(v1), len(v0), ctypes.byref(parameters), *_depth(_depth_argument), _ptr(x), _ptr(y), ctypes.byref(result)))
     return x, y, result.iterationCount, result.step, result.energy
 
 
-def dev_graph_layout(vertex_count, edge_vertex0, edge_vertex1, parameters=None):
+def graph_layout_pyramid(vertex_count, edge_vertex0, edge_vertex1, parameters=None, depth=LAYOUT_DEPTH_AUTO):
+    """em2_graph_layout_pyramid: the same with the repulsion approximated beyond a vertex's neighbourhood.
+    depth: LAYOUT_DEPTH_AUTO or 0 ... LAYOUT_MAX_DEPTH."""
+    return graph_layout(vertex_count, edge_vertex0, edge_vertex1, parameters, _depth_argument=depth)
+
+
+def dev_graph_layout_pyramid(vertex_count, edge_vertex0, edge_vertex1, parameters=None, depth=LAYOUT_DEPTH_AUTO):
+    """The same through em2_dev_graph_layout_pyramid."""
+    return dev_graph_layout(vertex_count, edge_vertex0, edge_vertex1, parameters, _depth_argument=depth)
+
+
+def dev_graph_layout(vertex_count, edge_vertex0, edge_vertex1, parameters=None, _depth_argument=None):
     """The same through em2_dev_graph_layout: the edges go to torch device buffers first, the positions come back from two."""
     import torch
     n, v0, v1 = _layout_edges(vertex_count, edge_vertex0, edge_vertex1)
@@ -759,13 +787,18 @@ def dev_graph_layout(vertex_count, edge_vertex0, edge_vertex1, parameters=None):
     d_y = torch.zeros(n, dtype=torch.float32, device=device)
     torch.cuda.synchronize()
     result = LayoutResult()
-    check(load().em2_dev_graph_layout(n, d_v0.data_ptr() if len(v0) else None, d_v1.data_ptr() if len(v0) else None, len(v0),
-                                      ctypes.byref(parameters), d_x.data_ptr() if n else None, d_y.data_ptr() if n else None,
-                                      ctypes.byref(result)))
+    entry = load().em2_dev_graph_layout if _depth_argument is None else load().em2_dev_graph_layout_pyramid
+    check(entry(n, d_v0.data_ptr() if len(v0) else None, d_v1.data_ptr() if len(v0) else None, len(v0), ctypes.byref(parameters),
+                *_depth(_depth_argument), d_x.data_ptr() if n else None, d_y.data_ptr() if n else None, ctypes.byref(result)))
     return d_x.cpu().numpy(), d_y.cpu().numpy(), result.iterationCount, result.step, result.energy
 
 
-def graph_layout_forces(vertex_count, edge_vertex0, edge_vertex1, gravity, x, y):
+def graph_layout_forces_pyramid(vertex_count, edge_vertex0, edge_vertex1, gravity, x, y, depth=LAYOUT_DEPTH_AUTO):
+    """em2_graph_layout_forces_pyramid (for tests): the same evaluation with the approximated repulsion."""
+    return graph_layout_forces(vertex_count, edge_vertex0, edge_vertex1, gravity, x, y, _depth_argument=depth)
+
+
+def graph_layout_forces(vertex_count, edge_vertex0, edge_vertex1, gravity, x, y, _depth_argument=None):
     """em2_graph_layout_forces (for tests): one evaluation at the positions x / y -> (fx float32 [V], fy float32 [V], energy)."""
     n, v0, v1 = _layout_edges(vertex_count, edge_vertex0, edge_vertex1)
     x = np.ascontiguousarray(x, dtype=np.float32)
@@ -774,8 +807,9 @@ def graph_layout_forces(vertex_count, edge_vertex0, edge_vertex1, gravity, x, y)
         raise ValueError("x and y must hold one position per vertex")
     fx, fy = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.float32)
     energy = ctypes.c_double(0.)
-    check(load().em2_graph_layout_forces(n, _ptr(v0), _ptr(v1), len(v0), float(gravity), _ptr(x), _ptr(y), _ptr(fx), _ptr(fy),
-                                         ctypes.byref(energy)))
+    entry = load().em2_graph_layout_forces if _depth_argument is None else load().em2_graph_layout_forces_pyramid
+    check(entry(n, _ptr(v0), _ptr(v1), len(v0), float(gravity), *_depth(_depth_argument), _ptr(x), _ptr(y), _ptr(fx), _ptr(fy),
+                ctypes.byref(energy)))
     return fx, fy, energy.value
 
 

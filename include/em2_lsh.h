@@ -802,6 +802,46 @@ int em2_dev_graph_layout(uint32_t vertexCount, const uint32_t* d_edgeVertex0, co
 int em2_graph_layout_forces(uint32_t vertexCount, const uint32_t* edgeVertex0, const uint32_t* edgeVertex1, uint64_t edgeCount,
                             double gravity, const float* x, const float* y, float* fx, float* fy, double* energy);
 
+/* The same model with the repulsion approximated beyond a vertex's neighbourhood: a pyramid of fixed depth over the bounding
+ * square of the current positions.  An option next to the exact entries above, which stay as they are.  Still
+ * a function of the input alone, bit for bit: every sum that many threads share is an integer sum.  Per force evaluation, at
+ * the current float32 positions:
+ *   box      xmin, xmax, ymin, ymax over all vertices; S = fmaxf(xmax - xmin, ymax - ymin).  S == 0: every vertex is in cell 0
+ *            of every level.
+ *   q        u = fminf(fmaxf((x - xmin) / S, 0), 1), q = uint32_t(u * 2^31) <= 2^31, per axis.  Nothing but q forms an index.
+ *   levels   level l = 0 ... D has 2^l x 2^l cells; the cell of a vertex is min(2^l - 1, q >> (31 - l)) per axis.  D is the
+ *            smallest value in 0 ... EM2_LAYOUT_MAX_DEPTH with EM2_LAYOUT_LEAF_TARGET * 4^D >= vertexCount, else the maximum;
+ *            `depth` forces it (EM2_LAYOUT_DEPTH_AUTO: that rule).
+ *   order    the vertices sorted by (morton(cell at level D), vertex), one radix sort of distinct keys: within a leaf they
+ *            ascend by index.
+ *   moments  per cell a count and the integer sums of q_x and q_y (uint64); a parent is the sum of its four children.  The
+ *            centroid of a non-empty cell, one rounding from double: m = float(double(xmin) + double(S) * t) with
+ *            t = double(sum q) / (double(count) * 2^31).
+ *   far      for l = 2 ... D ascending, (ax, ay) the vertex's cell: the cells (bx, by) of level l with by ascending from
+ *            2 ((ay >> 1) - 1) to 2 ((ay >> 1) + 1) + 1 and bx likewise inside, that are inside the grid, not empty and not
+ *            within Chebyshev distance 1 of (ax, ay) -- at most 27 a level.  Per cell dx = x_i - m_x, dy = y_i - m_y,
+ *            d2 = fmaf(dx, dx, dy * dy), w = (0.2f * float(count)) / fmaxf(d2, 1e-30f), fx = fmaf(dx, w, fx), fy likewise:
+ *            one sequential sum from +0.
+ *   near     the leaves within Chebyshev distance 1 of the vertex's own (by ascending, then bx), their vertices in ascending
+ *            index, the exact pair term: a second sequential sum from +0.  The repulsion is far + near.
+ * Everything else (attraction, gravity, the move, the energy in vertex order, the step, the start positions, the stop rule)
+ * is that of the exact entries.  Known limits: the cells are separated by one cell width only (theta <= 1 in Barnes-Hut's
+ * terms, where sfdp uses 0.6); a layout that collapses into a few dense clusters fills few leaves, and the near field then
+ * grows towards the exact cost -- the tree is not adaptive.  No multilevel coarsening.
+ * The checks, codes and texts are those of the exact entries; a depth that is neither EM2_LAYOUT_DEPTH_AUTO nor
+ * <= EM2_LAYOUT_MAX_DEPTH is EM2_ERROR_INVALID_ARGUMENT. */
+#define EM2_LAYOUT_DEPTH_AUTO 0xffffffffu
+#define EM2_LAYOUT_MAX_DEPTH 10u
+#define EM2_LAYOUT_LEAF_TARGET 8u /* part of the contract: it decides the automatic depth and so the bits of the result */
+int em2_graph_layout_pyramid(uint32_t vertexCount, const uint32_t* edgeVertex0, const uint32_t* edgeVertex1, uint64_t edgeCount,
+                             const em2_layout_parameters* parameters, uint32_t depth, float* x, float* y, em2_layout_result* result);
+int em2_dev_graph_layout_pyramid(uint32_t vertexCount, const uint32_t* d_edgeVertex0, const uint32_t* d_edgeVertex1, uint64_t edgeCount,
+                                 const em2_layout_parameters* parameters, uint32_t depth, float* d_x, float* d_y,
+                                 em2_layout_result* result);
+int em2_graph_layout_forces_pyramid(uint32_t vertexCount, const uint32_t* edgeVertex0, const uint32_t* edgeVertex1, uint64_t edgeCount,
+                                    double gravity, uint32_t depth, const float* x, const float* y, float* fx, float* fy,
+                                    double* energy);
+
 /* ------------------------------------------------------------------------------------------------------
  * The contingency table of two labelings of n items.  csrc/em2_contingency.hip, DESIGN.md 3.16.  Integers only: every output
  * is exact.
