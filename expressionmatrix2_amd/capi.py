@@ -46,6 +46,7 @@ SYMBOLS = {
                                               _c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_size_t,
                                               _c.c_void_p]),
     "em2_dev_compute_signatures_tier": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_int, _c.c_void_p]),
+    "em2_dev_compute_signatures_listed": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_int, _c.c_void_p]),
     "em2_dev_vector_aux_bytes": (_c.c_size_t, [_c.c_uint32, _c.c_uint32]),
     "em2_dev_prepare_vectors": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_void_p, _c.c_void_p]),
     "em2_dev_find_similar_pairs4_workspace": (_c.c_size_t, [_c.c_uint32, _c.c_uint32, _c.c_uint32, _c.c_uint32]),
@@ -1283,6 +1284,14 @@ def dev_compute_signatures_tier(workspace_ptr, cell_count, lsh_count, have_vecto
     tier = ctypes.c_int(-1)
     check(load().em2_dev_compute_signatures_tier(workspace_ptr, cell_count, lsh_count, 1 if have_vector_aux else 0, ctypes.byref(tier)))
     return TIER_NAMES[tier.value]
+
+
+def dev_compute_signatures_listed(workspace_ptr, cell_count, lsh_count, have_vector_aux=True):
+    """How far the tiers of the last dev_compute_signatures call on this workspace got (include/em2_lsh.h): the words listed for
+    the float tier's word form, the words listed by a single bit, the entries left to the exact tier."""
+    listed = (ctypes.c_uint32 * 3)()
+    check(load().em2_dev_compute_signatures_listed(workspace_ptr, cell_count, lsh_count, 1 if have_vector_aux else 0, listed))
+    return {"words": int(listed[0]), "bits": int(listed[1]), "exact": int(listed[2])}
 
 
 def dev_vector_aux_bytes(gene_count, lsh_count):

@@ -490,6 +490,32 @@ int em2_dev_compute_signatures_tier(const void* d_workspace, uint32_t cellCount,
 }
 
 
+int em2_dev_compute_signatures_listed(const void* d_workspace, uint32_t cellCount, uint32_t lshCount, int haveVectorAux, uint32_t* listed)
+{
+    if (!listed) return failNull("em2_dev_compute_signatures_listed");
+    if (lshCount == 0) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dev_compute_signatures_listed: bad argument");
+    listed[0] = listed[1] = listed[2] = 0;
+    if (!haveVectorAux || lshCount % 4u != 0u || cellCount == 0) return EM2_OK;
+    if (!d_workspace) return fail(EM2_ERROR_INVALID_ARGUMENT, "em2_dev_compute_signatures_listed: null workspace");
+    // (the counters behind the two per-cell arrays of the workspace, csrc/em2_project.hip: launchProjectionScreened -- word 0 the
+    // first tier's list of words, word 32 the 16-bit tier's list of single bits, word 16 what the float tier leaves behind the
+    // 16-bit tier; a float first tier lists straight for the exact tier, in word 0)
+    const char* ws = reinterpret_cast<const char*>(alignUp(reinterpret_cast<size_t>(d_workspace)));
+    const size_t a = (size_t(cellCount) * sizeof(double) + 255u) & ~size_t(255u);
+    uint32_t counters[33];
+    EM2_HIP(hipDeviceSynchronize());          // (as em2_dev_compute_signatures_tier: every stream of the device)
+    EM2_HIP(hipMemcpy(counters, ws + 2u * a, sizeof(counters), hipMemcpyDeviceToHost));
+    if (lshCount % 64u == 0u) {
+        listed[0] = counters[0];
+        listed[1] = counters[32];
+        listed[2] = counters[16];
+    } else {
+        listed[2] = counters[0];
+    }
+    return EM2_OK;
+}
+
+
 size_t em2_dev_find_similar_pairs4_workspace(uint32_t cellCount, uint32_t rowCount, uint32_t lshCount, uint32_t k)
 {
     if (lshCount == 0) return 0;

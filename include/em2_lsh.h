@@ -295,6 +295,16 @@ int em2_dev_compute_signatures(const uint64_t* d_toc, const em2_count* d_data, u
 enum { EM2_TIER_EXACT = 0, EM2_TIER_FLOAT = 1, EM2_TIER_FIXED16_FLOAT = 2, EM2_TIER_FIXED16_INTEGER = 3 };
 int em2_dev_compute_signatures_tier(const void* d_workspace, uint32_t cellCount, uint32_t lshCount, int haveVectorAux, int* tier);
 
+/* How far the tiers of that call got, read from the same workspace under the same conditions (it waits for the whole device, the
+ * workspace must be untouched since the call); nothing is launched and nothing written on the device.  listed[3]:
+ *   listed[0]  64-bit words the 16-bit tier listed for the word form of the float tier (several undecided bits)
+ *   listed[1]  64-bit words the 16-bit tier listed by their single undecided bit, for the per-bit form of the float tier
+ *   listed[2]  list entries left to the exact arithmetic: words behind the 16-bit and float tiers; where the float copy is the
+ *              first tier, one entry per (cell, word) at lshCount no multiple of 32 and one per (cell, 32-bit slice) otherwise
+ * Zeros for a tier the width does not have (listed[0], listed[1] at lshCount no multiple of 64) and all zeros when the call
+ * had no auxiliary block or lshCount is no multiple of 4 (the exact arithmetic ran alone, without a list). */
+int em2_dev_compute_signatures_listed(const void* d_workspace, uint32_t cellCount, uint32_t lshCount, int haveVectorAux, uint32_t* listed);
+
 /* Bytes of device scratch em2_dev_find_similar_pairs4 needs for rowCount rows. */
 size_t em2_dev_find_similar_pairs4_workspace(uint32_t cellCount, uint32_t rowCount, uint32_t lshCount,
                                              uint32_t k);

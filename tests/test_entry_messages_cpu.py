@@ -102,6 +102,7 @@ VALID = {
     "em2_dev_find_similar_pairs4_last_launch": (None, 9),
     "em2_dev_find_similar_pairs5_last_launch": (None, 12),
     "em2_dev_fsp4_sharded_plan": (N, L, K, 0, 1, None, 12),
+    "em2_dev_compute_signatures_listed": (None, N, L, 1, U32),
 }
 
 # (entry point, index of the argument that is null, the text in front of ": null pointer")
@@ -169,7 +170,20 @@ NULL_CASES = [
     ("em2_dev_find_similar_pairs4_last_launch", 0, "em2_dev_find_similar_pairs4_last_launch"),
     ("em2_dev_find_similar_pairs5_last_launch", 0, "em2_dev_find_similar_pairs5_last_launch"),
     ("em2_dev_fsp4_sharded_plan", 5, "em2_dev_fsp4_sharded_plan"),
+    ("em2_dev_compute_signatures_listed", 4, "em2_dev_compute_signatures_listed"),
 ]
+
+
+def test_the_read_back_of_the_projection_lists_checks_its_arguments():
+    """em2_dev_compute_signatures_listed: its two other refusals, and the zeros it reports without touching the device when the
+    call it asks about had no list (no auxiliary block, a width that is no multiple of 4, no cells)."""
+    listed = np.full(3, 7, dtype=np.uint32)
+    assert call("em2_dev_compute_signatures_listed", (None, N, 0, 1, listed)) == (INVALID, "em2_dev_compute_signatures_listed: bad argument")
+    assert call("em2_dev_compute_signatures_listed", (None, N, L, 1, listed)) == (INVALID, "em2_dev_compute_signatures_listed: null workspace")
+    for cells, lsh_count, aux in [(N, L, 0), (N, 63, 1), (0, L, 1)]:
+        listed[:] = 7
+        assert capi.load().em2_dev_compute_signatures_listed(None, cells, lsh_count, aux, listed.ctypes.data) == 0
+        assert listed.tolist() == [0, 0, 0]
 
 # (entry point, the text in front of the sentence): every entry point of VALID that looks for the device
 NO_DEVICE_CASES = [

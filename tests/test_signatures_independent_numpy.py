@@ -1,4 +1,4 @@
-"""A second, independent restatement of Lsh::computeCellLshSignatures (src/Lsh.cpp:118-224) and of the per-cell sums it reads
+"""The oracle against a second, independent restatement of Lsh::computeCellLshSignatures (src/Lsh.cpp:118-224) and of the per-cell sums it reads
 (ExpressionMatrixSubset::computeSums, src/ExpressionMatrixSubset.cpp:46-58) in numpy float64 -- sharing no code with
 oracle/em2_oracle.cpp.  The signature of a cell is the sign pattern of sequentially rounded double sums, so the ORDER of the
 additions and the separate rounding of every product (no fused multiply-add: the reference is an SSE4.2 build) are what is
@@ -10,27 +10,7 @@ import numpy as np
 import pytest
 
 import synth
-
-
-def compute_signatures(toc, genes, counts, gene_count, vectors, lsh_count):
-    cells = len(toc) - 1
-    words = (lsh_count - 1) // 64 + 1                                       # :127
-    sums = np.zeros(lsh_count, dtype=np.float64)
-    for g in range(gene_count):                                             # :137-144, ascending gene id
-        sums += vectors[g]
-    out = np.zeros((cells, words), dtype=np.uint64)
-    for c in range(cells):
-        lo, hi = int(toc[c]), int(toc[c + 1])
-        sum1 = np.float64(0.0)
-        for x in counts[lo:hi]:                                             # computeSums: double += float, stored order
-            sum1 = sum1 + np.float64(x)
-        mean = sum1 / np.float64(gene_count)                                # :167-168
-        sp = -mean * sums                                                   # :180-182
-        for g, x in zip(genes[lo:hi], counts[lo:hi]):                       # :188-198, stored (ascending local gene id) order
-            sp = sp + np.float64(x) * vectors[int(g)]
-        for i in np.nonzero(sp > 0.0)[0]:                                   # :201-206; bit i -> word i >> 6, position 63 - (i & 63)
-            out[c, int(i) >> 6] |= np.uint64(1) << np.uint64(63 - (int(i) & 63))
-    return out
+from projection_limit_cases import compute_signatures      # the restatement itself: tests/projection_limit_cases.py (reference_values)
 
 
 @pytest.mark.parametrize("cells,genes,L,density,scale", [

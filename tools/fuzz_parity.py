@@ -21,7 +21,11 @@ Two legs draw from tests/ingest_limit_cases.py: csv_parse (random structure and 
 subset through csv_binding.assert_parse, against the model of em2_dev_csv_parse) and ingest (row lengths around 512 and the LDS
 row limit, value kinds, orders, duplicates, zeros and skip flags through ingest_binding.assert_same, against the restatement of
 addCell's storing part).  FUZZ_ONLY=csv_parse / ingest selects them; a difference prints the draw's dict (its seed rebuilds it:
-ingest_limit_cases.draw_csv_parse(None, seed) / draw_ingest(None, seed))."""
+ingest_limit_cases.draw_csv_parse(None, seed) / draw_ingest(None, seed)).
+
+One leg draws from tests/projection_limit_cases.py (FUZZ_ONLY=projection_limits): quantisation traps, float-copy traps and flip
+points with random seeds, sizes and widths through capi.compute_signatures, against the oracle; a difference prints the draw
+(projection_limit_cases.build(draw) rebuilds the case)."""
 import os
 import sys
 import time
@@ -34,6 +38,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import expression_cases  # noqa: E402
 import fsp6_binding  # noqa: E402
 import oracle_binding  # noqa: E402
+import projection_limit_cases  # noqa: E402
 import synth  # noqa: E402
 from label_graphs import fast_graph  # noqa: E402
 from expressionmatrix2_amd import capi  # noqa: E402
@@ -55,10 +60,21 @@ def main():
     for name in expression_cases.ENTRIES:
         runs.update({name: 0, name + "_skipped": 0, name + "_discarded": 0})
     runs.update({name: 0 for name in WRITE_LEGS})
+    runs["projection_limits"] = 0
     references = {}
     while time.time() < deadline:
         for key in KNOBS:
             os.environ.pop(key, None)
+        if os.environ.get("FUZZ_ONLY") == "projection_limits" or (rng.random() < 0.08 and not os.environ.get("FUZZ_ONLY")):
+            draw = projection_limit_cases.draw(rng)
+            case = projection_limit_cases.build(draw)
+            arguments = (case["gene_count"], case["vectors"], case["L"])
+            expect = oracle.compute_signatures(case["toc"], case["genes"], case["counts"], *arguments)
+            got = capi.compute_signatures(case["toc"], capi.make_counts(case["genes"], case["counts"]), *arguments)
+            if not np.array_equal(expect, got):
+                raise SystemExit("PARITY FAILURE projection_limits %r" % draw)
+            runs["projection_limits"] += 1
+            continue
         if os.environ.get("FUZZ_ONLY") in WRITE_LEGS or (rng.random() < 0.1 and not os.environ.get("FUZZ_ONLY")):
             write_leg(rng, os.environ.get("FUZZ_ONLY") or str(rng.choice(WRITE_LEGS)), runs)
             continue
