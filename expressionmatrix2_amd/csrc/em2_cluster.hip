@@ -36,6 +36,7 @@
 
 #include "em2_device.h"
 #include "em2_hip_util.h"
+#include "em2_primitives.h"
 #include "em2_select_wave.h"
 
 #include <algorithm>
@@ -51,8 +52,6 @@
 #include <numeric>
 #include <random>
 #include <vector>
-
-#include <rocprim/rocprim.hpp>
 
 namespace em2 {
 namespace {
@@ -1509,14 +1508,9 @@ static hipError_t runLabelPropagationBody(const uint32_t* vertexCellIds, uint32_
         uint32_t keyBits = 1;
         while (keyBits < 32u && (1ull << keyBits) < vertexCount) ++keyBits;
         size_t sortBytes = 0, scanBytes = 0, maxBytes = 0;
-        {
-            uint32_t* const noWords = nullptr;          // (the queries only look at types and sizes)
-            uint64_t* const noOffsets = nullptr;
-            EM2_TRY(rocprim::radix_sort_pairs(nullptr, sortBytes, noWords, noWords, noWords, noWords, size_t(slots), 0u, keyBits, stream));
-            EM2_TRY(rocprim::exclusive_scan(nullptr, scanBytes, noWords, noOffsets, uint64_t(0), size_t(vertexCount) + 1,
-                                            rocprim::plus<uint64_t>(), stream));
-            EM2_TRY(rocprim::reduce(nullptr, maxBytes, noWords, noWords, 0u, size_t(vertexCount), rocprim::maximum<uint32_t>(), stream));
-        }
+        EM2_TRY(sortPairsU32U32Bytes(size_t(slots), 0u, keyBits, sortBytes));
+        EM2_TRY(exclusiveScanU32ToU64Bytes(size_t(vertexCount) + 1, scanBytes));
+        EM2_TRY(reduceMaxBytes(size_t(vertexCount), maxBytes));
         const size_t tempBytes = std::max(sortBytes, std::max(scanBytes, maxBytes));
         Pool edgePool;
         EM2_TRY(edgePool.reserve(3 * Pool::rounded(edgeCount * sizeof(uint32_t)) + 4 * Pool::rounded(slots * sizeof(uint32_t)) +
@@ -1537,12 +1531,10 @@ static hipError_t runLabelPropagationBody(const uint32_t* vertexCellIds, uint32_
         edgeEndsKernel<<<endGrid, block, 0, stream>>>(dEdge0.as<uint32_t>(), dEdge1.as<uint32_t>(), uint32_t(slots),
                                                       dKeys.as<uint32_t>(), dEnds.as<uint32_t>(), dDegree.as<uint32_t>());
         EM2_TRY(hipGetLastError());
-        EM2_TRY(rocprim::radix_sort_pairs(dTemp.p, sortBytes, dKeys.as<uint32_t>(), dKeysSorted.as<uint32_t>(), dEnds.as<uint32_t>(),
-                                          dEndsSorted.as<uint32_t>(), size_t(slots), 0u, keyBits, stream));
-        EM2_TRY(rocprim::exclusive_scan(dTemp.p, scanBytes, dDegree.as<uint32_t>(), dOffsets.as<uint64_t>(), uint64_t(0),
-                                        size_t(vertexCount) + 1, rocprim::plus<uint64_t>(), stream));
-        EM2_TRY(rocprim::reduce(dTemp.p, maxBytes, dDegree.as<uint32_t>(), dMax.as<uint32_t>(), 0u, size_t(vertexCount),
-                                rocprim::maximum<uint32_t>(), stream));
+        EM2_TRY(sortPairs(dTemp.p, sortBytes, dKeys.as<uint32_t>(), dKeysSorted.as<uint32_t>(), dEnds.as<uint32_t>(), dEndsSorted.as<uint32_t>(),
+                          size_t(slots), 0u, keyBits, stream));
+        EM2_TRY(exclusiveScan(dTemp.p, scanBytes, dDegree.as<uint32_t>(), dOffsets.as<uint64_t>(), size_t(vertexCount) + 1, stream));
+        EM2_TRY(reduceMax(dTemp.p, maxBytes, dDegree.as<uint32_t>(), dMax.as<uint32_t>(), size_t(vertexCount), stream));
         adjacencyKernel<<<endGrid, block, 0, stream>>>(dEndsSorted.as<uint32_t>(), uint32_t(slots), dEdge0.as<uint32_t>(),
                                                        dEdge1.as<uint32_t>(), dSimilarity.as<float>(), dNeighbour.as<uint32_t>(),
                                                        dWeight.as<float>());

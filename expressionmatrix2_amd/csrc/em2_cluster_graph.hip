@@ -34,11 +34,10 @@
 #include "em2_expression.h"
 #include "em2_entry.h"
 #include "em2_csr.h"
+#include "em2_primitives.h"
 #include "../../include/em2_lsh.h"
 
 #include <cstring>
-
-#include <rocprim/rocprim.hpp>
 
 #include <algorithm>
 #include <chrono>
@@ -341,9 +340,7 @@ ClusterStatus ClusterDevice::averages(const char* who, const uint32_t* cellRows,
     const size_t tableBytes = size_t(accumulatorCount) * sizeof(double);
     size_t sortTempBytes = 0;
     if (entryCount) {
-        EM2_TRYC(rocprim::radix_sort_pairs(nullptr, sortTempBytes, static_cast<uint64_t*>(nullptr), static_cast<uint64_t*>(nullptr),
-                                           static_cast<float*>(nullptr), static_cast<float*>(nullptr), size_t(entryCount), 0u, 64u,
-                                           static_cast<hipStream_t>(nullptr)));
+        EM2_TRYC(sortPairsU64F32Bytes(size_t(entryCount), 0u, 64u, sortTempBytes));
     }
     const size_t scratchBytes = size_t(entryCount) * 24u + sortTempBytes + size_t(listCount) * 16u + size_t(clusterCount) * 8u;
     s.table.release();
@@ -393,8 +390,8 @@ ClusterStatus ClusterDevice::averages(const char* who, const uint32_t* cellRows,
         // the keys' live low bits only (begin_bit 0; the upper bits are zero)
         unsigned endBit = 1u;
         while (endBit < 64u && (accumulatorCount >> endBit) != 0u) ++endBit;
-        EM2_TRYC(rocprim::radix_sort_pairs(temp.p, sortTempBytes, keysIn.as<uint64_t>(), keysOut.as<uint64_t>(), valuesIn.as<float>(),
-                                           valuesOut.as<float>(), size_t(entryCount), 0u, endBit, stream));
+        EM2_TRYC(sortPairs(temp.p, sortTempBytes, keysIn.as<uint64_t>(), keysOut.as<uint64_t>(), valuesIn.as<float>(), valuesOut.as<float>(),
+                           size_t(entryCount), 0u, endBit, stream));
         clusterRunKernel<<<dim3(blocksOf(entryCount, 256u)), dim3(256), 0, stream>>>(keysOut.as<uint64_t>(), entryCount,
                                                                                    s.table.as<unsigned long long>());
         EM2_TRYC(hipGetLastError());

@@ -12,7 +12,7 @@
 //       denseTriplesKernel   one workgroup turns that table into the ascending triples (a scan over its 256 threads);
 //   * sort path, any n0 and n1:
 //       keysKernel           key = id0 << bits(n1) | id1;
-//       rocPRIM's radix sort of the keys over exactly bits(n0) + bits(n1) bits;
+//       a radix sort of the keys over exactly bits(n0) + bits(n1) bits;
 //       headFlagsKernel, an inclusive scan of the flags, runStartsKernel, runCountsKernel: a run of equal keys is a table cell.
 // Both end the same way: triplesTotalsKernel adds every triple to its row and column total (vector atomics on 64-bit words) and
 // sums v (v - 1); pairSumKernel sums t (t - 1) over the row totals and over the column totals.
@@ -20,11 +20,10 @@
 // that fails and raises the error word; the host reads that word before anything derived from the ids is used.
 
 #include "em2_entry.h"
+#include "em2_primitives.h"
+#include "em2_runs.h"
 #include "em2_scratch.h"
 #include "em2_wave.h"
-
-#include <cstring>            // (rocPRIM calls memset without including it)
-#include <rocprim/rocprim.hpp>
 
 #include <algorithm>
 #include <memory>
@@ -167,15 +166,6 @@ keysKernel(const uint32_t* __restrict__ id0, const uint32_t* __restrict__ id1, u
     if (bad) atomicOr(error, 1u);
 }
 
-// flags[i] = 1 where a run of equal keys begins.
-__global__ void __launch_bounds__(256)
-headFlagsKernel(const uint64_t* __restrict__ keys, uint64_t n, uint32_t* __restrict__ flags)
-{
-    for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += uint64_t(gridDim.x) * blockDim.x) {
-        flags[i] = i == 0u || keys[i] != keys[i - 1u] ? 1u : 0u;
-    }
-}
-
 // rank: the inclusive scan of the flags.  Run r = rank[i] - 1 begins at the i whose flag is set: its first element and its ids.
 __global__ void __launch_bounds__(256)
 runStartsKernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ flags, const uint32_t* __restrict__ rank, uint64_t n,
@@ -262,50 +252,41 @@ hipError_t runContingency(const uint32_t* d_id0, const uint32_t* d_id1, uint64_t
     StageTimer timer(lds ? "contingency (LDS)" : "contingency (sort)");
     const dim3 threads(256);
     const size_t capacity = lds ? size_t(cells64) : size_t(n);            // of the triples: the cells that are not zero
-    size_t at = 0;
-    const auto take = [&at](size_t bytes) {
-        const size_t here = at;
-        at += alignUp(bytes ? bytes : 1u);
-        return here;
-    };
+    ArenaPlan plan;
     // (everything up to offZeroEnd starts as zero)
-    const size_t offWords = take(256);                                      // error, nnz, the three sums
-    const size_t offRowTotals = take(size_t(n0) * sizeof(u64));
-    const size_t offColumnTotals = take(size_t(n1) * sizeof(u64));
-    const size_t offTable = take(lds ? size_t(cells64) * sizeof(u64) : 0u);
-    const size_t offZeroEnd = at;
-    const size_t offI0 = take(capacity * sizeof(uint32_t));
-    const size_t offI1 = take(capacity * sizeof(uint32_t));
-    const size_t offCount = take(capacity * sizeof(u64));
+    const size_t offWords = plan.take(256);                                 // error, nnz, the three sums
+    const size_t offRowTotals = plan.takeFor<u64>(n0);
+    const size_t offColumnTotals = plan.takeFor<u64>(n1);
+    const size_t offTable = plan.take(lds ? size_t(cells64) * sizeof(u64) : 0u);
+    const size_t offZeroEnd = plan.bytes;
+    const size_t offI0 = plan.takeFor<uint32_t>(capacity);
+    const size_t offI1 = plan.takeFor<uint32_t>(capacity);
+    const size_t offCount = plan.takeFor<u64>(capacity);
     size_t offKeysA = 0, offKeysB = 0, offFlags = 0, offRank = 0, offStarts = 0, offTemp = 0, sortBytes = 0, scanBytes = 0;
     const uint32_t bits1 = bitsFor(n1);
     const uint32_t keyBits = bitsFor(n0) + bits1 ? bitsFor(n0) + bits1 : 1u;      // (n0 == n1 == 1: every key is 0, one bit)
     if (!lds) {
-        offKeysA = take(size_t(n) * sizeof(uint64_t));
-        offKeysB = take(size_t(n) * sizeof(uint64_t));
-        offFlags = take(size_t(n) * sizeof(uint32_t));
-        offRank = take(size_t(n) * sizeof(uint32_t));
-        offStarts = take(size_t(n) * sizeof(uint32_t));
-        {
-            rocprim::double_buffer<uint64_t> keys(nullptr, nullptr);
-            EM2_TRY(rocprim::radix_sort_keys(nullptr, sortBytes, keys, size_t(n), 0u, keyBits, stream));
-            uint32_t* in = nullptr;
-            EM2_TRY(rocprim::inclusive_scan(nullptr, scanBytes, in, in, size_t(n), rocprim::plus<uint32_t>(), stream));
-        }
-        offTemp = take(sortBytes > scanBytes ? sortBytes : scanBytes);
+        offKeysA = plan.takeFor<uint64_t>(n);
+        offKeysB = plan.takeFor<uint64_t>(n);
+        offFlags = plan.takeFor<uint32_t>(n);
+        offRank = plan.takeFor<uint32_t>(n);
+        offStarts = plan.takeFor<uint32_t>(n);
+        EM2_TRY(sortKeysBufferBytes(size_t(n), 0u, keyBits, sortBytes));
+        EM2_TRY(inclusiveScanBytes(size_t(n), scanBytes));
+        offTemp = plan.take(sortBytes > scanBytes ? sortBytes : scanBytes);
     }
     CachedBuffer arena;
-    EM2_TRY(arena.allocate(at));
+    EM2_TRY(arena.allocate(plan.bytes));
     char* base = arena.as<char>();
-    uint32_t* error = reinterpret_cast<uint32_t*>(base + offWords);
-    u64* nnz = reinterpret_cast<u64*>(base + offWords + 8);
-    u64* sums = reinterpret_cast<u64*>(base + offWords + 16);               // cells, rows, columns
-    u64* rowTotals = reinterpret_cast<u64*>(base + offRowTotals);
-    u64* columnTotals = reinterpret_cast<u64*>(base + offColumnTotals);
-    u64* table = reinterpret_cast<u64*>(base + offTable);
-    uint32_t* i0 = reinterpret_cast<uint32_t*>(base + offI0);
-    uint32_t* i1 = reinterpret_cast<uint32_t*>(base + offI1);
-    u64* count = reinterpret_cast<u64*>(base + offCount);
+    uint32_t* error = arenaAt<uint32_t>(base, offWords);
+    u64* nnz = arenaAt<u64>(base, offWords + 8);
+    u64* sums = arenaAt<u64>(base, offWords + 16);                          // cells, rows, columns
+    u64* rowTotals = arenaAt<u64>(base, offRowTotals);
+    u64* columnTotals = arenaAt<u64>(base, offColumnTotals);
+    u64* table = arenaAt<u64>(base, offTable);
+    uint32_t* i0 = arenaAt<uint32_t>(base, offI0);
+    uint32_t* i1 = arenaAt<uint32_t>(base, offI1);
+    u64* count = arenaAt<u64>(base, offCount);
     EM2_TRY(hipMemsetAsync(base, 0, offZeroEnd, stream));
 
     // an id out of range: nothing was written for it, and nothing below may use what the kernel left
@@ -341,10 +322,10 @@ hipError_t runContingency(const uint32_t* d_id0, const uint32_t* d_id1, uint64_t
         denseTriplesKernel<<<dim3(1), threads, 0, stream>>>(table, uint32_t(cells64), n1, i0, i1, count, nnz);
         EM2_TRY(hipGetLastError());
     } else {
-        rocprim::double_buffer<uint64_t> keys(reinterpret_cast<uint64_t*>(base + offKeysA), reinterpret_cast<uint64_t*>(base + offKeysB));
-        uint32_t* flags = reinterpret_cast<uint32_t*>(base + offFlags);
-        uint32_t* rank = reinterpret_cast<uint32_t*>(base + offRank);
-        uint32_t* starts = reinterpret_cast<uint32_t*>(base + offStarts);
+        DoubleBuffer<uint64_t> keys{arenaAt<uint64_t>(base, offKeysA), arenaAt<uint64_t>(base, offKeysB)};
+        uint32_t* flags = arenaAt<uint32_t>(base, offFlags);
+        uint32_t* rank = arenaAt<uint32_t>(base, offRank);
+        uint32_t* starts = arenaAt<uint32_t>(base, offStarts);
         keysKernel<<<dim3(gridFor(n)), threads, 0, stream>>>(d_id0, d_id1, n, n0, n1, bits1, keys.current(), error);
         EM2_TRY(hipGetLastError());
         EM2_TRY(inputChecked());
@@ -353,12 +334,12 @@ hipError_t runContingency(const uint32_t* d_id0, const uint32_t* d_id1, uint64_t
             return hipSuccess;
         }
         EM2_TRY(timer.stage("keys", stream));
-        EM2_TRY(rocprim::radix_sort_keys(base + offTemp, sortBytes, keys, size_t(n), 0u, keyBits, stream));
+        EM2_TRY(sortKeys(base + offTemp, sortBytes, keys, size_t(n), 0u, keyBits, stream));
         EM2_TRY(timer.stage("sort", stream));
         const uint64_t* sorted = keys.current();
         headFlagsKernel<<<dim3(gridFor(n)), threads, 0, stream>>>(sorted, n, flags);
         EM2_TRY(hipGetLastError());
-        EM2_TRY(rocprim::inclusive_scan(base + offTemp, scanBytes, flags, rank, size_t(n), rocprim::plus<uint32_t>(), stream));
+        EM2_TRY(inclusiveScan(base + offTemp, scanBytes, flags, rank, size_t(n), stream));
         runStartsKernel<<<dim3(gridFor(n)), threads, 0, stream>>>(sorted, flags, rank, n, bits1, starts, i0, i1);
         EM2_TRY(hipGetLastError());
         runCountsKernel<<<dim3(gridFor(n)), threads, 0, stream>>>(starts, rank, n, count, nnz);

@@ -3,7 +3,7 @@
 // the decided counts of all chunks on the device, sorts them by (cell, line) and hands the CSR to em2_dev_ingest_count / _fill.
 //
 //   csvCountKernel    a workgroup per tile of the text, 16-byte loads: the '\n' bytes of the tile
-//   (rocprim)         exclusive scan of the tiles' counts: the line number at which each tile starts
+//   (em2_primitives)  exclusive scan of the tiles' counts: the line number at which each tile starts
 //   csvLinesKernel    the same read once more: the offset of the '\n' that ends line i, and the lines that hold a '\\'
 //   csvFieldsKernel   a wave per line, 64 bytes per step, a byte per lane: the ballots of '"' and separator bytes, the quote
 //                     state as a prefix XOR over the quote ballot, the separators outside quotes; the lane that owns the byte
@@ -19,12 +19,11 @@
 // to the host, which has the box's strtof.
 #include "em2_csv.h"
 #include "em2_entry.h"
+#include "em2_primitives.h"
 #include "em2_scratch.h"
 #include "em2_wave.h"
 
 #include <cstring>
-
-#include <rocprim/rocprim.hpp>
 
 #include <atomic>
 #include <memory>
@@ -382,11 +381,9 @@ hipError_t runParse(const uint8_t* d_text, uint32_t n, uint64_t separators, uint
     csvCountKernel<<<dim3(tileBlocks), dim3(256), 0, stream>>>(d_text, n, misalign, tileBytes, tileCount, newlinesOfTile.as<uint32_t>());
     EM2_TRY(hipGetLastError());
     size_t tempBytes = 0;
-    EM2_TRY(rocprim::exclusive_scan(nullptr, tempBytes, newlinesOfTile.as<uint32_t>(), firstLineOfTile.as<uint32_t>(), uint32_t(0),
-                                    size_t(tileCount), rocprim::plus<uint32_t>(), stream));
+    EM2_TRY(exclusiveScanU32Bytes(size_t(tileCount), tempBytes));
     EM2_TRY(scanTemp.allocate(tempBytes));
-    EM2_TRY(rocprim::exclusive_scan(scanTemp.p, tempBytes, newlinesOfTile.as<uint32_t>(), firstLineOfTile.as<uint32_t>(), uint32_t(0),
-                                    size_t(tileCount), rocprim::plus<uint32_t>(), stream));
+    EM2_TRY(exclusiveScan(scanTemp.p, tempBytes, newlinesOfTile.as<uint32_t>(), firstLineOfTile.as<uint32_t>(), size_t(tileCount), stream));
     csvTotalKernel<<<dim3(1), dim3(1), 0, stream>>>(d_text, n, newlinesOfTile.as<uint32_t>(), firstLineOfTile.as<uint32_t>(), tileCount,
                                                     totals.as<uint32_t>());
     EM2_TRY(hipGetLastError());
@@ -623,11 +620,10 @@ int csvSessionFinish(CsvSession* session, const std::vector<CsvTriple>& extra, u
         csvPackKeysKernel<<<dim3(gridFor(total)), dim3(256)>>>(keysIn.as<uint64_t>(), total, lineBits);
         EM2_HIP_FOR(who, hipGetLastError());
         size_t tempBytes = 0;
-        EM2_HIP_FOR(who, rocprim::radix_sort_pairs(nullptr, tempBytes, keysIn.as<uint64_t>(), keysOut.as<uint64_t>(), valuesIn.as<float>(),
-                                              valuesOut.as<float>(), size_t(total), 0u, lineBits + cellBits));
+        EM2_HIP_FOR(who, sortPairsU64F32Bytes(size_t(total), 0u, lineBits + cellBits, tempBytes));
         EM2_HIP_FOR(who, sortTemp.allocate(tempBytes));
-        EM2_HIP_FOR(who, rocprim::radix_sort_pairs(sortTemp.p, tempBytes, keysIn.as<uint64_t>(), keysOut.as<uint64_t>(), valuesIn.as<float>(),
-                                              valuesOut.as<float>(), size_t(total), 0u, lineBits + cellBits));
+        EM2_HIP_FOR(who, sortPairs(sortTemp.p, tempBytes, keysIn.as<uint64_t>(), keysOut.as<uint64_t>(), valuesIn.as<float>(), valuesOut.as<float>(),
+                                   size_t(total), 0u, lineBits + cellBits, hipStream_t(nullptr)));
         sortedKeys = keysOut.as<uint64_t>();
         sortedValues = valuesOut.as<float>();
         csvIndicesKernel<<<dim3(gridFor(total)), dim3(256)>>>(sortedKeys, total, lineBits, dIndices.as<uint32_t>());

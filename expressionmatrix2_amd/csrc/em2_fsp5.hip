@@ -21,6 +21,8 @@
 
 #include "em2_device.h"
 #include "em2_hip_util.h"
+#include "em2_primitives.h"
+#include "em2_runs.h"
 #include "em2_scratch.h"
 #include "em2_select_wave.h"
 #include "em2_wave.h"
@@ -28,9 +30,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>      // rocprim/iterator/texture_cache_iterator.hpp calls memset without including it
-
-#include <rocprim/rocprim.hpp>
+#include <cstring>
 
 #include <algorithm>
 #include <mutex>
@@ -42,16 +42,6 @@ namespace {
 constexpr uint32_t kSelectLdsEntries = 4096;        // lists up to this length are cut in 48 KB of LDS ...
 constexpr uint32_t kSelectLdsEntriesBig = 12288;    // ... up to this length in 144 KB, longer ones in HBM
 
-__device__ __forceinline__ uint32_t sliceValue(const uint64_t* sig, uint32_t slice, uint32_t q)
-{
-    const uint32_t b0 = slice * q;
-    const uint32_t w = b0 >> 6;
-    const uint32_t o = b0 & 63u;
-    uint64_t window = sig[w] << o;
-    if (o + q > 64u) window |= sig[w + 1] >> (64u - o);
-    return uint32_t(window >> (64u - q));
-}
-
 __global__ void __launch_bounds__(256)
 sliceKeysKernel(const uint64_t* __restrict__ sig, uint32_t cellCount, uint32_t words, uint32_t q, uint32_t sliceCount,
                 uint64_t* __restrict__ keys, uint32_t* __restrict__ cells)
@@ -60,32 +50,8 @@ sliceKeysKernel(const uint64_t* __restrict__ sig, uint32_t cellCount, uint32_t w
     for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < total; i += uint64_t(gridDim.x) * blockDim.x) {
         const uint32_t s = uint32_t(i / cellCount);
         const uint32_t c = uint32_t(i % cellCount);
-        keys[i] = (uint64_t(s) << 32) | sliceValue(sig + size_t(c) * words, s, q);
+        keys[i] = (uint64_t(s) << 32) | uint32_t(sliceValue64(sig + size_t(c) * words, s, q));
         cells[i] = c;
-    }
-}
-
-__global__ void __launch_bounds__(256)
-runFlagsKernel(const uint64_t* __restrict__ sortedKeys, uint64_t total, uint32_t* __restrict__ flags)
-{
-    for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < total; i += uint64_t(gridDim.x) * blockDim.x) {
-        flags[i] = (i == 0 || sortedKeys[i] != sortedKeys[i - 1]) ? 1u : 0u;
-    }
-}
-
-// runIndex[i] = (inclusive scan of flags)[i] - 1.  Records where each run starts and which run every
-// (slice, cell) belongs to.
-__global__ void __launch_bounds__(256)
-runTablesKernel(const uint64_t* __restrict__ sortedKeys, const uint32_t* __restrict__ sortedCells,
-                const uint32_t* __restrict__ flags, const uint32_t* __restrict__ scan, uint64_t total,
-                uint32_t cellCount, uint32_t sliceCount, uint32_t* __restrict__ runStart, uint32_t* __restrict__ runOfSliceCell)
-{
-    for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < total; i += uint64_t(gridDim.x) * blockDim.x) {
-        const uint32_t run = scan[i] - 1u;
-        if (flags[i]) runStart[run] = uint32_t(i);
-        const uint32_t s = uint32_t(sortedKeys[i] >> 32);
-        runOfSliceCell[size_t(sortedCells[i]) * sliceCount + s] = run;        // [cell][slice]: a cell's descriptors are one contiguous read
-        if (i == total - 1) runStart[run + 1u] = uint32_t(total);
     }
 }
 
@@ -931,11 +897,10 @@ hipError_t runFsp5(const uint64_t* d_sig, uint32_t cellCount, uint32_t rowBegin,
     EM2_TRY(hipGetLastError());
     const uint32_t endBit = 32u + bitsFor(sliceCount - 1u);
     size_t tempBytes = 0;
-    EM2_TRY(rocprim::radix_sort_pairs(nullptr, tempBytes, keysA.as<uint64_t>(), keysB.as<uint64_t>(), cellsA.as<uint32_t>(),
-                                      cellsB.as<uint32_t>(), size_t(total), 0u, endBit, stream));
+    EM2_TRY(sortPairsU64U32Bytes(size_t(total), 0u, endBit, tempBytes));
     EM2_TRY(temp.allocate(tempBytes));
-    EM2_TRY(rocprim::radix_sort_pairs(temp.p, tempBytes, keysA.as<uint64_t>(), keysB.as<uint64_t>(), cellsA.as<uint32_t>(),
-                                      cellsB.as<uint32_t>(), size_t(total), 0u, endBit, stream));
+    EM2_TRY(sortPairs(temp.p, tempBytes, keysA.as<uint64_t>(), keysB.as<uint64_t>(), cellsA.as<uint32_t>(), cellsB.as<uint32_t>(),
+                      size_t(total), 0u, endBit, stream));
     const uint64_t* sortedKeys = keysB.as<uint64_t>();
     const uint32_t* sortedCells = cellsB.as<uint32_t>();
 
@@ -947,15 +912,15 @@ hipError_t runFsp5(const uint64_t* d_sig, uint32_t cellCount, uint32_t rowBegin,
     EM2_TRY(runStart.allocate((total + 1) * sizeof(uint32_t)));
     EM2_TRY(runOf.allocate(total * sizeof(uint32_t)));
     EM2_TRY(counts.allocate(size_t(cellCount) * sizeof(uint64_t)));
-    runFlagsKernel<<<gridFor(total), 256, 0, stream>>>(sortedKeys, total, flags.as<uint32_t>());
+    headFlagsKernel<<<gridFor(total), 256, 0, stream>>>(sortedKeys, total, flags.as<uint32_t>());
     EM2_TRY(hipGetLastError());
     size_t scanBytes = 0;
-    EM2_TRY(rocprim::inclusive_scan(nullptr, scanBytes, flags.as<uint32_t>(), scan.as<uint32_t>(), size_t(total), rocprim::plus<uint32_t>(), stream));
+    EM2_TRY(inclusiveScanBytes(size_t(total), scanBytes));
     Buffer scanTemp;
     EM2_TRY(scanTemp.allocate(scanBytes));
-    EM2_TRY(rocprim::inclusive_scan(scanTemp.p, scanBytes, flags.as<uint32_t>(), scan.as<uint32_t>(), size_t(total), rocprim::plus<uint32_t>(), stream));
-    runTablesKernel<<<gridFor(total), 256, 0, stream>>>(sortedKeys, sortedCells, flags.as<uint32_t>(), scan.as<uint32_t>(), total,
-                                                        cellCount, sliceCount, runStart.as<uint32_t>(), runOf.as<uint32_t>());
+    EM2_TRY(inclusiveScan(scanTemp.p, scanBytes, flags.as<uint32_t>(), scan.as<uint32_t>(), size_t(total), stream));
+    runTablesKernel<32, true><<<gridFor(total), 256, 0, stream>>>(sortedKeys, sortedCells, flags.as<uint32_t>(), scan.as<uint32_t>(), total,
+                                                                  cellCount, sliceCount, runStart.as<uint32_t>(), runOf.as<uint32_t>());
     EM2_TRY(hipGetLastError());
     stage("run tables");
     // the labels that order the filter's visits, and in the same walk over the cells' bucket descriptors the number of members
@@ -1089,8 +1054,7 @@ hipError_t runFsp5(const uint64_t* d_sig, uint32_t cellCount, uint32_t rowBegin,
         EM2_TRY(orderKeysB.allocate(size_t(maxCells) * sizeof(uint32_t)));
         EM2_TRY(orderLocalsA.allocate(size_t(maxCells) * sizeof(uint32_t)));
         EM2_TRY(orderLocalsB.allocate(size_t(maxCells) * sizeof(uint32_t)));
-        EM2_TRY(rocprim::radix_sort_pairs(nullptr, orderTempBytes, orderKeysA.as<uint32_t>(), orderKeysB.as<uint32_t>(), orderLocalsA.as<uint32_t>(),
-                                          orderLocalsB.as<uint32_t>(), size_t(maxCells), 0u, 32u, stream));
+        EM2_TRY(sortPairsU32U32Bytes(size_t(maxCells), 0u, 32u, orderTempBytes));
         EM2_TRY(orderTemp.allocate(orderTempBytes));
     }
     size_t sortTempBytes = 0;
@@ -1118,15 +1082,14 @@ hipError_t runFsp5(const uint64_t* d_sig, uint32_t cellCount, uint32_t rowBegin,
                                                                      segBegin.as<uint32_t>(), candA.as<uint32_t>());
             EM2_TRY(hipGetLastError());
             size_t segBytes = 0;
-            EM2_TRY(rocprim::segmented_radix_sort_keys(nullptr, segBytes, candA.as<uint32_t>(), candB.as<uint32_t>(), batchTotal, batchCells,
-                                                       segBegin.as<uint32_t>(), segBegin.as<uint32_t>() + 1, 0u, idBits, stream));
+            EM2_TRY(segmentedSortKeysBytes(batchTotal, batchCells, 0u, idBits, segBytes));
             if (segBytes > sortTempBytes) {
                 EM2_TRY(hipStreamSynchronize(stream));
                 EM2_TRY(sortTemp.allocate(segBytes));
                 sortTempBytes = segBytes;
             }
-            EM2_TRY(rocprim::segmented_radix_sort_keys(sortTemp.p, segBytes, candA.as<uint32_t>(), candB.as<uint32_t>(), batchTotal, batchCells,
-                                                       segBegin.as<uint32_t>(), segBegin.as<uint32_t>() + 1, 0u, idBits, stream));
+            EM2_TRY(segmentedSortKeys(sortTemp.p, segBytes, candA.as<uint32_t>(), candB.as<uint32_t>(), batchTotal, batchCells,
+                                      segBegin.as<uint32_t>(), segBegin.as<uint32_t>() + 1, 0u, idBits, stream));
             sorted = candB.as<uint32_t>();
         }
         stage("  batch: union");
@@ -1137,9 +1100,8 @@ hipError_t runFsp5(const uint64_t* d_sig, uint32_t cellCount, uint32_t rowBegin,
             batchOrderKeysKernel<<<(batchCells + 255u) / 256u, 256, 0, stream>>>(labelsA.as<uint32_t>(), batchBegin, batchCells,
                                                                                  orderKeysA.as<uint32_t>(), orderLocalsA.as<uint32_t>());
             EM2_TRY(hipGetLastError());
-            size_t bytes = orderTempBytes;
-            EM2_TRY(rocprim::radix_sort_pairs(orderTemp.p, bytes, orderKeysA.as<uint32_t>(), orderKeysB.as<uint32_t>(), orderLocalsA.as<uint32_t>(),
-                                              orderLocalsB.as<uint32_t>(), size_t(batchCells), 0u, idBits, stream));
+            EM2_TRY(sortPairs(orderTemp.p, orderTempBytes, orderKeysA.as<uint32_t>(), orderKeysB.as<uint32_t>(), orderLocalsA.as<uint32_t>(),
+                              orderLocalsB.as<uint32_t>(), size_t(batchCells), 0u, idBits, stream));
             order = orderLocalsB.as<uint32_t>();
             orderChunk = ((batchCells + 7u) / 8u + 3u) & ~3u;
         }

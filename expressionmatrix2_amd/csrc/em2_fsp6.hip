@@ -27,11 +27,10 @@
 
 #include "em2_device.h"
 #include "em2_hip_util.h"
+#include "em2_primitives.h"
 #include "em2_wave.h"
 
 #include <cstring>
-
-#include <rocprim/rocprim.hpp>
 
 #include <algorithm>
 #include <numeric>
@@ -346,8 +345,7 @@ hipError_t runFsp6(const uint64_t* d_sig, uint32_t cellCount, uint32_t rowBegin,
         EM2_TRY(keysOut.allocate(size_t(n) * sizeof(uint64_t)));
         EM2_TRY(idsIn.allocate(size_t(n) * sizeof(uint32_t)));
         size_t tempBytes = 0;
-        EM2_TRY(rocprim::radix_sort_pairs(nullptr, tempBytes, keysIn.as<uint64_t>(), keysOut.as<uint64_t>(), idsIn.as<uint32_t>(),
-                                           cellIds.as<uint32_t>(), size_t(n), 0u, 64u, stream));
+        EM2_TRY(sortPairsU64U32Bytes(size_t(n), 0u, 64u, tempBytes));
         EM2_TRY(temp.allocate(tempBytes));
         for (uint32_t p = 0; p < permutationCount; ++p) {
             const uint64_t* words = permWords.as<uint64_t>() + size_t(p) * prefixWords * n;
@@ -360,8 +358,8 @@ hipError_t runFsp6(const uint64_t* d_sig, uint32_t cellCount, uint32_t rowBegin,
                 EM2_TRY(hipMemcpyAsync(idsIn.p, ids, size_t(n) * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
                 // All 64 bits, the last word's included (its bits after permutedBitCount are zero).  Sorting only that
                 // word's live high bits (begin_bit > 0) gave a wrong order from a few thousand cells on.
-                EM2_TRY(rocprim::radix_sort_pairs(temp.p, tempBytes, keysIn.as<uint64_t>(), keysOut.as<uint64_t>(),
-                                                   idsIn.as<uint32_t>(), ids, size_t(n), 0u, 64u, stream));
+                EM2_TRY(sortPairs(temp.p, tempBytes, keysIn.as<uint64_t>(), keysOut.as<uint64_t>(), idsIn.as<uint32_t>(), ids, size_t(n), 0u, 64u,
+                                  stream));
             }
             scatterKernel<<<gridFor(n), 256, 0, stream>>>(words, ids, n, prefixWords, position.as<uint32_t>() + size_t(p) * n,
                                                             sortedPrefix.as<uint64_t>() + size_t(p) * n * prefixWords);

@@ -21,11 +21,11 @@
 
 #include "em2_device.h"
 #include "em2_hip_util.h"
+#include "em2_primitives.h"
+#include "em2_runs.h"
 #include "em2_wave.h"
 
 #include <cstring>
-
-#include <rocprim/rocprim.hpp>
 
 #include <vector>
 
@@ -52,16 +52,6 @@ __device__ __forceinline__ uint64_t murmur8(uint64_t value)
     return h;
 }
 
-__device__ __forceinline__ uint64_t sliceValue64(const uint64_t* sig, uint32_t slice, uint32_t length)
-{
-    const uint32_t b0 = slice * length;
-    const uint32_t w = b0 >> 6;
-    const uint32_t o = b0 & 63u;
-    uint64_t window = sig[w] << o;
-    if (o + length > 64u) window |= sig[w + 1] >> (64u - o);
-    return window >> (64u - length);
-}
-
 __global__ void __launch_bounds__(256)
 tableKeysKernel(const uint64_t* __restrict__ sig, uint32_t cellCount, uint32_t words, const uint32_t* __restrict__ tableLength,
                 const uint32_t* __restrict__ tableSlice, uint32_t tableCount, uint32_t log2BucketCount,
@@ -77,28 +67,6 @@ tableKeysKernel(const uint64_t* __restrict__ sig, uint32_t cellCount, uint32_t w
         const uint64_t bucket = length < log2BucketCount ? value : (murmur8(value) & bucketMask);
         keys[i] = (uint64_t(t) << kBucketBits) | bucket;
         cells[i] = c;
-    }
-}
-
-__global__ void __launch_bounds__(256)
-runFlagsKernel7(const uint64_t* __restrict__ sortedKeys, uint64_t total, uint32_t* __restrict__ flags)
-{
-    for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < total; i += uint64_t(gridDim.x) * blockDim.x) {
-        flags[i] = (i == 0 || sortedKeys[i] != sortedKeys[i - 1]) ? 1u : 0u;
-    }
-}
-
-__global__ void __launch_bounds__(256)
-runTablesKernel7(const uint64_t* __restrict__ sortedKeys, const uint32_t* __restrict__ sortedCells,
-                 const uint32_t* __restrict__ flags, const uint32_t* __restrict__ scan, uint64_t total, uint32_t cellCount,
-                 uint32_t* __restrict__ runStart, uint32_t* __restrict__ runOfTableCell)
-{
-    for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < total; i += uint64_t(gridDim.x) * blockDim.x) {
-        const uint32_t run = scan[i] - 1u;
-        if (flags[i]) runStart[run] = uint32_t(i);
-        const uint32_t t = uint32_t(sortedKeys[i] >> kBucketBits);
-        runOfTableCell[size_t(t) * cellCount + sortedCells[i]] = run;
-        if (i == total - 1) runStart[run + 1u] = uint32_t(total);
     }
 }
 
@@ -262,11 +230,10 @@ hipError_t runFsp7(const uint64_t* d_sig, uint32_t cellCount, uint32_t rowBegin,
                                                           log2BucketCount, keysA.as<uint64_t>(), cellsA.as<uint32_t>());
     EM2_TRY(hipGetLastError());
     size_t tempBytes = 0;
-    EM2_TRY(rocprim::radix_sort_pairs(nullptr, tempBytes, keysA.as<uint64_t>(), keysB.as<uint64_t>(), cellsA.as<uint32_t>(),
-                                       cellsB.as<uint32_t>(), size_t(total), 0u, 64u, stream));
+    EM2_TRY(sortPairsU64U32Bytes(size_t(total), 0u, 64u, tempBytes));
     EM2_TRY(temp.allocate(tempBytes));
-    EM2_TRY(rocprim::radix_sort_pairs(temp.p, tempBytes, keysA.as<uint64_t>(), keysB.as<uint64_t>(), cellsA.as<uint32_t>(),
-                                       cellsB.as<uint32_t>(), size_t(total), 0u, 64u, stream));
+    EM2_TRY(sortPairs(temp.p, tempBytes, keysA.as<uint64_t>(), keysB.as<uint64_t>(), cellsA.as<uint32_t>(), cellsB.as<uint32_t>(),
+                      size_t(total), 0u, 64u, stream));
     const uint64_t* sortedKeys = keysB.as<uint64_t>();
     const uint32_t* sortedCells = cellsB.as<uint32_t>();
 
@@ -275,14 +242,14 @@ hipError_t runFsp7(const uint64_t* d_sig, uint32_t cellCount, uint32_t rowBegin,
     EM2_TRY(scan.allocate(total * sizeof(uint32_t)));
     EM2_TRY(runStart.allocate((total + 1) * sizeof(uint32_t)));
     EM2_TRY(runOf.allocate(total * sizeof(uint32_t)));
-    runFlagsKernel7<<<gridFor(total), 256, 0, stream>>>(sortedKeys, total, flags.as<uint32_t>());
+    headFlagsKernel<<<gridFor(total), 256, 0, stream>>>(sortedKeys, total, flags.as<uint32_t>());
     EM2_TRY(hipGetLastError());
     size_t scanBytes = 0;
-    EM2_TRY(rocprim::inclusive_scan(nullptr, scanBytes, flags.as<uint32_t>(), scan.as<uint32_t>(), size_t(total), rocprim::plus<uint32_t>(), stream));
+    EM2_TRY(inclusiveScanBytes(size_t(total), scanBytes));
     EM2_TRY(scanTemp.allocate(scanBytes));
-    EM2_TRY(rocprim::inclusive_scan(scanTemp.p, scanBytes, flags.as<uint32_t>(), scan.as<uint32_t>(), size_t(total), rocprim::plus<uint32_t>(), stream));
-    runTablesKernel7<<<gridFor(total), 256, 0, stream>>>(sortedKeys, sortedCells, flags.as<uint32_t>(), scan.as<uint32_t>(), total, cellCount,
-                                                           runStart.as<uint32_t>(), runOf.as<uint32_t>());
+    EM2_TRY(inclusiveScan(scanTemp.p, scanBytes, flags.as<uint32_t>(), scan.as<uint32_t>(), size_t(total), stream));
+    runTablesKernel<kBucketBits, false><<<gridFor(total), 256, 0, stream>>>(sortedKeys, sortedCells, flags.as<uint32_t>(), scan.as<uint32_t>(),
+                                                                            total, cellCount, tableCount, runStart.as<uint32_t>(), runOf.as<uint32_t>());
     EM2_TRY(hipGetLastError());
     EM2_TRY(hipStreamSynchronize(stream));
     keysA.release(); cellsA.release(); flags.release(); scan.release(); scanTemp.release(); temp.release(); keysB.release();

@@ -24,10 +24,8 @@
 #include "em2_device.h"
 #include "em2_adjacency.h"
 #include "em2_entry.h"
+#include "em2_primitives.h"
 #include "em2_scratch.h"
-
-#include <cstring>            // (rocPRIM calls memset without including it)
-#include <rocprim/rocprim.hpp>
 
 #include <algorithm>
 #include <memory>
@@ -156,42 +154,33 @@ hipError_t runGeneGraph(const PairOut* d_pairs, const uint32_t* d_usedCount, uin
     out.geneCount = graphGeneCount;
     StageTimer timer("geneGraph");
     const dim3 threads(256);
-    size_t at = 0;
-    const auto take = [&at](size_t bytes) {
-        const size_t here = at;
-        at += alignUp(bytes ? bytes : 1u);
-        return here;
-    };
+    ArenaPlan plan;
 
     // the stored pairs, then the edges in insertion order
     const size_t slots = size_t(graphGeneCount) * maxConnectivity;
     const size_t n1 = size_t(graphGeneCount) + 1u;
-    const size_t offError = take(256);
-    const size_t offEdge0 = take(slots * sizeof(uint32_t));
-    const size_t offEdge1 = take(slots * sizeof(uint32_t));
-    const size_t offEdgeSimilarity = take(slots * sizeof(float));
-    const size_t offOffsets = take(n1 * sizeof(uint64_t));
-    const size_t offAlive = take(n1 * sizeof(uint32_t));
-    const size_t offRank = take(n1 * sizeof(uint64_t));
-    const size_t offVertices = take(size_t(graphGeneCount) * sizeof(uint32_t));
+    const size_t offError = plan.take(256);
+    const size_t offEdge0 = plan.takeFor<uint32_t>(slots);
+    const size_t offEdge1 = plan.takeFor<uint32_t>(slots);
+    const size_t offEdgeSimilarity = plan.takeFor<float>(slots);
+    const size_t offOffsets = plan.takeFor<uint64_t>(n1);
+    const size_t offAlive = plan.takeFor<uint32_t>(n1);
+    const size_t offRank = plan.takeFor<uint64_t>(n1);
+    const size_t offVertices = plan.takeFor<uint32_t>(graphGeneCount);
     size_t scanBytes = 0;
-    {
-        uint32_t* in = nullptr;
-        uint64_t* to = nullptr;
-        EM2_TRY(rocprim::exclusive_scan(nullptr, scanBytes, in, to, uint64_t(0), n1, rocprim::plus<uint64_t>(), stream));
-    }
-    const size_t offScanTemp = take(scanBytes);
+    EM2_TRY(exclusiveScanU32ToU64Bytes(n1, scanBytes));
+    const size_t offScanTemp = plan.take(scanBytes);
     CachedBuffer arena, recordArena;
-    EM2_TRY(arena.allocate(at));
+    EM2_TRY(arena.allocate(plan.bytes));
     char* base = arena.as<char>();
-    uint32_t* error = reinterpret_cast<uint32_t*>(base + offError);
-    uint32_t* edge0 = reinterpret_cast<uint32_t*>(base + offEdge0);
-    uint32_t* edge1 = reinterpret_cast<uint32_t*>(base + offEdge1);
-    float* edgeSimilarity = reinterpret_cast<float*>(base + offEdgeSimilarity);
-    uint64_t* offsets = reinterpret_cast<uint64_t*>(base + offOffsets);
-    uint32_t* alive = reinterpret_cast<uint32_t*>(base + offAlive);
-    uint64_t* rank = reinterpret_cast<uint64_t*>(base + offRank);
-    uint32_t* vertices = reinterpret_cast<uint32_t*>(base + offVertices);
+    uint32_t* error = arenaAt<uint32_t>(base, offError);
+    uint32_t* edge0 = arenaAt<uint32_t>(base, offEdge0);
+    uint32_t* edge1 = arenaAt<uint32_t>(base, offEdge1);
+    float* edgeSimilarity = arenaAt<float>(base, offEdgeSimilarity);
+    uint64_t* offsets = arenaAt<uint64_t>(base, offOffsets);
+    uint32_t* alive = arenaAt<uint32_t>(base, offAlive);
+    uint64_t* rank = arenaAt<uint64_t>(base, offRank);
+    uint32_t* vertices = arenaAt<uint32_t>(base, offVertices);
 
     EM2_TRY(hipMemsetAsync(error, 0, 256, stream));
     checkStoredPairsKernel<<<dim3(gridFor(uint64_t(pairsGeneCount) * (k ? k : 1u))), threads, 0, stream>>>(d_pairs, d_usedCount, pairsGeneCount,
@@ -222,28 +211,24 @@ hipError_t runGeneGraph(const PairOut* d_pairs, const uint32_t* d_usedCount, uin
     const uint32_t* sortedValues = nullptr;
     uint32_t* neighbours = nullptr;
     if (recordCount) {
-        at = 0;
-        const size_t offKeysA = take(recordCount * sizeof(uint64_t));
-        const size_t offKeysB = take(recordCount * sizeof(uint64_t));
-        const size_t offValuesA = take(recordCount * sizeof(uint32_t));
-        const size_t offValuesB = take(recordCount * sizeof(uint32_t));
-        const size_t offNeighbours = take(recordCount * sizeof(uint32_t));
+        ArenaPlan records;
+        const size_t offKeysA = records.takeFor<uint64_t>(recordCount);
+        const size_t offKeysB = records.takeFor<uint64_t>(recordCount);
+        const size_t offValuesA = records.takeFor<uint32_t>(recordCount);
+        const size_t offValuesB = records.takeFor<uint32_t>(recordCount);
+        const size_t offNeighbours = records.takeFor<uint32_t>(recordCount);
         size_t sortBytes = 0;
-        {
-            rocprim::double_buffer<uint64_t> keys(nullptr, nullptr);
-            rocprim::double_buffer<uint32_t> values(nullptr, nullptr);
-            EM2_TRY(rocprim::radix_sort_pairs(nullptr, sortBytes, keys, values, size_t(recordCount), 0u, 64u, stream));
-        }
-        const size_t offSortTemp = take(sortBytes);
-        EM2_TRY(recordArena.allocate(at));
+        EM2_TRY(sortPairsU64U32BufferBytes(size_t(recordCount), 0u, 64u, sortBytes));
+        const size_t offSortTemp = records.take(sortBytes);
+        EM2_TRY(recordArena.allocate(records.bytes));
         char* recordBase = recordArena.as<char>();
-        rocprim::double_buffer<uint64_t> keys(reinterpret_cast<uint64_t*>(recordBase + offKeysA), reinterpret_cast<uint64_t*>(recordBase + offKeysB));
-        rocprim::double_buffer<uint32_t> values(reinterpret_cast<uint32_t*>(recordBase + offValuesA), reinterpret_cast<uint32_t*>(recordBase + offValuesB));
-        neighbours = reinterpret_cast<uint32_t*>(recordBase + offNeighbours);
+        DoubleBuffer<uint64_t> keys{arenaAt<uint64_t>(recordBase, offKeysA), arenaAt<uint64_t>(recordBase, offKeysB)};
+        DoubleBuffer<uint32_t> values{arenaAt<uint32_t>(recordBase, offValuesA), arenaAt<uint32_t>(recordBase, offValuesB)};
+        neighbours = arenaAt<uint32_t>(recordBase, offNeighbours);
         edgeRecordsKernel<<<dim3(gridFor(edgeCount)), threads, 0, stream>>>(edge0, edge1, edgeSimilarity, edgeCount, keys.current(),
                                                                            values.current());
         EM2_TRY(hipGetLastError());
-        EM2_TRY(rocprim::radix_sort_pairs(recordBase + offSortTemp, sortBytes, keys, values, size_t(recordCount), 0u, 64u, stream));
+        EM2_TRY(sortPairs(recordBase + offSortTemp, sortBytes, keys, values, size_t(recordCount), 0u, 64u, stream));
         sortedKeys = keys.current();
         sortedValues = values.current();
         EM2_TRY(timer.stage("records and sort", stream));
@@ -252,7 +237,7 @@ hipError_t runGeneGraph(const PairOut* d_pairs, const uint32_t* d_usedCount, uin
     // (with no record the searches find nothing and read nothing: every offset 0, nobody alive)
     connectivityOffsetsKernel<<<dim3(gridFor(n1)), threads, 0, stream>>>(sortedKeys, recordCount, graphGeneCount, offsets, alive);
     EM2_TRY(hipGetLastError());
-    EM2_TRY(rocprim::exclusive_scan(base + offScanTemp, scanBytes, alive, rank, uint64_t(0), n1, rocprim::plus<uint64_t>(), stream));
+    EM2_TRY(exclusiveScan(base + offScanTemp, scanBytes, alive, rank, n1, stream));
     geneGraphCompactKernel<<<dim3(gridFor(recordCount > graphGeneCount ? recordCount : graphGeneCount)), threads, 0, stream>>>(
         alive, rank, graphGeneCount, sortedKeys, recordCount, vertices, neighbours);
     EM2_TRY(hipGetLastError());

@@ -33,10 +33,8 @@
 #include "em2_expression.h"
 #include "em2_entry.h"
 #include "em2_csr.h"
+#include "em2_primitives.h"
 #include "em2_wave.h"
-
-#include <cstring>            // (rocPRIM calls memset without including it)
-#include <rocprim/rocprim.hpp>
 
 #include <atomic>
 #include <chrono>
@@ -247,38 +245,29 @@ struct Layout {
 
 hipError_t layoutOf(uint64_t entryCount, uint32_t geneCount, Layout& l)
 {
-    size_t at = 0;
-    const auto take = [&at](size_t bytes) {
-        const size_t here = at;
-        at += alignUp(bytes ? bytes : 1u);
-        return here;
-    };
+    ArenaPlan plan;
     const size_t perGene = (size_t(geneCount) + 1u) * sizeof(uint64_t);
-    l.words = take(256);
-    l.keysA = take(entryCount * sizeof(uint32_t));
-    l.keysB = take(entryCount * sizeof(uint32_t));
-    l.valuesA = take(entryCount * sizeof(float));
-    l.valuesB = take(entryCount * sizeof(float));
-    l.offsets = take(perGene);
-    l.chunkCounts = take(perGene);
-    l.chunkStarts = take(perGene);
-    l.table = take(chunkBound(entryCount, geneCount) * sizeof(ChunkRef));
-    l.partials = take(chunkBound(entryCount, geneCount) * sizeof(double));
-    l.sums = take(perGene);
-    l.inverseSums = take(perGene);
+    l.words = plan.take(256);
+    l.keysA = plan.takeFor<uint32_t>(entryCount);
+    l.keysB = plan.takeFor<uint32_t>(entryCount);
+    l.valuesA = plan.takeFor<float>(entryCount);
+    l.valuesB = plan.takeFor<float>(entryCount);
+    l.offsets = plan.take(perGene);
+    l.chunkCounts = plan.take(perGene);
+    l.chunkStarts = plan.take(perGene);
+    l.table = plan.takeFor<ChunkRef>(chunkBound(entryCount, geneCount));
+    l.partials = plan.takeFor<double>(chunkBound(entryCount, geneCount));
+    l.sums = plan.take(perGene);
+    l.inverseSums = plan.take(perGene);
     l.sortTempBytes = 0;
     if (entryCount && geneBitsOf(geneCount)) {
-        rocprim::double_buffer<uint32_t> keys(nullptr, nullptr);
-        rocprim::double_buffer<float> values(nullptr, nullptr);
-        EM2_TRY(rocprim::radix_sort_pairs(nullptr, l.sortTempBytes, keys, values, size_t(entryCount), 0u, geneBitsOf(geneCount), hipStream_t(nullptr)));
+        EM2_TRY(sortPairsU32F32BufferBytes(size_t(entryCount), 0u, geneBitsOf(geneCount), l.sortTempBytes));
     }
     l.scanTempBytes = 0;
-    uint64_t* none = nullptr;
-    EM2_TRY(rocprim::exclusive_scan(nullptr, l.scanTempBytes, none, none, uint64_t(0), size_t(geneCount) + 1u, rocprim::plus<uint64_t>(),
-                                    hipStream_t(nullptr)));
-    l.sortTemp = take(l.sortTempBytes);
-    l.scanTemp = take(l.scanTempBytes);
-    l.total = at;
+    EM2_TRY(exclusiveScanU64Bytes(size_t(geneCount) + 1u, l.scanTempBytes));
+    l.sortTemp = plan.take(l.sortTempBytes);
+    l.scanTemp = plan.take(l.scanTempBytes);
+    l.total = plan.bytes;
     return hipSuccess;
 }
 
@@ -311,16 +300,16 @@ hipError_t runGeneInformation(const uint64_t* d_toc, const CountIn* d_data, uint
     if (workspaceBytes < l.total) return hipErrorInvalidValue;
     StageTimer timer("geneInformationContent");
     char* base = static_cast<char*>(workspace);
-    uint32_t* words = reinterpret_cast<uint32_t*>(base + l.words);
-    uint64_t* offsets = reinterpret_cast<uint64_t*>(base + l.offsets);
-    uint64_t* chunkCounts = reinterpret_cast<uint64_t*>(base + l.chunkCounts);
-    uint64_t* chunkStarts = reinterpret_cast<uint64_t*>(base + l.chunkStarts);
-    ChunkRef* table = reinterpret_cast<ChunkRef*>(base + l.table);
-    double* partials = reinterpret_cast<double*>(base + l.partials);
-    double* sums = reinterpret_cast<double*>(base + l.sums);
-    double* inverseSums = reinterpret_cast<double*>(base + l.inverseSums);
-    rocprim::double_buffer<uint32_t> keys(reinterpret_cast<uint32_t*>(base + l.keysA), reinterpret_cast<uint32_t*>(base + l.keysB));
-    rocprim::double_buffer<float> values(reinterpret_cast<float*>(base + l.valuesA), reinterpret_cast<float*>(base + l.valuesB));
+    uint32_t* words = arenaAt<uint32_t>(base, l.words);
+    uint64_t* offsets = arenaAt<uint64_t>(base, l.offsets);
+    uint64_t* chunkCounts = arenaAt<uint64_t>(base, l.chunkCounts);
+    uint64_t* chunkStarts = arenaAt<uint64_t>(base, l.chunkStarts);
+    ChunkRef* table = arenaAt<ChunkRef>(base, l.table);
+    double* partials = arenaAt<double>(base, l.partials);
+    double* sums = arenaAt<double>(base, l.sums);
+    double* inverseSums = arenaAt<double>(base, l.inverseSums);
+    DoubleBuffer<uint32_t> keys{arenaAt<uint32_t>(base, l.keysA), arenaAt<uint32_t>(base, l.keysB)};
+    DoubleBuffer<float> values{arenaAt<float>(base, l.valuesA), arenaAt<float>(base, l.valuesB)};
 
     EM2_TRY(hipMemsetAsync(words, 0, 256, stream));
     entriesKernel<<<dim3(waveGridFor(cellCount)), dim3(256), 0, stream>>>(d_toc, d_data, cellCount, geneCount, entryCount, d_normInverse,
@@ -334,17 +323,14 @@ hipError_t runGeneInformation(const uint64_t* d_toc, const CountIn* d_data, uint
 
     // one gene (no key bits): the stream is in cell order already
     if (entryCount && geneBitsOf(geneCount)) {
-        size_t tempBytes = l.sortTempBytes;
-        EM2_TRY(rocprim::radix_sort_pairs(base + l.sortTemp, tempBytes, keys, values, size_t(entryCount), 0u, geneBitsOf(geneCount), stream));
+        EM2_TRY(sortPairs(base + l.sortTemp, l.sortTempBytes, keys, values, size_t(entryCount), 0u, geneBitsOf(geneCount), stream));
     }
     EM2_TRY(timer.stage("sort", stream));
 
     geneSegmentsKernel<<<dim3(gridFor(uint64_t(geneCount) + 1u)), dim3(256), 0, stream>>>(keys.current(), entryCount, geneCount, offsets,
                                                                                          chunkCounts, d_expressingCellCount);
     EM2_TRY(hipGetLastError());
-    size_t scanBytes = l.scanTempBytes;
-    EM2_TRY(rocprim::exclusive_scan(base + l.scanTemp, scanBytes, chunkCounts, chunkStarts, uint64_t(0), size_t(geneCount) + 1u,
-                                    rocprim::plus<uint64_t>(), stream));
+    EM2_TRY(exclusiveScan(base + l.scanTemp, l.scanTempBytes, chunkCounts, chunkStarts, size_t(geneCount) + 1u, stream));
     const uint64_t bound = chunkBound(entryCount, geneCount);
     chunkTableKernel<<<dim3(gridFor(bound)), dim3(256), 0, stream>>>(chunkStarts, geneCount, table);
     EM2_TRY(hipGetLastError());

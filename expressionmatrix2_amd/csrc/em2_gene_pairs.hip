@@ -30,10 +30,8 @@
 #include "em2_expression.h"
 #include "em2_entry.h"
 #include "em2_csr.h"
+#include "em2_primitives.h"
 #include "em2_wave.h"
-
-#include <cstring>            // (rocPRIM calls memset without including it)
-#include <rocprim/rocprim.hpp>
 
 #include <atomic>
 #include <chrono>
@@ -438,15 +436,15 @@ hipError_t runGenePairs(const uint64_t* d_toc, const CountIn* d_data, uint32_t c
     EM2_TRY(keysB.allocate(count * sizeof(uint64_t)));
     EM2_TRY(valuesB.allocate(count * sizeof(float)));
     EM2_TRY(offsets.allocate((size_t(geneCount) + 1u) * sizeof(uint64_t)));
-    rocprim::double_buffer<uint64_t> keys(keysA.as<uint64_t>(), keysB.as<uint64_t>());
-    rocprim::double_buffer<float> values(valuesA.as<float>(), valuesB.as<float>());
+    DoubleBuffer<uint64_t> keys{keysA.as<uint64_t>(), keysB.as<uint64_t>()};
+    DoubleBuffer<float> values{valuesA.as<float>(), valuesB.as<float>()};
     if (count) {
         uint32_t geneBits = 1;
         while (geneBits < 32u && (1ull << geneBits) < geneCount) ++geneBits;
         size_t tempBytes = 0;
-        EM2_TRY(rocprim::radix_sort_pairs(nullptr, tempBytes, keys, values, size_t(count), 0u, 32u + geneBits, stream));
+        EM2_TRY(sortPairsU64F32BufferBytes(size_t(count), 0u, 32u + geneBits, tempBytes));
         EM2_TRY(temp.allocate(tempBytes));
-        EM2_TRY(rocprim::radix_sort_pairs(temp.p, tempBytes, keys, values, size_t(count), 0u, 32u + geneBits, stream));
+        EM2_TRY(sortPairs(temp.p, tempBytes, keys, values, size_t(count), 0u, 32u + geneBits, stream));
     }
     geneOffsetsKernel<<<dim3(gridFor(geneCount)), dim3(256), 0, stream>>>(keys.current(), count, geneCount, k, offsets.as<uint64_t>(), longest);
     EM2_TRY(hipGetLastError());

@@ -13,10 +13,9 @@
 
 #include "em2_device.h"
 #include "em2_hip_util.h"
+#include "em2_primitives.h"
 
 #include <cstring>
-
-#include <rocprim/rocprim.hpp>
 
 namespace em2 {
 namespace {
@@ -136,11 +135,9 @@ hipError_t runCellGraphEdges(const PairOut* pairs, const uint32_t* usedCount, ui
                                                          nullptr, nullptr);
     EM2_TRY(hipGetLastError());
     size_t tempBytes = 0;
-    EM2_TRY(rocprim::exclusive_scan(nullptr, tempBytes, kept.as<uint32_t>(), offsets.as<uint64_t>(), uint64_t(0),
-                                    size_t(graphCellCount), rocprim::plus<uint64_t>(), stream));
+    EM2_TRY(exclusiveScanU32ToU64Bytes(size_t(graphCellCount), tempBytes));
     EM2_TRY(temp.allocate(tempBytes));
-    EM2_TRY(rocprim::exclusive_scan(temp.p, tempBytes, kept.as<uint32_t>(), offsets.as<uint64_t>(), uint64_t(0),
-                                    size_t(graphCellCount), rocprim::plus<uint64_t>(), stream));
+    EM2_TRY(exclusiveScan(temp.p, tempBytes, kept.as<uint32_t>(), offsets.as<uint64_t>(), size_t(graphCellCount), stream));
     filterEdgesKernel<true><<<grid, block, 0, stream>>>(selVertex.as<uint32_t>(), selSim.as<float>(), selCount.as<uint32_t>(),
                                                         graphCellCount, maxConnectivity, nullptr, offsets.as<uint64_t>(), edge0,
                                                         edge1, edgeSimilarity);

@@ -1,9 +1,13 @@
 // em2_hip_util.h -- the host-side plumbing every driver needs: bail out on a HIP error, a device allocation that frees
-// itself and copies typed arrays in and out, the 1-D grid of a 256-thread kernel, blocks per items, 256-byte alignment,
-// signature words, the stage timer.  (The device-side counterpart is em2_wave.h; device scratch that outlives a call is
-// em2_scratch.h; what a C entry point reports its errors with is em2_entry.h.)
+// itself and copies typed arrays in and out, the 1-D grid of a 256-thread kernel, blocks per items, signature words, the
+// stage timer; with em2_arena.h, which it includes, 256-byte alignment and the layout of one allocation that holds several
+// arrays.  (The device-side counterpart is em2_wave.h; device scratch that outlives a call is em2_scratch.h; what a C entry
+// point reports its errors with is em2_entry.h; the device-wide sorts, scans and reductions are em2_primitives.h; the kernels
+// for runs of equal sorted keys are em2_runs.h.)
 #ifndef EM2_HIP_UTIL_H
 #define EM2_HIP_UTIL_H
+
+#include "em2_arena.h"
 
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -64,8 +68,6 @@ inline uint32_t gridFor(uint64_t n)
 
 // Blocks of perBlock items that hold `items` items.
 inline uint32_t blocksOf(uint64_t items, uint32_t perBlock) { return uint32_t((items + perBlock - 1u) / perBlock); }
-
-inline size_t alignUp(size_t x) { return (x + 255u) & ~size_t(255u); }
 
 // 64-bit words of a signature of lshCount > 0 bits.
 inline uint32_t wordCountOf(uint32_t lshCount) { return (lshCount - 1u) / 64u + 1u; }

@@ -19,11 +19,10 @@
 // (__fmul_rn: never contracted), sqrt and the divisions are __dsqrt_rn and __ddiv_rn.
 #include "em2_ingest.h"
 #include "em2_entry.h"
+#include "em2_primitives.h"
 #include "em2_wave.h"
 
 #include <cstring>
-
-#include <rocprim/rocprim.hpp>
 
 #include <atomic>
 #include <string>
@@ -347,11 +346,9 @@ hipError_t runIngest(IngestArguments a, uint64_t* outTocOfCount, uint32_t* error
     }
     if (!FILL) {                                                              // the cells' places in the output
         size_t tempBytes = 0;
-        EM2_TRY(rocprim::exclusive_scan(nullptr, tempBytes, a.keptCount, outTocOfCount, uint64_t(0), size_t(a.cellCount),
-                                        rocprim::plus<uint64_t>(), stream));
+        EM2_TRY(exclusiveScanU32ToU64Bytes(size_t(a.cellCount), tempBytes));
         EM2_TRY(scanTemp.allocate(tempBytes));
-        EM2_TRY(rocprim::exclusive_scan(scanTemp.p, tempBytes, a.keptCount, outTocOfCount, uint64_t(0), size_t(a.cellCount),
-                                        rocprim::plus<uint64_t>(), stream));
+        EM2_TRY(exclusiveScan(scanTemp.p, tempBytes, a.keptCount, outTocOfCount, size_t(a.cellCount), stream));
         ingestLastOffsetKernel<<<dim3(1), dim3(1), 0, stream>>>(a.keptCount, outTocOfCount, a.cellCount);
         EM2_TRY(hipGetLastError());
     } else {

@@ -29,12 +29,11 @@
 
 #include "em2_adjacency.h"
 #include "em2_entry.h"
+#include "em2_primitives.h"
 #include "em2_scratch.h"
 
 #include <cmath>
-#include <cstring>            // (rocPRIM calls memset without including it)
 #include <limits>
-#include <rocprim/rocprim.hpp>
 #include <string>
 
 // What the device code and the C entry points at the end of this file share.
@@ -579,56 +578,50 @@ struct LayoutWork {
         const uint32_t cellCount = layoutLevelBegin(depth + 1u), leafCount = 1u << (2u * depth);
         const dim3 threads(256);
         const uint64_t recordCount = 2u * edgeCount;
-        size_t at = 0;
-        const auto take = [&at](size_t bytes) {
-            const size_t here = at;
-            at += alignUp(bytes ? bytes : 1u);
-            return here;
-        };
-        const size_t offError = take(256);
-        const size_t offState = take(sizeof(LayoutState));
-        const size_t offPosition0 = take(size_t(n) * sizeof(float2));
-        const size_t offPosition1 = take(size_t(n) * sizeof(float2));
-        const size_t offForce = take(size_t(n) * sizeof(float2));
-        const size_t offPartial = take(size_t(n) * (pyramid ? 1u : kLayoutSliceCount) * sizeof(float2));
-        const size_t offChunk = take(size_t(chunkCount) * sizeof(double));
-        const size_t offOffsets = take((size_t(n) + 1u) * sizeof(uint64_t));
-        const size_t offNeighbours = take(size_t(recordCount) * sizeof(uint32_t));
+        ArenaPlan plan;
+        const size_t offError = plan.take(256);
+        const size_t offState = plan.take(sizeof(LayoutState));
+        const size_t offPosition0 = plan.takeFor<float2>(n);
+        const size_t offPosition1 = plan.takeFor<float2>(n);
+        const size_t offForce = plan.takeFor<float2>(n);
+        const size_t offPartial = plan.take(size_t(n) * (pyramid ? 1u : kLayoutSliceCount) * sizeof(float2));
+        const size_t offChunk = plan.takeFor<double>(chunkCount);
+        const size_t offOffsets = plan.take((size_t(n) + 1u) * sizeof(uint64_t));
+        const size_t offNeighbours = plan.takeFor<uint32_t>(recordCount);
         size_t offMoment = 0, offRecord = 0, offLeafBegin = 0, offLeafRange = 0, offSorted = 0, offKeys0 = 0, offKeys1 = 0, offTemp = 0;
         if (pyramid) {
-            offMoment = take(size_t(cellCount) * sizeof(LayoutMoment) + 4u * sizeof(uint32_t));      // (and the box behind it)
-            offRecord = take(size_t(cellCount) * sizeof(float4));
-            offLeafBegin = take(size_t(leafCount) * sizeof(uint32_t));
-            offLeafRange = take(size_t(leafCount) * sizeof(uint2));
-            offSorted = take(size_t(n) * sizeof(float2));
-            offKeys0 = take(size_t(n) * sizeof(uint64_t));
-            offKeys1 = take(size_t(n) * sizeof(uint64_t));
-            rocprim::double_buffer<uint64_t> keys(nullptr, nullptr);
-            EM2_TRY(rocprim::radix_sort_keys(nullptr, sortTempBytes, keys, size_t(n), 0u, vertexBits + 2u * depth, stream));
-            offTemp = take(sortTempBytes);
+            offMoment = plan.take(size_t(cellCount) * sizeof(LayoutMoment) + 4u * sizeof(uint32_t));      // (and the box behind it)
+            offRecord = plan.takeFor<float4>(cellCount);
+            offLeafBegin = plan.takeFor<uint32_t>(leafCount);
+            offLeafRange = plan.takeFor<uint2>(leafCount);
+            offSorted = plan.takeFor<float2>(n);
+            offKeys0 = plan.takeFor<uint64_t>(n);
+            offKeys1 = plan.takeFor<uint64_t>(n);
+            EM2_TRY(sortKeysBufferBytes(size_t(n), 0u, vertexBits + 2u * depth, sortTempBytes));
+            offTemp = plan.take(sortTempBytes);
         }
-        EM2_TRY(arena.allocate(at));
+        EM2_TRY(arena.allocate(plan.bytes));
         char* base = arena.as<char>();
         if (pyramid) {
-            moment = reinterpret_cast<LayoutMoment*>(base + offMoment);
+            moment = arenaAt<LayoutMoment>(base, offMoment);
             box = reinterpret_cast<uint32_t*>(moment + cellCount);
-            record = reinterpret_cast<float4*>(base + offRecord);
-            leafBegin = reinterpret_cast<uint32_t*>(base + offLeafBegin);
-            leafRange = reinterpret_cast<uint2*>(base + offLeafRange);
-            sortedPosition = reinterpret_cast<float2*>(base + offSorted);
-            pyramidKeys[0] = reinterpret_cast<uint64_t*>(base + offKeys0);
-            pyramidKeys[1] = reinterpret_cast<uint64_t*>(base + offKeys1);
+            record = arenaAt<float4>(base, offRecord);
+            leafBegin = arenaAt<uint32_t>(base, offLeafBegin);
+            leafRange = arenaAt<uint2>(base, offLeafRange);
+            sortedPosition = arenaAt<float2>(base, offSorted);
+            pyramidKeys[0] = arenaAt<uint64_t>(base, offKeys0);
+            pyramidKeys[1] = arenaAt<uint64_t>(base, offKeys1);
             sortTemp = base + offTemp;
         }
-        uint32_t* error = reinterpret_cast<uint32_t*>(base + offError);
-        state = reinterpret_cast<LayoutState*>(base + offState);
-        position[0] = reinterpret_cast<float2*>(base + offPosition0);
-        position[1] = reinterpret_cast<float2*>(base + offPosition1);
-        force = reinterpret_cast<float2*>(base + offForce);
-        partial = reinterpret_cast<float2*>(base + offPartial);
-        chunkEnergy = reinterpret_cast<double*>(base + offChunk);
-        offsets = reinterpret_cast<uint64_t*>(base + offOffsets);
-        neighbours = reinterpret_cast<uint32_t*>(base + offNeighbours);
+        uint32_t* error = arenaAt<uint32_t>(base, offError);
+        state = arenaAt<LayoutState>(base, offState);
+        position[0] = arenaAt<float2>(base, offPosition0);
+        position[1] = arenaAt<float2>(base, offPosition1);
+        force = arenaAt<float2>(base, offForce);
+        partial = arenaAt<float2>(base, offPartial);
+        chunkEnergy = arenaAt<double>(base, offChunk);
+        offsets = arenaAt<uint64_t>(base, offOffsets);
+        neighbours = arenaAt<uint32_t>(base, offNeighbours);
 
         EM2_TRY(hipMemsetAsync(error, 0, 256, stream));
         checkEdgesKernel<<<dim3(gridFor(edgeCount)), threads, 0, stream>>>(d_edge0, d_edge1, edgeCount, n, error);
@@ -641,22 +634,18 @@ struct LayoutWork {
         // equal records, so the sorted array is a function of the input alone.
         const uint64_t* sortedKeys = nullptr;
         if (recordCount) {
-            at = 0;
-            const size_t offKeysA = take(recordCount * sizeof(uint64_t));
-            const size_t offKeysB = take(recordCount * sizeof(uint64_t));
+            ArenaPlan records;
+            const size_t offKeysA = records.takeFor<uint64_t>(recordCount);
+            const size_t offKeysB = records.takeFor<uint64_t>(recordCount);
             size_t sortBytes = 0;
-            {
-                rocprim::double_buffer<uint64_t> keys(nullptr, nullptr);
-                EM2_TRY(rocprim::radix_sort_keys(nullptr, sortBytes, keys, size_t(recordCount), 0u, 64u, stream));
-            }
-            const size_t offSortTemp = take(sortBytes);
-            EM2_TRY(recordArena.allocate(at));
+            EM2_TRY(sortKeysBufferBytes(size_t(recordCount), 0u, 64u, sortBytes));
+            const size_t offSortTemp = records.take(sortBytes);
+            EM2_TRY(recordArena.allocate(records.bytes));
             char* recordBase = recordArena.as<char>();
-            rocprim::double_buffer<uint64_t> keys(reinterpret_cast<uint64_t*>(recordBase + offKeysA),
-                                                  reinterpret_cast<uint64_t*>(recordBase + offKeysB));
+            DoubleBuffer<uint64_t> keys{arenaAt<uint64_t>(recordBase, offKeysA), arenaAt<uint64_t>(recordBase, offKeysB)};
             layoutRecordsKernel<<<dim3(gridFor(edgeCount)), threads, 0, stream>>>(d_edge0, d_edge1, edgeCount, keys.current());
             EM2_TRY(hipGetLastError());
-            EM2_TRY(rocprim::radix_sort_keys(recordBase + offSortTemp, sortBytes, keys, size_t(recordCount), 0u, 64u, stream));
+            EM2_TRY(sortKeys(recordBase + offSortTemp, sortBytes, keys, size_t(recordCount), 0u, 64u, stream));
             sortedKeys = keys.current();
         }
         // (with no record the searches find nothing and read nothing: every offset 0)
@@ -682,8 +671,8 @@ struct LayoutWork {
         EM2_TRY(stage("box", stream));
         pyramidKeysKernel<<<dim3(gridFor(n)), threads, 0, stream>>>(current, n, box, depth, vertexBits, pyramidKeys[0], leaves);
         EM2_TRY(hipGetLastError());
-        rocprim::double_buffer<uint64_t> keys(pyramidKeys[0], pyramidKeys[1]);
-        EM2_TRY(rocprim::radix_sort_keys(sortTemp, sortTempBytes, keys, size_t(n), 0u, vertexBits + 2u * depth, stream));
+        DoubleBuffer<uint64_t> keys{pyramidKeys[0], pyramidKeys[1]};
+        EM2_TRY(sortKeys(sortTemp, sortTempBytes, keys, size_t(n), 0u, vertexBits + 2u * depth, stream));
         pyramidGatherKernel<<<dim3(gridFor(n)), threads, 0, stream>>>(keys.current(), current, n, depth, vertexBits, sortedPosition,
                                                                      leafBegin);
         EM2_TRY(hipGetLastError());

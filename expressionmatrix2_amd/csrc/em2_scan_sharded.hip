@@ -740,21 +740,18 @@ hipError_t launchFsp4ShardPhase(const Fsp4ShardPlan& plan, int phase, const uint
         uint32_t ownerBits = 0;
         while ((1u << ownerBits) < plan.world) ++ownerBits;
         const uint32_t ownerShift = 13u + rowBits + 6u;
-        size_t tempBytes = plan.sortTempBytes;
-        return rocprim::radix_sort_keys(xs + plan.offTemp - plan.rankBytes, tempBytes, reinterpret_cast<uint64_t*>(ws + plan.offPool),
-                                        reinterpret_cast<uint64_t*>(xs + plan.offSorted - plan.rankBytes), size_t(gatheredCount),
-                                        ownerShift, ownerShift + ownerBits, stream);
+        return sortKeys(xs + plan.offTemp - plan.rankBytes, plan.sortTempBytes, reinterpret_cast<uint64_t*>(ws + plan.offPool),
+                        reinterpret_cast<uint64_t*>(xs + plan.offSorted - plan.rankBytes), size_t(gatheredCount), ownerShift,
+                        ownerShift + ownerBits, stream);
     }
     if (phase == 3) {
         if (gatheredCount > plan.capGathered) return hipErrorInvalidValue;
         lastLaunchInfo.inboxEntries = double(gatheredCount);
         const uint64_t* sorted = reinterpret_cast<const uint64_t*>(xs + plan.offGathered - plan.rankBytes);
         if (gatheredCount) {
-            size_t tempBytes = plan.sortTempBytes;
             uint64_t* in = reinterpret_cast<uint64_t*>(xs + plan.offGathered - plan.rankBytes);
             uint64_t* out = reinterpret_cast<uint64_t*>(xs + plan.offSorted - plan.rankBytes);
-            e = rocprim::radix_sort_keys(xs + plan.offTemp - plan.rankBytes, tempBytes, in, out, size_t(gatheredCount), 13u,
-                                         13u + 2u * rowBits, stream);
+            e = sortKeys(xs + plan.offTemp - plan.rankBytes, plan.sortTempBytes, in, out, size_t(gatheredCount), 13u, 13u + 2u * rowBits, stream);
             if (e != hipSuccess) return e;
             sorted = out;
         }

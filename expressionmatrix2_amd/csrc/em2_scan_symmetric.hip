@@ -1295,10 +1295,9 @@ hipError_t launchFsp4ScanSymmetric(Fsp4Args args, uint32_t paddedDw, bool identi
 
     const uint64_t* sorted = args.inbox;
     if (used) {
-        size_t tempBytes = layout.tempBytes;
         uint64_t* out = reinterpret_cast<uint64_t*>(ws + layout.poolB);
-        rocprim::double_buffer<uint64_t> keys(args.inbox, out);
-        e = rocprim::radix_sort_keys(ws + layout.temp, tempBytes, keys, size_t(used), 13u, 13u + 2u * rowBits, stream);
+        DoubleBuffer<uint64_t> keys{args.inbox, out};
+        e = sortKeys(ws + layout.temp, layout.tempBytes, keys, size_t(used), 13u, 13u + 2u * rowBits, stream);
         if (e != hipSuccess) return e;
         sorted = keys.current();
     }

@@ -7,12 +7,11 @@
 #ifndef EM2_SCAN_SYMMETRIC_DEVICE_H
 #define EM2_SCAN_SYMMETRIC_DEVICE_H
 
+#include "em2_primitives.h"
 #include "em2_scan_common.h"
 #include "em2_matrix_step_asm.h"
 
 #include <vector>
-
-#include <rocprim/rocprim.hpp>
 
 namespace em2 {
 namespace {
@@ -1815,17 +1814,14 @@ static bool matrixWideWanted(uint32_t paddedDw)
 static size_t inboxSortTempBytesDoubleBuffer(uint64_t capacity)
 {
     size_t bytes = 0;
-    uint64_t* none = nullptr;
-    rocprim::double_buffer<uint64_t> keys(none, none);
-    if (rocprim::radix_sort_keys(nullptr, bytes, keys, size_t(capacity), 0u, 64u, hipStream_t(nullptr)) != hipSuccess) return 0;
+    if (sortKeysBufferBytes(size_t(capacity), 0u, 64u, bytes) != hipSuccess) return 0;
     return bytes;
 }
 
 static size_t inboxSortTempBytes(uint64_t capacity)
 {
     size_t bytes = 0;
-    uint64_t* none = nullptr;
-    if (rocprim::radix_sort_keys(nullptr, bytes, none, none, size_t(capacity), 0u, 64u, hipStream_t(nullptr)) != hipSuccess) return 0;
+    if (sortKeysBytes(size_t(capacity), 0u, 64u, bytes) != hipSuccess) return 0;
     return bytes;
 }
 

@@ -30,11 +30,10 @@
 
 #include "em2_device.h"
 #include "em2_entry.h"
+#include "em2_primitives.h"
 #include "em2_scratch.h"
 #include "em2_wave.h"
 
-#include <cstring>            // (rocPRIM calls memset without including it)
-#include <rocprim/rocprim.hpp>
 #include <algorithm>
 #include <fstream>
 #include <map>
@@ -267,46 +266,32 @@ struct GroupLayout {
     size_t sortTempBytes, scanTempBytes;
 };
 
-hipError_t scanBytesFor(size_t count, size_t& bytes)
-{
-    bytes = 0;
-    uint32_t* in = nullptr;
-    uint64_t* out = nullptr;
-    return rocprim::exclusive_scan(nullptr, bytes, in, out, uint64_t(0), count, rocprim::plus<uint64_t>(), hipStream_t(nullptr));
-}
-
 hipError_t groupLayoutOf(uint32_t cellCount, uint32_t wordCount, GroupLayout& l)
 {
-    size_t at = 0;
-    const auto take = [&at](size_t bytes) {
-        const size_t here = at;
-        at += alignUp(bytes ? bytes : 1u);
-        return here;
-    };
+    ArenaPlan plan;
     const size_t n = cellCount, n1 = size_t(cellCount) + 1u;
-    l.error = take(256);
-    l.keysA = take(n * sizeof(uint64_t));
-    l.keysB = take(n * sizeof(uint64_t));
-    l.idsA = take(n * sizeof(uint32_t));
-    l.idsB = take(n * sizeof(uint32_t));
-    l.heads = take(n1 * sizeof(uint32_t));
-    l.headsBefore = take(n1 * sizeof(uint64_t));
-    l.groupStarts = take(n1 * sizeof(uint32_t));
-    l.keep = take(n1 * sizeof(uint32_t));
-    l.keptCells = take(n1 * sizeof(uint32_t));
-    l.vertexOfGroup = take(n1 * sizeof(uint64_t));
-    l.cellOffsetOfGroup = take(n1 * sizeof(uint64_t));
-    l.vertexSignatures = take(n * wordCount * sizeof(uint64_t));
-    l.vertexCellOffsets = take(n1 * sizeof(uint64_t));
-    l.cells = take(n * sizeof(uint32_t));
+    l.error = plan.take(256);
+    l.keysA = plan.takeFor<uint64_t>(n);
+    l.keysB = plan.takeFor<uint64_t>(n);
+    l.idsA = plan.takeFor<uint32_t>(n);
+    l.idsB = plan.takeFor<uint32_t>(n);
+    l.heads = plan.takeFor<uint32_t>(n1);
+    l.headsBefore = plan.takeFor<uint64_t>(n1);
+    l.groupStarts = plan.takeFor<uint32_t>(n1);
+    l.keep = plan.takeFor<uint32_t>(n1);
+    l.keptCells = plan.takeFor<uint32_t>(n1);
+    l.vertexOfGroup = plan.takeFor<uint64_t>(n1);
+    l.cellOffsetOfGroup = plan.takeFor<uint64_t>(n1);
+    l.vertexSignatures = plan.takeFor<uint64_t>(n * wordCount);
+    l.vertexCellOffsets = plan.takeFor<uint64_t>(n1);
+    l.cells = plan.takeFor<uint32_t>(n);
     l.sortTempBytes = 0;
-    rocprim::double_buffer<uint64_t> keys(nullptr, nullptr);
-    rocprim::double_buffer<uint32_t> ids(nullptr, nullptr);
-    EM2_TRY(rocprim::radix_sort_pairs(nullptr, l.sortTempBytes, keys, ids, n, 0u, 64u, hipStream_t(nullptr)));
-    EM2_TRY(scanBytesFor(n1, l.scanTempBytes));
-    l.sortTemp = take(l.sortTempBytes);
-    l.scanTemp = take(l.scanTempBytes);
-    l.total = at;
+    EM2_TRY(sortPairsU64U32BufferBytes(n, 0u, 64u, l.sortTempBytes));
+    l.scanTempBytes = 0;
+    EM2_TRY(exclusiveScanU32ToU64Bytes(n1, l.scanTempBytes));
+    l.sortTemp = plan.take(l.sortTempBytes);
+    l.scanTemp = plan.take(l.scanTempBytes);
+    l.total = plan.bytes;
     return hipSuccess;
 }
 
@@ -325,19 +310,19 @@ hipError_t runSignatureGraph(const uint64_t* d_signatures, uint32_t cellCount, u
     CachedBuffer arena, edgeArena, edges;
     EM2_TRY(arena.allocate(l.total));
     char* base = arena.as<char>();
-    uint32_t* error = reinterpret_cast<uint32_t*>(base + l.error);
-    uint32_t* heads = reinterpret_cast<uint32_t*>(base + l.heads);
-    uint64_t* headsBefore = reinterpret_cast<uint64_t*>(base + l.headsBefore);
-    uint32_t* groupStarts = reinterpret_cast<uint32_t*>(base + l.groupStarts);
-    uint32_t* keep = reinterpret_cast<uint32_t*>(base + l.keep);
-    uint32_t* keptCells = reinterpret_cast<uint32_t*>(base + l.keptCells);
-    uint64_t* vertexOfGroup = reinterpret_cast<uint64_t*>(base + l.vertexOfGroup);
-    uint64_t* cellOffsetOfGroup = reinterpret_cast<uint64_t*>(base + l.cellOffsetOfGroup);
-    uint64_t* vertexSignatures = reinterpret_cast<uint64_t*>(base + l.vertexSignatures);
-    uint64_t* vertexCellOffsets = reinterpret_cast<uint64_t*>(base + l.vertexCellOffsets);
-    uint32_t* cells = reinterpret_cast<uint32_t*>(base + l.cells);
-    rocprim::double_buffer<uint64_t> keys(reinterpret_cast<uint64_t*>(base + l.keysA), reinterpret_cast<uint64_t*>(base + l.keysB));
-    rocprim::double_buffer<uint32_t> ids(reinterpret_cast<uint32_t*>(base + l.idsA), reinterpret_cast<uint32_t*>(base + l.idsB));
+    uint32_t* error = arenaAt<uint32_t>(base, l.error);
+    uint32_t* heads = arenaAt<uint32_t>(base, l.heads);
+    uint64_t* headsBefore = arenaAt<uint64_t>(base, l.headsBefore);
+    uint32_t* groupStarts = arenaAt<uint32_t>(base, l.groupStarts);
+    uint32_t* keep = arenaAt<uint32_t>(base, l.keep);
+    uint32_t* keptCells = arenaAt<uint32_t>(base, l.keptCells);
+    uint64_t* vertexOfGroup = arenaAt<uint64_t>(base, l.vertexOfGroup);
+    uint64_t* cellOffsetOfGroup = arenaAt<uint64_t>(base, l.cellOffsetOfGroup);
+    uint64_t* vertexSignatures = arenaAt<uint64_t>(base, l.vertexSignatures);
+    uint64_t* vertexCellOffsets = arenaAt<uint64_t>(base, l.vertexCellOffsets);
+    uint32_t* cells = arenaAt<uint32_t>(base, l.cells);
+    DoubleBuffer<uint64_t> keys{arenaAt<uint64_t>(base, l.keysA), arenaAt<uint64_t>(base, l.keysB)};
+    DoubleBuffer<uint32_t> ids{arenaAt<uint32_t>(base, l.idsA), arenaAt<uint32_t>(base, l.idsB)};
     const size_t n1 = size_t(cellCount) + 1u;
     const dim3 perCell(gridFor(n1)), threads(256);
 
@@ -353,9 +338,7 @@ hipError_t runSignatureGraph(const uint64_t* d_signatures, uint32_t cellCount, u
         signatureKeysKernel<<<perCell, threads, 0, stream>>>(d_signatures, cellCount, wordCount, w, pass == 0u ? nullptr : ids.current(),
                                                             padMask, shift, keys.current(), pass == 0u ? ids.current() : nullptr, error);
         EM2_TRY(hipGetLastError());
-        size_t tempBytes = l.sortTempBytes;
-        EM2_TRY(rocprim::radix_sort_pairs(base + l.sortTemp, tempBytes, keys, ids, size_t(cellCount), 0u, pass == 0u ? liveBitsOfLastWord : 64u,
-                                          stream));
+        EM2_TRY(sortPairs(base + l.sortTemp, l.sortTempBytes, keys, ids, size_t(cellCount), 0u, pass == 0u ? liveBitsOfLastWord : 64u, stream));
     }
     EM2_TRY(hipMemcpyAsync(inputError, error, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     EM2_TRY(hipStreamSynchronize(stream));
@@ -368,16 +351,13 @@ hipError_t runSignatureGraph(const uint64_t* d_signatures, uint32_t cellCount, u
 
     groupHeadsKernel<<<perCell, threads, 0, stream>>>(d_signatures, order, cellCount, wordCount, heads);
     EM2_TRY(hipGetLastError());
-    size_t scanBytes = l.scanTempBytes;
-    EM2_TRY(rocprim::exclusive_scan(base + l.scanTemp, scanBytes, heads, headsBefore, uint64_t(0), n1, rocprim::plus<uint64_t>(), stream));
+    EM2_TRY(exclusiveScan(base + l.scanTemp, l.scanTempBytes, heads, headsBefore, n1, stream));
     groupStartsKernel<<<perCell, threads, 0, stream>>>(heads, headsBefore, cellCount, groupStarts);
     EM2_TRY(hipGetLastError());
     groupKeepKernel<<<perCell, threads, 0, stream>>>(groupStarts, headsBefore, cellCount, minCellCount, keep, keptCells);
     EM2_TRY(hipGetLastError());
-    scanBytes = l.scanTempBytes;
-    EM2_TRY(rocprim::exclusive_scan(base + l.scanTemp, scanBytes, keep, vertexOfGroup, uint64_t(0), n1, rocprim::plus<uint64_t>(), stream));
-    scanBytes = l.scanTempBytes;
-    EM2_TRY(rocprim::exclusive_scan(base + l.scanTemp, scanBytes, keptCells, cellOffsetOfGroup, uint64_t(0), n1, rocprim::plus<uint64_t>(), stream));
+    EM2_TRY(exclusiveScan(base + l.scanTemp, l.scanTempBytes, keep, vertexOfGroup, n1, stream));
+    EM2_TRY(exclusiveScan(base + l.scanTemp, l.scanTempBytes, keptCells, cellOffsetOfGroup, n1, stream));
     groupCompactKernel<<<perCell, threads, 0, stream>>>(d_signatures, order, heads, headsBefore, groupStarts, keep, vertexOfGroup,
                                                        cellOffsetOfGroup, cellCount, wordCount, vertexSignatures, vertexCellOffsets, cells);
     EM2_TRY(hipGetLastError());
@@ -404,29 +384,23 @@ hipError_t runSignatureGraph(const uint64_t* d_signatures, uint32_t cellCount, u
 
     if (withEdges && vertexCount) {
         const uint64_t items = vertexCount * wordCount;
-        size_t at = 0;
-        const auto take = [&at](size_t bytes) {
-            const size_t here = at;
-            at += alignUp(bytes);
-            return here;
-        };
-        const size_t offFound = take(items * sizeof(uint64_t));
-        const size_t offCounts = take((items + 1u) * sizeof(uint32_t));
-        const size_t offOffsets = take((items + 1u) * sizeof(uint64_t));
+        ArenaPlan plan;
+        const size_t offFound = plan.takeFor<uint64_t>(items);
+        const size_t offCounts = plan.takeFor<uint32_t>(items + 1u);
+        const size_t offOffsets = plan.takeFor<uint64_t>(items + 1u);
         size_t edgeScanBytes = 0;
-        EM2_TRY(scanBytesFor(items + 1u, edgeScanBytes));
-        const size_t offTemp = take(edgeScanBytes ? edgeScanBytes : 1u);
-        EM2_TRY(edgeArena.allocate(at));
+        EM2_TRY(exclusiveScanU32ToU64Bytes(items + 1u, edgeScanBytes));
+        const size_t offTemp = plan.take(edgeScanBytes);
+        EM2_TRY(edgeArena.allocate(plan.bytes));
         char* edgeBase = edgeArena.as<char>();
-        uint64_t* found = reinterpret_cast<uint64_t*>(edgeBase + offFound);
-        uint32_t* counts = reinterpret_cast<uint32_t*>(edgeBase + offCounts);
-        uint64_t* offsets = reinterpret_cast<uint64_t*>(edgeBase + offOffsets);
+        uint64_t* found = arenaAt<uint64_t>(edgeBase, offFound);
+        uint32_t* counts = arenaAt<uint32_t>(edgeBase, offCounts);
+        uint64_t* offsets = arenaAt<uint64_t>(edgeBase, offOffsets);
         EM2_TRY(hipMemsetAsync(counts + items, 0, sizeof(uint32_t), stream));
         signatureEdgesKernel<0><<<dim3(gridFor(items * 64u)), threads, 0, stream>>>(vertexSignatures, vertexCount, wordCount, lshCount, found,
                                                                                  counts, nullptr, nullptr, nullptr);
         EM2_TRY(hipGetLastError());
-        EM2_TRY(rocprim::exclusive_scan(edgeBase + offTemp, edgeScanBytes, counts, offsets, uint64_t(0), size_t(items) + 1u,
-                                        rocprim::plus<uint64_t>(), stream));
+        EM2_TRY(exclusiveScan(edgeBase + offTemp, edgeScanBytes, counts, offsets, size_t(items) + 1u, stream));
         uint64_t edgeCount = 0;
         EM2_TRY(hipMemcpyAsync(&edgeCount, offsets + items, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
         EM2_TRY(hipStreamSynchronize(stream));

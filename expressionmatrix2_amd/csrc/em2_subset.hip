@@ -7,11 +7,10 @@
 // Index / byte work only; the counts are copied bit for bit.
 
 #include "em2_device.h"
+#include "em2_primitives.h"
 #include "em2_wave.h"
 
 #include <cstring>
-
-#include <rocprim/rocprim.hpp>
 
 namespace em2 {
 namespace {
@@ -62,9 +61,7 @@ subsetKernel(const uint64_t* __restrict__ globalToc, const CountIn* __restrict__
 size_t subsetWorkspaceBytes(uint32_t cellCount)
 {
     size_t temp = 0;
-    uint64_t* none = nullptr;
-    (void)rocprim::exclusive_scan(nullptr, temp, none, none, uint64_t(0), size_t(cellCount) + 1u, rocprim::plus<uint64_t>(),
-                                  hipStream_t(nullptr));
+    (void)exclusiveScanU64Bytes(size_t(cellCount) + 1u, temp);
     return ((size_t(cellCount) + 1u) * sizeof(uint64_t) + 255u) / 256u * 256u + temp + 256u;
 }
 
@@ -86,7 +83,7 @@ hipError_t launchSubsetCount(const uint64_t* globalToc, const CountIn* globalDat
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
-    return rocprim::exclusive_scan(temp, tempBytes, counts, toc, uint64_t(0), size_t(cellCount) + 1u, rocprim::plus<uint64_t>(), stream);
+    return exclusiveScan(temp, tempBytes, counts, toc, size_t(cellCount) + 1u, stream);
 }
 
 hipError_t launchSubsetFill(const uint64_t* globalToc, const CountIn* globalData, const uint32_t* cellIds, uint32_t cellCount,
