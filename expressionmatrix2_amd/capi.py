@@ -162,6 +162,16 @@ SYMBOLS = {
                                                 _c.c_void_p, _c.c_void_p]),
     "em2_graph_layout_forces_pyramid": (_c.c_int, [_c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_double, _c.c_uint32, _c.c_void_p,
                                                    _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_double)]),
+    "em2_graph_layout_multilevel": (_c.c_int, [_c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint32, _c.c_void_p,
+                                               _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "em2_dev_graph_layout_multilevel": (_c.c_int, [_c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint32,
+                                                   _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "em2_graph_layout_coarsen": (_c.c_int, [_c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_uint32,
+                                            _c.c_uint32, _c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_uint32), _c.POINTER(_c.c_uint32),
+                                            _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.POINTER(_c.c_uint64)]),
+    "em2_graph_layout_forces_weighted": (_c.c_int, [_c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64,
+                                                    _c.c_double, _c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                                    _c.POINTER(_c.c_double)]),
     "em2_matrix_create_gene_graph": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_int64, _c.c_double, _c.POINTER(_c.c_void_p)]),
     "em2_matrix_create_gene_set_intersection": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.POINTER(_c.c_int)]),
     "em2_matrix_create_gene_set_union": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.POINTER(_c.c_int)]),
@@ -811,6 +821,97 @@ def graph_layout_forces(vertex_count, edge_vertex0, edge_vertex1, gravity, x, y,
     entry = load().em2_graph_layout_forces if _depth_argument is None else load().em2_graph_layout_forces_pyramid
     check(entry(n, _ptr(v0), _ptr(v1), len(v0), float(gravity), *_depth(_depth_argument), _ptr(x), _ptr(y), _ptr(fx), _ptr(fy),
                 ctypes.byref(energy)))
+    return fx, fy, energy.value
+
+
+LAYOUT_DEPTH_EXACT = 0xfffffffe                               # EM2_LAYOUT_DEPTH_EXACT
+LAYOUT_COARSEST = 32                                          # EM2_LAYOUT_COARSEST
+LAYOUT_MAX_LEVELS = 32                                        # EM2_LAYOUT_MAX_LEVELS
+LAYOUT_EXACT_LIMIT = 4096                                     # EM2_LAYOUT_EXACT_LIMIT
+
+
+class LayoutLevels(_c.Structure):
+    """em2_layout_levels."""
+    _fields_ = [("levelCount", _c.c_uint32), ("reserved", _c.c_uint32), ("vertexCount", _c.c_uint32 * LAYOUT_MAX_LEVELS),
+                ("matchingRounds", _c.c_uint32 * LAYOUT_MAX_LEVELS), ("iterationCount", _c.c_uint32 * LAYOUT_MAX_LEVELS),
+                ("reserved2", _c.c_uint32 * LAYOUT_MAX_LEVELS), ("edgeCount", _c.c_uint64 * LAYOUT_MAX_LEVELS)]
+
+    def as_list(self):
+        """[(vertexCount, edgeCount, matchingRounds, iterationCount)], level 0 first."""
+        return [(self.vertexCount[l], self.edgeCount[l], self.matchingRounds[l], self.iterationCount[l]) for l in range(self.levelCount)]
+
+
+def graph_layout_multilevel(vertex_count, edge_vertex0, edge_vertex1, parameters=None, depth=LAYOUT_DEPTH_EXACT):
+    """em2_graph_layout_multilevel -> (x float32 [V], y float32 [V], iterations of all levels, final step, final
+    energy, levels: [(vertexCount, edgeCount, matchingRounds, iterationCount)], level 0 first).  depth: LAYOUT_DEPTH_EXACT,
+    LAYOUT_DEPTH_AUTO or 0 ... LAYOUT_MAX_DEPTH."""
+    n, v0, v1 = _layout_edges(vertex_count, edge_vertex0, edge_vertex1)
+    parameters = parameters if parameters is not None else LayoutParameters()
+    x, y = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.float32)
+    result, levels = LayoutResult(), LayoutLevels()
+    check(load().em2_graph_layout_multilevel(n, _ptr(v0), _ptr(v1), len(v0), ctypes.byref(parameters), int(depth) % 2 ** 32, _ptr(x), _ptr(y),
+                                             ctypes.byref(result), ctypes.byref(levels)))
+    return x, y, result.iterationCount, result.step, result.energy, levels.as_list()
+
+
+def dev_graph_layout_multilevel(vertex_count, edge_vertex0, edge_vertex1, parameters=None, depth=LAYOUT_DEPTH_EXACT):
+    """The same through em2_dev_graph_layout_multilevel."""
+    import torch
+    n, v0, v1 = _layout_edges(vertex_count, edge_vertex0, edge_vertex1)
+    parameters = parameters if parameters is not None else LayoutParameters()
+    device = torch.device("cuda")
+    d_v0 = torch.from_numpy(v0.view(np.int32).copy()).to(device)
+    d_v1 = torch.from_numpy(v1.view(np.int32).copy()).to(device)
+    d_x = torch.zeros(n, dtype=torch.float32, device=device)
+    d_y = torch.zeros(n, dtype=torch.float32, device=device)
+    torch.cuda.synchronize()
+    result, levels = LayoutResult(), LayoutLevels()
+    check(load().em2_dev_graph_layout_multilevel(n, d_v0.data_ptr() if len(v0) else None, d_v1.data_ptr() if len(v0) else None, len(v0),
+                                                 ctypes.byref(parameters), int(depth) % 2 ** 32, d_x.data_ptr() if n else None,
+                                                 d_y.data_ptr() if n else None, ctypes.byref(result), ctypes.byref(levels)))
+    return d_x.cpu().numpy(), d_y.cpu().numpy(), result.iterationCount, result.step, result.energy, levels.as_list()
+
+
+def _optional_u32(a, count, what):
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, dtype=np.uint32)
+    if a.shape != (count,):
+        raise ValueError("%s must hold %d values" % (what, count))
+    return a
+
+
+def graph_layout_coarsen(vertex_count, edge_vertex0, edge_vertex1, seed, level, mass=None, edge_weight=None):
+    """em2_graph_layout_coarsen (for tests): one coarsening step -> dict: mate, coarseOf uint32 [V], coarseCount, rounds,
+    coarseMass uint32 [coarseCount], coarseEdges (a, b, w), each uint32 and ascending by (a, b)."""
+    n, v0, v1 = _layout_edges(vertex_count, edge_vertex0, edge_vertex1)
+    mass, edge_weight = _optional_u32(mass, n, "mass"), _optional_u32(edge_weight, len(v0), "edge_weight")
+    mate, coarse_of, coarse_mass = (np.zeros(n, dtype=np.uint32) for _ in range(3))
+    a, b, w = (np.zeros(len(v0), dtype=np.uint32) for _ in range(3))
+    count, rounds, edge_count = _c.c_uint32(0), _c.c_uint32(0), _c.c_uint64(0)
+    check(load().em2_graph_layout_coarsen(n, None if mass is None else _ptr(mass), _ptr(v0), _ptr(v1),
+                                          None if edge_weight is None else _ptr(edge_weight), len(v0), int(seed), int(level), _ptr(mate),
+                                          _ptr(coarse_of), ctypes.byref(count), ctypes.byref(rounds), _ptr(coarse_mass), _ptr(a), _ptr(b),
+                                          _ptr(w), ctypes.byref(edge_count)))
+    m = edge_count.value
+    return dict(mate=mate, coarseOf=coarse_of, coarseCount=count.value, rounds=rounds.value, coarseMass=coarse_mass[:count.value].copy(),
+                coarseEdges=(a[:m].copy(), b[:m].copy(), w[:m].copy()))
+
+
+def graph_layout_forces_weighted(vertex_count, edge_vertex0, edge_vertex1, gravity, x, y, depth=LAYOUT_DEPTH_EXACT, mass=None,
+                                 edge_weight=None):
+    """em2_graph_layout_forces_weighted (for tests): one evaluation with masses and edge weights -> (fx, fy, energy)."""
+    n, v0, v1 = _layout_edges(vertex_count, edge_vertex0, edge_vertex1)
+    mass, edge_weight = _optional_u32(mass, n, "mass"), _optional_u32(edge_weight, len(v0), "edge_weight")
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    if x.shape != (n,) or y.shape != (n,):
+        raise ValueError("x and y must hold one position per vertex")
+    fx, fy = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.float32)
+    energy = ctypes.c_double(0.)
+    check(load().em2_graph_layout_forces_weighted(n, None if mass is None else _ptr(mass), _ptr(v0), _ptr(v1),
+                                                  None if edge_weight is None else _ptr(edge_weight), len(v0), float(gravity),
+                                                  int(depth) % 2 ** 32, _ptr(x), _ptr(y), _ptr(fx), _ptr(fy), ctypes.byref(energy)))
     return fx, fy, energy.value
 
 

@@ -26,15 +26,26 @@
 //                          float(count) of every cell as one 16-byte record;
 //   * pyramidWalkKernel    the hot path: a lane per vertex in sorted order, the far cells of the levels 2 ... D in the stated
 //                          order, then the vertices of the nine leaves around its own; far + near goes to the vertex's slot.
+// The multilevel entries run these kernels level by level over a hierarchy built with integers only:
+//   * mergeKeysKernel, a pair sort, em2_runs.h's head flags, a scan, mergeRunsKernel: the merged, weighted edges of a level;
+//   * matchPointKernel / matchPairKernel   one round of locally dominant edges, a lane per vertex; the rounds end in the greedy
+//                          matching over the total key (weight, hash, a, b);
+//   * groupFlagsKernel, a scan, groupMapKernel: the coarse ids and masses; prolongKernel: the positions of the finer level;
+//   * the force kernels above as templates on kWeighted: masses in the repulsion and the pyramid, weights in the attraction.
+//                          The unweighted instantiations are what the single-level entries and level 0 run.
 
 #include "em2_adjacency.h"
 #include "em2_entry.h"
 #include "em2_primitives.h"
+#include "em2_runs.h"
 #include "em2_scratch.h"
 
 #include <cmath>
+#include <cstring>
 #include <limits>
+#include <memory>
 #include <string>
+#include <vector>
 
 // What the device code and the C entry points at the end of this file share.
 namespace em2 {
@@ -53,7 +64,11 @@ constexpr uint32_t kLayoutMaxVertexCount = 1u << 30;
 constexpr uint32_t kLayoutLeafTarget = EM2_LAYOUT_LEAF_TARGET;
 constexpr uint32_t kLayoutMaxDepth = EM2_LAYOUT_MAX_DEPTH;
 constexpr uint32_t kLayoutDepthAuto = EM2_LAYOUT_DEPTH_AUTO;
-constexpr uint32_t kLayoutDepthExact = 0xfffffffeu;  // (internal) no pyramid: the exact repulsion
+constexpr uint32_t kLayoutDepthExact = EM2_LAYOUT_DEPTH_EXACT;   // no pyramid: the exact repulsion (the pyramid entries refuse it)
+// The multilevel layout.  All three are part of the contract.
+constexpr uint32_t kLayoutCoarsest = EM2_LAYOUT_COARSEST;
+constexpr uint32_t kLayoutMaxLevels = EM2_LAYOUT_MAX_LEVELS;
+constexpr uint32_t kLayoutExactLimit = EM2_LAYOUT_EXACT_LIMIT;
 constexpr uint32_t kLayoutBoxBlocks = 512;           // workgroups of the box kernel (no effect on any result: minima and maxima)
 
 struct LayoutParameters {
@@ -171,12 +186,14 @@ unpackKernel(const float2* __restrict__ position, uint32_t vertexCount, float* _
     }
 }
 
-// One pair: (fx, fy) += (p_i - p_j) * C / max(d^2, delta).  dy * dy is a product of its own, the rest are fmaf.
-__device__ __forceinline__ void repel(float xi, float yi, float2 pj, float& fx, float& fy)
+// One pair: (fx, fy) += (p_i - p_j) * C / max(d^2, delta).  dy * dy is a product of its own, the rest are fmaf.  kWeighted (a
+// coarse level of the multilevel layout): C is multiplied by the mass of j first; with a mass of 1 that is C.
+template <bool kWeighted>
+__device__ __forceinline__ void repel(float xi, float yi, float2 pj, float mj, float& fx, float& fy)
 {
     const float dx = xi - pj.x, dy = yi - pj.y;
     const float d2 = fmaf(dx, dx, dy * dy);
-    const float w = kLayoutC / fmaxf(d2, kLayoutFloor);
+    const float w = (kWeighted ? kLayoutC * mj : kLayoutC) / fmaxf(d2, kLayoutFloor);
     fx = fmaf(dx, w, fx);
     fy = fmaf(dy, w, fy);
 }
@@ -184,10 +201,27 @@ __device__ __forceinline__ void repel(float xi, float yi, float2 pj, float& fx, 
 // Workgroup (b, s): the vertices [256 b, 256 b + 256) against slice s of the j range, [s L, min(N, s L + L)).  The slice goes
 // through LDS in tiles of kLayoutTile positions; every lane of a wave reads the same tile entry (a broadcast, no conflict).
 // partial[s N + i] = the slice's sum for vertex i, terms added in ascending j from 0.  An empty slice writes zeros.
-__global__ void __launch_bounds__(kLayoutBlockVertices)
-repulsionKernel(const float2* __restrict__ position, uint32_t vertexCount, uint32_t sliceLength, float2* __restrict__ partial)
+// kWeighted: the masses of the tile's vertices go through LDS with their positions (mass is not read otherwise); the
+// unweighted kernel's LDS is the positions alone, as before.
+template <bool kWeighted> struct LayoutTile {
+    float2 position[kLayoutTile];
+    float mass[kLayoutTile];
+};
+template <> struct LayoutTile<false> {
+    float2 position[kLayoutTile];
+};
+template <bool kWeighted> __device__ __forceinline__ float tileMassAt(const LayoutTile<kWeighted>& tile, uint32_t j)
 {
-    __shared__ float2 tile[kLayoutTile];
+    if constexpr (kWeighted) return tile.mass[j];
+    else return 1.f;
+}
+
+template <bool kWeighted>
+__global__ void __launch_bounds__(kLayoutBlockVertices)
+repulsionKernel(const float2* __restrict__ position, const uint32_t* __restrict__ mass, uint32_t vertexCount, uint32_t sliceLength,
+                float2* __restrict__ partial)
+{
+    __shared__ LayoutTile<kWeighted> tile;
     const uint32_t i = blockIdx.x * kLayoutBlockVertices + threadIdx.x;
     const uint32_t slice = blockIdx.y;
     const uint64_t sliceBegin = uint64_t(slice) * sliceLength;
@@ -198,13 +232,16 @@ repulsionKernel(const float2* __restrict__ position, uint32_t vertexCount, uint3
     for (uint32_t t = begin; t < end; t += kLayoutTile) {
         const uint32_t count = end - t < kLayoutTile ? end - t : kLayoutTile;
         __syncthreads();                                        // (everybody has finished with the tile before)
-        if (threadIdx.x < count) tile[threadIdx.x] = position[t + threadIdx.x];
+        if (threadIdx.x < count) {
+            tile.position[threadIdx.x] = position[t + threadIdx.x];
+            if constexpr (kWeighted) tile.mass[threadIdx.x] = float(mass[t + threadIdx.x]);
+        }
         __syncthreads();
         if (count == kLayoutTile) {
 #pragma unroll 8
-            for (uint32_t j = 0; j < kLayoutTile; j++) repel(pi.x, pi.y, tile[j], fx, fy);
+            for (uint32_t j = 0; j < kLayoutTile; j++) repel<kWeighted>(pi.x, pi.y, tile.position[j], tileMassAt(tile, j), fx, fy);
         } else {
-            for (uint32_t j = 0; j < count; j++) repel(pi.x, pi.y, tile[j], fx, fy);
+            for (uint32_t j = 0; j < count; j++) repel<kWeighted>(pi.x, pi.y, tile.position[j], tileMassAt(tile, j), fx, fy);
         }
     }
     if (i < vertexCount) partial[uint64_t(slice) * vertexCount + i] = make_float2(fx, fy);
@@ -229,10 +266,13 @@ __device__ __forceinline__ double blockTree(double value, double* shared)
 // attraction).  The move (nextPosition != NULL): p_i + f * (float(step) / |f|), |f| = sqrtf(fmaf(fx, fx, fy * fy)), nothing
 // where |f| = 0.  chunkEnergy[block] = the tree sum of double(fx) * double(fx) + double(fy) * double(fy), 0 for the threads
 // past N.  (kSliceCount: 16 for the exact repulsion; 1 for the pyramid, whose walk leaves one sum per vertex.)
-template <uint32_t kSliceCount>
+// kWeighted: an attraction term is fmaf(dx, d * float(w_ij), ax) and the sum is divided by float(m_i) once, before it is
+// subtracted; with weights and masses of 1 both are exact and the bits are those of the unweighted force.
+template <uint32_t kSliceCount, bool kWeighted>
 __global__ void __launch_bounds__(kLayoutBlockVertices)
 forceKernel(const float2* __restrict__ position, uint32_t vertexCount, const float2* __restrict__ partial,
-            const uint64_t* __restrict__ offsets, const uint32_t* __restrict__ neighbours, float gravity,
+            const uint64_t* __restrict__ offsets, const uint32_t* __restrict__ neighbours, const uint32_t* __restrict__ mass,
+            const uint32_t* __restrict__ neighbourWeights, float gravity,
             const LayoutState* __restrict__ state, float2* __restrict__ nextPosition, float2* __restrict__ force,
             double* __restrict__ chunkEnergy)
 {
@@ -253,9 +293,15 @@ forceKernel(const float2* __restrict__ position, uint32_t vertexCount, const flo
         for (uint64_t k = offsets[i]; k < last; k++) {
             const float2 pj = position[neighbours[k]];
             const float dx = pi.x - pj.x, dy = pi.y - pj.y;
-            const float d = sqrtf(fmaf(dx, dx, dy * dy));
+            float d = sqrtf(fmaf(dx, dx, dy * dy));
+            if (kWeighted) d = d * float(neighbourWeights[k]);
             ax = fmaf(dx, d, ax);
             ay = fmaf(dy, d, ay);
+        }
+        if (kWeighted) {
+            const float mi = float(mass[i]);
+            ax = ax / mi;
+            ay = ay / mi;
         }
         float fx = rx - ax, fy = ry - ay;
         fx = fmaf(-gravity, pi.x, fx);
@@ -308,8 +354,8 @@ energyStepKernel(const double* __restrict__ chunkEnergy, uint32_t chunkCount, bo
 
 struct LayoutMoment {
     unsigned long long sumX, sumY;                  // the sums of q over the cell's vertices: at most 2^30 * 2^31
-    uint32_t count;
-    uint32_t unused;
+    uint32_t count;                                 // (with masses: the sum of the masses, and the sums above are of m * q)
+    uint32_t vertices;                              // the vertices of a leaf where they are not its count: with masses only
 };
 
 __host__ __device__ __forceinline__ uint32_t layoutLevelBegin(uint32_t level) { return ((1u << (2u * level)) - 1u) / 3u; }
@@ -403,9 +449,13 @@ __device__ __forceinline__ uint32_t quantise(float v, float lo, float side)
 }
 
 // Vertex i: keys[i] = morton(leaf) << vertexBits | i, and the leaf's moments.  (moment: the leaf level, zeroed before.)
+// kWeighted: the vertex counts as mass[i] vertices at its place -- the masses of a graph sum to at most 2^30, so the sums stay
+// below 2^61 -- and the leaf counts its vertices apart.
+template <bool kWeighted>
 __global__ void __launch_bounds__(256)
-pyramidKeysKernel(const float2* __restrict__ position, uint32_t vertexCount, const uint32_t* __restrict__ box, uint32_t depth,
-                  uint32_t vertexBits, uint64_t* __restrict__ keys, LayoutMoment* __restrict__ moment)
+pyramidKeysKernel(const float2* __restrict__ position, const uint32_t* __restrict__ mass, uint32_t vertexCount,
+                  const uint32_t* __restrict__ box, uint32_t depth, uint32_t vertexBits, uint64_t* __restrict__ keys,
+                  LayoutMoment* __restrict__ moment)
 {
     const LayoutBox b = readBox(box);
     const uint32_t last = (1u << depth) - 1u;
@@ -415,23 +465,37 @@ pyramidKeysKernel(const float2* __restrict__ position, uint32_t vertexCount, con
         const uint32_t cx = min(last, qx >> (31u - depth)), cy = min(last, qy >> (31u - depth));
         keys[i] = uint64_t(spreadBits(cx) | spreadBits(cy) << 1) << vertexBits | i;
         LayoutMoment* leaf = moment + (cy << depth | cx);
-        atomicAdd(&leaf->count, 1u);
-        atomicAdd(&leaf->sumX, (unsigned long long)qx);
-        atomicAdd(&leaf->sumY, (unsigned long long)qy);
+        if (kWeighted) {
+            const uint32_t m = mass[i];
+            atomicAdd(&leaf->count, m);
+            atomicAdd(&leaf->sumX, (unsigned long long)m * qx);
+            atomicAdd(&leaf->sumY, (unsigned long long)m * qy);
+            atomicAdd(&leaf->vertices, 1u);
+        } else {
+            atomicAdd(&leaf->count, 1u);
+            atomicAdd(&leaf->sumX, (unsigned long long)qx);
+            atomicAdd(&leaf->sumY, (unsigned long long)qy);
+        }
     }
 }
 
 // Sorted place k: the position of its vertex, and where a leaf begins (leafBegin is written for the leaves that hold a vertex).
+// kWeighted: also float(its mass).
+template <bool kWeighted>
 __global__ void __launch_bounds__(256)
-pyramidGatherKernel(const uint64_t* __restrict__ keys, const float2* __restrict__ position, uint32_t vertexCount, uint32_t depth,
-                    uint32_t vertexBits, float2* __restrict__ sortedPosition, uint32_t* __restrict__ leafBegin)
+pyramidGatherKernel(const uint64_t* __restrict__ keys, const float2* __restrict__ position, const uint32_t* __restrict__ mass,
+                    uint32_t vertexCount, uint32_t depth, uint32_t vertexBits, float2* __restrict__ sortedPosition,
+                    float* __restrict__ sortedMass, uint32_t* __restrict__ leafBegin)
 {
     const uint32_t last = (1u << depth) - 1u;
     for (uint64_t k = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; k < vertexCount; k += uint64_t(gridDim.x) * blockDim.x) {
         const uint64_t key = keys[k];
         const uint32_t vertex = uint32_t(key & ((1ull << vertexBits) - 1u));
         const uint32_t morton = uint32_t(key >> vertexBits);
-        if (vertex < vertexCount) sortedPosition[k] = position[vertex];
+        if (vertex < vertexCount) {
+            sortedPosition[k] = position[vertex];
+            if (kWeighted) sortedMass[k] = float(mass[vertex]);
+        }
         if (k == 0 || uint32_t(keys[k - 1u] >> vertexBits) != morton) {
             leafBegin[(gatherBits(morton >> 1) & last) << depth | (gatherBits(morton) & last)] = uint32_t(k);
         }
@@ -440,7 +504,8 @@ pyramidGatherKernel(const uint64_t* __restrict__ keys, const float2* __restrict_
 
 // The cells of one level: the sum of the four children (below the leaf level), then the record the walk reads:
 // (m_x, m_y, float(count), unused), m = float(double(lo) + double(S) * (double(sum) / (double(count) * 2^31))).  At the leaf
-// level also leafRange = (begin, count) in the sorted order.
+// level also leafRange = (begin, vertices) in the sorted order.
+template <bool kWeighted>
 __global__ void __launch_bounds__(256)
 pyramidLevelKernel(uint32_t level, uint32_t depth, const uint32_t* __restrict__ box, LayoutMoment* __restrict__ moment,
                    float4* __restrict__ record, const uint32_t* __restrict__ leafBegin, uint2* __restrict__ leafRange)
@@ -454,7 +519,7 @@ pyramidLevelKernel(uint32_t level, uint32_t depth, const uint32_t* __restrict__ 
         if (level < depth) {
             const uint32_t bx = c & ((1u << level) - 1u), by = c >> level;
             m.sumX = m.sumY = 0ull;
-            m.count = m.unused = 0u;
+            m.count = m.vertices = 0u;
             for (uint32_t child = 0; child < 4u; child++) {
                 const LayoutMoment& other = below[(2u * by + (child >> 1)) << (level + 1u) | (2u * bx + (child & 1u))];
                 m.sumX += other.sumX;
@@ -464,7 +529,7 @@ pyramidLevelKernel(uint32_t level, uint32_t depth, const uint32_t* __restrict__ 
             mine[c] = m;
         } else {
             m = mine[c];
-            leafRange[c] = m.count ? make_uint2(leafBegin[c], m.count) : make_uint2(0u, 0u);
+            leafRange[c] = m.count ? make_uint2(leafBegin[c], kWeighted ? m.vertices : m.count) : make_uint2(0u, 0u);
         }
         float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
         if (m.count) {
@@ -493,9 +558,11 @@ __device__ __forceinline__ void repelCell(float xi, float yi, float4 cell, float
 // cells of the parent's neighbourhood (by ascending, bx inside) that are in the grid, not within Chebyshev distance 1 of the
 // vertex's cell and not empty.  Near: the 3 x 3 leaves around its own, their vertices in sorted (= ascending index) order.  Two
 // sums from +0; repulsion[vertex] = far + near.  Lanes whose lists differ in length run their own loops under the wave's mask.
+// kWeighted: a near pair carries the mass of j (a far cell's float(count) is its mass sum already).
+template <bool kWeighted>
 __global__ void __launch_bounds__(kLayoutBlockVertices)
-pyramidWalkKernel(const uint64_t* __restrict__ keys, const float2* __restrict__ sortedPosition, uint32_t vertexCount, uint32_t depth,
-                  uint32_t vertexBits, const float4* __restrict__ record, const uint2* __restrict__ leafRange,
+pyramidWalkKernel(const uint64_t* __restrict__ keys, const float2* __restrict__ sortedPosition, const float* __restrict__ sortedMass,
+                  uint32_t vertexCount, uint32_t depth, uint32_t vertexBits, const float4* __restrict__ record, const uint2* __restrict__ leafRange,
                   float2* __restrict__ repulsion)
 {
     const uint32_t k = blockIdx.x * kLayoutBlockVertices + threadIdx.x;
@@ -531,10 +598,215 @@ pyramidWalkKernel(const uint64_t* __restrict__ keys, const float2* __restrict__ 
             const uint2 range = leafRange[uint32_t(by) << depth | uint32_t(bx)];
             const uint32_t begin = range.x < vertexCount ? range.x : vertexCount;
             const uint32_t end = range.y < vertexCount - begin ? begin + range.y : vertexCount;
-            for (uint32_t j = begin; j < end; j++) repel(p.x, p.y, sortedPosition[j], nearX, nearY);
+            for (uint32_t j = begin; j < end; j++) {
+                repel<kWeighted>(p.x, p.y, sortedPosition[j], kWeighted ? sortedMass[j] : 1.f, nearX, nearY);
+            }
         }
     }
     if (vertex < vertexCount) repulsion[vertex] = make_float2(farX + nearX, farY + nearY);
+}
+
+// ---- the levels of the multilevel layout: integers only ----
+// A level is a graph of merged edges (a, b), a < b, each once, with a weight; its vertices have masses.  `none` stands for
+// "no vertex" in mate and pointer, and an edge key of all ones for an edge that is dropped (a self-loop, an edge inside a group).
+
+constexpr uint32_t kLayoutNone = 0xffffffffu;
+constexpr uint64_t kLayoutDroppedEdge = ~0ull;
+
+// The finaliser of splitmix64 after its increment (initialKernel's hash), and the hash of (seed, level, what): the caller
+// passes salt = layoutMix(seed << 32 | level).
+__host__ __device__ __forceinline__ uint64_t layoutMix(uint64_t z)
+{
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+__global__ void __launch_bounds__(256)
+fillKernel(uint32_t* __restrict__ out, uint64_t count, uint32_t value)
+{
+    for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < count; i += uint64_t(gridDim.x) * blockDim.x) out[i] = value;
+}
+
+// Edge e as an unordered pair of the images of its ends under `map` (null: the ends themselves): keys[e] = min << 32 | max,
+// or the dropped key where the two coincide; values[e] = its weight (weight null: 1).
+__global__ void __launch_bounds__(256)
+mergeKeysKernel(const uint32_t* __restrict__ edge0, const uint32_t* __restrict__ edge1, const uint32_t* __restrict__ weight,
+                uint64_t edgeCount, const uint32_t* __restrict__ map, uint64_t* __restrict__ keys, uint32_t* __restrict__ values)
+{
+    for (uint64_t e = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; e < edgeCount; e += uint64_t(gridDim.x) * blockDim.x) {
+        uint32_t a = edge0[e], b = edge1[e];
+        if (map) {
+            a = map[a];
+            b = map[b];
+        }
+        keys[e] = a == b ? kLayoutDroppedEdge : uint64_t(min(a, b)) << 32 | max(a, b);
+        values[e] = weight ? weight[e] : 1u;
+    }
+}
+
+// The sorted keys with their head flags and the inclusive scan of the flags: run r = scan - 1 becomes edge r, its weight the
+// sum of the run's values (integer atomics into zeroed words: no order).  The dropped keys sort last and form the last run,
+// which is not counted: *mergedCount = the runs before it.
+__global__ void __launch_bounds__(256)
+mergeRunsKernel(const uint64_t* __restrict__ sorted, const uint32_t* __restrict__ values, const uint32_t* __restrict__ flags,
+                const uint32_t* __restrict__ scan, uint64_t count, uint32_t* __restrict__ edge0, uint32_t* __restrict__ edge1,
+                uint32_t* __restrict__ weight, uint64_t* __restrict__ mergedCount)
+{
+    for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < count; i += uint64_t(gridDim.x) * blockDim.x) {
+        const uint64_t key = sorted[i];
+        const bool dropped = key == kLayoutDroppedEdge;
+        if (i == count - 1u) *mergedCount = uint64_t(scan[i]) - (dropped ? 1u : 0u);
+        if (dropped) continue;
+        const uint32_t run = scan[i] - 1u;
+        if (flags[i]) {
+            edge0[run] = uint32_t(key >> 32);
+            edge1[run] = uint32_t(key);
+        }
+        atomicAdd(weight + run, values[i]);
+    }
+}
+
+// Two directed records per edge, the weight as the value.
+__global__ void __launch_bounds__(256)
+weightedRecordsKernel(const uint32_t* __restrict__ edge0, const uint32_t* __restrict__ edge1, const uint32_t* __restrict__ weight,
+                      uint64_t edgeCount, uint64_t* __restrict__ keys, uint32_t* __restrict__ values)
+{
+    for (uint64_t e = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; e < edgeCount; e += uint64_t(gridDim.x) * blockDim.x) {
+        const uint64_t v0 = edge0[e], v1 = edge1[e];
+        keys[2u * e] = v0 << 32 | v1;
+        keys[2u * e + 1u] = v1 << 32 | v0;
+        values[2u * e] = values[2u * e + 1u] = weight ? weight[e] : 1u;
+    }
+}
+
+// layoutOffsetsKernel with the weights of the sorted records.
+__global__ void __launch_bounds__(256)
+weightedOffsetsKernel(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ values, uint64_t recordCount, uint32_t vertexCount,
+                      uint64_t* __restrict__ offsets, uint32_t* __restrict__ neighbours, uint32_t* __restrict__ neighbourWeights)
+{
+    const uint64_t stride = uint64_t(gridDim.x) * blockDim.x;
+    const uint64_t first = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    for (uint64_t v = first; v <= vertexCount; v += stride) offsets[v] = lowerBound(keys, recordCount, v << 32);
+    for (uint64_t i = first; i < recordCount; i += stride) {
+        neighbours[i] = uint32_t(keys[i]);
+        neighbourWeights[i] = values[i];
+    }
+}
+
+// One round of the matching, first half.  A lane per vertex: an unmatched vertex scans its whole adjacency (a hub serialises
+// the round: a known limit) for its live edges, those to unmatched neighbours, and points at the other end of the one with the
+// largest key (weight, hash of (seed, level, a, b), a, b); pointer[v] = none where it has none or is matched.  *liveCount: the
+// vertices that point somewhere, one atomic per wave.  The hash is only computed where the weights tie.
+__global__ void __launch_bounds__(256)
+matchPointKernel(uint32_t vertexCount, const uint64_t* __restrict__ offsets, const uint32_t* __restrict__ neighbours,
+                 const uint32_t* __restrict__ neighbourWeights, const uint32_t* __restrict__ mate, uint64_t salt,
+                 uint32_t* __restrict__ pointer, uint32_t* __restrict__ liveCount)
+{
+    uint32_t live = 0u;
+    for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < vertexCount; i += uint64_t(gridDim.x) * blockDim.x) {
+        const uint32_t v = uint32_t(i);
+        uint32_t best = kLayoutNone, bestWeight = 0u;
+        uint64_t bestHash = 0ull;
+        bool bestHashed = false;
+        if (mate[v] == kLayoutNone) {
+            const uint64_t last = offsets[i + 1u];
+            for (uint64_t k = offsets[i]; k < last; k++) {
+                const uint32_t u = neighbours[k];
+                if (u >= vertexCount || mate[u] != kLayoutNone) continue;
+                const uint32_t w = neighbourWeights[k];
+                if (best != kLayoutNone && w < bestWeight) continue;
+                bool better = best == kLayoutNone || w > bestWeight;
+                uint64_t hash = 0ull;
+                bool hashed = false;
+                if (!better) {
+                    // equal weights: the hashes of the two edges, then (a, b) -- the edges share v, so the other ends decide
+                    if (!bestHashed) {
+                        bestHash = layoutMix(salt ^ (uint64_t(min(v, best)) << 32 | max(v, best)));
+                        bestHashed = true;
+                    }
+                    hash = layoutMix(salt ^ (uint64_t(min(v, u)) << 32 | max(v, u)));
+                    hashed = true;
+                    if (hash != bestHash) {
+                        better = hash > bestHash;
+                    } else {
+                        const uint32_t a = min(v, u), b = max(v, u), bestA = min(v, best), bestB = max(v, best);
+                        better = a != bestA ? a > bestA : b > bestB;
+                    }
+                }
+                if (better) {
+                    best = u;
+                    bestWeight = w;
+                    bestHash = hash;
+                    bestHashed = hashed;
+                }
+            }
+        }
+        pointer[v] = best;
+        if (best != kLayoutNone) live++;
+    }
+    for (int offset = 32; offset >= 1; offset /= 2) live += __shfl_xor(live, offset);
+    if ((threadIdx.x & 63u) == 0u && live) atomicAdd(liveCount, live);
+}
+
+// ... second half: two vertices that point at each other are matched.  Every thread writes its own vertex only.
+__global__ void __launch_bounds__(256)
+matchPairKernel(uint32_t vertexCount, const uint32_t* __restrict__ pointer, uint32_t* __restrict__ mate)
+{
+    for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < vertexCount; i += uint64_t(gridDim.x) * blockDim.x) {
+        const uint32_t p = pointer[i];
+        if (p < vertexCount && pointer[p] == uint32_t(i)) mate[i] = p;
+    }
+}
+
+// flags[v] = 1 where v is the representative of its group: unmatched, or the smaller index of its pair.
+__global__ void __launch_bounds__(256)
+groupFlagsKernel(uint32_t vertexCount, const uint32_t* __restrict__ mate, uint32_t* __restrict__ flags)
+{
+    for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < vertexCount; i += uint64_t(gridDim.x) * blockDim.x) {
+        const uint32_t m = mate[i];
+        flags[i] = (m == kLayoutNone || uint32_t(i) < m) ? 1u : 0u;
+    }
+}
+
+// scan: the exclusive scan of the flags, so the coarse id of a representative.  coarseOf[v] = the id of v's representative;
+// the representative writes the group's mass; *coarseCount = the groups.
+__global__ void __launch_bounds__(256)
+groupMapKernel(uint32_t vertexCount, const uint32_t* __restrict__ mate, const uint32_t* __restrict__ flags, const uint32_t* __restrict__ scan,
+               const uint32_t* __restrict__ mass, uint32_t* __restrict__ coarseOf, uint32_t* __restrict__ coarseMass,
+               uint32_t* __restrict__ coarseCount)
+{
+    for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < vertexCount; i += uint64_t(gridDim.x) * blockDim.x) {
+        const uint32_t m = mate[i];
+        if (flags[i]) {
+            coarseOf[i] = scan[i];
+            coarseMass[scan[i]] = mass[i] + (m < vertexCount ? mass[m] : 0u);
+        } else {
+            coarseOf[i] = m < vertexCount ? scan[m] : 0u;
+        }
+        if (i == vertexCount - 1u) *coarseCount = scan[i] + flags[i];
+    }
+}
+
+// From a level to the finer one below it: a representative takes its group's position, the other member of a pair that
+// position plus an offset in [-0.5, 0.5)^2 hashed from (seed, the finer level, vertex) -- coincident vertices would never
+// separate, their pair terms being exact zeros.  salt = layoutMix(seed << 32 | level).
+__global__ void __launch_bounds__(256)
+prolongKernel(uint32_t vertexCount, const uint32_t* __restrict__ mate, const uint32_t* __restrict__ coarseOf, uint32_t coarseCount,
+              const float2* __restrict__ coarsePosition, uint64_t salt, float2* __restrict__ position)
+{
+    for (uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < vertexCount; i += uint64_t(gridDim.x) * blockDim.x) {
+        const uint32_t c = coarseOf[i];
+        float2 p = c < coarseCount ? coarsePosition[c] : make_float2(0.f, 0.f);
+        const uint32_t m = mate[i];
+        if (m != kLayoutNone && m < uint32_t(i)) {
+            const uint64_t z = layoutMix(salt ^ i);
+            p.x += float(uint32_t(z >> 40)) * 0x1p-24f - 0.5f;
+            p.y += float(uint32_t(z >> 16) & 0xffffffu) * 0x1p-24f - 0.5f;
+        }
+        position[i] = p;
+    }
 }
 
 // What a run and the forces entry share: the edge check, the adjacency, the buffers.
@@ -560,14 +832,20 @@ struct LayoutWork {
     uint64_t* pyramidKeys[2] = {nullptr, nullptr};
     void* sortTemp = nullptr;
     size_t sortTempBytes = 0;
+    // a coarse level of the multilevel layout: the masses of the vertices and the weights of `neighbours`,
+    // which then live with the level, like `offsets` and `neighbours`.  Null: the unweighted kernels run.
+    const uint32_t* mass = nullptr;
+    const uint32_t* neighbourWeights = nullptr;
+    float* sortedMass = nullptr;
+    uint32_t* error = nullptr;
 
     void idle() { arena.idle = recordArena.idle = true; }
 
+    // The buffers of an evaluation over n vertices.  ownAdjacency: with `offsets` and `neighbours` for recordCount entries,
+    // which the caller then fills; else those two stay null until borrowGraph() points them at a level's arrays.
     // wantedDepth: kLayoutDepthExact, kLayoutDepthAuto or a depth <= kLayoutMaxDepth (the entries have checked it).
-    hipError_t prepare(uint32_t n, const uint32_t* d_edge0, const uint32_t* d_edge1, uint64_t edgeCount, uint32_t wantedDepth,
-                       uint32_t* inputError, hipStream_t stream)
+    hipError_t allocate(uint32_t n, uint64_t recordCount, uint32_t wantedDepth, bool weighted, bool ownAdjacency = true)
     {
-        *inputError = 0;
         vertexCount = n;
         chunkCount = blocksOf(n, kLayoutBlockVertices);
         sliceLength = blocksOf(n, kLayoutSliceCount);
@@ -576,8 +854,6 @@ struct LayoutWork {
         vertexBits = 1u;                                        // the bits of n - 1, at least one (a sort needs a bit)
         while (vertexBits < 32u && (uint64_t(n) - 1u) >> vertexBits) vertexBits++;
         const uint32_t cellCount = layoutLevelBegin(depth + 1u), leafCount = 1u << (2u * depth);
-        const dim3 threads(256);
-        const uint64_t recordCount = 2u * edgeCount;
         ArenaPlan plan;
         const size_t offError = plan.take(256);
         const size_t offState = plan.take(sizeof(LayoutState));
@@ -586,9 +862,10 @@ struct LayoutWork {
         const size_t offForce = plan.takeFor<float2>(n);
         const size_t offPartial = plan.take(size_t(n) * (pyramid ? 1u : kLayoutSliceCount) * sizeof(float2));
         const size_t offChunk = plan.takeFor<double>(chunkCount);
-        const size_t offOffsets = plan.take((size_t(n) + 1u) * sizeof(uint64_t));
-        const size_t offNeighbours = plan.takeFor<uint32_t>(recordCount);
+        const size_t offOffsets = ownAdjacency ? plan.take((size_t(n) + 1u) * sizeof(uint64_t)) : 0u;
+        const size_t offNeighbours = ownAdjacency ? plan.takeFor<uint32_t>(recordCount) : 0u;
         size_t offMoment = 0, offRecord = 0, offLeafBegin = 0, offLeafRange = 0, offSorted = 0, offKeys0 = 0, offKeys1 = 0, offTemp = 0;
+        size_t offSortedMass = 0;
         if (pyramid) {
             offMoment = plan.take(size_t(cellCount) * sizeof(LayoutMoment) + 4u * sizeof(uint32_t));      // (and the box behind it)
             offRecord = plan.takeFor<float4>(cellCount);
@@ -599,6 +876,7 @@ struct LayoutWork {
             offKeys1 = plan.takeFor<uint64_t>(n);
             EM2_TRY(sortKeysBufferBytes(size_t(n), 0u, vertexBits + 2u * depth, sortTempBytes));
             offTemp = plan.take(sortTempBytes);
+            if (weighted) offSortedMass = plan.takeFor<float>(n);
         }
         EM2_TRY(arena.allocate(plan.bytes));
         char* base = arena.as<char>();
@@ -612,22 +890,50 @@ struct LayoutWork {
             pyramidKeys[0] = arenaAt<uint64_t>(base, offKeys0);
             pyramidKeys[1] = arenaAt<uint64_t>(base, offKeys1);
             sortTemp = base + offTemp;
+            if (weighted) sortedMass = arenaAt<float>(base, offSortedMass);
         }
-        uint32_t* error = arenaAt<uint32_t>(base, offError);
+        error = arenaAt<uint32_t>(base, offError);
         state = arenaAt<LayoutState>(base, offState);
         position[0] = arenaAt<float2>(base, offPosition0);
         position[1] = arenaAt<float2>(base, offPosition1);
         force = arenaAt<float2>(base, offForce);
         partial = arenaAt<float2>(base, offPartial);
         chunkEnergy = arenaAt<double>(base, offChunk);
-        offsets = arenaAt<uint64_t>(base, offOffsets);
-        neighbours = arenaAt<uint32_t>(base, offNeighbours);
+        offsets = ownAdjacency ? arenaAt<uint64_t>(base, offOffsets) : nullptr;
+        neighbours = ownAdjacency ? arenaAt<uint32_t>(base, offNeighbours) : nullptr;
+        return hipSuccess;
+    }
 
+    // The graph of a coarse level, which the level owns and outlives this work with: nothing of it is in `arena`.
+    void borrowGraph(const uint64_t* levelOffsets, const uint32_t* levelNeighbours, const uint32_t* levelNeighbourWeights,
+                     const uint32_t* levelMass)
+    {
+        offsets = const_cast<uint64_t*>(levelOffsets);          // (read only from here on: the kernels take them as const)
+        neighbours = const_cast<uint32_t*>(levelNeighbours);
+        neighbourWeights = levelNeighbourWeights;
+        mass = levelMass;
+    }
+
+    // *inputError = kLayoutEdgeRange where an edge end is not below n, else 0.  Synchronises the stream.
+    hipError_t checkEdges(uint32_t n, const uint32_t* d_edge0, const uint32_t* d_edge1, uint64_t edgeCount, uint32_t* inputError,
+                          hipStream_t stream)
+    {
+        *inputError = 0;
         EM2_TRY(hipMemsetAsync(error, 0, 256, stream));
-        checkEdgesKernel<<<dim3(gridFor(edgeCount)), threads, 0, stream>>>(d_edge0, d_edge1, edgeCount, n, error);
+        checkEdgesKernel<<<dim3(gridFor(edgeCount)), dim3(256), 0, stream>>>(d_edge0, d_edge1, edgeCount, n, error);
         EM2_TRY(hipGetLastError());
         EM2_TRY(hipMemcpyAsync(inputError, error, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        EM2_TRY(hipStreamSynchronize(stream));
+        return hipStreamSynchronize(stream);
+    }
+
+    // The unweighted graph of the single-level entries and of level 0: the buffers, the edge check, the adjacency.
+    hipError_t prepare(uint32_t n, const uint32_t* d_edge0, const uint32_t* d_edge1, uint64_t edgeCount, uint32_t wantedDepth,
+                       uint32_t* inputError, hipStream_t stream)
+    {
+        const dim3 threads(256);
+        const uint64_t recordCount = 2u * edgeCount;
+        EM2_TRY(allocate(n, recordCount, wantedDepth, false));
+        EM2_TRY(checkEdges(n, d_edge0, d_edge1, edgeCount, inputError, stream));
         if (*inputError) return hipSuccess;
 
         // the adjacency: 2 E directed records in (vertex, neighbour) order.  Equal keys (a repeated edge, a self-loop) are
@@ -660,7 +966,7 @@ struct LayoutWork {
     StageTimer* timer = nullptr;
     hipError_t stage(const char* name, hipStream_t stream) { return timer ? timer->stage(name, stream) : hipSuccess; }
 
-    hipError_t pyramidRepulsion(const float2* current, hipStream_t stream)
+    template <bool kWeighted> hipError_t pyramidRepulsion(const float2* current, hipStream_t stream)
     {
         const dim3 threads(256);
         const uint32_t n = vertexCount, leafCount = 1u << (2u * depth);
@@ -669,24 +975,24 @@ struct LayoutWork {
         boxKernel<<<dim3(gridFor(n) < kLayoutBoxBlocks ? gridFor(n) : kLayoutBoxBlocks), threads, 0, stream>>>(current, n, box);
         EM2_TRY(hipGetLastError());
         EM2_TRY(stage("box", stream));
-        pyramidKeysKernel<<<dim3(gridFor(n)), threads, 0, stream>>>(current, n, box, depth, vertexBits, pyramidKeys[0], leaves);
+        pyramidKeysKernel<kWeighted><<<dim3(gridFor(n)), threads, 0, stream>>>(current, mass, n, box, depth, vertexBits, pyramidKeys[0], leaves);
         EM2_TRY(hipGetLastError());
         DoubleBuffer<uint64_t> keys{pyramidKeys[0], pyramidKeys[1]};
         EM2_TRY(sortKeys(sortTemp, sortTempBytes, keys, size_t(n), 0u, vertexBits + 2u * depth, stream));
-        pyramidGatherKernel<<<dim3(gridFor(n)), threads, 0, stream>>>(keys.current(), current, n, depth, vertexBits, sortedPosition,
-                                                                     leafBegin);
+        pyramidGatherKernel<kWeighted><<<dim3(gridFor(n)), threads, 0, stream>>>(keys.current(), current, mass, n, depth, vertexBits,
+                                                                                sortedPosition, sortedMass, leafBegin);
         EM2_TRY(hipGetLastError());
         EM2_TRY(stage("keys and sort", stream));
         // the leaf level (its ranges are the near field's), then the levels above it that the far field reads: down to 2
         for (uint32_t level = depth;; level--) {
-            pyramidLevelKernel<<<dim3(gridFor(1u << (2u * level))), threads, 0, stream>>>(level, depth, box, moment, record, leafBegin,
-                                                                                         leafRange);
+            pyramidLevelKernel<kWeighted><<<dim3(gridFor(1u << (2u * level))), threads, 0, stream>>>(level, depth, box, moment, record,
+                                                                                                    leafBegin, leafRange);
             EM2_TRY(hipGetLastError());
             if (level <= 2u) break;
         }
         EM2_TRY(stage("pyramid", stream));
-        pyramidWalkKernel<<<dim3(chunkCount), dim3(kLayoutBlockVertices), 0, stream>>>(keys.current(), sortedPosition, n, depth, vertexBits,
-                                                                                      record, leafRange, partial);
+        pyramidWalkKernel<kWeighted><<<dim3(chunkCount), dim3(kLayoutBlockVertices), 0, stream>>>(
+            keys.current(), sortedPosition, sortedMass, n, depth, vertexBits, record, leafRange, partial);
         EM2_TRY(hipGetLastError());
         return stage("walk", stream);
     }
@@ -694,25 +1000,287 @@ struct LayoutWork {
     // One evaluation at position[from]; the move goes to position[1 - from] where `move` is set, f to `force` where wanted.
     hipError_t evaluate(uint32_t from, float gravity, bool move, bool keepForce, hipStream_t stream)
     {
+        return mass ? evaluateAs<true>(from, gravity, move, keepForce, stream) : evaluateAs<false>(from, gravity, move, keepForce, stream);
+    }
+
+    template <bool kWeighted> hipError_t evaluateAs(uint32_t from, float gravity, bool move, bool keepForce, hipStream_t stream)
+    {
         const dim3 threads(kLayoutBlockVertices);
         float2* next = move ? position[1u - from] : nullptr;
         float2* kept = keepForce ? force : nullptr;
         if (pyramid) {
-            EM2_TRY(pyramidRepulsion(position[from], stream));
-            forceKernel<1u><<<dim3(chunkCount), threads, 0, stream>>>(position[from], vertexCount, partial, offsets, neighbours, gravity,
-                                                                     state, next, kept, chunkEnergy);
+            EM2_TRY(pyramidRepulsion<kWeighted>(position[from], stream));
+            forceKernel<1u, kWeighted><<<dim3(chunkCount), threads, 0, stream>>>(position[from], vertexCount, partial, offsets, neighbours, mass,
+                                                                                neighbourWeights, gravity, state, next, kept, chunkEnergy);
         } else {
-            repulsionKernel<<<dim3(chunkCount, kLayoutSliceCount), threads, 0, stream>>>(position[from], vertexCount, sliceLength, partial);
+            repulsionKernel<kWeighted><<<dim3(chunkCount, kLayoutSliceCount), threads, 0, stream>>>(position[from], mass, vertexCount,
+                                                                                                   sliceLength, partial);
             EM2_TRY(hipGetLastError());
-            forceKernel<kLayoutSliceCount><<<dim3(chunkCount), threads, 0, stream>>>(position[from], vertexCount, partial, offsets, neighbours,
-                                                                                    gravity, state, next, kept, chunkEnergy);
+            forceKernel<kLayoutSliceCount, kWeighted><<<dim3(chunkCount), threads, 0, stream>>>(
+                position[from], vertexCount, partial, offsets, neighbours, mass, neighbourWeights, gravity, state, next, kept, chunkEnergy);
         }
         EM2_TRY(hipGetLastError());
         energyStepKernel<<<dim3(1), threads, 0, stream>>>(chunkEnergy, chunkCount, move, state);
         EM2_TRY(hipGetLastError());
         return pyramid ? stage("force", stream) : hipSuccess;
     }
+
+    // Hu's adaptive iteration from position[from], at initialStep and an energy of +infinity, until maxIterationCount or
+    // step < tolerance.  The positions stay on the device; the new step, one double, comes back after every iteration.
+    // Afterwards position[from] holds the result, and the stream has been waited for.
+    hipError_t iterate(const LayoutParameters& parameters, uint32_t& from, LayoutResult& result, hipStream_t stream)
+    {
+        LayoutState host;
+        host.step = parameters.initialStep;
+        host.energy = std::numeric_limits<double>::infinity();
+        host.progress = host.unused = 0u;
+        EM2_TRY(hipMemcpyAsync(state, &host, sizeof(host), hipMemcpyHostToDevice, stream));
+        const float gravity = float(parameters.gravity);
+        double step = parameters.initialStep;
+        uint32_t iterations = 0;
+        while (iterations < parameters.maxIterationCount && !(step < parameters.tolerance)) {
+            EM2_TRY(evaluate(from, gravity, true, false, stream));
+            EM2_TRY(hipMemcpyAsync(&step, &state->step, sizeof(double), hipMemcpyDeviceToHost, stream));
+            EM2_TRY(hipStreamSynchronize(stream));
+            from = 1u - from;
+            iterations++;
+        }
+        EM2_TRY(hipMemcpyAsync(&host, state, sizeof(host), hipMemcpyDeviceToHost, stream));
+        EM2_TRY(hipStreamSynchronize(stream));
+        result.iterationCount = iterations;
+        result.step = host.step;
+        result.energy = host.energy;
+        return hipSuccess;
+    }
+
+    // One evaluation at the positions d_x / d_y, no move: d_fx / d_fy and *energy.  Synchronises the stream.
+    hipError_t evaluateOnce(double gravity, const float* d_x, const float* d_y, float* d_fx, float* d_fy, double* energy, hipStream_t stream)
+    {
+        LayoutState host;
+        host.step = 0.;
+        host.energy = std::numeric_limits<double>::infinity();
+        host.progress = host.unused = 0u;
+        EM2_TRY(hipMemcpyAsync(state, &host, sizeof(host), hipMemcpyHostToDevice, stream));
+        packKernel<<<dim3(gridFor(vertexCount)), dim3(256), 0, stream>>>(d_x, d_y, vertexCount, position[0]);
+        EM2_TRY(hipGetLastError());
+        EM2_TRY(evaluate(0u, float(gravity), false, true, stream));
+        unpackKernel<<<dim3(gridFor(vertexCount)), dim3(256), 0, stream>>>(force, vertexCount, d_fx, d_fy);
+        EM2_TRY(hipGetLastError());
+        EM2_TRY(hipMemcpyAsync(&host, state, sizeof(host), hipMemcpyDeviceToHost, stream));
+        EM2_TRY(hipStreamSynchronize(stream));
+        *energy = host.energy;
+        return hipSuccess;
+    }
 };
+
+// One level of the multilevel layout, in device memory for the whole run: the masses, the merged edges with their weights, the
+// adjacency over them (neighbours ascending and distinct), and, once the level has been coarsened, the matching and the map
+// to the next level.  Two blocks: what is sized by the vertices, and what is sized by the edges.
+struct LayoutLevel {
+    CachedBuffer vertexArena, edgeArena;
+    uint32_t vertexCount = 0;
+    uint64_t edgeCount = 0;
+    uint32_t rounds = 0;                            // of the matching that made this level from the one below it
+    uint32_t* mass = nullptr;
+    uint32_t* mate = nullptr;
+    uint32_t* coarseOf = nullptr;
+    uint64_t* offsets = nullptr;
+    uint32_t* edge0 = nullptr;
+    uint32_t* edge1 = nullptr;
+    uint32_t* edgeWeight = nullptr;
+    uint32_t* neighbours = nullptr;
+    uint32_t* neighbourWeights = nullptr;
+
+    void idle() { vertexArena.idle = edgeArena.idle = true; }
+
+    hipError_t allocateVertices(uint32_t n)
+    {
+        vertexCount = n;
+        ArenaPlan plan;
+        const size_t offMass = plan.takeFor<uint32_t>(n), offMate = plan.takeFor<uint32_t>(n), offCoarse = plan.takeFor<uint32_t>(n);
+        const size_t offOffsets = plan.takeFor<uint64_t>(size_t(n) + 1u);
+        EM2_TRY(vertexArena.allocate(plan.bytes));
+        char* base = vertexArena.as<char>();
+        mass = arenaAt<uint32_t>(base, offMass);
+        mate = arenaAt<uint32_t>(base, offMate);
+        coarseOf = arenaAt<uint32_t>(base, offCoarse);
+        offsets = arenaAt<uint64_t>(base, offOffsets);
+        return hipSuccess;
+    }
+
+    // Room for at most `capacity` merged edges.
+    hipError_t allocateEdges(uint64_t capacity)
+    {
+        ArenaPlan plan;
+        const size_t off0 = plan.takeFor<uint32_t>(capacity), off1 = plan.takeFor<uint32_t>(capacity), offWeight = plan.takeFor<uint32_t>(capacity);
+        const size_t offNeighbours = plan.takeFor<uint32_t>(2u * capacity), offNeighbourWeights = plan.takeFor<uint32_t>(2u * capacity);
+        EM2_TRY(edgeArena.allocate(plan.bytes));
+        char* base = edgeArena.as<char>();
+        edge0 = arenaAt<uint32_t>(base, off0);
+        edge1 = arenaAt<uint32_t>(base, off1);
+        edgeWeight = arenaAt<uint32_t>(base, offWeight);
+        neighbours = arenaAt<uint32_t>(base, offNeighbours);
+        neighbourWeights = arenaAt<uint32_t>(base, offNeighbourWeights);
+        return hipSuccess;
+    }
+};
+
+// offsets / neighbours / neighbourWeights of the graph of n vertices and the edges (edge0, edge1, weight; weight null: 1), as
+// LayoutWork::prepare builds the unweighted one: two records per edge, one stable radix sort of (key, weight) pairs, a search.
+// Synchronises the stream (the scratch goes back to the cache).
+hipError_t buildWeightedAdjacency(uint32_t n, const uint32_t* edge0, const uint32_t* edge1, const uint32_t* weight, uint64_t edgeCount,
+                                  uint64_t* offsets, uint32_t* neighbours, uint32_t* neighbourWeights, hipStream_t stream)
+{
+    const dim3 threads(256);
+    const uint64_t recordCount = 2u * edgeCount;
+    CachedBuffer scratch;
+    const uint64_t* sortedKeys = nullptr;
+    const uint32_t* sortedValues = nullptr;
+    if (recordCount) {
+        ArenaPlan plan;
+        const size_t offKeysA = plan.takeFor<uint64_t>(recordCount), offKeysB = plan.takeFor<uint64_t>(recordCount);
+        const size_t offValuesA = plan.takeFor<uint32_t>(recordCount), offValuesB = plan.takeFor<uint32_t>(recordCount);
+        size_t sortBytes = 0;
+        EM2_TRY(sortPairsU64U32BufferBytes(size_t(recordCount), 0u, 64u, sortBytes));
+        const size_t offSortTemp = plan.take(sortBytes);
+        EM2_TRY(scratch.allocate(plan.bytes));
+        char* base = scratch.as<char>();
+        DoubleBuffer<uint64_t> keys{arenaAt<uint64_t>(base, offKeysA), arenaAt<uint64_t>(base, offKeysB)};
+        DoubleBuffer<uint32_t> values{arenaAt<uint32_t>(base, offValuesA), arenaAt<uint32_t>(base, offValuesB)};
+        weightedRecordsKernel<<<dim3(gridFor(edgeCount)), threads, 0, stream>>>(edge0, edge1, weight, edgeCount, keys.current(), values.current());
+        EM2_TRY(hipGetLastError());
+        EM2_TRY(sortPairs(base + offSortTemp, sortBytes, keys, values, size_t(recordCount), 0u, 64u, stream));
+        sortedKeys = keys.current();
+        sortedValues = values.current();
+    }
+    weightedOffsetsKernel<<<dim3(gridFor(recordCount > n ? recordCount : uint64_t(n) + 1u)), threads, 0, stream>>>(
+        sortedKeys, sortedValues, recordCount, n, offsets, neighbours, neighbourWeights);
+    EM2_TRY(hipGetLastError());
+    EM2_TRY(hipStreamSynchronize(stream));
+    scratch.idle = true;
+    return hipSuccess;
+}
+
+// The merged edges of `level` (its vertices are allocated) from the edges (edge0, edge1, weight; weight null: 1) with their
+// ends mapped through `map` (null: as they are), and the adjacency over them.  Every end, mapped, is below level.vertexCount.
+hipError_t buildLevelEdges(LayoutLevel& level, const uint32_t* edge0, const uint32_t* edge1, const uint32_t* weight, uint64_t edgeCount,
+                           const uint32_t* map, hipStream_t stream)
+{
+    const dim3 threads(256);
+    EM2_TRY(level.allocateEdges(edgeCount));
+    level.edgeCount = 0;
+    if (edgeCount) {
+        CachedBuffer scratch;
+        ArenaPlan plan;
+        const size_t offKeysA = plan.takeFor<uint64_t>(edgeCount), offKeysB = plan.takeFor<uint64_t>(edgeCount);
+        const size_t offValuesA = plan.takeFor<uint32_t>(edgeCount), offValuesB = plan.takeFor<uint32_t>(edgeCount);
+        const size_t offFlags = plan.takeFor<uint32_t>(edgeCount), offScan = plan.takeFor<uint32_t>(edgeCount);
+        const size_t offCount = plan.take(sizeof(uint64_t));
+        size_t sortBytes = 0, scanBytes = 0;
+        EM2_TRY(sortPairsU64U32BufferBytes(size_t(edgeCount), 0u, 64u, sortBytes));
+        EM2_TRY(inclusiveScanBytes(size_t(edgeCount), scanBytes));
+        const size_t offSortTemp = plan.take(sortBytes), offScanTemp = plan.take(scanBytes);
+        EM2_TRY(scratch.allocate(plan.bytes));
+        char* base = scratch.as<char>();
+        DoubleBuffer<uint64_t> keys{arenaAt<uint64_t>(base, offKeysA), arenaAt<uint64_t>(base, offKeysB)};
+        DoubleBuffer<uint32_t> values{arenaAt<uint32_t>(base, offValuesA), arenaAt<uint32_t>(base, offValuesB)};
+        uint32_t* flags = arenaAt<uint32_t>(base, offFlags);
+        uint32_t* scan = arenaAt<uint32_t>(base, offScan);
+        uint64_t* mergedCount = arenaAt<uint64_t>(base, offCount);
+        const dim3 grid(gridFor(edgeCount));
+        mergeKeysKernel<<<grid, threads, 0, stream>>>(edge0, edge1, weight, edgeCount, map, keys.current(), values.current());
+        EM2_TRY(hipGetLastError());
+        EM2_TRY(sortPairs(base + offSortTemp, sortBytes, keys, values, size_t(edgeCount), 0u, 64u, stream));
+        headFlagsKernel<<<grid, threads, 0, stream>>>(keys.current(), edgeCount, flags);
+        EM2_TRY(hipGetLastError());
+        EM2_TRY(inclusiveScan(base + offScanTemp, scanBytes, flags, scan, size_t(edgeCount), stream));
+        EM2_TRY(hipMemsetAsync(level.edgeWeight, 0, size_t(edgeCount) * sizeof(uint32_t), stream));
+        mergeRunsKernel<<<grid, threads, 0, stream>>>(keys.current(), values.current(), flags, scan, edgeCount, level.edge0, level.edge1,
+                                                     level.edgeWeight, mergedCount);
+        EM2_TRY(hipGetLastError());
+        EM2_TRY(hipMemcpyAsync(&level.edgeCount, mergedCount, sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        EM2_TRY(hipStreamSynchronize(stream));
+        scratch.idle = true;
+    }
+    return buildWeightedAdjacency(level.vertexCount, level.edge0, level.edge1, level.edgeWeight, level.edgeCount, level.offsets,
+                                  level.neighbours, level.neighbourWeights, stream);
+}
+
+// One coarsening step: the matching of `fine` by rounds of locally dominant edges (one counter comes back per round), the
+// groups, and `coarse` with its masses, edges and adjacency.  fine.mate and fine.coarseOf are filled.
+hipError_t coarsenLevel(LayoutLevel& fine, uint32_t seed, uint32_t levelIndex, LayoutLevel& coarse, hipStream_t stream)
+{
+    const dim3 threads(256);
+    const uint32_t n = fine.vertexCount;
+    const dim3 grid(gridFor(n));
+    CachedBuffer scratch;
+    ArenaPlan plan;
+    const size_t offPointer = plan.takeFor<uint32_t>(n), offFlags = plan.takeFor<uint32_t>(n), offScan = plan.takeFor<uint32_t>(n);
+    const size_t offMass = plan.takeFor<uint32_t>(n), offCounter = plan.take(sizeof(uint32_t));
+    size_t scanBytes = 0;
+    EM2_TRY(exclusiveScanU32Bytes(size_t(n), scanBytes));
+    const size_t offScanTemp = plan.take(scanBytes);
+    EM2_TRY(scratch.allocate(plan.bytes));
+    char* base = scratch.as<char>();
+    uint32_t* pointer = arenaAt<uint32_t>(base, offPointer);
+    uint32_t* flags = arenaAt<uint32_t>(base, offFlags);
+    uint32_t* scan = arenaAt<uint32_t>(base, offScan);
+    uint32_t* coarseMass = arenaAt<uint32_t>(base, offMass);
+    uint32_t* counter = arenaAt<uint32_t>(base, offCounter);
+
+    const uint64_t salt = layoutMix(uint64_t(seed) << 32 | levelIndex);
+    EM2_TRY(hipMemsetAsync(fine.mate, 0xff, size_t(n) * sizeof(uint32_t), stream));
+    coarse.rounds = 0;
+    for (;;) {
+        uint32_t live = 0;
+        EM2_TRY(hipMemsetAsync(counter, 0, sizeof(uint32_t), stream));
+        matchPointKernel<<<grid, threads, 0, stream>>>(n, fine.offsets, fine.neighbours, fine.neighbourWeights, fine.mate, salt, pointer, counter);
+        EM2_TRY(hipGetLastError());
+        EM2_TRY(hipMemcpyAsync(&live, counter, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        EM2_TRY(hipStreamSynchronize(stream));
+        if (!live) break;
+        // (the best live edge of all is dominant at both of its ends, so every round matches a pair: at most n / 2 rounds)
+        matchPairKernel<<<grid, threads, 0, stream>>>(n, pointer, fine.mate);
+        EM2_TRY(hipGetLastError());
+        if (++coarse.rounds > n) return hipErrorUnknown;         // (cannot be: the loop must not depend on that)
+    }
+
+    uint32_t coarseCount = 0;
+    groupFlagsKernel<<<grid, threads, 0, stream>>>(n, fine.mate, flags);
+    EM2_TRY(hipGetLastError());
+    EM2_TRY(exclusiveScan(base + offScanTemp, scanBytes, flags, scan, size_t(n), stream));
+    groupMapKernel<<<grid, threads, 0, stream>>>(n, fine.mate, flags, scan, fine.mass, fine.coarseOf, coarseMass, counter);
+    EM2_TRY(hipGetLastError());
+    EM2_TRY(hipMemcpyAsync(&coarseCount, counter, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    EM2_TRY(hipStreamSynchronize(stream));
+    EM2_TRY(coarse.allocateVertices(coarseCount));
+    EM2_TRY(hipMemcpyAsync(coarse.mass, coarseMass, size_t(coarseCount) * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+    EM2_TRY(buildLevelEdges(coarse, fine.edge0, fine.edge1, fine.edgeWeight, fine.edgeCount, fine.coarseOf, stream));
+    scratch.idle = true;                                        // (buildLevelEdges has waited for the stream)
+    return hipSuccess;
+}
+
+// Level 0 of a graph whose edge ends have been checked: the masses (null: 1) and the merged edges.
+hipError_t buildFinestLevel(LayoutLevel& level, uint32_t n, const uint32_t* d_mass, const uint32_t* d_edge0, const uint32_t* d_edge1,
+                            const uint32_t* d_weight, uint64_t edgeCount, hipStream_t stream)
+{
+    EM2_TRY(level.allocateVertices(n));
+    if (d_mass) {
+        EM2_TRY(hipMemcpyAsync(level.mass, d_mass, size_t(n) * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+    } else {
+        fillKernel<<<dim3(gridFor(n)), dim3(256), 0, stream>>>(level.mass, n, 1u);
+        EM2_TRY(hipGetLastError());
+    }
+    return buildLevelEdges(level, d_edge0, d_edge1, d_weight, edgeCount, nullptr, stream);
+}
+
+// What a level of n vertices evaluates its repulsion with, from the entry's depth argument: level 0 is the single-level
+// entry of that argument; under kLayoutDepthAuto a coarse level of at most kLayoutExactLimit vertices is exact.
+uint32_t depthOfLevel(uint32_t depth, uint32_t level, uint32_t n)
+{
+    if (depth == kLayoutDepthAuto && level > 0u && n <= kLayoutExactLimit) return kLayoutDepthExact;
+    return depth;
+}
 
 }  // namespace
 
@@ -730,35 +1298,16 @@ hipError_t runGraphLayout(uint32_t vertexCount, const uint32_t* d_edge0, const u
     EM2_TRY(timer.stage("check and adjacency", stream));
     work.timer = &timer;
 
-    LayoutState host;
-    host.step = parameters.initialStep;
-    host.energy = std::numeric_limits<double>::infinity();
-    host.progress = host.unused = 0u;
-    EM2_TRY(hipMemcpyAsync(work.state, &host, sizeof(host), hipMemcpyHostToDevice, stream));
     initialKernel<<<dim3(gridFor(vertexCount)), dim3(256), 0, stream>>>(parameters.seed, vertexCount, sqrtf(float(vertexCount)),
                                                                        work.position[0]);
     EM2_TRY(hipGetLastError());
-
-    // The positions stay on the device; the new step, one double, comes back after every iteration.
-    const float gravity = float(parameters.gravity);
-    double step = parameters.initialStep;
-    uint32_t iterations = 0, from = 0;
-    while (iterations < parameters.maxIterationCount && !(step < parameters.tolerance)) {
-        EM2_TRY(work.evaluate(from, gravity, true, false, stream));
-        EM2_TRY(hipMemcpyAsync(&step, &work.state->step, sizeof(double), hipMemcpyDeviceToHost, stream));
-        EM2_TRY(hipStreamSynchronize(stream));
-        from = 1u - from;
-        iterations++;
-    }
+    uint32_t from = 0;
+    EM2_TRY(work.iterate(parameters, from, result, stream));
     EM2_TRY(timer.stage("iterations", stream));
 
     unpackKernel<<<dim3(gridFor(vertexCount)), dim3(256), 0, stream>>>(work.position[from], vertexCount, d_x, d_y);
     EM2_TRY(hipGetLastError());
-    EM2_TRY(hipMemcpyAsync(&host, work.state, sizeof(host), hipMemcpyDeviceToHost, stream));
     EM2_TRY(hipStreamSynchronize(stream));
-    result.iterationCount = iterations;
-    result.step = host.step;
-    result.energy = host.energy;
     work.idle();                                                // (everything that used the blocks has been waited for)
     return hipSuccess;
 }
@@ -773,20 +1322,161 @@ hipError_t runGraphLayoutForces(uint32_t vertexCount, const uint32_t* d_edge0, c
         work.idle();
         return hipSuccess;
     }
-    LayoutState host;
-    host.step = 0.;
-    host.energy = std::numeric_limits<double>::infinity();
-    host.progress = host.unused = 0u;
-    EM2_TRY(hipMemcpyAsync(work.state, &host, sizeof(host), hipMemcpyHostToDevice, stream));
-    packKernel<<<dim3(gridFor(vertexCount)), dim3(256), 0, stream>>>(d_x, d_y, vertexCount, work.position[0]);
-    EM2_TRY(hipGetLastError());
-    EM2_TRY(work.evaluate(0u, float(gravity), false, true, stream));
-    unpackKernel<<<dim3(gridFor(vertexCount)), dim3(256), 0, stream>>>(work.force, vertexCount, d_fx, d_fy);
-    EM2_TRY(hipGetLastError());
-    EM2_TRY(hipMemcpyAsync(&host, work.state, sizeof(host), hipMemcpyDeviceToHost, stream));
-    EM2_TRY(hipStreamSynchronize(stream));
-    *energy = host.energy;
+    EM2_TRY(work.evaluateOnce(gravity, d_x, d_y, d_fx, d_fy, energy, stream));
     work.idle();
+    return hipSuccess;
+}
+
+// The multilevel layout: the levels by matching and contraction until the stop rule, the coarsest level from
+// the hashed start positions, then level by level down to level 0, each from the prolonged positions of the one above, at
+// initialStep and with the whole iteration budget.  Level 0 runs the unweighted kernels on the input as it is.  depth as
+// runGraphLayout takes it.  result: the iterations of all levels, the step and energy of level 0's end.  levels: what was done.
+static hipError_t runGraphLayoutMultilevel(uint32_t vertexCount, const uint32_t* d_edge0, const uint32_t* d_edge1, uint64_t edgeCount,
+                                    const LayoutParameters& parameters, uint32_t depth, float* d_x, float* d_y, LayoutResult& result,
+                                    em2_layout_levels& report, uint32_t* inputError, hipStream_t stream)
+{
+    StageTimer timer("graphLayoutMultilevel");
+    const dim3 threads(256);
+    LayoutWork finest;
+    EM2_TRY(finest.prepare(vertexCount, d_edge0, d_edge1, edgeCount, depthOfLevel(depth, 0u, vertexCount), inputError, stream));
+    if (*inputError) {
+        finest.idle();
+        return hipSuccess;
+    }
+
+    std::vector<std::unique_ptr<LayoutLevel>> levels;
+    levels.emplace_back(new LayoutLevel);
+    EM2_TRY(buildFinestLevel(*levels[0], vertexCount, nullptr, d_edge0, d_edge1, nullptr, edgeCount, stream));
+    while (levels.back()->vertexCount > kLayoutCoarsest && levels.size() < kLayoutMaxLevels) {
+        std::unique_ptr<LayoutLevel> next(new LayoutLevel);
+        LayoutLevel& fine = *levels.back();
+        EM2_TRY(coarsenLevel(fine, parameters.seed, uint32_t(levels.size() - 1u), *next, stream));
+        const bool shrinks = 4ull * next->vertexCount <= 3ull * fine.vertexCount;
+        if (!shrinks) {
+            next->idle();                                       // (coarsenLevel has waited for the stream)
+            break;
+        }
+        levels.push_back(std::move(next));
+    }
+    EM2_TRY(timer.stage("levels", stream));
+
+    const uint32_t last = uint32_t(levels.size() - 1u);
+    std::unique_ptr<LayoutWork> above;                          // the work of the level above the current one, whose positions it holds
+    uint32_t aboveFrom = 0, total = 0;
+    memset(&report, 0, sizeof(report));
+    report.levelCount = uint32_t(levels.size());
+    for (uint32_t l = last;; l--) {
+        LayoutLevel& level = *levels[l];
+        std::unique_ptr<LayoutWork> own;
+        LayoutWork* work = &finest;
+        if (l > 0u) {
+            own.reset(new LayoutWork);
+            work = own.get();
+            EM2_TRY(work->allocate(level.vertexCount, 0u, depthOfLevel(depth, l, level.vertexCount), true, false));
+            work->borrowGraph(level.offsets, level.neighbours, level.neighbourWeights, level.mass);
+        }
+        const dim3 grid(gridFor(level.vertexCount));
+        if (l == last) {
+            initialKernel<<<grid, threads, 0, stream>>>(parameters.seed, level.vertexCount, sqrtf(float(vertexCount)), work->position[0]);
+        } else {
+            prolongKernel<<<grid, threads, 0, stream>>>(level.vertexCount, level.mate, level.coarseOf, levels[l + 1u]->vertexCount,
+                                                       above->position[aboveFrom], layoutMix(uint64_t(parameters.seed) << 32 | l),
+                                                       work->position[0]);
+        }
+        EM2_TRY(hipGetLastError());
+        if (above) {
+            EM2_TRY(hipStreamSynchronize(stream));
+            above->idle();
+            above.reset();
+        }
+        uint32_t from = 0;
+        LayoutResult levelResult;
+        EM2_TRY(work->iterate(parameters, from, levelResult, stream));
+        report.vertexCount[l] = level.vertexCount;
+        report.edgeCount[l] = level.edgeCount;
+        report.matchingRounds[l] = level.rounds;
+        report.iterationCount[l] = levelResult.iterationCount;
+        total += levelResult.iterationCount;
+        EM2_TRY(timer.stage(("level " + std::to_string(l)).c_str(), stream));
+        if (l == 0u) {
+            result = levelResult;
+            result.iterationCount = total;
+            unpackKernel<<<grid, threads, 0, stream>>>(finest.position[from], vertexCount, d_x, d_y);
+            EM2_TRY(hipGetLastError());
+            EM2_TRY(hipStreamSynchronize(stream));
+            break;
+        }
+        above = std::move(own);
+        aboveFrom = from;
+    }
+    for (auto& level : levels) level->idle();
+    finest.idle();
+    return hipSuccess;
+}
+
+// For tests: one coarsening step of the graph (d_mass, d_weight null: 1) at `level`.  The outputs in device memory: d_mate,
+// d_coarseOf, d_coarseMass [vertexCount], d_coarseEdge0 / 1 / Weight [edgeCount]; counts: the coarse vertices, the rounds,
+// the coarse edges.
+static hipError_t runGraphLayoutCoarsen(uint32_t vertexCount, const uint32_t* d_mass, const uint32_t* d_edge0, const uint32_t* d_edge1,
+                                 const uint32_t* d_weight, uint64_t edgeCount, uint32_t seed, uint32_t level, uint32_t* d_mate,
+                                 uint32_t* d_coarseOf, uint32_t* d_coarseMass, uint32_t* d_coarseEdge0, uint32_t* d_coarseEdge1,
+                                 uint32_t* d_coarseWeight, uint64_t counts[3], uint32_t* inputError, hipStream_t stream)
+{
+    LayoutWork check;
+    EM2_TRY(check.allocate(1u, 0u, kLayoutDepthExact, false, false));   // (for its error word)
+    EM2_TRY(check.checkEdges(vertexCount, d_edge0, d_edge1, edgeCount, inputError, stream));
+    check.idle();
+    if (*inputError) return hipSuccess;
+    LayoutLevel fine, coarse;
+    EM2_TRY(buildFinestLevel(fine, vertexCount, d_mass, d_edge0, d_edge1, d_weight, edgeCount, stream));
+    EM2_TRY(coarsenLevel(fine, seed, level, coarse, stream));
+    const size_t word = sizeof(uint32_t);
+    EM2_TRY(hipMemcpyAsync(d_mate, fine.mate, vertexCount * word, hipMemcpyDeviceToDevice, stream));
+    EM2_TRY(hipMemcpyAsync(d_coarseOf, fine.coarseOf, vertexCount * word, hipMemcpyDeviceToDevice, stream));
+    EM2_TRY(hipMemcpyAsync(d_coarseMass, coarse.mass, coarse.vertexCount * word, hipMemcpyDeviceToDevice, stream));
+    EM2_TRY(hipMemcpyAsync(d_coarseEdge0, coarse.edge0, coarse.edgeCount * word, hipMemcpyDeviceToDevice, stream));
+    EM2_TRY(hipMemcpyAsync(d_coarseEdge1, coarse.edge1, coarse.edgeCount * word, hipMemcpyDeviceToDevice, stream));
+    EM2_TRY(hipMemcpyAsync(d_coarseWeight, coarse.edgeWeight, coarse.edgeCount * word, hipMemcpyDeviceToDevice, stream));
+    EM2_TRY(hipStreamSynchronize(stream));
+    counts[0] = coarse.vertexCount;
+    counts[1] = coarse.rounds;
+    counts[2] = coarse.edgeCount;
+    fine.idle();
+    coarse.idle();
+    return hipSuccess;
+}
+
+// For tests: one evaluation with masses and weighted edges (d_mass, d_weight null: 1) through the weighted kernels.  The
+// edges are taken as they are: two entries of a vertex for the same neighbour stay two, in the order of the edges.
+static hipError_t runGraphLayoutForcesWeighted(uint32_t vertexCount, const uint32_t* d_mass, const uint32_t* d_edge0, const uint32_t* d_edge1,
+                                        const uint32_t* d_weight, uint64_t edgeCount, double gravity, uint32_t depth, const float* d_x,
+                                        const float* d_y, float* d_fx, float* d_fy, double* energy, uint32_t* inputError, hipStream_t stream)
+{
+    LayoutWork work;
+    EM2_TRY(work.allocate(vertexCount, 2u * edgeCount, depth, true));
+    EM2_TRY(work.checkEdges(vertexCount, d_edge0, d_edge1, edgeCount, inputError, stream));
+    if (*inputError) {
+        work.idle();
+        return hipSuccess;
+    }
+    CachedBuffer extra;
+    ArenaPlan plan;
+    const size_t offMass = plan.takeFor<uint32_t>(vertexCount), offWeights = plan.takeFor<uint32_t>(2u * edgeCount);
+    EM2_TRY(extra.allocate(plan.bytes));
+    uint32_t* mass = arenaAt<uint32_t>(extra.p, offMass);
+    uint32_t* neighbourWeights = arenaAt<uint32_t>(extra.p, offWeights);
+    if (d_mass) {
+        EM2_TRY(hipMemcpyAsync(mass, d_mass, size_t(vertexCount) * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+    } else {
+        fillKernel<<<dim3(gridFor(vertexCount)), dim3(256), 0, stream>>>(mass, vertexCount, 1u);
+        EM2_TRY(hipGetLastError());
+    }
+    EM2_TRY(buildWeightedAdjacency(vertexCount, d_edge0, d_edge1, d_weight, edgeCount, work.offsets, work.neighbours, neighbourWeights, stream));
+    work.mass = mass;
+    work.neighbourWeights = neighbourWeights;
+    EM2_TRY(work.evaluateOnce(gravity, d_x, d_y, d_fx, d_fy, energy, stream));
+    work.idle();
+    extra.idle = true;
     return hipSuccess;
 }
 
@@ -929,6 +1619,171 @@ int em2_graph_layout_forces_pyramid(uint32_t vertexCount, const uint32_t* edgeVe
 {
     return graphLayoutForces("em2_graph_layout_forces_pyramid", vertexCount, edgeVertex0, edgeVertex1, edgeCount, gravity,
                              depth == em2::kLayoutDepthExact ? em2::kLayoutMaxDepth + 1u : depth, x, y, fx, fy, energy);
+}
+
+static int graphLayoutMultilevel(const char* who, bool onDevice, uint32_t vertexCount, const uint32_t* edgeVertex0,
+                                 const uint32_t* edgeVertex1, uint64_t edgeCount, const em2_layout_parameters* parameters, uint32_t depth,
+                                 float* x, float* y, em2_layout_result* result, em2_layout_levels* levels)
+{
+    if (!parameters || (vertexCount && (!x || !y)) || (edgeCount && (!edgeVertex0 || !edgeVertex1))) return failNull(who);
+    if (!(parameters->tolerance >= 0.)) return failArgument(who, "tolerance must not be negative");
+    if (!(parameters->gravity >= 0.)) return failArgument(who, "gravity must not be negative");
+    if (!(parameters->initialStep >= 0.)) return failArgument(who, "initialStep must not be negative");
+    if (depth != em2::kLayoutDepthExact && !depthIsValid(depth)) return failArgument(who, kDepthText);
+    if (vertexCount > em2::kLayoutMaxVertexCount) return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": vertexCount is above 2^30");
+    if (edgeCount >> 32) return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": edgeCount is 2^32 or more");
+    em2_layout_levels report;
+    memset(&report, 0, sizeof(report));
+    em2::LayoutResult r;
+    r.step = parameters->initialStep;
+    r.energy = std::numeric_limits<double>::infinity();
+    if (vertexCount == 0) {
+        if (edgeCount) return failArgument(who, "an edge names a vertex outside the graph");
+    } else {
+        if (!haveDevice()) return failNoDevice(who);
+        DeviceBuffer d0, d1, dx, dy;
+        if (!onDevice) {
+            const int status = uploadEdges(edgeVertex0, edgeVertex1, edgeCount, d0, d1);
+            if (status != EM2_OK) return status;
+        }
+        // (also for the device entry: a run that fails half-way must not have written the caller's arrays)
+        EM2_HIP(dx.allocateFor<float>(vertexCount));
+        EM2_HIP(dy.allocateFor<float>(vertexCount));
+        const em2::LayoutParameters p = {parameters->seed, parameters->maxIterationCount, parameters->tolerance, parameters->gravity,
+                                         parameters->initialStep};
+        uint32_t inputError = 0;
+        EM2_HIP(em2::runGraphLayoutMultilevel(vertexCount, onDevice ? edgeVertex0 : d0.as<uint32_t>(), onDevice ? edgeVertex1 : d1.as<uint32_t>(),
+                                              edgeCount, p, depth, dx.as<float>(), dy.as<float>(), r, report, &inputError, nullptr));
+        if (inputError) return failArgument(who, "an edge names a vertex outside the graph");
+        if (onDevice) {
+            EM2_HIP(hipMemcpy(x, dx.p, size_t(vertexCount) * sizeof(float), hipMemcpyDeviceToDevice));
+            EM2_HIP(hipMemcpy(y, dy.p, size_t(vertexCount) * sizeof(float), hipMemcpyDeviceToDevice));
+        } else {
+            EM2_HIP(dx.download(x, vertexCount));
+            EM2_HIP(dy.download(y, vertexCount));
+        }
+    }
+    if (result) {
+        result->iterationCount = r.iterationCount;
+        result->reserved = 0u;
+        result->step = r.step;
+        result->energy = r.energy;
+    }
+    if (levels) *levels = report;
+    return EM2_OK;
+}
+
+int em2_graph_layout_multilevel(uint32_t vertexCount, const uint32_t* edgeVertex0, const uint32_t* edgeVertex1, uint64_t edgeCount,
+                                const em2_layout_parameters* parameters, uint32_t depth, float* x, float* y, em2_layout_result* result,
+                                em2_layout_levels* levels)
+{
+    return graphLayoutMultilevel("em2_graph_layout_multilevel", false, vertexCount, edgeVertex0, edgeVertex1, edgeCount, parameters, depth, x,
+                                 y, result, levels);
+}
+
+int em2_dev_graph_layout_multilevel(uint32_t vertexCount, const uint32_t* d_edgeVertex0, const uint32_t* d_edgeVertex1, uint64_t edgeCount,
+                                    const em2_layout_parameters* parameters, uint32_t depth, float* d_x, float* d_y,
+                                    em2_layout_result* result, em2_layout_levels* levels)
+{
+    return graphLayoutMultilevel("em2_dev_graph_layout_multilevel", true, vertexCount, d_edgeVertex0, d_edgeVertex1, edgeCount, parameters,
+                                 depth, d_x, d_y, result, levels);
+}
+
+// The masses and weights of a test entry: each mass >= 1, their sum at most 2^30; the weights' sum below 2^32.
+static int checkMassesAndWeights(const char* who, uint32_t vertexCount, const uint32_t* mass, const uint32_t* edgeWeight, uint64_t edgeCount)
+{
+    uint64_t massSum = 0, weightSum = 0;
+    for (uint32_t v = 0; mass && v < vertexCount; v++) {
+        if (!mass[v]) return failArgument(who, "a mass is 0");
+        massSum += mass[v];
+    }
+    for (uint64_t e = 0; e < edgeCount; e++) weightSum += edgeWeight ? edgeWeight[e] : 1u;
+    if (massSum > em2::kLayoutMaxVertexCount) return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": the masses sum to more than 2^30");
+    if (weightSum >> 32) return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": the edge weights sum to 2^32 or more");
+    return EM2_OK;
+}
+
+int em2_graph_layout_coarsen(uint32_t vertexCount, const uint32_t* mass, const uint32_t* edgeVertex0, const uint32_t* edgeVertex1,
+                             const uint32_t* edgeWeight, uint64_t edgeCount, uint32_t seed, uint32_t level, uint32_t* mate,
+                             uint32_t* coarseOf, uint32_t* coarseVertexCount, uint32_t* matchingRounds, uint32_t* coarseMass,
+                             uint32_t* coarseEdge0, uint32_t* coarseEdge1, uint32_t* coarseWeight, uint64_t* coarseEdgeCount)
+{
+    const char* who = "em2_graph_layout_coarsen";
+    if (!mate || !coarseOf || !coarseVertexCount || !matchingRounds || !coarseMass || !coarseEdgeCount ||
+        (edgeCount && (!edgeVertex0 || !edgeVertex1 || !coarseEdge0 || !coarseEdge1 || !coarseWeight))) {
+        return failNull(who);
+    }
+    if (vertexCount == 0) return failArgument(who, "vertexCount must not be 0");
+    if (vertexCount > em2::kLayoutMaxVertexCount) return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": vertexCount is above 2^30");
+    const int checked = checkMassesAndWeights(who, vertexCount, mass, edgeWeight, edgeCount);
+    if (checked != EM2_OK) return checked;
+    if (!haveDevice()) return failNoDevice(who);
+    DeviceBuffer d0, d1, dMass, dWeight, dMate, dCoarseOf, dCoarseMass, dC0, dC1, dCw;
+    const int status = uploadEdges(edgeVertex0, edgeVertex1, edgeCount, d0, d1);
+    if (status != EM2_OK) return status;
+    if (mass) EM2_HIP(dMass.upload(mass, vertexCount));
+    if (edgeWeight) EM2_HIP(dWeight.upload(edgeWeight, size_t(edgeCount)));
+    EM2_HIP(dMate.allocateFor<uint32_t>(vertexCount));
+    EM2_HIP(dCoarseOf.allocateFor<uint32_t>(vertexCount));
+    EM2_HIP(dCoarseMass.allocateFor<uint32_t>(vertexCount));
+    EM2_HIP(dC0.allocateFor<uint32_t>(size_t(edgeCount)));
+    EM2_HIP(dC1.allocateFor<uint32_t>(size_t(edgeCount)));
+    EM2_HIP(dCw.allocateFor<uint32_t>(size_t(edgeCount)));
+    uint32_t inputError = 0;
+    uint64_t counts[3] = {0, 0, 0};
+    EM2_HIP(em2::runGraphLayoutCoarsen(vertexCount, mass ? dMass.as<uint32_t>() : nullptr, d0.as<uint32_t>(), d1.as<uint32_t>(),
+                                       edgeWeight ? dWeight.as<uint32_t>() : nullptr, edgeCount, seed, level, dMate.as<uint32_t>(),
+                                       dCoarseOf.as<uint32_t>(), dCoarseMass.as<uint32_t>(), dC0.as<uint32_t>(), dC1.as<uint32_t>(),
+                                       dCw.as<uint32_t>(), counts, &inputError, nullptr));
+    if (inputError) return failArgument(who, "an edge names a vertex outside the graph");
+    EM2_HIP(dMate.download(mate, vertexCount));
+    EM2_HIP(dCoarseOf.download(coarseOf, vertexCount));
+    EM2_HIP(dCoarseMass.download(coarseMass, size_t(counts[0])));
+    EM2_HIP(dC0.download(coarseEdge0, size_t(counts[2])));
+    EM2_HIP(dC1.download(coarseEdge1, size_t(counts[2])));
+    EM2_HIP(dCw.download(coarseWeight, size_t(counts[2])));
+    *coarseVertexCount = uint32_t(counts[0]);
+    *matchingRounds = uint32_t(counts[1]);
+    *coarseEdgeCount = counts[2];
+    return EM2_OK;
+}
+
+int em2_graph_layout_forces_weighted(uint32_t vertexCount, const uint32_t* mass, const uint32_t* edgeVertex0, const uint32_t* edgeVertex1,
+                                     const uint32_t* edgeWeight, uint64_t edgeCount, double gravity, uint32_t depth, const float* x,
+                                     const float* y, float* fx, float* fy, double* energy)
+{
+    const char* who = "em2_graph_layout_forces_weighted";
+    if ((vertexCount && (!x || !y || !fx || !fy)) || (edgeCount && (!edgeVertex0 || !edgeVertex1))) return failNull(who);
+    if (!(gravity >= 0.)) return failArgument(who, "gravity must not be negative");
+    if (depth != em2::kLayoutDepthExact && !depthIsValid(depth)) return failArgument(who, kDepthText);
+    if (vertexCount > em2::kLayoutMaxVertexCount) return fail(EM2_ERROR_UNSUPPORTED, std::string(who) + ": vertexCount is above 2^30");
+    const int checked = checkMassesAndWeights(who, vertexCount, mass, edgeWeight, edgeCount);
+    if (checked != EM2_OK) return checked;
+    if (vertexCount == 0) {
+        if (edgeCount) return failArgument(who, "an edge names a vertex outside the graph");
+        if (energy) *energy = 0.;
+        return EM2_OK;
+    }
+    if (!haveDevice()) return failNoDevice(who);
+    DeviceBuffer d0, d1, dMass, dWeight, dx, dy, dfx, dfy;
+    const int status = uploadEdges(edgeVertex0, edgeVertex1, edgeCount, d0, d1);
+    if (status != EM2_OK) return status;
+    if (mass) EM2_HIP(dMass.upload(mass, vertexCount));
+    if (edgeWeight) EM2_HIP(dWeight.upload(edgeWeight, size_t(edgeCount)));
+    EM2_HIP(dx.upload(x, vertexCount));
+    EM2_HIP(dy.upload(y, vertexCount));
+    EM2_HIP(dfx.allocateFor<float>(vertexCount));
+    EM2_HIP(dfy.allocateFor<float>(vertexCount));
+    uint32_t inputError = 0;
+    double e = 0.;
+    EM2_HIP(em2::runGraphLayoutForcesWeighted(vertexCount, mass ? dMass.as<uint32_t>() : nullptr, d0.as<uint32_t>(), d1.as<uint32_t>(),
+                                              edgeWeight ? dWeight.as<uint32_t>() : nullptr, edgeCount, gravity, depth, dx.as<float>(),
+                                              dy.as<float>(), dfx.as<float>(), dfy.as<float>(), &e, &inputError, nullptr));
+    if (inputError) return failArgument(who, "an edge names a vertex outside the graph");
+    EM2_HIP(dfx.download(fx, vertexCount));
+    EM2_HIP(dfy.download(fy, vertexCount));
+    if (energy) *energy = e;
+    return EM2_OK;
 }
 
 }  // extern "C"

@@ -858,22 +858,35 @@ class ExpressionMatrix:
         c0, c1 = self._cell_graph(graphName)["edgeCellIds"]
         return list(zip(c0.tolist(), c1.tolist()))
 
-    def computeCellGraphLayout(self, graphName, seed=231, maxIterationCount=300, tolerance=0.01, gravity=0.02, repulsion="exact"):
+    def computeCellGraphLayout(self, graphName, seed=231, maxIterationCount=300, tolerance=0.01, gravity=0.02, repulsion="exact",
+                               levels="single"):
         """ExpressionMatrix::computeCellGraphLayout (src/ExpressionMatrix.cpp:1850-1864).  The reference runs Graphviz's sfdp
         on the graph; here the model sfdp minimises is iterated on the GPU at a single level (em2_graph_layout, DESIGN.md
         3.19), in units of the natural edge length.  The keyword arguments are this project's (the reference has none).
         repulsion: "exact", the N-body sum over all vertices, or "pyramid", which approximates it beyond a vertex's
         neighbourhood (em2_graph_layout_pyramid at the automatic depth): the choice for large graphs.
+        levels: "single", or "multi": the graph is coarsened by matching, the coarsest graph laid out and the layout refined
+        level by level, as sfdp does it (em2_graph_layout_multilevel) -- every level exact with
+        repulsion="exact"; with "pyramid" level 0 always uses the pyramid, as the single-level "pyramid" does, and a coarse
+        level uses it above 4 096 vertices and the exact sum below.  So on a graph of a few thousand vertices
+        levels="multi", repulsion="pyramid" approximates level 0 where the exact sum would be cheaper and better: use
+        repulsion="exact" there.
         Computed once per graph, like the reference's layoutWasComputed: a second call does nothing."""
         if repulsion not in ("exact", "pyramid"):
             raise ValueError('repulsion must be "exact" or "pyramid", not %r' % (repulsion,))
+        if levels not in ("single", "multi"):
+            raise ValueError('levels must be "single" or "multi", not %r' % (levels,))
         g = self._cell_graph(graphName)
         if "layout" in g:
             return
         v0, v1 = g["edgeVertices"]
         parameters = capi.LayoutParameters(seed=seed, maxIterationCount=maxIterationCount, tolerance=tolerance, gravity=gravity)
-        layout = capi.graph_layout if repulsion == "exact" else capi.graph_layout_pyramid
-        x, y, _, _, _ = layout(g["vertexCount"], v0, v1, parameters)
+        if levels == "multi":
+            depth = capi.LAYOUT_DEPTH_EXACT if repulsion == "exact" else capi.LAYOUT_DEPTH_AUTO
+            x, y = capi.graph_layout_multilevel(g["vertexCount"], v0, v1, parameters, depth)[:2]
+        else:
+            layout = capi.graph_layout if repulsion == "exact" else capi.graph_layout_pyramid
+            x, y, _, _, _ = layout(g["vertexCount"], v0, v1, parameters)
         g["layout"] = (x.astype(np.float64), y.astype(np.float64))
 
     def getCellGraphVertices(self, graphName):

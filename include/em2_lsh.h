@@ -757,7 +757,7 @@ void em2_gene_graph_free(em2_gene_graph* graph);
  * The layout of a graph in the plane.  csrc/em2_layout.hip, DESIGN.md 3.19.
  * The reference writes Graph.dot and runs Graphviz's sfdp (src/CellGraph.cpp:210-264).  This is the model sfdp minimises --
  * Hu's spring-electrical model -- at a single level with the exact N-body repulsion: no multilevel coarsening, no
- * approximation of the far field, no overlap removal, no edge smoothing.  The positions are not sfdp's; they are a function
+ * approximation of the far field (both are options further down), no overlap removal, no edge smoothing.  The positions are not sfdp's; they are a function
  * of the input alone, bit for bit (every rounding and the shape of every sum are fixed).
  * ------------------------------------------------------------------------------------------------------ */
 
@@ -837,7 +837,7 @@ int em2_graph_layout_forces(uint32_t vertexCount, const uint32_t* edgeVertex0, c
  * Everything else (attraction, gravity, the move, the energy in vertex order, the step, the start positions, the stop rule)
  * is that of the exact entries.  Known limits: the cells are separated by one cell width only (theta <= 1 in Barnes-Hut's
  * terms, where sfdp uses 0.6); a layout that collapses into a few dense clusters fills few leaves, and the near field then
- * grows towards the exact cost -- the tree is not adaptive.  No multilevel coarsening.
+ * grows towards the exact cost -- the tree is not adaptive.  No multilevel coarsening (em2_graph_layout_multilevel below).
  * The checks, codes and texts are those of the exact entries; a depth that is neither EM2_LAYOUT_DEPTH_AUTO nor
  * <= EM2_LAYOUT_MAX_DEPTH is EM2_ERROR_INVALID_ARGUMENT. */
 #define EM2_LAYOUT_DEPTH_AUTO 0xffffffffu
@@ -851,6 +851,94 @@ int em2_dev_graph_layout_pyramid(uint32_t vertexCount, const uint32_t* d_edgeVer
 int em2_graph_layout_forces_pyramid(uint32_t vertexCount, const uint32_t* edgeVertex0, const uint32_t* edgeVertex1, uint64_t edgeCount,
                                     double gravity, uint32_t depth, const float* x, const float* y, float* fx, float* fy,
                                     double* energy);
+
+/* The same model over a hierarchy of graphs, as sfdp does it: coarsen by matching, lay the coarsest graph out, then refine
+ * level by level.  An option next to the entries above, which stay as they are, bit for bit.  Still a
+ * function of the input alone: everything about the levels is integer arithmetic, and the forces keep their fixed shapes.
+ *   levels     level 0 is the input graph.  Level l has n_l vertices, each with an integer mass, and merged edges (a, b),
+ *              a < b, each pair once, with an integer weight.  At level 0 every mass is 1 and the weight of (a, b) is the
+ *              number of input edges between a and b; self-loops carry no weight and take no part in coarsening.
+ *   hash       mix(z): z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB;
+ *              z ^ z >> 31 (uint64: the start positions' hash is mix(seed << 32 | vertex)).  h(seed, level, w) =
+ *              mix(mix(seed << 32 | level) ^ w) for a 64-bit w.
+ *   matching   the greedy maximal matching over the level's merged edges in descending order of the total key (weight,
+ *              h(seed, level, a << 32 | b), a, b).  The device finds it in rounds of locally dominant edges: every unmatched
+ *              vertex points at the other end of its best live edge (one to an unmatched neighbour), two vertices that point at
+ *              each other are matched, until no live edge is left (one counter comes back to the host per round).  Under a
+ *              total order that is the greedy matching, not merely a maximal one.
+ *   groups     an unmatched vertex or a matched pair; its representative is its smaller index; the coarse ids ascend with
+ *              the representative; the coarse mass is the sum of the group's masses; the coarse edges are the fine edges with
+ *              mapped ends, those inside a group dropped, parallel ones merged and their weights added.
+ *   stop       level l is the coarsest when n_l <= EM2_LAYOUT_COARSEST, or when the next level would have
+ *              4 n_(l+1) > 3 n_l (that level is discarded), or when l + 1 == EM2_LAYOUT_MAX_LEVELS.  A graph that does not
+ *              coarsen -- a star, a graph without edges, any graph of at most 32 vertices -- has one level.
+ *   force      at a level l >= 1 the force on i is that of a group of m_i coincident level-0 vertices, divided by m_i:
+ *                  sum over every j of m_j (p_i - p_j) C / max(d^2, 1e-30)
+ *                    - (1 / m_i) sum over the edges (i, j), j ascending, of w_ij (p_i - p_j) d  -  gravity * p_i
+ *              with these roundings: the repulsion weight is (0.2f * float(m_j)) / fmaxf(d2, 1e-30f); an attraction term is
+ *              ax = fmaf(dx, d * float(w_ij), ax); the attraction sums are divided by float(m_i) once, then subtracted.  The
+ *              sum shapes, the energy, the move and the step control are those of the single-level entries; with all masses
+ *              and weights 1 so are the bits.  In the pyramid a cell's count is its mass sum (float(count) is the far
+ *              weight's factor as before), its moments are the sums of m * q (at most 2^61), a near pair carries float(m_j),
+ *              and the automatic depth is that of n_l.
+ *   level 0    is the input as the single-level entries see it, through their unweighted kernels: a repeated edge attracts
+ *              twice (two terms, not one of weight 2).
+ *   schedule   the coarsest level starts from the hash of (seed, vertex) on the square of side sqrtf(float(vertexCount)) --
+ *              the INPUT's vertex count -- and runs the adaptive iteration with the caller's parameters.  Then level by level
+ *              down to 0: a representative takes its group's position, the other member of a pair that position plus
+ *              (ux, uy), the two 24-bit halves of h(seed, l, vertex) as the start positions form them, in [-0.5, 0.5)^2 (l: the
+ *              level that receives the positions; coincident vertices would never separate, their pair terms being exact
+ *              zeros).  Each level starts again at initialStep with an energy of +infinity and has the whole iteration budget.
+ *              A graph of one level gets exactly what the single-level entry of the same `depth` returns.
+ *   depth      EM2_LAYOUT_DEPTH_EXACT: every level uses the exact repulsion.  EM2_LAYOUT_DEPTH_AUTO: level 0 is
+ *              em2_graph_layout_pyramid's level at the automatic depth; a coarse level of at most EM2_LAYOUT_EXACT_LIMIT
+ *              vertices is exact, a larger one uses the pyramid at the automatic depth of n_l.  0 ... EM2_LAYOUT_MAX_DEPTH:
+ *              every level uses the pyramid at that depth (for tests).
+ * Known limits: a lane scans the whole adjacency of its vertex in a matching round, so a hub of 10^6 neighbours serialises the
+ * round; isolated vertices never merge, so a graph that is mostly isolated vertices stops coarsening early; still no overlap
+ * removal and no edge smoothing.  All levels stay in device memory (their sizes sum to at most four times the finest).
+ * The checks, codes and texts are those of the entries above; edgeCount >= 2^32 is EM2_ERROR_UNSUPPORTED (the weights are
+ * uint32).  An error return leaves x, y, result and levels as they were. */
+#define EM2_LAYOUT_DEPTH_EXACT 0xfffffffeu
+#define EM2_LAYOUT_COARSEST 32u
+#define EM2_LAYOUT_MAX_LEVELS 32u
+#define EM2_LAYOUT_EXACT_LIMIT 4096u
+/* What a multilevel run did, level 0 first.  edgeCount: the merged edges; matchingRounds: the rounds of the matching that made
+ * the level from the one below it (0 at level 0); iterationCount: the iterations at the level.  The entries past levelCount
+ * are 0.  (em2_layout_result: iterationCount is the total over the levels, step and energy are those of level 0's end.) */
+typedef struct em2_layout_levels {
+    uint32_t levelCount;
+    uint32_t reserved;
+    uint32_t vertexCount[EM2_LAYOUT_MAX_LEVELS];
+    uint32_t matchingRounds[EM2_LAYOUT_MAX_LEVELS];
+    uint32_t iterationCount[EM2_LAYOUT_MAX_LEVELS];
+    uint32_t reserved2[EM2_LAYOUT_MAX_LEVELS];
+    uint64_t edgeCount[EM2_LAYOUT_MAX_LEVELS];
+} em2_layout_levels;
+int em2_graph_layout_multilevel(uint32_t vertexCount, const uint32_t* edgeVertex0, const uint32_t* edgeVertex1, uint64_t edgeCount,
+                                const em2_layout_parameters* parameters, uint32_t depth, float* x, float* y, em2_layout_result* result,
+                                em2_layout_levels* levels);
+int em2_dev_graph_layout_multilevel(uint32_t vertexCount, const uint32_t* d_edgeVertex0, const uint32_t* d_edgeVertex1, uint64_t edgeCount,
+                                    const em2_layout_parameters* parameters, uint32_t depth, float* d_x, float* d_y,
+                                    em2_layout_result* result, em2_layout_levels* levels);
+
+/* For tests: one coarsening step.  The graph: vertexCount > 0 vertices with masses (mass NULL: 1; else each >= 1 and their sum at
+ * most 2^30) and any edges with weights (edgeWeight NULL: 1; their sum below 2^32), merged first as level 0 is: loops dropped,
+ * repeats added.  `level` enters the hash.  mate [vertexCount] (0xffffffff where unmatched), coarseOf [vertexCount];
+ * coarseMass [vertexCount] and coarseEdge0 / coarseEdge1 / coarseWeight [edgeCount] are filled from the front (ascending by
+ * (coarseEdge0, coarseEdge1)); *coarseVertexCount, *matchingRounds, *coarseEdgeCount.  Host pointers, none NULL but mass and
+ * edgeWeight (the edge arrays where edgeCount is 0).  The stop rule is not applied. */
+int em2_graph_layout_coarsen(uint32_t vertexCount, const uint32_t* mass, const uint32_t* edgeVertex0, const uint32_t* edgeVertex1,
+                             const uint32_t* edgeWeight, uint64_t edgeCount, uint32_t seed, uint32_t level, uint32_t* mate,
+                             uint32_t* coarseOf, uint32_t* coarseVertexCount, uint32_t* matchingRounds, uint32_t* coarseMass,
+                             uint32_t* coarseEdge0, uint32_t* coarseEdge1, uint32_t* coarseWeight, uint64_t* coarseEdgeCount);
+
+/* For tests: em2_graph_layout_forces through the weighted kernels, with masses and weighted edges as above (taken as they
+ * are, not merged: two edges between the same vertices are two terms, in the order given).  depth: EM2_LAYOUT_DEPTH_EXACT,
+ * EM2_LAYOUT_DEPTH_AUTO or 0 ... EM2_LAYOUT_MAX_DEPTH. */
+int em2_graph_layout_forces_weighted(uint32_t vertexCount, const uint32_t* mass, const uint32_t* edgeVertex0, const uint32_t* edgeVertex1,
+                                     const uint32_t* edgeWeight, uint64_t edgeCount, double gravity, uint32_t depth, const float* x,
+                                     const float* y, float* fx, float* fy, double* energy);
 
 /* ------------------------------------------------------------------------------------------------------
  * The contingency table of two labelings of n items.  csrc/em2_contingency.hip, DESIGN.md 3.16.  Integers only: every output
