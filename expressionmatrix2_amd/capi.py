@@ -184,6 +184,41 @@ SYMBOLS = {
                                         _c.c_uint32, _c.c_int, _c.c_int, _c.c_void_p, _c.c_uint64]),
     "em2_matrix_dense_expression": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_int, _c.c_int, _c.c_uint32, _c.c_uint32,
                                                _c.c_void_p]),
+    "em2_dev_cell_similarities_to_cell_workspace": (_c.c_size_t, [_c.c_uint32, _c.c_uint32]),
+    "em2_cell_similarities_row_in_lds": (_c.c_int, [_c.c_uint32]),
+    "em2_dev_cell_similarities_to_cell": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_uint32, _c.c_uint32,
+                                                     _c.c_uint32, _c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_size_t,
+                                                     _c.c_void_p]),
+    "em2_cell_similarities_to_cell": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_uint32, _c.c_uint32,
+                                                 _c.c_uint32, _c.c_void_p, _c.c_uint32, _c.c_void_p]),
+    "em2_matrix_cell_similarities_to_cell": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_uint32, _c.c_void_p, _c.c_uint32, _c.c_void_p]),
+    "em2_dev_gene_expression_of_cells_workspace": (_c.c_size_t, []),
+    "em2_dev_gene_expression_of_cells": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_uint32, _c.c_uint32,
+                                                    _c.c_uint32, _c.c_int, _c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_void_p,
+                                                    _c.c_size_t, _c.c_void_p]),
+    "em2_gene_expression_of_cells": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_uint32, _c.c_uint32,
+                                                _c.c_uint32, _c.c_int, _c.c_void_p, _c.c_uint32, _c.c_void_p]),
+    "em2_matrix_gene_expression_of_cells": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_uint32, _c.c_int, _c.c_void_p, _c.c_uint32,
+                                                       _c.c_void_p]),
+    "em2_dev_spectral_colors_workspace": (_c.c_size_t, []),
+    "em2_dev_spectral_colors": (_c.c_int, [_c.c_void_p, _c.c_uint64, _c.c_double, _c.c_double, _c.c_int, _c.c_int, _c.c_void_p,
+                                           _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "em2_spectral_colors": (_c.c_int, [_c.c_void_p, _c.c_uint64, _c.c_double, _c.c_double, _c.c_int, _c.c_int, _c.c_void_p,
+                                       _c.c_void_p]),
+    "em2_meta_data_number": (_c.c_int, [_c.c_char_p, _c.c_uint64, _c.POINTER(_c.c_double)]),
+    "em2_graph_draw_long_edge_steps": (_c.c_uint32, []),
+    "em2_dev_graph_draw_workspace": (_c.c_size_t, [_c.c_uint32, _c.c_uint64]),
+    "em2_dev_graph_draw": (_c.c_int, [_c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_int,
+                                      _c.c_uint32, _c.c_double, _c.c_double, _c.c_double, _c.c_double, _c.c_void_p, _c.c_void_p,
+                                      _c.c_void_p, _c.c_size_t, _c.c_void_p]),
+    "em2_graph_draw": (_c.c_int, [_c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_uint32,
+                                  _c.c_double, _c.c_double, _c.c_double, _c.c_double, _c.c_void_p, _c.c_void_p]),
+    "em2_dev_graph_compose": (_c.c_int, [_c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_void_p]),
+    "em2_graph_compose": (_c.c_int, [_c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_void_p]),
+    "em2_graph_write_svg": (_c.c_int, [_c.c_char_p, _c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p,
+                                       _c.c_void_p, _c.c_int, _c.c_double, _c.c_double, _c.c_double, _c.c_double, _c.c_double,
+                                       _c.c_double, _c.c_char_p, _c.c_uint64, _c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_char_p,
+                                       _c.c_uint64, _c.c_char_p]),
     "em2_matrix_cell_expression_counts": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.POINTER(_c.c_uint64), _c.c_void_p]),
     "em2_matrix_create_cell_set": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_void_p, _c.c_uint32]),
     "em2_matrix_create_cell_set_intersection": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p]),
@@ -1158,6 +1193,157 @@ def dev_dense_expression(d_toc, d_data, cell_count, gene_count, normalization_me
                                        global_gene_count, gene_count, int(normalization_method), row_begin, row_end, element_type,
                                        d_out.data_ptr(), pitch, d_workspace.data_ptr(), d_workspace.numel(), stream.cuda_stream))
     return d_out
+
+
+# ---- colouring and drawing a laid-out graph (include/em2_lsh.h) ----
+COLOR_NONE = 0x80000000
+COLOR_BLACK = 0x40000000
+NO_VALUE = float(np.finfo(np.float64).max)      # std::numeric_limits<double>::max(), the page's "no value"
+
+
+def _optional_ids(ids, what):
+    if ids is None:
+        return None
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    if ids.ndim != 1:
+        raise ValueError(what + " must be one-dimensional")
+    return ids
+
+
+def cell_similarities_to_cell(toc, data, gene_count, cell_id0, cell_ids, gene_local_ids=None):
+    """em2_cell_similarities_to_cell -> float64 [len(cell_ids)]: computeCellSimilarity of cell_id0 against every listed cell."""
+    toc = np.ascontiguousarray(toc, dtype=np.uint64)
+    data = np.ascontiguousarray(data, dtype=COUNT_DTYPE)
+    cell_ids = _optional_ids(cell_ids, "cell_ids")
+    local = _optional_ids(gene_local_ids, "gene_local_ids")
+    out = np.empty(len(cell_ids), dtype=np.float64)
+    check(load().em2_cell_similarities_to_cell(_ptr(toc), _ptr(data), len(toc) - 1, _ptr(local) if local is not None else None,
+                                               len(local) if local is not None else 0, gene_count, cell_id0, _ptr(cell_ids),
+                                               len(cell_ids), _ptr(out)))
+    return out
+
+
+def cell_similarities_row_in_lds(gene_count):
+    return bool(load().em2_cell_similarities_row_in_lds(gene_count))
+
+
+def gene_expression_of_cells(toc, data, gene_count, gene_id, normalization_method, cell_ids, gene_local_ids=None):
+    """em2_gene_expression_of_cells -> float32 [len(cell_ids)]: the normalized value of one gene in every listed cell."""
+    toc = np.ascontiguousarray(toc, dtype=np.uint64)
+    data = np.ascontiguousarray(data, dtype=COUNT_DTYPE)
+    cell_ids = _optional_ids(cell_ids, "cell_ids")
+    local = _optional_ids(gene_local_ids, "gene_local_ids")
+    out = np.empty(len(cell_ids), dtype=np.float32)
+    check(load().em2_gene_expression_of_cells(_ptr(toc), _ptr(data), len(toc) - 1, _ptr(local) if local is not None else None,
+                                              len(local) if local is not None else 0, gene_count, gene_id, int(normalization_method),
+                                              _ptr(cell_ids), len(cell_ids), _ptr(out)))
+    return out
+
+
+def spectral_colors(values, min_color_value=None, max_color_value=None):
+    """em2_spectral_colors -> (rgb uint32 [n], range float64 [4] = minValue, maxValue, minColorValue, maxColorValue)."""
+    values = np.ascontiguousarray(values, dtype=np.float64)
+    rgb = np.empty(len(values), dtype=np.uint32)
+    value_range = np.zeros(4, dtype=np.float64)
+    check(load().em2_spectral_colors(_ptr(values), len(values), 0. if min_color_value is None else float(min_color_value),
+                                     0. if max_color_value is None else float(max_color_value), int(min_color_value is not None),
+                                     int(max_color_value is not None), _ptr(rgb), _ptr(value_range)))
+    return rgb, value_range
+
+
+def color_strings(rgb):
+    """The page's colour string per packed colour: "" for none, "black", else "#rrggbb" from the same integers."""
+    return ["" if c & COLOR_NONE else ("black" if c & COLOR_BLACK else "#%02x%02x%02x" % ((c >> 16) & 255, (c >> 8) & 255, c & 255))
+            for c in np.asarray(rgb, dtype=np.uint32).tolist()]
+
+
+def meta_data_number(value):
+    raw = value if isinstance(value, bytes) else value.encode("utf-8", "surrogateescape")
+    number = ctypes.c_double(0.)
+    check(load().em2_meta_data_number(raw, len(raw), ctypes.byref(number)))
+    return number.value
+
+
+def graph_draw_long_edge_steps():
+    return int(load().em2_graph_draw_long_edge_steps())
+
+
+def graph_draw(x, y, edge_vertex0, edge_vertex1, size_pixels, x_view_box_center, y_view_box_center, view_box_half_size, vertex_radius,
+               hide_edges=False, vertex_top=None, edge_hits=None):
+    """em2_graph_draw -> (vertexTop, edgeHits), uint32 [S, S] each (row j, column i).  Arrays passed in are written in place."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    if x.shape != y.shape or x.ndim != 1:
+        raise ValueError("x and y must be one-dimensional and of one length")
+    v0 = np.ascontiguousarray(edge_vertex0, dtype=np.uint32)
+    v1 = np.ascontiguousarray(edge_vertex1, dtype=np.uint32)
+    if v0.shape != v1.shape or v0.ndim != 1:
+        raise ValueError("edge_vertex0 and edge_vertex1 must be one-dimensional and of one length")
+    size = int(size_pixels)
+    shape = (size, size) if 1 <= size <= 8192 else (1, 1)          # (the entry reports a size out of range)
+    if vertex_top is None:
+        vertex_top = np.zeros(shape, dtype=np.uint32)
+    if edge_hits is None:
+        edge_hits = np.zeros(shape, dtype=np.uint32)
+    for layer in (vertex_top, edge_hits):
+        if layer.dtype != np.uint32 or layer.shape != shape or not layer.flags.c_contiguous:
+            raise ValueError("a layer must be a C-contiguous uint32 [S, S] array")
+    check(load().em2_graph_draw(len(x), _ptr(x), _ptr(y), len(v0), _ptr(v0), _ptr(v1), int(bool(hide_edges)), size & 0xffffffff,
+                                float(x_view_box_center), float(y_view_box_center), float(view_box_half_size), float(vertex_radius),
+                                _ptr(vertex_top), _ptr(edge_hits)))
+    return vertex_top, edge_hits
+
+
+def graph_compose(vertex_top, edge_hits, vertex_rgb=None, edge_shade=255):
+    """em2_graph_compose -> uint8 [S, S, 4]."""
+    vertex_top = np.ascontiguousarray(vertex_top, dtype=np.uint32)
+    edge_hits = np.ascontiguousarray(edge_hits, dtype=np.uint32)
+    if vertex_top.ndim != 2 or vertex_top.shape[0] != vertex_top.shape[1] or edge_hits.shape != vertex_top.shape:
+        raise ValueError("the layers must be two [S, S] arrays")
+    if vertex_rgb is None:
+        vertex_rgb = np.zeros(int(vertex_top.max(initial=0)), dtype=np.uint32)
+    vertex_rgb = np.ascontiguousarray(vertex_rgb, dtype=np.uint32)
+    size = vertex_top.shape[0]
+    rgba = np.empty((size, size, 4), dtype=np.uint8)
+    check(load().em2_graph_compose(size, _ptr(vertex_top), _ptr(edge_hits), _ptr(vertex_rgb), len(vertex_rgb), int(edge_shade), _ptr(rgba)))
+    return rgba
+
+
+def _packed(strings):
+    return b"".join(s.encode("utf-8", "surrogateescape") + b"\0" for s in strings)
+
+
+def graph_write_svg(file_name, x, y, cell_ids, edge_vertex0, edge_vertex1, hide_edges, svg_size_pixels, x_view_box_center,
+                    y_view_box_center, view_box_half_size, vertex_radius, edge_thickness, gene_set_name, vertex_colors=None,
+                    vertex_groups=None, group_colors=None):
+    """em2_graph_write_svg: CellGraph::writeSvg into file_name.  group_colors: {group: colour}, the reference's map; empty or
+    None draws every vertex with its own colour (vertex_colors, a str per vertex, "" for none)."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    cell_ids = np.ascontiguousarray(cell_ids, dtype=np.uint32)
+    v0 = np.ascontiguousarray(edge_vertex0, dtype=np.uint32)
+    v1 = np.ascontiguousarray(edge_vertex1, dtype=np.uint32)
+    if not (len(x) == len(y) == len(cell_ids)) or len(v0) != len(v1):
+        raise ValueError("the vertex arrays, and the edge arrays, must be of one length each")
+    colors = None
+    if vertex_colors is not None:
+        if len(vertex_colors) != len(x):
+            raise ValueError("vertex_colors must hold one string per vertex")
+        colors = _packed(vertex_colors)
+    group_colors = dict(group_colors or {})
+    groups = None
+    group_ids = np.asarray(sorted(group_colors), dtype=np.int32)
+    group_strings = _packed([group_colors[g] for g in sorted(group_colors)])
+    if group_colors:
+        groups = np.ascontiguousarray(vertex_groups, dtype=np.uint32)
+        if len(groups) != len(x):
+            raise ValueError("vertex_groups must hold one group per vertex")
+    check(load().em2_graph_write_svg(os.fsencode(file_name), len(x), _ptr(x), _ptr(y), _ptr(cell_ids), len(v0), _ptr(v0), _ptr(v1),
+                                     int(bool(hide_edges)), float(svg_size_pixels), float(x_view_box_center), float(y_view_box_center),
+                                     float(view_box_half_size), float(vertex_radius), float(edge_thickness), colors,
+                                     len(colors) if colors is not None else 0, _ptr(groups) if groups is not None else None,
+                                     len(group_ids), _ptr(group_ids), group_strings, len(group_strings),
+                                     gene_set_name.encode("utf-8", "surrogateescape")))
 
 
 def apply_gene_pairs_buffer():

@@ -1122,6 +1122,62 @@ double Matrix::computeCellSimilarity(const std::string& geneSetName, uint32_t ce
     return numerator / denominator;
 }
 
+void Matrix::gatherRows(const char* who, const uint32_t* cellIds, uint32_t count, const std::vector<uint32_t>& more,
+                        std::vector<uint64_t>& toc, std::vector<em2_count>& data) const
+{
+    const uint64_t* globalToc = static_cast<const uint64_t*>(toc_.data());
+    const em2_count* globalData = static_cast<const em2_count*>(data_.data());
+    const size_t rows = size_t(count) + more.size();
+    const auto idOf = [&](size_t i) { return i < count ? cellIds[i] : more[i - count]; };
+    toc.assign(rows + 1, 0);
+    for (size_t i = 0; i < rows; i++) {
+        const uint32_t id = idOf(i);
+        if (id >= cellCount()) fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": a cell id is not below the cell count");
+        toc[i + 1] = toc[i] + (globalToc[id + 1] - globalToc[id]);
+    }
+    data.resize(toc[rows]);
+    for (size_t i = 0; i < rows; i++) {
+        const uint64_t n = toc[i + 1] - toc[i];
+        if (n) std::memcpy(data.data() + toc[i], globalData + globalToc[idOf(i)], n * sizeof(em2_count));
+    }
+}
+
+void Matrix::cellSimilaritiesToCell(const std::string& geneSetName, uint32_t cellId0, const uint32_t* cellIds, uint32_t count,
+                                    double* out) const
+{
+    const char* who = "em2_matrix_cell_similarities_to_cell";
+    const GeneSet& genes = geneSet(geneSetName);
+    if (genes.size() == 0) fail(EM2_ERROR_RUNTIME, "Gene set " + geneSetName + " is empty.");
+    if (count == 0xffffffffu) fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": too many cells");
+    std::vector<uint64_t> toc;
+    std::vector<em2_count> data;
+    gatherRows(who, cellIds, count, std::vector<uint32_t>(1, cellId0), toc, data);         // cell 0 is row `count`
+    if (count == 0) return;
+    const int rc = em2_cell_similarities_to_cell(toc.data(), data.data(), count + 1u, static_cast<const uint32_t*>(genes.localIds.data()),
+                                                 uint32_t(genes.localIds.objectCount()), genes.size(), count, nullptr, count, out);
+    if (rc != EM2_OK) fail(rc, em2_last_error());
+}
+
+void Matrix::geneExpressionOfCells(const std::string& geneSetName, uint32_t globalGeneId, int normalizationMethod, const uint32_t* cellIds,
+                                   uint32_t count, float* out) const
+{
+    const char* who = "em2_matrix_gene_expression_of_cells";
+    const GeneSet& genes = geneSet(geneSetName);
+    if (normalizationMethod < 0 || normalizationMethod > 2) fail(EM2_ERROR_RUNTIME, "Invalid normalization method.");
+    if (genes.localId(globalGeneId) == kInvalidId) {                                        // CZI_ASSERT, :821
+        fail(EM2_ERROR_RUNTIME, std::string(who) + ": Assertion failed: localGeneId != invalidGeneId (gene " + std::to_string(globalGeneId) +
+                                    " is not in gene set " + geneSetName + ")");
+    }
+    std::vector<uint64_t> toc;
+    std::vector<em2_count> data;
+    gatherRows(who, cellIds, count, std::vector<uint32_t>(), toc, data);
+    if (count == 0) return;
+    const int rc = em2_gene_expression_of_cells(toc.data(), data.data(), count, static_cast<const uint32_t*>(genes.localIds.data()),
+                                                uint32_t(genes.localIds.objectCount()), genes.size(), globalGeneId, normalizationMethod,
+                                                nullptr, count, out);
+    if (rc != EM2_OK) fail(rc, em2_last_error());
+}
+
 void Matrix::compareSimilarPairs(const std::string& similarPairsName0, const std::string& similarPairsName1,
                                  const std::string& outputDirectory) const
 {

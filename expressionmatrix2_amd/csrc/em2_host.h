@@ -131,6 +131,13 @@ public:
     void analyzeSimilarPairs(const std::string& similarPairsName, double csvDownsample, const std::string& outputDirectory) const;
     // ExpressionMatrix::computeCellSimilarity (src/ExpressionMatrix.cpp:1456-1537): global cell ids, one pair, on the host.
     double computeCellSimilarity(const std::string& geneSetName, uint32_t cellId0, uint32_t cellId1) const;
+    // The two colourings of the cell graph that are numbers per cell (src/ExpressionMatrixHttpServerGraphs.cpp:788-850), on the
+    // device: computeCellSimilarity of cellId0 against every cell of a list (em2_cell_similarities_to_cell), and the value
+    // computeExpressionVector gives one gene in every cell of a list (em2_gene_expression_of_cells).  Global ids; only the rows
+    // the call needs go to the device.  A gene outside the gene set is the reference's CZI_ASSERT (:821), EM2_ERROR_RUNTIME.
+    void cellSimilaritiesToCell(const std::string& geneSetName, uint32_t cellId0, const uint32_t* cellIds, uint32_t count, double* out) const;
+    void geneExpressionOfCells(const std::string& geneSetName, uint32_t globalGeneId, int normalizationMethod, const uint32_t* cellIds,
+                               uint32_t count, float* out) const;
     // ExpressionMatrix::compareSimilarPairs (src/ExpressionMatrixLsh.cpp:1199-1240): writes CompareSimilarPairs.csv.
     void compareSimilarPairs(const std::string& similarPairsName0, const std::string& similarPairsName1,
                              const std::string& outputDirectory) const;
@@ -246,6 +253,9 @@ public:
     const MappedFile& cellSet(const std::string& name) const;              // throws "Cell set X does not exist."
 
 private:
+    // The rows of `cellIds`, then the rows of `more`, as a CSR of their own with the global gene ids.
+    void gatherRows(const char* who, const uint32_t* cellIds, uint32_t count, const std::vector<uint32_t>& more, std::vector<uint64_t>& toc,
+                    std::vector<em2_count>& data) const;
     // Writes GeneSet-<name>-* for the genes of `from` that `keep` names (ascending local id) and opens the new set.
     void addGeneSubset(const std::string& name, const GeneSet& from, const std::vector<bool>& keep);
     // The same for ascending global ids.

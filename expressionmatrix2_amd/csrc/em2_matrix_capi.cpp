@@ -224,6 +224,20 @@ int em2_matrix_compute_cell_similarity(em2_matrix* matrix, const char* geneSetNa
     return guarded([&] { *similarity = matrix->impl->computeCellSimilarity(geneSetName, cellId0, cellId1); });
 }
 
+int em2_matrix_cell_similarities_to_cell(em2_matrix* matrix, const char* geneSetName, uint32_t cellId0, const uint32_t* cellIds, uint32_t count,
+                                         double* out)
+{
+    if (!matrix || !geneSetName || (count && (!cellIds || !out))) return nullArgument("em2_matrix_cell_similarities_to_cell");
+    return guarded([&] { matrix->impl->cellSimilaritiesToCell(geneSetName, cellId0, cellIds, count, out); });
+}
+
+int em2_matrix_gene_expression_of_cells(em2_matrix* matrix, const char* geneSetName, uint32_t globalGeneId, int normalizationMethod,
+                                        const uint32_t* cellIds, uint32_t count, float* out)
+{
+    if (!matrix || !geneSetName || (count && (!cellIds || !out))) return nullArgument("em2_matrix_gene_expression_of_cells");
+    return guarded([&] { matrix->impl->geneExpressionOfCells(geneSetName, globalGeneId, normalizationMethod, cellIds, count, out); });
+}
+
 int em2_matrix_compare_similar_pairs(em2_matrix* matrix, const char* similarPairsName0, const char* similarPairsName1,
                                      const char* outputDirectory)
 {

@@ -68,6 +68,39 @@ class CellGraphVertexInfo:
         return "CellGraphVertexInfo(cellId=%d, x=%r, y=%r)" % (self.cellId, self.position[0], self.position[1])
 
 
+# The twelve colours the page gives the twelve most frequent categories (colorPalette1, src/color.cpp:113-136).
+CATEGORY_PALETTE = ("#00ff00", "#0000ff", "#ffff00", "#ff00ff", "#00ffff", "#ff8000", "#804000", "#ffa0a0", "#308000", "#900080",
+                    "#9999ff", "#b0b0b0")
+
+
+def _rgb_of(color):
+    """0x00rrggbb of "#rrggbb"; "" (no colour) is black, as the SVG draws it.  Colour names are not parsed."""
+    if color == "":
+        return 0
+    if len(color) == 7 and color[0] == "#" and all(c in "0123456789abcdefABCDEF" for c in color[1:]):
+        return int(color[1:], 16)
+    raise ValueError("drawCellGraph(): the colour %r is not of the form #rrggbb" % (color,))
+
+
+def write_png(fileName, image):
+    """An uint8 [height, width, 4] array as an 8-bit RGBA PNG: one IDAT, every row with filter 0."""
+    import struct
+    import zlib
+    image = np.ascontiguousarray(image, dtype=np.uint8)
+    if image.ndim != 3 or image.shape[2] != 4:
+        raise ValueError("write_png(): an uint8 [height, width, 4] array is required")
+    height, width = image.shape[:2]
+    rows = np.zeros((height, 1 + width * 4), dtype=np.uint8)
+    rows[:, 1:] = image.reshape(height, width * 4)
+
+    def chunk(kind, payload):
+        return struct.pack(">I", len(payload)) + kind + payload + struct.pack(">I", zlib.crc32(kind + payload) & 0xffffffff)
+
+    with open(fileName, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", width, height, 8, 6, 0, 0, 0)) +
+                chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + chunk(b"IEND", b""))
+
+
 def _b(s):
     if not isinstance(s, str):
         raise TypeError("expected a string, got %r" % (s,))
@@ -896,6 +929,172 @@ class ExpressionMatrix:
             raise RuntimeError("Layout for graph " + graphName + " is not available.")
         x, y = g["layout"]
         return [CellGraphVertexInfo(cellId, (px, py)) for cellId, px, py in zip(g["vertexCellIds"].tolist(), x.tolist(), y.tolist())]
+
+    # ---- ExpressionMatrix::exploreCellGraph (src/ExpressionMatrixHttpServerGraphs.cpp:350-1150) without its page ----
+    def _laid_out_cell_graph(self, graphName):
+        g = self._cell_graph(graphName)
+        if "layout" not in g:
+            raise RuntimeError("Layout for graph " + graphName + " is not available.")
+        return g
+
+    def computeCellGraphColors(self, graphName, coloringOption="noColoring", geneId=None, cellId=None, metaDataName=None,
+                               metaDataMeaning="category", normalizationMethod=NormalizationMethod.L2, minColorValue=None,
+                               maxColorValue=None, reuseColors=False):
+        """The colouring of the page's request (:788-1040), stored in the graph for writeCellGraphSvg and drawCellGraph and
+        returned as a dict.  The keyword names are the page's request parameters.
+          coloringOption "byGeneExpression"  the value of gene geneId (an id or a name) in every vertex's cell, normalized over the
+                                             gene set of the graph's SimilarPairs (em2_matrix_gene_expression_of_cells, GPU);
+                         "bySimilarity"      the exact similarity of cell cellId to every vertex's cell over that gene set
+                                             (em2_matrix_cell_similarities_to_cell, GPU);
+                         "byMetaData"        by the field metaDataName, read as metaDataMeaning: "category" (a group per value,
+                                             by frequency over the graph's vertices descending, then value descending; the
+                                             twelve colours of the reference's palette, "black" from the thirteenth group
+                                             on; counted on the host), "color" (the value is the colour string) or "number"
+                                             (strtod of the whole value; what does not parse has no value and no colour);
+                         anything else       no colouring.
+        Numbers become colours on the GPU (em2_spectral_colors): red at minColorValue through yellow to green at
+        maxColorValue, which default to the smallest and largest value.
+        Returns values (float64 per vertex or None; capi.NO_VALUE is "no value"), groups (int per vertex), colors (a str per
+        vertex, "" for none; in "category" the vertex's group colour), groupColors ({group: colour}, empty unless "category"),
+        frequencyTable ([(count, value)] in group order), couldNotColor, minValue and maxValue (None unless numbers).
+        Errors in the reference's words: "Gene not found.", "Invalid cell id.".  reuseColors
+        (CellGraph::assignColorsToGroups) is not built."""
+        g = self._laid_out_cell_graph(graphName)
+        if reuseColors:
+            raise NotImplementedError("reuseColors (CellGraph::assignColorsToGroups) is not built")
+        lib = capi.load()
+        vertices = np.ascontiguousarray(g["vertexCellIds"], dtype=np.uint32)
+        n = len(vertices)
+        result = {"coloringOption": coloringOption, "values": None, "groups": np.zeros(n, dtype=np.uint32), "colors": [""] * n,
+                  "groupColors": {}, "frequencyTable": [], "couldNotColor": 0, "minValue": None, "maxValue": None, "rgb": None}
+        values = None
+        if coloringOption in ("byGeneExpression", "bySimilarity"):
+            _, _, geneSetName, _ = files.similar_pairs_info(self.directoryName, g["similarPairsName"])      # :818-819
+        if coloringOption == "byGeneExpression":
+            try:
+                gene = self._gene_id(geneId) if geneId is not None else INVALID_ID
+            except (RuntimeError, ValueError):
+                gene = INVALID_ID
+            if not 0 <= gene < INVALID_ID:
+                raise RuntimeError("Gene not found.")                                        # :790-793
+            method = int(NormalizationMethod(normalizationMethod))
+            column = np.zeros(n, dtype=np.float32)
+            capi.check(lib.em2_matrix_gene_expression_of_cells(self._handle, _b(geneSetName), gene, method, capi._ptr(vertices), n,
+                                                               capi._ptr(column)))
+            values = column.astype(np.float64)                                               # vertex.value = p.second, :829
+        elif coloringOption == "bySimilarity":
+            if cellId is None or int(cellId) < 0 or int(cellId) >= self.cellCount():
+                raise RuntimeError("Invalid cell id.")                                       # :839-842
+            values = np.zeros(n, dtype=np.float64)
+            capi.check(lib.em2_matrix_cell_similarities_to_cell(self._handle, _b(geneSetName), int(cellId), capi._ptr(vertices), n,
+                                                                capi._ptr(values)))
+        elif coloringOption == "byMetaData":
+            if metaDataName is None:
+                raise TypeError("computeCellGraphColors(): byMetaData needs metaDataName")
+            if metaDataMeaning in ("category", "color", "number"):
+                metaData = [self.getCellMetaDataValue(c, metaDataName) for c in vertices.tolist()]
+            if metaDataMeaning == "category":                                                # :863-927
+                raw = [m.encode("utf-8", "surrogateescape") for m in metaData]
+                frequency = {}
+                for m in raw:
+                    frequency[m] = frequency.get(m, 0) + 1
+                table = sorted(((count, m) for m, count in frequency.items()), reverse=True)  # std::greater<pair<int, string>>
+                groupOf = {m: group for group, (_, m) in enumerate(table)}
+                result["groups"] = np.asarray([groupOf[m] for m in raw], dtype=np.uint32)
+                result["groupColors"] = {group: (CATEGORY_PALETTE[group] if group < 12 else "black") for group in range(len(table))}
+                result["frequencyTable"] = [(count, m.decode("utf-8", "surrogateescape")) for count, m in table]
+                result["couldNotColor"] = sum(count for count, _ in table[12:])
+                result["colors"] = [result["groupColors"][group] for group in result["groups"].tolist()]
+                palette = np.asarray([int(c[1:], 16) for c in CATEGORY_PALETTE] + [capi.COLOR_BLACK], dtype=np.uint32)
+                result["rgb"] = palette[np.minimum(result["groups"], 12)]
+            elif metaDataMeaning == "color":                                                 # :935-943
+                result["colors"] = metaData
+            elif metaDataMeaning == "number":                                                # :949-964
+                parsed = {}
+                for m in metaData:
+                    if m not in parsed:
+                        parsed[m] = capi.meta_data_number(m)
+                values = np.asarray([parsed[m] for m in metaData], dtype=np.float64)
+        if values is not None:                                                               # :1003-1040
+            rgb, valueRange = capi.spectral_colors(values, minColorValue, maxColorValue)
+            result.update(values=values, rgb=rgb, colors=capi.color_strings(rgb), minValue=float(valueRange[0]),
+                          maxValue=float(valueRange[1]))
+        g["coloring"] = result
+        return {key: value for key, value in result.items() if key not in ("rgb", "coloringOption")}
+
+    def _cell_graph_view(self, g, sizePixels, xViewBoxCenter, yViewBoxCenter, viewBoxHalfSize, vertexRadius, edgeThickness):
+        """The page's defaults (:411-438): the coordinate range enlarged to a square and by 5 %, a radius of 1.5 pixels and
+        a thickness of 0.05 pixel.  CellGraph::computeCoordinateRange (src/CellGraph.cpp:270-290) is reproduced as written:
+        its maxima start at numeric_limits<double>::min(), the smallest positive normal double, not at lowest(), so a layout
+        entirely at negative x has xMax = 2.2e-308, not its largest x."""
+        x, y = g["layout"]
+        largest, tiny = float(np.finfo(np.float64).max), float(np.finfo(np.float64).tiny)
+        xMin, xMax = min([largest] + ([float(x.min())] if len(x) else [])), max([tiny] + ([float(x.max())] if len(x) else []))
+        yMin, yMax = min([largest] + ([float(y.min())] if len(y) else [])), max([tiny] + ([float(y.max())] if len(y) else []))
+        deltaX, deltaY = xMax - xMin, yMax - yMin
+        if deltaX <= deltaY:
+            delta = deltaY
+            xMax = xMin + delta
+        else:
+            delta = deltaX
+            yMax = yMin + delta
+        delta *= 1.05
+        sizePixels = float(sizePixels)
+        return (float((xMin + xMax) / 2.) if xViewBoxCenter is None else float(xViewBoxCenter),
+                float((yMin + yMax) / 2.) if yViewBoxCenter is None else float(yViewBoxCenter),
+                float(delta / 2.) if viewBoxHalfSize is None else float(viewBoxHalfSize),
+                float(1.5 * delta / sizePixels) if vertexRadius is None else float(vertexRadius),
+                float(0.05 * delta / sizePixels) if edgeThickness is None else float(edgeThickness))
+
+    def writeCellGraphSvg(self, graphName, fileName, hideEdges=False, svgSizePixels=600, xViewBoxCenter=None, yViewBoxCenter=None,
+                          viewBoxHalfSize=None, vertexRadius=None, edgeThickness=None):
+        """CellGraph::writeSvg (src/CellGraph.cpp:301-439) into fileName, byte for byte what the page embeds for the same
+        request, with the colouring computeCellGraphColors stored last (none before it was called).  The view's defaults
+        are the page's: see _cell_graph_view, which also states a quirk of the reference that is kept.  Written by the host
+        (em2_graph_write_svg); at a million vertices it is hundreds of MB of text: use drawCellGraph there."""
+        g = self._laid_out_cell_graph(graphName)
+        xc, yc, half, radius, thickness = self._cell_graph_view(g, svgSizePixels, xViewBoxCenter, yViewBoxCenter, viewBoxHalfSize,
+                                                                vertexRadius, edgeThickness)
+        coloring = g.get("coloring")
+        _, _, geneSetName, _ = files.similar_pairs_info(self.directoryName, g["similarPairsName"])
+        x, y = g["layout"]
+        v0, v1 = g["edgeVertices"]
+        capi.graph_write_svg(fileName, x, y, g["vertexCellIds"], v0, v1, hideEdges, svgSizePixels, xc, yc, half, radius, thickness,
+                             geneSetName, vertex_colors=coloring["colors"] if coloring else None,
+                             vertex_groups=coloring["groups"] if coloring else None,
+                             group_colors=coloring["groupColors"] if coloring else None)
+
+    def drawCellGraph(self, graphName, fileName=None, sizePixels=1024, edgeShade=255, hideEdges=False, xViewBoxCenter=None,
+                      yViewBoxCenter=None, viewBoxHalfSize=None, vertexRadius=None):
+        """The picture of writeCellGraphSvg as an image, rastered on the GPU (em2_graph_draw, em2_graph_compose; the
+        definition is in include/em2_lsh.h): uint8 [sizePixels, sizePixels, 4], rows from the top, r g b a.  The same view
+        parameters and defaults, sizePixels in the place of svgSizePixels.  No anti-aliasing; the edges are one-pixel lines
+        whatever the thickness (the reference's default is a hairline of 0.05 pixel), black at edgeShade=255, and with a
+        smaller edgeShade a pixel darkens with the number of edges through it.  A vertex without a colour is black, as in the
+        SVG.  With groups the vertices are painted in the SVG's order: group ascending, then vertex order.
+        A "color" value that is not #rrggbb raises ValueError naming it: colour names are not parsed (the SVG passes them on).
+        With fileName the image is also written as a PNG (zlib and struct only, filter 0)."""
+        g = self._laid_out_cell_graph(graphName)
+        xc, yc, half, radius, _ = self._cell_graph_view(g, sizePixels, xViewBoxCenter, yViewBoxCenter, viewBoxHalfSize, vertexRadius, None)
+        x, y = g["layout"]
+        v0, v1 = g["edgeVertices"]
+        coloring = g.get("coloring")
+        rgb = None
+        if coloring:
+            rgb = coloring["rgb"]
+            if rgb is None:
+                rgb = np.asarray([_rgb_of(c) for c in coloring["colors"]], dtype=np.uint32)
+            if coloring["groupColors"]:
+                order = np.argsort(coloring["groups"], kind="stable")                # the SVG's painter order
+                position = np.empty(len(order), dtype=np.uint32)
+                position[order] = np.arange(len(order), dtype=np.uint32)
+                x, y, rgb = x[order], y[order], rgb[order]
+                v0, v1 = position[v0], position[v1]
+        vertexTop, edgeHits = capi.graph_draw(x, y, v0, v1, sizePixels, xc, yc, half, radius, hideEdges)
+        image = capi.graph_compose(vertexTop, edgeHits, rgb if rgb is not None else np.zeros(len(x), dtype=np.uint32), edgeShade)
+        if fileName is not None:
+            write_png(fileName, image)
+        return image
 
     def labelPropagationClustering(self, graphName, seed=231, stableIterationCountThreshold=3, maxIterationCount=100):
         """CellGraph::labelPropagationClustering (src/CellGraph.cpp:443-612), the first step of

@@ -240,6 +240,127 @@ int em2_dense_expression(const uint64_t* toc, const em2_count* data, uint32_t cs
                          const uint32_t* geneLocalIds, uint32_t globalGeneCount, uint32_t geneCount, int normalizationMethod,
                          int elementType, void* out, uint64_t pitchElements);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Colouring and drawing a laid-out graph (ExpressionMatrix::exploreCellGraph, src/ExpressionMatrixHttpServerGraphs.cpp:350-1150,
+ * and CellGraph::writeSvg, src/CellGraph.cpp:301-439; csrc/em2_cell_values.hip, em2_draw.hip, em2_draw_host.cpp).
+ * ------------------------------------------------------------------------------------------------------
+ * Values per cell.  Both read a CSR with d_geneLocalIds as em2_dev_dense_expression does (NULL: local ids already), cellCount
+ * cells, and a list of `count` cells (d_cellIds NULL: the cells 0 .. count - 1).  A listed cell id not below cellCount, a kept
+ * gene id not below geneCount and kept ids that do not ascend within a cell are EM2_ERROR_INVALID_ARGUMENT; what out then holds
+ * is unspecified.  Both synchronise the stream.
+ *
+ * em2_dev_cell_similarities_to_cell: out[i] = ExpressionMatrix::computeCellSimilarity(geneSet, cellId0, cellIds[i])
+ * (src/ExpressionMatrix.cpp:1468-1537), the reference's double: sum01 from the float products of the genes both cells keep, in
+ * ascending gene order, widened to double; sum0, sum00, sum1, sum11 over each cell's kept entries in stored order (count * count
+ * a float product); n = geneCount; (n sum01 - sum0 sum1) / sqrt((n sum00 - sum0^2)(n sum11 - sum1^2)) with no guard, so a cell
+ * without a kept entry gives 0/0 = NaN.  Where the NaN sits is the contract; its sign and payload are the hardware's.  Presence,
+ * not the value, decides what both cells have: a stored zero, inf or NaN takes part as in the reference's merge loop.  cellId0
+ * need not be listed and is computed like any other cell where it is.  Cell 0 as a dense vector lives in LDS, or in the workspace
+ * for gene sets that do not fit (em2_cell_similarities_row_in_lds(geneCount) says which: 1 for LDS).  The workspace is
+ * em2_dev_cell_similarities_to_cell_workspace(geneCount, count) bytes.
+ *
+ * em2_dev_gene_expression_of_cells: out[i] = the value ExpressionMatrix::computeExpressionVector (:1253-1296) gives gene
+ * globalGeneId in cell cellIds[i], as the page stores it (src/ExpressionMatrixHttpServerGraphs.cpp:817-833): factor * count, a
+ * float product, with the factor of em2_dev_dense_expression over the kept entries; 0 where the cell stores nothing for the
+ * gene.  It is column localGene of em2_dev_dense_expression's EM2_DENSE_FLOAT32 matrix, NaN for a stored zero in a zero-sum cell
+ * included.  (globalGeneId is a local id where d_geneLocalIds is NULL.)  A gene outside the gene set is the reference's
+ * CZI_ASSERT at :821: EM2_ERROR_RUNTIME.  The workspace is em2_dev_gene_expression_of_cells_workspace() bytes.
+ *
+ * The forms without _dev take host buffers; the em2_matrix_ forms a gene set of the directory and global cell ids, and send only
+ * the rows they need to the device.  "Gene set X does not exist." as everywhere. */
+size_t em2_dev_cell_similarities_to_cell_workspace(uint32_t geneCount, uint32_t count);
+int em2_cell_similarities_row_in_lds(uint32_t geneCount);
+int em2_dev_cell_similarities_to_cell(const uint64_t* d_toc, const em2_count* d_data, uint32_t cellCount, const uint32_t* d_geneLocalIds,
+                                      uint32_t globalGeneCount, uint32_t geneCount, uint32_t cellId0, const uint32_t* d_cellIds,
+                                      uint32_t count, double* d_out, void* d_workspace, size_t workspaceBytes, void* stream);
+int em2_cell_similarities_to_cell(const uint64_t* toc, const em2_count* data, uint32_t cellCount, const uint32_t* geneLocalIds,
+                                  uint32_t globalGeneCount, uint32_t geneCount, uint32_t cellId0, const uint32_t* cellIds, uint32_t count,
+                                  double* out);
+size_t em2_dev_gene_expression_of_cells_workspace(void);
+int em2_dev_gene_expression_of_cells(const uint64_t* d_toc, const em2_count* d_data, uint32_t cellCount, const uint32_t* d_geneLocalIds,
+                                     uint32_t globalGeneCount, uint32_t geneCount, uint32_t globalGeneId, int normalizationMethod,
+                                     const uint32_t* d_cellIds, uint32_t count, float* d_out, void* d_workspace, size_t workspaceBytes,
+                                     void* stream);
+int em2_gene_expression_of_cells(const uint64_t* toc, const em2_count* data, uint32_t cellCount, const uint32_t* geneLocalIds,
+                                 uint32_t globalGeneCount, uint32_t geneCount, uint32_t globalGeneId, int normalizationMethod,
+                                 const uint32_t* cellIds, uint32_t count, float* out);
+
+/* Colours from numbers (src/ExpressionMatrixHttpServerGraphs.cpp:1003-1040 with spectralColor and color of src/color.cpp:13-79).
+ * minValue / maxValue are found over the values: numeric_limits<double>::max() is skipped as "no value", and a NaN never
+ * replaces a bound (std::min / std::max compare with <).  minColorValue / maxColorValue are the arguments where haveMin /
+ * haveMax say so, else minValue / maxValue.  If minValue == maxValue, or there is no value at all, every rgb is EM2_COLOR_BLACK
+ * (the page's "black").  Otherwise x = (1. / (maxColorValue - minColorValue)) * (value - minColorValue), red (x <= 0) through
+ * yellow (0.5) to green (x >= 1), clipped, int(c * 255): doubles, one rounding per operation.  A NaN value falls through every
+ * comparison and is 0x00ff00, as in the reference.  A value equal to max() is EM2_COLOR_NONE (the page leaves such a vertex the
+ * colour it had).  rgb[i] is 0x00rrggbb, or one of the two flags with zero colour bits; the string of a colour is
+ * "#%02x%02x%02x" of the same integers.  range[4] = minValue, maxValue, minColorValue, maxColorValue (max() and lowest() where
+ * there is no value; the sign of a bound that is zero is unspecified, nothing depends on it).  The workspace is
+ * em2_dev_spectral_colors_workspace() bytes.  em2_dev_spectral_colors does not synchronise. */
+#define EM2_COLOR_NONE 0x80000000u
+#define EM2_COLOR_BLACK 0x40000000u
+size_t em2_dev_spectral_colors_workspace(void);
+int em2_dev_spectral_colors(const double* d_values, uint64_t count, double minColorValue, double maxColorValue, int haveMin, int haveMax,
+                            uint32_t* d_rgb, double* d_range, void* d_workspace, size_t workspaceBytes, void* stream);
+int em2_spectral_colors(const double* values, uint64_t count, double minColorValue, double maxColorValue, int haveMin, int haveMax,
+                        uint32_t* rgb, double* range);
+
+/* The number a meta data value stands for when the page colours by it (:949-964): the whole string is given to strtod, with no
+ * leading white space allowed; anything else gives numeric_limits<double>::max(), "no value".  The reference uses
+ * boost::lexical_cast<double>: parity with Boost on exotic spellings ("inf", hexadecimal, a trailing "f") is unpinned. */
+int em2_meta_data_number(const char* value, uint64_t bytes, double* number);
+
+/* The raster of a laid-out graph: the painter's result of CellGraph::writeSvg without anti-aliasing, this project's own
+ * definition.  Any graph as plain arrays, like em2_graph_layout.  No result depends on an order between threads, and everything
+ * after one conversion of the coordinates is integer arithmetic.
+ *   S = sizePixels, 1 <= S <= 8192.  xMin = xViewBoxCenter - viewBoxHalfSize, likewise yMin; the y axis points down as SVG's does.
+ *   s256 = double(S) * 256. / (2. * viewBoxHalfSize).  Per vertex ux = floor((x - xMin) * s256) clamped to +-2^30, likewise uy; the
+ *   vertex's pixel is (ux >> 8, uy >> 8), an arithmetic shift.
+ *   Vertices: R = llround(vertexRadius * s256).  Pixel (i, j) is covered by a vertex iff (256 i + 128 - ux)^2 + (256 j + 128 - uy)^2
+ *   <= R^2 in 64-bit integers, or it is the vertex's own pixel (no vertex inside the image vanishes).  vertexTop[j * S + i] is the
+ *   largest index + 1 among the covering vertices, 0 if none: a later vertex is on top, as in the SVG, and the caller passes the
+ *   vertices in painter order.
+ *   Edges, unless hideEdges: a one-pixel line from the pixel of v0 to the pixel of v1, as stored.  The major axis is x if
+ *   |dx| >= |dy|, else y; dM and dm are the absolute extents; step k = 0 .. dM lies at major0 + sign k,
+ *   minor0 + sign floor((2 k dm + dM) / (2 dM)) (dM = 0: one pixel).  Steps outside the image are never touched.  edgeHits[p]
+ *   is the number of (edge, step) pairs that land on p.  The reference's default edge thickness is 0.05 pixel, a hairline: the
+ *   raster ignores thickness.
+ * EM2_ERROR_INVALID_ARGUMENT, and nothing is written: a position that is not finite, viewBoxHalfSize <= 0 or not finite, a radius
+ * above 256 pixels or negative, S out of range, an edge end not below vertexCount, edgeCount >= 2^32, vertexCount = 2^32 - 1.
+ * Work split: a lane per vertex for radii up to 4 pixels, a wave above; a lane per edge, and a wave for an edge with more than
+ * em2_graph_draw_long_edge_steps() steps inside the image.  The workspace is em2_dev_graph_draw_workspace(vertexCount, edgeCount)
+ * bytes.  em2_dev_graph_draw synchronises the stream.
+ *
+ * em2_dev_graph_compose: rgba[p] = white; where edgeHits > 0 the grey 255 - min(255, edgeShade * hits), edgeShade in [1, 255] (255
+ * is the SVG's black, smaller values give a density picture); where vertexTop > 0 the low 24 bits of vertexRgb[vertexTop - 1]
+ * (EM2_COLOR_NONE and EM2_COLOR_BLACK are black; vertexRgb NULL: every vertex black).  Bytes r, g, b, a = 255.  Does not
+ * synchronise.  The host form checks vertexTop against vertexCount. */
+uint32_t em2_graph_draw_long_edge_steps(void);
+size_t em2_dev_graph_draw_workspace(uint32_t vertexCount, uint64_t edgeCount);
+int em2_dev_graph_draw(uint32_t vertexCount, const double* d_x, const double* d_y, uint64_t edgeCount, const uint32_t* d_v0,
+                       const uint32_t* d_v1, int hideEdges, uint32_t sizePixels, double xViewBoxCenter, double yViewBoxCenter,
+                       double viewBoxHalfSize, double vertexRadius, uint32_t* d_vertexTop, uint32_t* d_edgeHits, void* d_workspace,
+                       size_t workspaceBytes, void* stream);
+int em2_graph_draw(uint32_t vertexCount, const double* x, const double* y, uint64_t edgeCount, const uint32_t* v0, const uint32_t* v1,
+                   int hideEdges, uint32_t sizePixels, double xViewBoxCenter, double yViewBoxCenter, double viewBoxHalfSize,
+                   double vertexRadius, uint32_t* vertexTop, uint32_t* edgeHits);
+int em2_dev_graph_compose(uint32_t sizePixels, const uint32_t* d_vertexTop, const uint32_t* d_edgeHits, const uint32_t* d_vertexRgb,
+                          uint32_t edgeShade, uint8_t* d_rgba, void* stream);
+int em2_graph_compose(uint32_t sizePixels, const uint32_t* vertexTop, const uint32_t* edgeHits, const uint32_t* vertexRgb,
+                      uint32_t vertexCount, uint32_t edgeShade, uint8_t* rgba);
+
+/* CellGraph::writeSvg (src/CellGraph.cpp:301-439) into a file, byte for byte for the same doubles and strings: the edges group
+ * first unless hideEdges (every edge "black": no edge has a colour of its own here), the xlink:href with geneSetName, ostream's
+ * default formatting (precision 6).  groupColorCount == 0 is the reference's empty groupColors map: one circle per vertex in
+ * vertex order, fill='<colour>' where vertexColors (vertexCount strings, each followed by a 0 byte; NULL: none) has a string
+ * that is not empty.  Otherwise the vertices group by group in ascending group order (vertexGroups[v]), every group in vertex
+ * order, with the colour the map (groupColorGroups[g] -> g-th string of groupColors) gives the group and "black" for a group
+ * without one.  Host only. */
+int em2_graph_write_svg(const char* fileName, uint32_t vertexCount, const double* x, const double* y, const uint32_t* cellIds,
+                        uint64_t edgeCount, const uint32_t* v0, const uint32_t* v1, int hideEdges, double svgSizePixels,
+                        double xViewBoxCenter, double yViewBoxCenter, double viewBoxHalfSize, double vertexRadius, double edgeThickness,
+                        const char* vertexColors, uint64_t vertexColorsBytes, const uint32_t* vertexGroups, uint32_t groupColorCount,
+                        const int32_t* groupColorGroups, const char* groupColors, uint64_t groupColorsBytes, const char* geneSetName);
+
 /* ExpressionMatrixSubset + Lsh + findSimilarPairs4 in one call on host buffers (SURVEY.md 8(a) row a1 on the device:
  * src/ExpressionMatrixSubset.cpp:9-42 followed by src/Lsh.cpp:118-224 and src/ExpressionMatrixLsh.cpp:200-285): the
  * global CSR (CellExpressionCounts toc/data, global gene ids) restricted to the cells cellIds[0..cellCount) (NULL =
@@ -1082,6 +1203,15 @@ int em2_matrix_analyze_similar_pairs(em2_matrix* matrix, const char* similarPair
  * the exact similarity of two cells given by GLOBAL id over the genes of a gene set.  Host code, one pair. */
 int em2_matrix_compute_cell_similarity(em2_matrix* matrix, const char* geneSetName, uint32_t cellId0, uint32_t cellId1,
                                        double* similarity);
+
+/* em2_cell_similarities_to_cell and em2_gene_expression_of_cells (above) for a gene set of the directory and GLOBAL cell ids:
+ * out[i] is the similarity of cellId0 to cellIds[i], or gene globalGeneId's value in cellIds[i].  A cell id not below the cell
+ * count: EM2_ERROR_INVALID_ARGUMENT.  "Gene set X is empty.", "Invalid normalization method." and the assertion for a gene outside
+ * the gene set: EM2_ERROR_RUNTIME. */
+int em2_matrix_cell_similarities_to_cell(em2_matrix* matrix, const char* geneSetName, uint32_t cellId0, const uint32_t* cellIds,
+                                         uint32_t count, double* out);
+int em2_matrix_gene_expression_of_cells(em2_matrix* matrix, const char* geneSetName, uint32_t globalGeneId, int normalizationMethod,
+                                        const uint32_t* cellIds, uint32_t count, float* out);
 
 /* ExpressionMatrix::compareSimilarPairs (src/ExpressionMatrixLsh.cpp:1199-1240): CompareSimilarPairs.csv in
  * outputDirectory (NULL or "": the working directory) with one line per cell whose stored count or last stored
