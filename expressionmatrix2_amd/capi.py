@@ -219,6 +219,34 @@ SYMBOLS = {
                                        _c.c_void_p, _c.c_int, _c.c_double, _c.c_double, _c.c_double, _c.c_double, _c.c_double,
                                        _c.c_double, _c.c_char_p, _c.c_uint64, _c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_char_p,
                                        _c.c_uint64, _c.c_char_p]),
+    "em2_pie_census_wave_cells": (_c.c_uint32, []),
+    "em2_pie_census_create": (_c.c_int, [_c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint32, _c.c_void_p,
+                                         _c.c_uint32, _c.POINTER(_c.c_void_p)]),
+    "em2_dev_pie_census": (_c.c_int, [_c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint32, _c.c_void_p,
+                                      _c.c_uint32, _c.POINTER(_c.c_void_p)]),
+    "em2_matrix_pie_census": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_uint32,
+                                         _c.c_char_p, _c.POINTER(_c.c_void_p)]),
+    "em2_pie_census_sizes": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_uint32), _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint32)]),
+    "em2_pie_census_get": (_c.c_int, [_c.c_void_p] * 5),
+    "em2_pie_census_values_sizes": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
+    "em2_pie_census_values_get": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "em2_pie_census_free": (None, [_c.c_void_p]),
+    "em2_order_by_count": (_c.c_int, [_c.c_void_p, _c.c_uint64, _c.c_void_p]),
+    "em2_signature_graph_random_colors": (_c.c_int, [_c.c_uint32, _c.c_void_p]),
+    "em2_graph_draw_pies_wave_radius": (_c.c_double, []),
+    "em2_dev_graph_draw_pies_workspace": (_c.c_size_t, [_c.c_uint32, _c.c_uint64]),
+    "em2_dev_graph_draw_pies": (_c.c_int, [_c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p,
+                                           _c.c_int, _c.c_uint32, _c.c_double, _c.c_double, _c.c_double, _c.c_void_p, _c.c_uint64,
+                                           _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                           _c.c_size_t, _c.c_void_p]),
+    "em2_graph_draw_pies": (_c.c_int, [_c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p,
+                                       _c.c_int, _c.c_uint32, _c.c_double, _c.c_double, _c.c_double, _c.c_void_p, _c.c_uint64,
+                                       _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "em2_pie_boundaries": (_c.c_int, [_c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "em2_signature_graph_write_svg": (_c.c_int, [_c.c_char_p, _c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64,
+                                                 _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_double, _c.c_double, _c.c_double,
+                                                 _c.c_double, _c.c_double, _c.c_double, _c.c_void_p, _c.c_char_p, _c.c_uint64,
+                                                 _c.c_void_p, _c.c_void_p]),
     "em2_matrix_cell_expression_counts": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.POINTER(_c.c_uint64), _c.c_void_p]),
     "em2_matrix_create_cell_set": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_void_p, _c.c_uint32]),
     "em2_matrix_create_cell_set_intersection": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p]),
@@ -1344,6 +1372,144 @@ def graph_write_svg(file_name, x, y, cell_ids, edge_vertex0, edge_vertex1, hide_
                                      len(colors) if colors is not None else 0, _ptr(groups) if groups is not None else None,
                                      len(group_ids), _ptr(group_ids), group_strings, len(group_strings),
                                      gene_set_name.encode("utf-8", "surrogateescape")))
+
+
+PIE_COLOR_COUNT = 13          # the colour indices of a census: the twelve of the reference's palette, then "black"
+
+
+def pie_census_wave_cells():
+    return int(load().em2_pie_census_wave_cells())
+
+
+def pie_census_take(handle):
+    """The content of an em2_pie_census as a dict, and the handle freed: sliceOffsets uint64 [V + 1], sliceColor uint8,
+    sliceCells uint32 and sliceFraction float64 per slice, waveVertexCount, and, from em2_matrix_pie_census, values (str) and
+    valueCells (int) in the order that gave the values their colours."""
+    lib = load()
+    try:
+        vertices, waves, slices = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint64(0)
+        check(lib.em2_pie_census_sizes(handle, ctypes.byref(vertices), ctypes.byref(slices), ctypes.byref(waves)))
+        out = {"sliceOffsets": np.zeros(vertices.value + 1, dtype=np.uint64), "sliceColor": np.zeros(slices.value, dtype=np.uint8),
+               "sliceCells": np.zeros(slices.value, dtype=np.uint32), "sliceFraction": np.zeros(slices.value, dtype=np.float64)}
+        check(lib.em2_pie_census_get(handle, *[_ptr(out[key]) for key in ("sliceOffsets", "sliceColor", "sliceCells", "sliceFraction")]))
+        out["waveVertexCount"] = waves.value
+        count, size = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        check(lib.em2_pie_census_values_sizes(handle, ctypes.byref(count), ctypes.byref(size)))
+        raw, cells = ctypes.create_string_buffer(max(1, size.value)), np.zeros(count.value, dtype=np.uint64)
+        check(lib.em2_pie_census_values_get(handle, raw, _ptr(cells)))
+        out["values"] = [v.decode("utf-8", "surrogateescape") for v in raw.raw[:size.value].split(b"\0")[:count.value]]
+        out["valueCells"] = cells.tolist()
+    finally:
+        lib.em2_pie_census_free(handle)
+    return out
+
+
+def _pie_census_arrays(cell_offsets, cells, id_of_cell, color_of_value):
+    cell_offsets = np.ascontiguousarray(cell_offsets, dtype=np.uint64)
+    if cell_offsets.ndim != 1 or len(cell_offsets) < 1:
+        raise ValueError("cell_offsets must hold vertexCount + 1 offsets")
+    return (cell_offsets, np.ascontiguousarray(cells, dtype=np.uint32), np.ascontiguousarray(id_of_cell, dtype=np.uint32),
+            np.ascontiguousarray(color_of_value, dtype=np.uint8))
+
+
+def pie_census(cell_offsets, cells, id_of_cell, color_of_value):
+    """em2_pie_census_create on host arrays -> the dict of pie_census_take."""
+    cell_offsets, cells, id_of_cell, color_of_value = _pie_census_arrays(cell_offsets, cells, id_of_cell, color_of_value)
+    handle = ctypes.c_void_p(None)
+    check(load().em2_pie_census_create(len(cell_offsets) - 1, _ptr(cell_offsets), _ptr(cells), len(cells), _ptr(id_of_cell), len(id_of_cell),
+                                       _ptr(color_of_value), len(color_of_value), ctypes.byref(handle)))
+    return pie_census_take(handle)
+
+
+def order_by_count(counts):
+    """em2_order_by_count: the indices as std::sort leaves (index, count) under OrderPairsBySecondGreater, uint32."""
+    counts = np.ascontiguousarray(counts, dtype=np.uint64)
+    order = np.zeros(len(counts), dtype=np.uint32)
+    check(load().em2_order_by_count(_ptr(counts), len(counts), _ptr(order)))
+    return order
+
+
+def signature_graph_random_colors(vertex_count):
+    """em2_signature_graph_random_colors: colorRandom's colour per vertex as 0x00rrggbb, uint32."""
+    rgb = np.zeros(int(vertex_count), dtype=np.uint32)
+    check(load().em2_signature_graph_random_colors(len(rgb), _ptr(rgb)))
+    return rgb
+
+
+def pie_boundaries(slice_offsets, slice_fraction):
+    """em2_pie_boundaries -> (boundaryX int32, boundaryY int32, largeArc uint8), one per slice."""
+    slice_offsets = np.ascontiguousarray(slice_offsets, dtype=np.uint64)
+    slice_fraction = np.ascontiguousarray(slice_fraction, dtype=np.float64)
+    if len(slice_offsets) < 1 or int(slice_offsets[-1]) != len(slice_fraction):
+        raise ValueError("slice_offsets must end at the number of slices")
+    bx, by = np.zeros(len(slice_fraction), dtype=np.int32), np.zeros(len(slice_fraction), dtype=np.int32)
+    arc = np.zeros(len(slice_fraction), dtype=np.uint8)
+    check(load().em2_pie_boundaries(len(slice_offsets) - 1, _ptr(slice_offsets), _ptr(slice_fraction), _ptr(bx), _ptr(by), _ptr(arc)))
+    return bx, by, arc
+
+
+def graph_draw_pies_wave_radius():
+    return float(load().em2_graph_draw_pies_wave_radius())
+
+
+def graph_draw_pies(x, y, radius, edge_vertex0, edge_vertex1, size_pixels, x_view_box_center, y_view_box_center, view_box_half_size,
+                    slice_offsets, boundary_x, boundary_y, large_arc, hide_edges=False, vertex_top=None, slice_top=None, edge_hits=None):
+    """em2_graph_draw_pies -> (vertexTop, sliceTop, edgeHits), uint32 [S, S] each (row j, column i).  Arrays passed in are written
+    in place."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    radius = np.ascontiguousarray(radius, dtype=np.float64)
+    if not (x.shape == y.shape == radius.shape) or x.ndim != 1:
+        raise ValueError("x, y and radius must be one-dimensional and of one length")
+    v0 = np.ascontiguousarray(edge_vertex0, dtype=np.uint32)
+    v1 = np.ascontiguousarray(edge_vertex1, dtype=np.uint32)
+    if v0.shape != v1.shape or v0.ndim != 1:
+        raise ValueError("edge_vertex0 and edge_vertex1 must be one-dimensional and of one length")
+    slice_offsets = np.ascontiguousarray(slice_offsets, dtype=np.uint64)
+    bx = np.ascontiguousarray(boundary_x, dtype=np.int32)
+    by = np.ascontiguousarray(boundary_y, dtype=np.int32)
+    arc = np.ascontiguousarray(large_arc, dtype=np.uint8)
+    if len(slice_offsets) != len(x) + 1 or not (bx.shape == by.shape == arc.shape) or bx.ndim != 1:
+        raise ValueError("slice_offsets must hold vertexCount + 1 offsets, and the three slice arrays must be of one length")
+    size = int(size_pixels)
+    shape = (size, size) if 1 <= size <= 8192 else (1, 1)          # (the entry reports a size out of range)
+    layers = [np.zeros(shape, dtype=np.uint32) if layer is None else layer for layer in (vertex_top, slice_top, edge_hits)]
+    for layer in layers:
+        if layer.dtype != np.uint32 or layer.shape != shape or not layer.flags.c_contiguous:
+            raise ValueError("a layer must be a C-contiguous uint32 [S, S] array")
+    check(load().em2_graph_draw_pies(len(x), _ptr(x), _ptr(y), _ptr(radius), len(v0), _ptr(v0), _ptr(v1), int(bool(hide_edges)),
+                                     size & 0xffffffff, float(x_view_box_center), float(y_view_box_center), float(view_box_half_size),
+                                     _ptr(slice_offsets), len(bx), _ptr(bx), _ptr(by), _ptr(arc), *[_ptr(layer) for layer in layers]))
+    return tuple(layers)
+
+
+def signature_graph_write_svg(file_name, x, y, cell_counts, edge_vertex0, edge_vertex1, hide_edges=False, svg_size_pixels=500., x_shift=0.,
+                              y_shift=0., zoom_factor=1., vertex_size_factor=1., edge_thickness_factor=1., slice_offsets=None,
+                              slice_colors=None, slice_fraction=None):
+    """em2_signature_graph_write_svg: SignatureGraph::writeSvg into file_name -> (xCenter, yCenter, halfViewBoxSize, pixelSize).
+    slice_offsets None: every vertex is the black circle; else slice_colors holds a str and slice_fraction a float per slice."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    cell_counts = np.ascontiguousarray(cell_counts, dtype=np.uint64)
+    v0 = np.ascontiguousarray(edge_vertex0, dtype=np.uint32)
+    v1 = np.ascontiguousarray(edge_vertex1, dtype=np.uint32)
+    if not (len(x) == len(y) == len(cell_counts)) or len(v0) != len(v1):
+        raise ValueError("the vertex arrays, and the edge arrays, must be of one length each")
+    offsets = fraction = colors = None
+    if slice_offsets is not None:
+        offsets = np.ascontiguousarray(slice_offsets, dtype=np.uint64)
+        fraction = np.ascontiguousarray(slice_fraction, dtype=np.float64)
+        if len(offsets) != len(x) + 1 or len(slice_colors) != len(fraction):
+            raise ValueError("slice_offsets must hold vertexCount + 1 offsets, slice_colors and slice_fraction one entry per slice")
+        colors = _packed(slice_colors)
+    parameters = np.zeros(4, dtype=np.float64)
+    check(load().em2_signature_graph_write_svg(os.fsencode(file_name), len(x), _ptr(x), _ptr(y), _ptr(cell_counts), len(v0), _ptr(v0),
+                                               _ptr(v1), int(bool(hide_edges)), float(svg_size_pixels), float(x_shift), float(y_shift),
+                                               float(zoom_factor), float(vertex_size_factor), float(edge_thickness_factor),
+                                               _ptr(offsets) if offsets is not None else None, colors,
+                                               len(colors) if colors is not None else 0,
+                                               _ptr(fraction) if fraction is not None else None, _ptr(parameters)))
+    return tuple(parameters.tolist())
 
 
 def apply_gene_pairs_buffer():

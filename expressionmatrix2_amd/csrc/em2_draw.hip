@@ -16,8 +16,10 @@
 // Maximum and integer addition do not depend on the order of their operands, so no result depends on how the threads run; the
 // order of the long edges' list does, and nothing reads it but the kernel that draws every member.
 // The layers stay where the atomics are done, in the L2 (4 S^2 bytes each); no tile is staged in LDS.
+// The view, the prepare kernel and the edge layer are also the raster with pies' (em2_pie.hip), through em2_draw.h.
 
 #include "em2_device.h"
+#include "em2_draw.h"
 #include "em2_entry.h"
 #include "em2_hip_util.h"
 
@@ -31,12 +33,8 @@ namespace {
 constexpr uint32_t kColorBlocks = 1024;
 constexpr uint32_t kLongEdgeSteps = 64;            // an edge with more steps inside the image gets a wave
 constexpr int64_t kWideRadius = 4 * 256;           // a radius above 4 pixels gets a wave per vertex
-constexpr uint32_t kMaxSizePixels = 8192;
 constexpr double kMaxRadiusPixels = 256.;
 constexpr int32_t kClamp = 1 << 30;
-
-constexpr uint32_t kBadPosition = 1u;
-constexpr uint32_t kBadEdge = 2u;
 
 // std::min(a, b) and std::max(a, b) as the page calls them: b only if it compares below (above) a.
 __device__ __forceinline__ double minOf(double a, double b) { return b < a ? b : a; }
@@ -133,12 +131,6 @@ spectralColorsKernel(const double* __restrict__ values, uint64_t count, const do
         rgb[i] = (r << 16) | (g << 8);
     }
 }
-
-struct DrawView {
-    double xMin, yMin, s256;
-    int32_t size;
-    int64_t radius;                // R, in 1/256 pixel
-};
 
 __device__ __forceinline__ int32_t toSubpixel(double position, double origin, double s256)
 {
@@ -353,10 +345,10 @@ size_t graphDrawWorkspaceBytes(uint32_t vertexCount, uint64_t edgeCount)
     return 256u + 2u * alignUp(size_t(vertexCount) * sizeof(int32_t)) + alignUp(size_t(edgeCount) * sizeof(uint32_t));
 }
 
-// *inputError: the prepare kernel's word; the outputs are untouched where it is not zero.
-hipError_t runGraphDraw(uint32_t vertexCount, const double* d_x, const double* d_y, uint64_t edgeCount, const uint32_t* d_v0,
-                        const uint32_t* d_v1, bool hideEdges, const DrawView& view, uint32_t* d_vertexTop, uint32_t* d_edgeHits,
-                        void* workspace, uint32_t* inputError, hipStream_t stream)
+hipError_t runGraphDrawBase(uint32_t vertexCount, const double* d_x, const double* d_y, uint64_t edgeCount, const uint32_t* d_v0,
+                            const uint32_t* d_v1, bool hideEdges, const DrawView& view, uint32_t* d_vertexTop, uint32_t* d_edgeHits,
+                            void* workspace, uint32_t* inputError, const int32_t** uxOut, const int32_t** uyOut, StageTimer& timer,
+                            hipStream_t stream)
 {
     char* at = static_cast<char*>(workspace);
     uint32_t* error = reinterpret_cast<uint32_t*>(at);
@@ -367,7 +359,8 @@ hipError_t runGraphDraw(uint32_t vertexCount, const double* d_x, const double* d
     int32_t* uy = reinterpret_cast<int32_t*>(at);
     at += alignUp(size_t(vertexCount) * sizeof(int32_t));
     uint32_t* longEdges = reinterpret_cast<uint32_t*>(at);
-    StageTimer timer("graphDraw");
+    *uxOut = ux;
+    *uyOut = uy;
     EM2_TRY(hipMemsetAsync(error, 0, 256, stream));
     const uint64_t larger = vertexCount > edgeCount ? vertexCount : edgeCount;
     drawPrepareKernel<<<dim3(gridFor(larger)), dim3(256), 0, stream>>>(vertexCount, d_x, d_y, edgeCount, d_v0, d_v1, view, ux, uy, error);
@@ -390,6 +383,19 @@ hipError_t runGraphDraw(uint32_t vertexCount, const double* d_x, const double* d
         EM2_TRY(hipGetLastError());
         EM2_TRY(timer.stage("edges", stream));
     }
+    return hipSuccess;
+}
+
+// *inputError: the prepare kernel's word; the outputs are untouched where it is not zero.
+hipError_t runGraphDraw(uint32_t vertexCount, const double* d_x, const double* d_y, uint64_t edgeCount, const uint32_t* d_v0,
+                        const uint32_t* d_v1, bool hideEdges, const DrawView& view, uint32_t* d_vertexTop, uint32_t* d_edgeHits,
+                        void* workspace, uint32_t* inputError, hipStream_t stream)
+{
+    StageTimer timer("graphDraw");
+    const int32_t *ux = nullptr, *uy = nullptr;
+    EM2_TRY(runGraphDrawBase(vertexCount, d_x, d_y, edgeCount, d_v0, d_v1, hideEdges, view, d_vertexTop, d_edgeHits, workspace, inputError,
+                             &ux, &uy, timer, stream));
+    if (*inputError) return hipSuccess;
     if (vertexCount) {
         const uint32_t lanes = view.radius > kWideRadius ? 64u : 1u;
         drawVerticesKernel<<<dim3(gridFor(uint64_t(vertexCount) * lanes)), dim3(256), 0, stream>>>(vertexCount, ux, uy, view, lanes, d_vertexTop);
@@ -446,9 +452,9 @@ uint32_t em2_graph_draw_long_edge_steps(void) { return em2::kLongEdgeSteps; }
 
 size_t em2_dev_graph_draw_workspace(uint32_t vertexCount, uint64_t edgeCount) { return em2::graphDrawWorkspaceBytes(vertexCount, edgeCount); }
 
-// The checks that need no device, and the view as the kernels take it.
-static int drawView(const char* who, uint32_t vertexCount, uint64_t edgeCount, uint32_t sizePixels, double xViewBoxCenter, double yViewBoxCenter,
-                    double viewBoxHalfSize, double vertexRadius, em2::DrawView& view)
+// The checks that need no device, and the view as the kernels take it (em2_draw.h: em2_pie.hip shares it).
+extern "C++" int em2::drawViewOf(const char* who, uint32_t vertexCount, uint64_t edgeCount, uint32_t sizePixels, double xViewBoxCenter,
+                    double yViewBoxCenter, double viewBoxHalfSize, em2::DrawView& view)
 {
     if (sizePixels < 1 || sizePixels > em2::kMaxSizePixels) return failArgument(who, "sizePixels must be in [1, 8192]");
     if (vertexCount == 0xffffffffu) return failArgument(who, "vertexCount must be below 2^32 - 1");
@@ -462,6 +468,15 @@ static int drawView(const char* who, uint32_t vertexCount, uint64_t edgeCount, u
     if (!std::isfinite(view.xMin) || !std::isfinite(view.yMin) || !std::isfinite(view.s256)) {
         return failArgument(who, "the view box does not convert to pixels");
     }
+    view.radius = 0;
+    return EM2_OK;
+}
+
+static int drawView(const char* who, uint32_t vertexCount, uint64_t edgeCount, uint32_t sizePixels, double xViewBoxCenter, double yViewBoxCenter,
+                    double viewBoxHalfSize, double vertexRadius, em2::DrawView& view)
+{
+    const int rc = em2::drawViewOf(who, vertexCount, edgeCount, sizePixels, xViewBoxCenter, yViewBoxCenter, viewBoxHalfSize, view);
+    if (rc != EM2_OK) return rc;
     const double radius = vertexRadius * view.s256;                    // in 1/256 pixel
     if (!(radius >= 0.) || radius > em2::kMaxRadiusPixels * 256.) return failArgument(who, "vertexRadius must be between 0 and 256 pixels");
     view.radius = std::llround(radius);

@@ -216,6 +216,10 @@ public:
                        MetaDataTable& out) const;
     void computeMetaDataRandIndex(const std::string& cellSetName, const std::string& metaDataName0, const std::string& metaDataName1,
                                   double& randIndex, double& adjustedRandIndex) const;
+    // colorByMetaDataInterpretedAsCategory (src/ExpressionMatrixSignatureGraph.cpp:198-264) for vertices that hold ids into
+    // globalCellIds (em2_pie_host.cpp; include/em2_lsh.h says what runs where).  The caller frees *census.
+    void pieCensus(uint32_t vertexCount, const uint64_t* cellOffsets, const uint32_t* cells, uint64_t cellCount,
+                   const uint32_t* globalCellIds, uint32_t cellSetSize, const std::string& metaDataName, em2_pie_census** census) const;
     void flush();
 
     // Ingest (em2_ingest_host.cpp; the files are in em2_ingest.h).  create is ExpressionMatrix::createNew

@@ -659,6 +659,18 @@ int em2_meta_data_table_get(const em2_meta_data_table* table, char* values0, uin
 
 void em2_meta_data_table_free(em2_meta_data_table* table) { delete table; }
 
+int em2_matrix_pie_census(em2_matrix* matrix, uint32_t vertexCount, const uint64_t* cellOffsets, const uint32_t* cells, uint64_t cellCount,
+                          const uint32_t* globalCellIds, uint32_t cellSetSize, const char* metaDataName, em2_pie_census** census)
+{
+    if (!matrix || !metaDataName || !census || (vertexCount && !cellOffsets) || (cellCount && !cells) || (cellSetSize && !globalCellIds)) {
+        return nullArgument("em2_matrix_pie_census");
+    }
+    *census = nullptr;
+    return guarded([&] {
+        matrix->impl->pieCensus(vertexCount, cellOffsets, cells, cellCount, globalCellIds, cellSetSize, metaDataName, census);
+    });
+}
+
 int em2_rand_index(uint64_t sumCells, uint64_t sumRows, uint64_t sumColumns, uint64_t n, double* randIndex, double* adjustedRandIndex)
 {
     if (!randIndex || !adjustedRandIndex) return nullArgument("em2_rand_index");

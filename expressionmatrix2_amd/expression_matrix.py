@@ -82,6 +82,15 @@ def _rgb_of(color):
     raise ValueError("drawCellGraph(): the colour %r is not of the form #rrggbb" % (color,))
 
 
+def _slice_rgb_of(color):
+    """0x00rrggbb of a slice's colour string: "#rrggbb", or "black"."""
+    if color == "black":
+        return 0
+    if len(color) == 7 and color[0] == "#" and all(c in "0123456789abcdefABCDEF" for c in color[1:]):
+        return int(color[1:], 16)
+    raise ValueError("drawSignatureGraph(): the colour %r is neither of the form #rrggbb nor black" % (color,))
+
+
 def write_png(fileName, image):
     """An uint8 [height, width, 4] array as an 8-bit RGBA PNG: one IDAT, every row with filter 0."""
     import struct
@@ -495,6 +504,158 @@ class ExpressionMatrix:
         """(vertex 0, vertex 1) per edge, uint32, in the order SignatureGraph::createEdges adds them; vertex 1 > vertex 0."""
         g = self._signature_graph(signatureGraphName)
         return g["edgeVertex0"].copy(), g["edgeVertex1"].copy()
+
+    # ---- SignatureGraph::computeLayout, the colourings and SignatureGraph::writeSvg (src/SignatureGraph.cpp:105-321,
+    # src/ExpressionMatrixSignatureGraph.cpp:163-278, src/ExpressionMatrixHttpServerSignatureGraphs.cpp:45-95) without the page ----
+    def computeSignatureGraphLayout(self, signatureGraphName, seed=231, maxIterationCount=300, tolerance=0.01, gravity=0.02,
+                                    repulsion="exact", levels="single"):
+        """SignatureGraph::computeLayout (src/SignatureGraph.cpp:105-171).  The reference runs Graphviz's sfdp; here the layout
+        entries of computeCellGraphLayout run over the graph's edges, with the same arguments, the same meaning and the same
+        validation (em2_graph_layout, em2_graph_layout_pyramid, em2_graph_layout_multilevel).  The reference also hands sfdp a
+        width per vertex and a weight per edge (computed from source(e) twice, :93-97); neither enters this force model.
+        Computed once per graph, like the reference's layoutWasComputed: a second call does nothing."""
+        if repulsion not in ("exact", "pyramid"):
+            raise ValueError('repulsion must be "exact" or "pyramid", not %r' % (repulsion,))
+        if levels not in ("single", "multi"):
+            raise ValueError('levels must be "single" or "multi", not %r' % (levels,))
+        g = self._signature_graph(signatureGraphName)
+        if "layout" in g:
+            return
+        vertexCount = len(g["cellOffsets"]) - 1
+        v0, v1 = g["edgeVertex0"], g["edgeVertex1"]
+        parameters = capi.LayoutParameters(seed=seed, maxIterationCount=maxIterationCount, tolerance=tolerance, gravity=gravity)
+        if levels == "multi":
+            depth = capi.LAYOUT_DEPTH_EXACT if repulsion == "exact" else capi.LAYOUT_DEPTH_AUTO
+            x, y = capi.graph_layout_multilevel(vertexCount, v0, v1, parameters, depth)[:2]
+        else:
+            layout = capi.graph_layout if repulsion == "exact" else capi.graph_layout_pyramid
+            x, y, _, _, _ = layout(vertexCount, v0, v1, parameters)
+        g["layout"] = (x.astype(np.float64), y.astype(np.float64))
+
+    def _laid_out_signature_graph(self, signatureGraphName):
+        g = self._signature_graph(signatureGraphName)
+        if "layout" not in g:
+            raise RuntimeError("Layout for signature graph " + signatureGraphName + " is not available.")
+        return g
+
+    def getSignatureGraphLayout(self, signatureGraphName):
+        """(x, y) of the vertices, float64 copies, in vertex order."""
+        x, y = self._laid_out_signature_graph(signatureGraphName)["layout"]
+        return x.copy(), y.copy()
+
+    def computeSignatureGraphColors(self, signatureGraphName, coloringOption="random", metaDataName=None, metaDataMeaning="category"):
+        """The colouring of the page's request (src/ExpressionMatrixHttpServerSignatureGraphs.cpp:81-94), stored with the graph
+        for writeSignatureGraphSvg and drawSignatureGraph and returned as a dict: every vertex gets a list of (colour,
+        fraction), its slices.
+          coloringOption "byMetaData"  by the field metaDataName; metaDataMeaning "category" (colorByMetaDataInterpretedAsCategory:
+                                       the values by their cells over the graph's vertices, the twelve colours of the palette
+                                       and "black" from the thirteenth value on; per vertex the cells of each colour, counted
+                                       on the GPU: em2_matrix_pie_census); "color" and "number" raise the reference's
+                                       "... is not implemented.";
+                         "random"      colorRandom: a colour per vertex from std::mt19937(231);
+                         anything else colorBlack.
+        Returns sliceOffsets (uint64 [vertices + 1]), sliceCells (uint32), sliceFraction (float64) and colors (a str) per slice,
+        sliceColor (the colour index 0 .. 12 per slice, "category" only, else None) and valueTable ([(value, cells, colour)] in
+        the reference's sorted order, "category" only, else [])."""
+        g = self._signature_graph(signatureGraphName)
+        cellOffsets = np.ascontiguousarray(g["cellOffsets"], dtype=np.uint64)
+        vertexCount = len(cellOffsets) - 1
+        whole = {"sliceOffsets": np.arange(vertexCount + 1, dtype=np.uint64), "sliceColor": None,
+                 "sliceCells": np.diff(cellOffsets).astype(np.uint32), "sliceFraction": np.ones(vertexCount, dtype=np.float64),
+                 "valueTable": []}
+        if coloringOption == "byMetaData":
+            if metaDataMeaning == "number":
+                raise RuntimeError("Signature graph coloring by meta data interpreted as number is not implemented.")      # :277
+            if metaDataMeaning == "color":
+                raise RuntimeError("Signature graph coloring by meta data interpreted as color is not implemented.")       # :270
+            if metaDataName is None:
+                raise TypeError("computeSignatureGraphColors(): byMetaData needs metaDataName")
+            cells = np.ascontiguousarray(g["cells"], dtype=np.uint32)
+            cellSet = np.ascontiguousarray(g["cellSet"], dtype=np.uint32)
+            handle = ctypes.c_void_p(None)
+            capi.check(capi.load().em2_matrix_pie_census(self._handle, vertexCount, capi._ptr(cellOffsets), capi._ptr(cells), len(cells),
+                                                         capi._ptr(cellSet), len(cellSet), _b(metaDataName), ctypes.byref(handle)))
+            census = capi.pie_census_take(handle)
+            palette = CATEGORY_PALETTE + ("black",)
+            result = {key: census[key] for key in ("sliceOffsets", "sliceColor", "sliceCells", "sliceFraction")}
+            result["colors"] = [palette[index] for index in census["sliceColor"].tolist()]
+            result["valueTable"] = [(value, count, palette[min(rank, 12)])
+                                    for rank, (value, count) in enumerate(zip(census["values"], census["valueCells"]))]
+        elif coloringOption == "random":
+            result = dict(whole, colors=capi.color_strings(capi.signature_graph_random_colors(vertexCount)))
+        else:
+            result = dict(whole, colors=["black"] * vertexCount)
+        g["coloring"] = result
+        return dict(result)
+
+    @staticmethod
+    def _signature_graph_view(g, xShift, yShift, zoomFactor):
+        """SignatureGraph::writeSvg's view (src/SignatureGraph.cpp:194-229), as written: like CellGraph's, the maxima start at
+        numeric_limits<double>::min() (see _cell_graph_view).  -> xCenter, yCenter, halfViewBoxSize, boundingBoxSize."""
+        x, y = g["layout"]
+        largest, tiny = float(np.finfo(np.float64).max), float(np.finfo(np.float64).tiny)
+        xMin, xMax = min([largest] + ([float(x.min())] if len(x) else [])), max([tiny] + ([float(x.max())] if len(x) else []))
+        yMin, yMax = min([largest] + ([float(y.min())] if len(y) else [])), max([tiny] + ([float(y.max())] if len(y) else []))
+        boundingBoxSize = max(xMax - xMin, yMax - yMin)
+        viewBoxSize = 1.05 * boundingBoxSize / float(zoomFactor)
+        return (xMin + xMax) / 2. - float(xShift), (yMin + yMax) / 2. - float(yShift), viewBoxSize / 2., boundingBoxSize
+
+    def writeSignatureGraphSvg(self, signatureGraphName, fileName, hideEdges=False, svgSizePixels=500, xShift=0., yShift=0.,
+                               zoomFactor=1., vertexSizeFactor=1., edgeThicknessFactor=1.):
+        """SignatureGraph::writeSvg (src/SignatureGraph.cpp:183-321) into fileName, byte for byte, with the colouring
+        computeSignatureGraphColors stored last; before any, every vertex is the black circle that the reference's
+        createSignatureGraph writes into SignatureGraph.svg.  The arguments are SvgParameters' (src/SignatureGraph.hpp:84-100).
+        A vertex is a circle whose area follows its cell count, a pie chart where it has several colours; the vertices are
+        written by decreasing cell count, in std::sort's order.  Written by the host (em2_signature_graph_write_svg).
+        Returns the four fields the reference fills in: {"xCenter", "yCenter", "halfViewBoxSize", "pixelSize"}."""
+        g = self._laid_out_signature_graph(signatureGraphName)
+        x, y = g["layout"]
+        coloring = g.get("coloring")
+        parameters = capi.signature_graph_write_svg(
+            fileName, x, y, np.diff(g["cellOffsets"]), g["edgeVertex0"], g["edgeVertex1"], hideEdges, svgSizePixels, xShift, yShift,
+            zoomFactor, vertexSizeFactor, edgeThicknessFactor, slice_offsets=coloring["sliceOffsets"] if coloring else None,
+            slice_colors=coloring["colors"] if coloring else None, slice_fraction=coloring["sliceFraction"] if coloring else None)
+        return dict(zip(("xCenter", "yCenter", "halfViewBoxSize", "pixelSize"), parameters))
+
+    def drawSignatureGraph(self, signatureGraphName, fileName=None, sizePixels=1024, edgeShade=255, hideEdges=False, xShift=0.,
+                           yShift=0., zoomFactor=1., vertexSizeFactor=1.):
+        """The picture of writeSignatureGraphSvg as an image, rastered on the GPU (em2_graph_draw_pies, em2_graph_compose; the
+        definition is in include/em2_lsh.h): uint8 [sizePixels, sizePixels, 4], rows from the top, r g b a.  The view is the
+        SVG's with sizePixels in the place of svgSizePixels; a vertex has the SVG's radius, vertexSizeFactor * (0.03 *
+        boundingBoxSize * sqrt(cells / most cells)), and the vertices are painted in the SVG's order.  The slice boundaries
+        come from the SVG's angles (em2_pie_boundaries).  No anti-aliasing; the edges are one-pixel lines as in drawCellGraph.
+        Before any colouring every vertex is black.  A colour that is neither #rrggbb nor "black" raises ValueError.
+        With fileName the image is also written as a PNG."""
+        g = self._laid_out_signature_graph(signatureGraphName)
+        x, y = g["layout"]
+        xc, yc, half, boundingBoxSize = self._signature_graph_view(g, xShift, yShift, zoomFactor)
+        cellCounts = np.diff(np.ascontiguousarray(g["cellOffsets"], dtype=np.uint64))
+        vertexCount = len(cellCounts)
+        coloring = g.get("coloring")
+        if coloring:
+            offsets, fraction = coloring["sliceOffsets"].astype(np.int64), coloring["sliceFraction"]
+            rgb = np.asarray([_slice_rgb_of(c) for c in coloring["colors"]], dtype=np.uint32)
+        else:
+            offsets, fraction, rgb = np.arange(vertexCount + 1, dtype=np.int64), np.ones(vertexCount), np.zeros(vertexCount, dtype=np.uint32)
+        if (np.diff(offsets) < 1).any():
+            raise RuntimeError("drawSignatureGraph(): a vertex of signature graph " + signatureGraphName + " has no cell")
+        largest = float(np.uint32(cellCounts.max(initial=0)))
+        with np.errstate(all="ignore"):
+            radius = float(vertexSizeFactor) * (0.03 * boundingBoxSize * np.sqrt(cellCounts.astype(np.uint32).astype(np.float64) / largest))
+        # the SVG's painter order: sortedVertices
+        order = capi.order_by_count(cellCounts)
+        position = np.empty(vertexCount, dtype=np.uint32)
+        position[order] = np.arange(vertexCount, dtype=np.uint32)
+        sliceCounts = np.diff(offsets)[order]
+        newOffsets = np.concatenate([[0], np.cumsum(sliceCounts)]).astype(np.int64)
+        gather = np.repeat(offsets[:-1][order] - newOffsets[:-1], sliceCounts) + np.arange(int(newOffsets[-1]), dtype=np.int64)
+        bx, by, arc = capi.pie_boundaries(newOffsets, fraction[gather])
+        _, sliceTop, edgeHits = capi.graph_draw_pies(x[order], y[order], radius[order], position[g["edgeVertex0"]], position[g["edgeVertex1"]],
+                                                     sizePixels, xc, yc, half, newOffsets, bx, by, arc, hideEdges)
+        image = capi.graph_compose(sliceTop, edgeHits, rgb[gather], edgeShade)
+        if fileName is not None:
+            write_png(fileName, image)
+        return image
 
     # ---- src/PythonModule.cpp:1137-1161 ----
     def createGeneGraph(self, geneGraphName=_REQUIRED, geneSetName="AllGenes", similarGenePairsName=_REQUIRED, k=_REQUIRED,

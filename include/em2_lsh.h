@@ -361,6 +361,119 @@ int em2_graph_write_svg(const char* fileName, uint32_t vertexCount, const double
                         const char* vertexColors, uint64_t vertexColorsBytes, const uint32_t* vertexGroups, uint32_t groupColorCount,
                         const int32_t* groupColorGroups, const char* groupColors, uint64_t groupColorsBytes, const char* geneSetName);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Colouring and drawing the signature graph: pie vertices (ExpressionMatrix::colorBlack, colorRandom and
+ * colorByMetaDataInterpretedAsCategory, src/ExpressionMatrixSignatureGraph.cpp:163-278, and SignatureGraph::writeSvg,
+ * src/SignatureGraph.cpp:183-321; csrc/em2_pie.hip, em2_pie_host.cpp).
+ * ------------------------------------------------------------------------------------------------------
+ * The colour census.  A vertex owns the cells cells[cellOffsets[v] .. cellOffsets[v + 1]) (ids into a cell set of cellSetSize
+ * cells, as em2_signature_graph_get gives them; cellCount is the length of cells[], below 2^32), a cell has the value id
+ * idOfCell[cell] < valueCount, a value the colour index colorOfValue[id] in 0 .. 12 (12 is "black": every value from the
+ * thirteenth rank on).  Per vertex, over its cells in stored order (:230-262): the cells of each colour index, the colours that
+ * occur in order of first occurrence, sorted by count descending with first occurrence deciding among equal counts (std::sort
+ * of at most 13 elements is libstdc++'s insertion sort, which is stable), sum = the sum of the counts, factor = 1. / sum,
+ * fraction = count * factor: doubles with one rounding each, the reference's bits.  The result is a CSR over the vertices:
+ * sliceOffsets [vertexCount + 1], and per slice sliceColor (0 .. 12), sliceCells and sliceFraction.  A vertex without cells has
+ * no slice.  Every id is tested before an address is formed with it: a cell not below cellSetSize, a value id not below
+ * valueCount, a colour index above 12, or offsets that do not ascend within cellCount are EM2_ERROR_INVALID_ARGUMENT, and no
+ * object is made.  Work split: a lane per vertex of at most em2_pie_census_wave_cells() cells, a wave per vertex above; a vertex
+ * of 10^6 cells is worked by that one wave, a known limit.  No result depends on an order between threads.
+ * The result is an object: em2_pie_census_sizes (any may be NULL; waveVertexCount: the vertices a wave worked), then
+ * em2_pie_census_get into arrays of those sizes (any may be NULL).  em2_dev_pie_census takes device pointers.
+ *
+ * em2_matrix_pie_census (declared with the em2_matrix_ entries below) is colorByMetaDataInterpretedAsCategory for a graph whose vertices hold ids into globalCellIds
+ * [cellSetSize]: the host walks the meta data lists of those cells once and writes one compact value id per cell, as
+ * em2_matrix_compute_meta_data_rand_index does (a cell without the field and a stored "" share an id; a field name the store
+ * does not know gives every cell "", as getCellMetaData(CellId, StringId) does for the invalid name id: one value, no error);
+ * the device counts the cells of each value over the cells of the vertices (em2_contingency_create with one column); the host
+ * puts the values that occur, in std::map order (string ascending), through std::sort with OrderPairsBySecondGreater
+ * (em2_order_by_count) and gives rank r the colour index min(r, 12); then the census above.  The object then also holds the
+ * value table in that sorted order: em2_pie_census_values_sizes, then em2_pie_census_values_get (values: the strings, each
+ * followed by a 0 byte). */
+typedef struct em2_pie_census em2_pie_census;
+uint32_t em2_pie_census_wave_cells(void);
+int em2_pie_census_create(uint32_t vertexCount, const uint64_t* cellOffsets, const uint32_t* cells, uint64_t cellCount,
+                          const uint32_t* idOfCell, uint32_t cellSetSize, const uint8_t* colorOfValue, uint32_t valueCount,
+                          em2_pie_census** census);
+int em2_dev_pie_census(uint32_t vertexCount, const uint64_t* d_cellOffsets, const uint32_t* d_cells, uint64_t cellCount,
+                       const uint32_t* d_idOfCell, uint32_t cellSetSize, const uint8_t* d_colorOfValue, uint32_t valueCount,
+                       em2_pie_census** census);
+int em2_pie_census_sizes(const em2_pie_census* census, uint32_t* vertexCount, uint64_t* sliceCount, uint32_t* waveVertexCount);
+int em2_pie_census_get(const em2_pie_census* census, uint64_t* sliceOffsets, uint8_t* sliceColor, uint32_t* sliceCells,
+                       double* sliceFraction);
+int em2_pie_census_values_sizes(const em2_pie_census* census, uint64_t* valueCount, uint64_t* valueBytes);
+int em2_pie_census_values_get(const em2_pie_census* census, char* values, uint64_t* valueCells);
+void em2_pie_census_free(em2_pie_census* census);
+
+/* order[] = the indices 0 .. count - 1 as std::sort leaves the pairs (index, counts[index]) under the reference's
+ * OrderPairsBySecondGreater (src/orderPairs.hpp:56-62), which looks at the count alone: std::sort is not stable above 16
+ * elements, and the order of equal counts is libstdc++'s; it depends on the comparator's results only, so this calls std::sort
+ * and restates nothing.  Both the value table of em2_matrix_pie_census and the painter order of the signature graph's vertices
+ * (sortedVertices, src/SignatureGraph.cpp:234-239) are this.  Host only. */
+int em2_order_by_count(const uint64_t* counts, uint64_t count, uint32_t* order);
+
+/* colorRandom (:176-194): per vertex, in vertex order, three draws of std::uniform_real_distribution<double>(0, 1.) from one
+ * std::mt19937(231), through color() of src/color.cpp:13-39 (clipped to [0, 1], int(c * 255)): rgb[v] = 0x00rrggbb, whose string
+ * is "#%02x%02x%02x".  <random> itself is called.  Host only. */
+int em2_signature_graph_random_colors(uint32_t vertexCount, uint32_t* rgb);
+
+/* The raster of a laid-out graph whose vertices are pie charts, this project's own definition.  Any graph as plain arrays.  The
+ * view, ux / uy, the own-pixel rule, the edge layer and edgeHits, the long-edge split and their checks are em2_graph_draw's,
+ * word for word (the same code runs).  After one conversion per vertex everything is integer arithmetic, and no result
+ * depends on an order between threads.
+ *   Vertices: the caller passes them in painter order (a later index is on top); vertex v has its own radius[v], in the
+ *   layout's units.  R_v = llround(radius[v] * s256).  Pixel (i, j) is covered by v iff (256 i + 128 - ux)^2 + (256 j + 128 -
+ *   uy)^2 <= R_v^2, or it is v's own pixel; vertexTop[j * S + i] is the largest index + 1 among the covering vertices, 0 if
+ *   none.  The bounding box is clipped to the image, so a vertex costs at most S^2 tests.
+ *   Slices: vertex v has the slices sliceOffsets[v] .. sliceOffsets[v + 1] - 1, at least one (sliceOffsets [vertexCount + 1]
+ *   begins at 0, ascends strictly and ends at sliceCount < 2^32 - 1).  Slice k starts at the direction (boundaryX[k],
+ *   boundaryY[k]), int32, and ends where the vertex's next slice starts, the last one where the first starts; largeArc[k] != 0
+ *   says that it spans more than half a turn.  The y axis points down in the raster as in the SVG, so the SVG's sweep flag 1 is
+ *   the direction of increasing angle in these coordinates.  With cross(p, q) = p.x q.y - p.y q.x in 64-bit integers, the
+ *   sector from a to b holds d iff cross(a, d) >= 0 && cross(d, b) > 0 when largeArc is 0, and iff
+ *   !(cross(b, d) >= 0 && cross(d, a) > 0) when it is not.  Once vertexTop is final, pixel p with the top vertex v and
+ *   d = (256 i + 128 - ux, 256 j + 128 - uy) belongs to v's first slice if v has one slice or d = (0, 0); otherwise to the first
+ *   of v's slices but the last whose sector holds d, else to the last.  sliceTop[p] = that slice's index + 1, 0 where vertexTop[p]
+ *   is 0.  em2_dev_graph_compose then takes sliceTop and a colour per slice, unchanged.
+ * EM2_ERROR_INVALID_ARGUMENT, and nothing is written: what em2_graph_draw refuses, a radius that is negative, not finite or above
+ * 8192 pixels, slice offsets that are not as above.
+ * Work split by radius class: a lane per vertex up to 4 pixels, a wave per vertex up to em2_graph_draw_pies_wave_radius() pixels,
+ * a workgroup per vertex above; the vertices are compacted into the three classes on the device, in any input order.  The
+ * workspace is em2_dev_graph_draw_pies_workspace(vertexCount, edgeCount) bytes.  em2_dev_graph_draw_pies synchronises the stream. */
+double em2_graph_draw_pies_wave_radius(void);
+size_t em2_dev_graph_draw_pies_workspace(uint32_t vertexCount, uint64_t edgeCount);
+int em2_dev_graph_draw_pies(uint32_t vertexCount, const double* d_x, const double* d_y, const double* d_radius, uint64_t edgeCount,
+                            const uint32_t* d_v0, const uint32_t* d_v1, int hideEdges, uint32_t sizePixels, double xViewBoxCenter,
+                            double yViewBoxCenter, double viewBoxHalfSize, const uint64_t* d_sliceOffsets, uint64_t sliceCount,
+                            const int32_t* d_boundaryX, const int32_t* d_boundaryY, const uint8_t* d_largeArc, uint32_t* d_vertexTop,
+                            uint32_t* d_sliceTop, uint32_t* d_edgeHits, void* d_workspace, size_t workspaceBytes, void* stream);
+int em2_graph_draw_pies(uint32_t vertexCount, const double* x, const double* y, const double* radius, uint64_t edgeCount, const uint32_t* v0,
+                        const uint32_t* v1, int hideEdges, uint32_t sizePixels, double xViewBoxCenter, double yViewBoxCenter,
+                        double viewBoxHalfSize, const uint64_t* sliceOffsets, uint64_t sliceCount, const int32_t* boundaryX,
+                        const int32_t* boundaryY, const uint8_t* largeArc, uint32_t* vertexTop, uint32_t* sliceTop, uint32_t* edgeHits);
+
+/* The boundary vectors of em2_graph_draw_pies from the fractions of a census, in the SVG's doubles (src/SignatureGraph.cpp:297-
+ * 311): per vertex totalAngle = 0.; per slice angle = fraction * 2. * pi, angle0 = totalAngle, boundaryX = llround(cos(angle0) *
+ * 1048576.), boundaryY = llround(sin(angle0) * 1048576.), largeArc = angle > pi, totalAngle = angle0 + angle.  The cosines and
+ * sines thereby stay out of the kernel, whose results are exact because the vectors are its inputs; 2^20 resolves two
+ * subpixels at the largest radius.  Host only; the C library's cos and sin. */
+int em2_pie_boundaries(uint32_t vertexCount, const uint64_t* sliceOffsets, const double* sliceFraction, int32_t* boundaryX,
+                       int32_t* boundaryY, uint8_t* largeArc);
+
+/* SignatureGraph::writeSvg (src/SignatureGraph.cpp:183-321) into a file, byte for byte for the same doubles and strings.  As
+ * written: the maxima of the coordinates start at numeric_limits<double>::min(); viewBoxSize = 1.05 * boundingBoxSize /
+ * zoomFactor; the vertices in the order of em2_order_by_count over cellCounts; the radius 0.03 * boundingBoxSize *
+ * sqrt(double(cellCount) / double(maxCellCount)); a circle for a vertex of fewer than two slices ("black" for none), else per
+ * slice a path with cos, sin, the large-arc flag angle > pi and the running totalAngle.  sliceOffsets NULL: no vertex has a
+ * colour, every vertex is the black circle (what the reference's createSignatureGraph writes into SignatureGraph.svg).
+ * sliceColors: sliceCount strings, each followed by a 0 byte.  svgParameters[4] = xCenter, yCenter, halfViewBoxSize, pixelSize,
+ * the four fields the reference fills in.  Host only. */
+int em2_signature_graph_write_svg(const char* fileName, uint32_t vertexCount, const double* x, const double* y, const uint64_t* cellCounts,
+                                  uint64_t edgeCount, const uint32_t* v0, const uint32_t* v1, int hideEdges, double svgSizePixels,
+                                  double xShift, double yShift, double zoomFactor, double vertexSizeFactor, double edgeThicknessFactor,
+                                  const uint64_t* sliceOffsets, const char* sliceColors, uint64_t sliceColorsBytes,
+                                  const double* sliceFraction, double* svgParameters);
+
 /* ExpressionMatrixSubset + Lsh + findSimilarPairs4 in one call on host buffers (SURVEY.md 8(a) row a1 on the device:
  * src/ExpressionMatrixSubset.cpp:9-42 followed by src/Lsh.cpp:118-224 and src/ExpressionMatrixLsh.cpp:200-285): the
  * global CSR (CellExpressionCounts toc/data, global gene ids) restricted to the cells cellIds[0..cellCount) (NULL =
@@ -1212,6 +1325,11 @@ int em2_matrix_cell_similarities_to_cell(em2_matrix* matrix, const char* geneSet
                                          uint32_t count, double* out);
 int em2_matrix_gene_expression_of_cells(em2_matrix* matrix, const char* geneSetName, uint32_t globalGeneId, int normalizationMethod,
                                         const uint32_t* cellIds, uint32_t count, float* out);
+
+/* colorByMetaDataInterpretedAsCategory for a graph over a cell set of the directory: see em2_pie_census_create above.  A global
+ * cell id not below the cell count, or a vertex cell not below cellSetSize: EM2_ERROR_INVALID_ARGUMENT. */
+int em2_matrix_pie_census(em2_matrix* matrix, uint32_t vertexCount, const uint64_t* cellOffsets, const uint32_t* cells, uint64_t cellCount,
+                          const uint32_t* globalCellIds, uint32_t cellSetSize, const char* metaDataName, em2_pie_census** census);
 
 /* ExpressionMatrix::compareSimilarPairs (src/ExpressionMatrixLsh.cpp:1199-1240): CompareSimilarPairs.csv in
  * outputDirectory (NULL or "": the working directory) with one line per cell whose stored count or last stored
