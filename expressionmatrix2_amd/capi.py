@@ -324,6 +324,20 @@ SYMBOLS = {
     "em2_contingency_get": (_c.c_int, [_c.c_void_p] * 7),
     "em2_contingency_free": (None, [_c.c_void_p]),
     "em2_rand_index": (_c.c_int, [_c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_uint64, _c.POINTER(_c.c_double), _c.POINTER(_c.c_double)]),
+    "em2_cell_graph_compare": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64] * 2 +
+                                         [_c.c_int, _c.POINTER(_c.c_void_p)]),
+    "em2_dev_cell_graph_compare": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64] * 2 +
+                                             [_c.c_int, _c.POINTER(_c.c_void_p)]),
+    "em2_graph_comparison_sizes": (_c.c_int, [_c.c_void_p] + [_c.POINTER(_c.c_uint64)] * 6 + [_c.POINTER(_c.c_int)]),
+    "em2_graph_comparison_get": (_c.c_int, [_c.c_void_p] * 3),
+    "em2_graph_comparison_free": (None, [_c.c_void_p]),
+    "em2_graph_group_colors": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_int,
+                                          _c.POINTER(_c.c_void_p)]),
+    "em2_dev_graph_group_colors": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_int,
+                                              _c.POINTER(_c.c_void_p)]),
+    "em2_group_colors_sizes": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_uint32), _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_int)]),
+    "em2_group_colors_get": (_c.c_int, [_c.c_void_p] * 5),
+    "em2_group_colors_free": (None, [_c.c_void_p]),
     "em2_matrix_set_cell_meta_data": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_char_p, _c.c_char_p]),
     "em2_matrix_get_cell_meta_data_value": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.c_char_p, _c.POINTER(_c.c_uint64), _c.c_void_p]),
     "em2_matrix_get_cell_meta_data": (_c.c_int, [_c.c_void_p, _c.c_uint32, _c.POINTER(_c.c_uint64), _c.c_void_p]),
@@ -1038,6 +1052,110 @@ def rand_index(sum_cells, sum_rows, sum_columns, n):
     ri, ari = ctypes.c_double(0.), ctypes.c_double(0.)
     check(load().em2_rand_index(sum_cells, sum_rows, sum_columns, n, ctypes.byref(ri), ctypes.byref(ari)))
     return ri.value, ari.value
+
+
+GRAPH_COMPARE_TABLE, GRAPH_COMPARE_LIST = 0, 1
+
+
+def graph_comparison_take(handle):
+    """The content of an em2_graph_comparison as a dict, and the handle freed: commonVertexCount, edgeCount0, edgeCount1 (distinct
+    unordered cell pairs), commonEdgeCount, commonIdenticalEdgeCount as Python ints, binDelta float32 and binCount uint64
+    ascending by binDelta, and path: the one that ran."""
+    lib = load()
+    try:
+        words = [ctypes.c_uint64(0) for _ in range(6)]
+        path = ctypes.c_int(0)
+        check(lib.em2_graph_comparison_sizes(handle, *[ctypes.byref(w) for w in words], ctypes.byref(path)))
+        names = ("commonVertexCount", "edgeCount0", "edgeCount1", "commonEdgeCount", "commonIdenticalEdgeCount")
+        out = {name: int(w.value) for name, w in zip(names, words)}
+        out["binDelta"] = np.zeros(words[5].value, dtype=np.float32)
+        out["binCount"] = np.zeros(words[5].value, dtype=np.uint64)
+        check(lib.em2_graph_comparison_get(handle, _ptr(out["binDelta"]), _ptr(out["binCount"])))
+        out["path"] = path.value
+    finally:
+        lib.em2_graph_comparison_free(handle)
+    return out
+
+
+def _compare_graph(graph):
+    """(vertexCellIds, edgeVertex0, edgeVertex1, edgeSimilarity) as contiguous arrays of the entry's types."""
+    cells, v0, v1, similarity = graph
+    cells = np.ascontiguousarray(cells, dtype=np.uint32)
+    v0 = np.ascontiguousarray(v0, dtype=np.uint32)
+    v1 = np.ascontiguousarray(v1, dtype=np.uint32)
+    similarity = np.ascontiguousarray(similarity, dtype=np.float32)
+    if cells.ndim != 1 or v0.ndim != 1 or not (v0.shape == v1.shape == similarity.shape):
+        raise ValueError("a graph is (vertexCellIds, edgeVertex0, edgeVertex1, edgeSimilarity), the three edge arrays with one "
+                         "entry per edge")
+    return cells, v0, v1, similarity
+
+
+def cell_graph_compare(graph0, graph1, path=GRAPH_COMPARE_TABLE):
+    """compareCellGraphs (src/ExpressionMatrixHttpServerGraphs.cpp:104-345) without its page, on the GPU (em2_cell_graph_compare):
+    each graph is (vertexCellIds, edgeVertex0, edgeVertex1, edgeSimilarity), the edges as vertex indices -> the dict of
+    graph_comparison_take."""
+    g0, g1 = _compare_graph(graph0), _compare_graph(graph1)
+    handle = ctypes.c_void_p(None)
+    check(load().em2_cell_graph_compare(_ptr(g0[0]), len(g0[0]), _ptr(g0[1]), _ptr(g0[2]), _ptr(g0[3]), len(g0[1]),
+                                        _ptr(g1[0]), len(g1[0]), _ptr(g1[1]), _ptr(g1[2]), _ptr(g1[3]), len(g1[1]),
+                                        int(path), ctypes.byref(handle)))
+    return graph_comparison_take(handle)
+
+
+def dev_cell_graph_compare(vertex_cell_ids0, v0_ptr0, v1_ptr0, sim_ptr0, edge_count0, vertex_cell_ids1, v0_ptr1, v1_ptr1, sim_ptr1,
+                           edge_count1, path=GRAPH_COMPARE_TABLE):
+    """The same over edge arrays in device memory (pointers, as dev_cell_graph_edges_to_device left them); the vertex lists
+    are host arrays."""
+    cells0 = np.ascontiguousarray(vertex_cell_ids0, dtype=np.uint32)
+    cells1 = np.ascontiguousarray(vertex_cell_ids1, dtype=np.uint32)
+    handle = ctypes.c_void_p(None)
+    check(load().em2_dev_cell_graph_compare(_ptr(cells0), len(cells0), v0_ptr0, v1_ptr0, sim_ptr0, int(edge_count0),
+                                            _ptr(cells1), len(cells1), v0_ptr1, v1_ptr1, sim_ptr1, int(edge_count1),
+                                            int(path), ctypes.byref(handle)))
+    return graph_comparison_take(handle)
+
+
+def group_colors_take(handle):
+    """The content of an em2_group_colors as a dict, and the handle freed: groupCount, pairGroup0 < pairGroup1 uint32 ascending
+    with pairEdgeCount uint64 (the group graph), colorTable uint32 [groupCount], and path: the contingency path that ran (0
+    where there was no edge)."""
+    lib = load()
+    try:
+        groups, pairs, path = ctypes.c_uint32(0), ctypes.c_uint64(0), ctypes.c_int(0)
+        check(lib.em2_group_colors_sizes(handle, ctypes.byref(groups), ctypes.byref(pairs), ctypes.byref(path)))
+        out = {
+            "groupCount": int(groups.value),
+            "pairGroup0": np.zeros(pairs.value, dtype=np.uint32),
+            "pairGroup1": np.zeros(pairs.value, dtype=np.uint32),
+            "pairEdgeCount": np.zeros(pairs.value, dtype=np.uint64),
+            "colorTable": np.zeros(groups.value, dtype=np.uint32),
+            "path": path.value,
+        }
+        check(lib.em2_group_colors_get(handle, *[_ptr(out[key]) for key in ("pairGroup0", "pairGroup1", "pairEdgeCount", "colorTable")]))
+    finally:
+        lib.em2_group_colors_free(handle)
+    return out
+
+
+def graph_group_colors(vertex_group, edge_vertex0, edge_vertex1, path=CONTINGENCY_AUTOMATIC):
+    """CellGraph::assignColorsToGroups (src/CellGraph.cpp:794-862): the group graph of the edges (on the GPU, through the
+    contingency code) and the reference's greedy colouring of it (em2_graph_group_colors) -> the dict of group_colors_take."""
+    group = np.ascontiguousarray(vertex_group, dtype=np.uint32)
+    v0 = np.ascontiguousarray(edge_vertex0, dtype=np.uint32)
+    v1 = np.ascontiguousarray(edge_vertex1, dtype=np.uint32)
+    if group.ndim != 1 or v0.ndim != 1 or v0.shape != v1.shape:
+        raise ValueError("one group per vertex and two vertices per edge are needed")
+    handle = ctypes.c_void_p(None)
+    check(load().em2_graph_group_colors(_ptr(group), len(group), _ptr(v0), _ptr(v1), len(v0), int(path), ctypes.byref(handle)))
+    return group_colors_take(handle)
+
+
+def dev_graph_group_colors(vertex_group, v0_ptr, v1_ptr, edge_count, path=CONTINGENCY_AUTOMATIC):
+    """The same over edge arrays in device memory (pointers); the groups are a host array."""
+    group = np.ascontiguousarray(vertex_group, dtype=np.uint32)
+    handle = ctypes.c_void_p(None)
+    check(load().em2_dev_graph_group_colors(_ptr(group), len(group), v0_ptr, v1_ptr, int(edge_count), int(path), ctypes.byref(handle)))
+    return group_colors_take(handle)
 
 
 def meta_data_table_take(handle):

@@ -1118,8 +1118,9 @@ class ExpressionMatrix:
         Returns values (float64 per vertex or None; capi.NO_VALUE is "no value"), groups (int per vertex), colors (a str per
         vertex, "" for none; in "category" the vertex's group colour), groupColors ({group: colour}, empty unless "category"),
         frequencyTable ([(count, value)] in group order), couldNotColor, minValue and maxValue (None unless numbers).
-        Errors in the reference's words: "Gene not found.", "Invalid cell id.".  reuseColors
-        (CellGraph::assignColorsToGroups) is not built."""
+        Errors in the reference's words: "Gene not found.", "Invalid cell id.".  The keyword reuseColors=True raises
+        NotImplementedError, as it always did: CellGraph::assignColorsToGroups is a step of its own here, reuseCellGraphColors,
+        to be called after a "category" colouring."""
         g = self._laid_out_cell_graph(graphName)
         if reuseColors:
             raise NotImplementedError("reuseColors (CellGraph::assignColorsToGroups) is not built")
@@ -1182,6 +1183,58 @@ class ExpressionMatrix:
                           maxValue=float(valueRange[1]))
         g["coloring"] = result
         return {key: value for key, value in result.items() if key not in ("rgb", "coloringOption")}
+
+    def reuseCellGraphColors(self, graphName):
+        """The page's reuseColors (:900-913) on the stored "category" colouring of computeCellGraphColors:
+        CellGraph::assignColorsToGroups (src/CellGraph.cpp:794-862) gives every group a colour index such that no two groups
+        joined by an edge share one (the group graph on the GPU, em2_graph_group_colors; the greedy on the host), and a group
+        is painted with the palette entry of that index where it is below 12, else "black".  Rewrites the stored groupColors,
+        colors and rgb, so that writeCellGraphSvg and drawCellGraph draw the new colours (the painter order stays by group),
+        and returns the dict of computeCellGraphColors plus colorTable (uint32 per group).  couldNotColor becomes the number of
+        vertices that are still black.  RuntimeError where the stored colouring is not the "category" one."""
+        g = self._laid_out_cell_graph(graphName)
+        result = g.get("coloring")
+        if not result or result["coloringOption"] != "byMetaData" or not result["frequencyTable"]:
+            raise RuntimeError("reuseCellGraphColors(): the colouring stored for graph " + graphName + " is not a \"category\" "
+                               "colouring (computeCellGraphColors with coloringOption=\"byMetaData\", metaDataMeaning=\"category\").")
+        v0, v1 = g["edgeVertices"]
+        table = capi.graph_group_colors(result["groups"], v0, v1)["colorTable"]
+        groupCount = len(result["frequencyTable"])
+        assert len(table) == groupCount or g["vertexCount"] == 0
+        colorOf = np.minimum(table, 12)
+        result["groupColors"] = {group: (CATEGORY_PALETTE[int(colorOf[group])] if colorOf[group] < 12 else "black")
+                                 for group in range(len(table))}
+        result["colors"] = [result["groupColors"][group] for group in result["groups"].tolist()]
+        palette = np.asarray([int(c[1:], 16) for c in CATEGORY_PALETTE] + [capi.COLOR_BLACK], dtype=np.uint32)
+        result["rgb"] = palette[colorOf[result["groups"]]] if len(table) else np.zeros(0, dtype=np.uint32)
+        result["couldNotColor"] = int((colorOf[result["groups"]] == 12).sum()) if len(table) else 0
+        result["colorTable"] = table
+        return {key: value for key, value in result.items() if key not in ("rgb", "coloringOption")}
+
+    def compareCellGraphs(self, graphName0, graphName1):
+        """ExpressionMatrix::compareCellGraphs (src/ExpressionMatrixHttpServerGraphs.cpp:104-345) without its HTML, on the GPU
+        (em2_cell_graph_compare).  Returns a dict: "graphs", per graph the stored creation parameters and counts
+        the page prints (cellSetName, similarPairsName, similarityThreshold, maxConnectivity, vertexCount,
+        isolatedRemovedVertexCount, and edgeCount: the distinct unordered cell pairs, the size of the reference's edge map);
+        commonVertexCount, commonEdgeCount, commonIdenticalEdgeCount; histogramDelta (float32) and histogramCount (uint64), the
+        distribution of similarity1 - similarity0 over the common edges in bins of 0.01, ascending.
+        RuntimeError in the page's words where a graph is missing or both names are the same."""
+        if graphName0 not in self._cellGraphs or graphName1 not in self._cellGraphs:
+            raise RuntimeError("Did not find one or both of the cell graphs to be compared.")            # :117-118
+        if graphName0 == graphName1:
+            raise RuntimeError("Comparison of a cell graph with itself requested. ")                     # :122-123
+        stored = [self._cellGraphs[graphName0], self._cellGraphs[graphName1]]
+        c = capi.cell_graph_compare(*[(g["vertexCellIds"], g["edgeVertices"][0], g["edgeVertices"][1], g["edgeSimilarity"])
+                                      for g in stored])
+        graphs = []
+        for g, edgeCount in zip(stored, (c["edgeCount0"], c["edgeCount1"])):
+            information = {key: g[key] for key in ("cellSetName", "similarPairsName", "similarityThreshold", "maxConnectivity",
+                                                   "vertexCount", "isolatedRemovedVertexCount")}
+            information["edgeCount"] = edgeCount
+            graphs.append(information)
+        return {"graphs": graphs, "commonVertexCount": c["commonVertexCount"], "commonEdgeCount": c["commonEdgeCount"],
+                "commonIdenticalEdgeCount": c["commonIdenticalEdgeCount"], "histogramDelta": c["binDelta"],
+                "histogramCount": c["binCount"]}
 
     def _cell_graph_view(self, g, sizePixels, xViewBoxCenter, yViewBoxCenter, viewBoxHalfSize, vertexRadius, edgeThickness):
         """The page's defaults (:411-438): the coordinate range enlarged to a square and by 5 %, a radius of 1.5 pixels and

@@ -1211,6 +1211,80 @@ void em2_contingency_free(em2_contingency* table);
 int em2_rand_index(uint64_t sumCells, uint64_t sumRows, uint64_t sumColumns, uint64_t n, double* randIndex, double* adjustedRandIndex);
 
 /* ------------------------------------------------------------------------------------------------------
+ * Two cell graphs compared, and the colours of a cell graph's vertex groups.  csrc/em2_graph_compare.hip, DESIGN.md 3.24.
+ * Integer sums and minima and single float operations: every output is the reference's, bit for bit.
+ * ------------------------------------------------------------------------------------------------------ */
+
+/* ExpressionMatrix::compareCellGraphs (src/ExpressionMatrixHttpServerGraphs.cpp:104-345) without its page.  Per graph g:
+ * vertexCellIds_g[vertexCount_g] in host memory, as for em2_cell_graph_label_propagation, and the edges as vertex indices with
+ * their similarities, edgeVertex0_g / edgeVertex1_g / edgeSimilarity_g[edgeCount_g] -- host memory here, DEVICE memory in
+ * em2_dev_cell_graph_compare (what em2_dev_cell_graph_edges left there), so a device-resident chain never brings its edges to
+ * the host.  Fewer than 2^32 edges per graph (EM2_ERROR_UNSUPPORTED).
+ *   - An edge is keyed by the cell ids of its two ends, the smaller first (:156-179): the two graphs number their vertices
+ *     independently.  Where a graph holds the same unordered cell pair more than once, in either orientation, the first in edge
+ *     order counts (map::insert does not overwrite, :166 and :178).  edgeCount0 / edgeCount1 of the result are the sizes of
+ *     those two maps (:301-302), not the input counts.
+ *   - commonVertexCount is the size of std::set_intersection of the two sorted id lists (:146-149), a multiset intersection:
+ *     an id that one list holds a times and the other b times counts min(a, b).
+ *   - commonEdgeCount: the keys both maps hold (:191-194).  commonIdenticalEdgeCount: those with similarity0 == similarity1
+ *     as floats (:197-199); +0 and -0 are identical.
+ *   - The bin of a common edge is 0.01f * std::round((similarity1 - similarity0) / 0.01f) (:200-201), every operation a
+ *     correctly rounded float operation and the rounding to the nearest integer with ties away from zero.  The bins are keyed by
+ *     the value of that product, as in the reference's std::map<float, size_t> (:189, :202-207); it can be +-inf.  The two zeros
+ *     are one bin, and binDelta gives it the sign of the key that map keeps: the one inserted first, which is the product of
+ *     the first common edge, ascending by (cellA, cellB), that falls into the bin.
+ *   - A common edge whose difference is not a number (a NaN similarity, or two infinities of one sign) makes that map
+ *     ill-formed: EM2_ERROR_UNSUPPORTED, and the message names the two cells.  A NaN on an edge only one graph has is ignored,
+ *     as in the reference.
+ *   - An edge whose two ends are the same cell is the reference's CZI_ASSERT(cellIdA != cellIdB) (:161, :173):
+ *     EM2_ERROR_RUNTIME.  A vertex index that is not below vertexCount_g is EM2_ERROR_INVALID_ARGUMENT: the kernel tests it
+ *     before it forms an address with it.  Neither creates an object.  Graph 0 is examined first, and in a graph the index
+ *     error is reported before the other.
+ * path: 0 counts the bins with |round(...)| <= 2048 in a table per workgroup in LDS and sends the other products through a
+ * sorted list; 1 sends every product through the list (tests: both give the same result).
+ * The result is an object: em2_graph_comparison_sizes (any pointer may be NULL; *path: the path that ran, as given), then
+ * em2_graph_comparison_get into binDelta[binCount] / binCountOut[binCount], ascending by binDelta (either may be NULL). */
+typedef struct em2_graph_comparison em2_graph_comparison;
+int em2_cell_graph_compare(const uint32_t* vertexCellIds0, uint32_t vertexCount0, const uint32_t* edgeVertex0_0, const uint32_t* edgeVertex1_0,
+                           const float* edgeSimilarity0, uint64_t edgeCount0, const uint32_t* vertexCellIds1, uint32_t vertexCount1,
+                           const uint32_t* edgeVertex0_1, const uint32_t* edgeVertex1_1, const float* edgeSimilarity1, uint64_t edgeCount1,
+                           int path, em2_graph_comparison** comparison);
+int em2_dev_cell_graph_compare(const uint32_t* vertexCellIds0, uint32_t vertexCount0, const uint32_t* d_edgeVertex0_0,
+                               const uint32_t* d_edgeVertex1_0, const float* d_edgeSimilarity0, uint64_t edgeCount0,
+                               const uint32_t* vertexCellIds1, uint32_t vertexCount1, const uint32_t* d_edgeVertex0_1,
+                               const uint32_t* d_edgeVertex1_1, const float* d_edgeSimilarity1, uint64_t edgeCount1, int path,
+                               em2_graph_comparison** comparison);
+int em2_graph_comparison_sizes(const em2_graph_comparison* comparison, uint64_t* commonVertexCount, uint64_t* edgeCount0,
+                               uint64_t* edgeCount1, uint64_t* commonEdgeCount, uint64_t* commonIdenticalEdgeCount, uint64_t* binCount,
+                               int* path);
+int em2_graph_comparison_get(const em2_graph_comparison* comparison, float* binDelta, uint64_t* binCountOut);
+void em2_graph_comparison_free(em2_graph_comparison* comparison);
+
+/* CellGraph::assignColorsToGroups (src/CellGraph.cpp:794-862; the page's reuseColors, src/ExpressionMatrixHttpServerGraphs.cpp:
+ * 900-913): colours for the groups of a graph's vertices such that no two groups joined by an edge share one, so that a few
+ * colours serve many groups.  vertexGroup[vertexCount] in host memory; the edges as vertex indices, host memory here and DEVICE
+ * memory in em2_dev_graph_group_colors.  Fewer than 2^32 edges (EM2_ERROR_UNSUPPORTED); a vertex index that is not below
+ * vertexCount is EM2_ERROR_INVALID_ARGUMENT (tested on the device before an address is formed with it).
+ *   groupCount                      the largest group + 1 (:799-808), 0 without vertices: a group no vertex has gets a colour too;
+ *   pairGroup0 < pairGroup1 [pairCount], ascending: the group graph (:813-825), with pairEdgeCount, the edges of the graph between
+ *                                   the two groups.  They are the cells off the diagonal of the contingency table of
+ *                                   (group of vertex 0, group of vertex 1) over the edges (em2_dev_contingency), folded over it;
+ *   colorTable[groupCount]          the reference's greedy (:830-861), on the host: the groups ascending, each the first index c
+ *                                   at which the sorted distinct colours of its adjacent smaller groups differ from c, else their
+ *                                   number.
+ * path is handed to em2_dev_contingency (0, 1 = LDS: groupCount^2 <= 16384, 2 = sort); *path of em2_group_colors_sizes is the
+ * one that ran, 0 where there was no edge.  em2_group_colors_get: any pointer may be NULL. */
+typedef struct em2_group_colors em2_group_colors;
+int em2_graph_group_colors(const uint32_t* vertexGroup, uint32_t vertexCount, const uint32_t* edgeVertex0, const uint32_t* edgeVertex1,
+                           uint64_t edgeCount, int path, em2_group_colors** colors);
+int em2_dev_graph_group_colors(const uint32_t* vertexGroup, uint32_t vertexCount, const uint32_t* d_edgeVertex0,
+                               const uint32_t* d_edgeVertex1, uint64_t edgeCount, int path, em2_group_colors** colors);
+int em2_group_colors_sizes(const em2_group_colors* colors, uint32_t* groupCount, uint64_t* pairCount, int* path);
+int em2_group_colors_get(const em2_group_colors* colors, uint32_t* pairGroup0, uint32_t* pairGroup1, uint64_t* pairEdgeCount,
+                         uint32_t* colorTable);
+void em2_group_colors_free(em2_group_colors* colors);
+
+/* ------------------------------------------------------------------------------------------------------
  * ExpressionMatrix-level entry points: the methods the reference binds to Python (src/PythonModule.cpp),
  * operating by NAME on a data directory in the reference's memory-mapped formats.  Results are files in
  * that directory (SimilarPairs-<name>-{Info,Pairs,CellInfo}, Lsh-<name>-{Info,Signatures}), byte-compatible
