@@ -6,6 +6,6 @@ ExpressionMatrix method names; and the gene side's all-pairs search, findSimilar
 include/em2_lsh.h.
 """
 from . import capi, files  # noqa: F401
-from .expression_matrix import CellGraphVertexInfo, ExpressionMatrix, NormalizationMethod  # noqa: F401
+from .expression_matrix import CellGraphVertexInfo, ExpressionMatrix, NormalizationMethod, topGenes  # noqa: F401
 
-__all__ = ["capi", "files", "CellGraphVertexInfo", "ExpressionMatrix", "NormalizationMethod"]
+__all__ = ["capi", "files", "CellGraphVertexInfo", "ExpressionMatrix", "NormalizationMethod", "topGenes"]

@@ -70,6 +70,15 @@ SYMBOLS = {
     "em2_dev_gene_information_content": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_uint64, _c.c_void_p,
                                                     _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t, _c.c_void_p]),
     "em2_set_gene_information_max_blocks": (None, [_c.c_uint32]),
+    "em2_rank_genes": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_void_p,
+                                  _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "em2_dev_rank_genes_workspace": (_c.c_size_t, [_c.c_uint32, _c.c_uint32, _c.c_uint64, _c.c_uint32]),
+    "em2_dev_rank_genes": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_uint64, _c.c_void_p, _c.c_void_p,
+                                      _c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_size_t,
+                                      _c.c_void_p]),
+    "em2_set_rank_genes_test_limits": (None, [_c.c_uint32, _c.c_uint32, _c.c_uint32]),
+    "em2_matrix_rank_genes": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_int, _c.c_void_p, _c.c_uint32, _c.c_void_p,
+                                         _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "em2_cell_norm_inverses": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_uint32, _c.c_void_p, _c.c_void_p]),
     "em2_matrix_gene_information_content": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_int, _c.c_void_p]),
     "em2_matrix_create_gene_set_using_information_content": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_int,
@@ -348,6 +357,7 @@ SYMBOLS = {
     "em2_matrix_meta_data_table": (_c.c_int, [_c.c_void_p, _c.c_char_p, _c.c_char_p, _c.c_char_p, _c.POINTER(_c.c_void_p)]),
     "em2_meta_data_table_sizes": (_c.c_int, [_c.c_void_p] + [_c.POINTER(_c.c_uint64)] * 5 + [_c.POINTER(_c.c_int)]),
     "em2_meta_data_table_get": (_c.c_int, [_c.c_void_p] * 9),
+    "em2_meta_data_table_cell_rows": (_c.c_int, [_c.c_void_p, _c.c_void_p]),
     "em2_meta_data_table_free": (None, [_c.c_void_p]),
     "em2_matrix_flush": (_c.c_int, [_c.c_void_p]),
     "em2_tool_create_meta_data": (_c.c_int, [_c.c_char_p, _c.c_uint32, _c.c_uint64, _c.c_uint64]),
@@ -1158,10 +1168,10 @@ def dev_graph_group_colors(vertex_group, v0_ptr, v1_ptr, edge_count, path=CONTIN
     return group_colors_take(handle)
 
 
-def meta_data_table_take(handle):
+def meta_data_table_take(handle, cell_rows=False):
     """The content of an em2_meta_data_table as a dict, and the handle freed: values0 / values1 (lists of str) with counts0 /
     counts1 (lists of int) in histogram order, triples [(row, column, count)], sums (four ints: the three of the contingency
-    table and n), path."""
+    table and n), path; with cell_rows also cellRow (uint32, per cell of the set the place of its value in values0)."""
     lib = load()
     try:
         sizes = [ctypes.c_uint64(0) for _ in range(5)]
@@ -1179,6 +1189,10 @@ def meta_data_table_take(handle):
         for f, size in enumerate((bytes0, bytes1)):
             out["values%d" % f] = [v.decode("utf-8", "surrogateescape") for v in values[f].raw[:size].split(b"\0")[:-1]]
             out["counts%d" % f] = counts[f].tolist()
+        if cell_rows:
+            out["cellRow"] = np.zeros(out["sums"][3], dtype=np.uint32)
+            if len(out["cellRow"]):
+                check(lib.em2_meta_data_table_cell_rows(handle, _ptr(out["cellRow"])))
     finally:
         lib.em2_meta_data_table_free(handle)
     return out
@@ -1280,6 +1294,77 @@ def dev_gene_information_content(toc, data, gene_count, norm_inverse=None):
                                                workspace_bytes, stream.cuda_stream))
     torch.cuda.current_stream().wait_stream(stream)
     return d_single.cpu().numpy(), d_double.cpu().numpy(), d_expressing.cpu().numpy().view(np.uint32)
+
+
+NO_GROUP, GROUP_EXCLUDED = 0xffffffff, 0xfffffffe          # EM2_NO_GROUP, EM2_GROUP_EXCLUDED
+
+
+def rank_genes_arrays(gene_count, group_count):
+    """The zeroed outputs of the rank genes entries: groupSize [groups], nonZeroCount and rankSum2 [genes][groups], tieSum
+    [genes], zScore and auc [genes][groups]."""
+    return {"groupSize": np.zeros(group_count, dtype=np.uint32), "nonZeroCount": np.zeros((gene_count, group_count), dtype=np.uint32),
+            "rankSum2": np.zeros((gene_count, group_count), dtype=np.uint64), "tieSum": np.zeros(gene_count, dtype=np.uint64),
+            "zScore": np.zeros((gene_count, group_count), dtype=np.float64), "auc": np.zeros((gene_count, group_count), dtype=np.float64)}
+
+
+def rank_genes(toc, data, gene_count, group, group_count, norm_inverse=None):
+    """em2_rank_genes: the rank-sum test of every gene of a subset's host CSR for every group of cells against the rest -> the
+    dict of rank_genes_arrays.  group: uint32 [cells], a group below group_count or NO_GROUP."""
+    toc = np.ascontiguousarray(toc, dtype=np.uint64)
+    data = np.ascontiguousarray(data, dtype=COUNT_DTYPE)
+    group = np.ascontiguousarray(group, dtype=np.uint32)
+    cell_count = len(toc) - 1
+    if len(group) != cell_count:
+        raise ValueError("group must have one value per cell")
+    if norm_inverse is not None:
+        norm_inverse = np.ascontiguousarray(norm_inverse, dtype=np.float64)
+        if len(norm_inverse) != cell_count:
+            raise ValueError("norm_inverse must have one value per cell")
+    out = rank_genes_arrays(gene_count, group_count)
+    check(load().em2_rank_genes(_ptr(toc), _ptr(data), cell_count, gene_count, _ptr(norm_inverse) if norm_inverse is not None else None,
+                                _ptr(group), group_count, _ptr(out["groupSize"]), _ptr(out["nonZeroCount"]), _ptr(out["rankSum2"]),
+                                _ptr(out["tieSum"]), _ptr(out["zScore"]), _ptr(out["auc"])))
+    return out
+
+
+def dev_rank_genes(toc, data, gene_count, group, group_count, norm_inverse=None, fill=0):
+    """The integers of rank_genes through em2_dev_rank_genes on torch device buffers (a stream of torch's).  The outputs start
+    as `fill` in every byte, so that a caller sees what a failed call left of them: on an error the RuntimeError carries them
+    as its `outputs`."""
+    import torch
+    toc = np.ascontiguousarray(toc, dtype=np.uint64)
+    data = np.ascontiguousarray(data, dtype=COUNT_DTYPE)
+    cell_count, entries = len(toc) - 1, len(data)
+    lib = load()
+    device = torch.device("cuda")
+    d_toc = torch.from_numpy(toc.view(np.int64).copy()).to(device)
+    d_data = torch.from_numpy(data.view(np.uint8).reshape(-1).copy()).to(device)
+    d_group = torch.from_numpy(np.ascontiguousarray(group, dtype=np.uint32).view(np.int32).copy()).to(device)
+    d_norm = torch.from_numpy(np.ascontiguousarray(norm_inverse, dtype=np.float64)).to(device) if norm_inverse is not None else None
+    counters = gene_count * group_count
+    d_out = {"groupSize": torch.full((group_count * 4,), fill, dtype=torch.uint8, device=device),
+             "nonZeroCount": torch.full((counters * 4,), fill, dtype=torch.uint8, device=device),
+             "rankSum2": torch.full((counters * 8,), fill, dtype=torch.uint8, device=device),
+             "tieSum": torch.full((gene_count * 8,), fill, dtype=torch.uint8, device=device)}
+    workspace_bytes = lib.em2_dev_rank_genes_workspace(cell_count, gene_count, entries, group_count)
+    d_workspace = torch.empty(max(workspace_bytes, 1), dtype=torch.uint8, device=device)
+    stream = torch.cuda.Stream()
+    stream.wait_stream(torch.cuda.current_stream())
+    rc = lib.em2_dev_rank_genes(d_toc.data_ptr(), d_data.data_ptr(), cell_count, gene_count, entries,
+                                d_norm.data_ptr() if d_norm is not None else None, d_group.data_ptr(), group_count,
+                                d_out["groupSize"].data_ptr(), d_out["nonZeroCount"].data_ptr(), d_out["rankSum2"].data_ptr(),
+                                d_out["tieSum"].data_ptr(), d_workspace.data_ptr(), workspace_bytes, stream.cuda_stream)
+    torch.cuda.current_stream().wait_stream(stream)
+    out = {"groupSize": d_out["groupSize"].cpu().numpy().view(np.uint32),
+           "nonZeroCount": d_out["nonZeroCount"].cpu().numpy().view(np.uint32).reshape(gene_count, group_count),
+           "rankSum2": d_out["rankSum2"].cpu().numpy().view(np.uint64).reshape(gene_count, group_count),
+           "tieSum": d_out["tieSum"].cpu().numpy().view(np.uint64)}
+    try:
+        check(rc)
+    except RuntimeError as error:
+        error.outputs = out
+        raise
+    return out
 
 
 DENSE_FLOAT64, DENSE_FLOAT32 = 0, 1

@@ -272,6 +272,21 @@ hipError_t runGeneInformation(const uint64_t* d_toc, const CountIn* d_data, uint
                               double* d_informationContentDouble, uint32_t* d_expressingCellCount, void* workspace, size_t workspaceBytes,
                               uint32_t* inputError, hipStream_t stream);
 
+// em2_rank_genes.hip: the integers of the rank-sum test of every gene for every group of cells against the rest (DESIGN.md
+// 3.25) on a subset's CSR in device memory, as runGeneInformation takes it.  d_group[cellCount]: a group below groupCount or
+// kNoGroup.  The outputs are [geneCount][groupCount] (d_groupSize [groupCount], d_tieSum [geneCount]).  *inputError != 0:
+// nothing was written outside the workspace (bits 0-2: as runGeneInformation's; bit 3: a value is NaN; bit 4: a group id is
+// neither below groupCount nor kNoGroup).  The caller has checked the limits (rankGenesUnsupported).  Synchronises the stream.
+constexpr uint32_t kNoGroup = 0xffffffffu;
+const char* rankGenesUnsupported(uint64_t cellCount, uint64_t geneCount, uint64_t entryCount, uint64_t groupCount);   // NULL: supported
+const char* rankGenesErrorText(uint32_t inputError);
+size_t rankGenesWorkspaceBytes(uint64_t entryCount, uint32_t geneCount, uint32_t groupCount);
+void setRankGenesTestLimits(uint32_t maxBlocks, uint32_t chunkEntries, uint32_t ldsGroupLimit);     // em2_set_rank_genes_test_limits
+hipError_t runRankGenes(const uint64_t* d_toc, const CountIn* d_data, uint32_t cellCount, uint32_t geneCount, uint64_t entryCount,
+                        const double* d_normInverse, const uint32_t* d_group, uint32_t groupCount, uint32_t* d_groupSize,
+                        uint32_t* d_nonZeroCount, uint64_t* d_rankSum2, uint64_t* d_tieSum, void* workspace, size_t workspaceBytes,
+                        uint32_t* inputError, hipStream_t stream);
+
 // em2_dense.hip: getDenseExpressionMatrix (src/PythonModule.cpp:112-138) for the rows [rowBegin, rowEnd) of a cell list (NULL: the
 // CSR's own rows) into d_out[(row - rowBegin) * pitchElements + gene], floats or doubles; d_geneLocalIds NULL: the CSR is in
 // local ids already.  *inputError != 0 (walkCell's word over the kept entries): nothing was written.  Synchronises the stream.

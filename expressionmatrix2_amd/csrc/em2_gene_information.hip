@@ -13,7 +13,7 @@
 //     ascending order, so the stream is a function of the input alone;
 //   * geneSegmentsKernel       the segment of every gene by binary search on the sorted keys; its length is the number of
 //                              expressing cells, stored zeros included; ceil(length / kChunk) chunks;
-//   * a scan over the chunk counts and chunkTableKernel: chunk t -> (gene, chunk within the gene).  The work of both passes is
+//   * a scan over the chunk counts and chunkTableKernel (em2_chunks.h): chunk t -> (gene, chunk within the gene).  The work of both passes is
 //     dealt by chunk, so a gene present in every cell and a gene present in one cell keep the machine equally busy;
 //   * chunkReduceKernel<PASS>  THE FIXED SHAPE.  A gene's segment is cut at kChunk, 2 kChunk, ... FROM ITS OWN START.  One wave
 //                              reduces one chunk: lane l adds the chunk's entries l, l + 64, l + 128, ... in ascending order
@@ -33,6 +33,7 @@
 #include "em2_expression.h"
 #include "em2_entry.h"
 #include "em2_csr.h"
+#include "em2_chunks.h"
 #include "em2_primitives.h"
 #include "em2_wave.h"
 
@@ -49,11 +50,6 @@ namespace {
 
 constexpr uint32_t kChunk = kGeneInformationChunk;       // entries of a gene one wave reduces
 constexpr uint32_t kPerLane = kChunk / 64u;
-
-struct ChunkRef {
-    uint32_t gene;
-    uint32_t index;           // the chunk's number within its gene: entries [index * kChunk, + kChunk) of the segment
-};
 
 __global__ void __launch_bounds__(256)
 cellNormInversesKernel(const uint64_t* __restrict__ toc, const CountIn* __restrict__ data, uint32_t cellCount, uint32_t geneCount,
@@ -127,24 +123,6 @@ geneSegmentsKernel(const uint32_t* __restrict__ sortedKeys, uint64_t count, uint
         offsets[g] = begin;
         chunkCounts[g] = (end - begin + kChunk - 1u) / kChunk;
         if (expressing) expressing[g] = uint32_t(end - begin);
-    }
-}
-
-// chunkStarts: the exclusive scan of chunkCounts, [geneCount + 1].  A thread per chunk finds its gene: the last g with
-// chunkStarts[g] <= t (genes without chunks share their start with the next gene and are passed over).
-__global__ void __launch_bounds__(256)
-chunkTableKernel(const uint64_t* __restrict__ chunkStarts, uint32_t geneCount, ChunkRef* __restrict__ table)
-{
-    const uint64_t total = chunkStarts[geneCount];
-    for (uint64_t t = blockIdx.x * blockDim.x + threadIdx.x; t < total; t += uint64_t(gridDim.x) * blockDim.x) {
-        uint32_t low = 0u, high = geneCount;               // the first g with chunkStarts[g] > t, in (0, geneCount]
-        while (low < high) {
-            const uint32_t middle = low + (high - low) / 2u;
-            if (chunkStarts[middle] <= t) low = middle + 1u;
-            else high = middle;
-        }
-        const uint32_t gene = low - 1u;
-        table[t] = ChunkRef{gene, uint32_t(t - chunkStarts[gene])};
     }
 }
 

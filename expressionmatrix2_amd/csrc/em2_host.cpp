@@ -14,6 +14,11 @@ extern "C" int em2_internal_gene_information(const uint64_t* rowToc, const em2_c
                                              int normalizationMethod, const double* normInverseOfRows, float* informationContent,
                                              uint32_t* expressingCellCount);
 
+extern "C" int em2_internal_rank_genes(const uint64_t* rowToc, const em2_count* rowData, uint32_t cellCount, const uint32_t* geneLocalIds,
+                                       uint32_t globalGeneCount, uint32_t geneCount, int normalizationMethod,
+                                       const double* normInverseOfRows, const uint32_t* group, uint32_t groupCount, uint32_t* groupSize,
+                                       uint32_t* nonZeroCount, uint64_t* rankSum2, uint64_t* tieSum, double* zScore, double* auc);
+
 #include <chrono>
 #include <functional>
 #include <future>
@@ -732,22 +737,74 @@ void Matrix::geneInformation(const std::string& geneSetName, const std::string& 
         }
         rowData = gathered.data();
     }
-    std::vector<double> fromFile;
-    if (normalizationMethod != 0 && fileExists(directoryName_ + "/Cells")) {
-        MappedFile cellsFile;
-        cellsFile.openExisting(directoryName_ + "/Cells", false, sizeof(CellRecord));
-        if (cellsFile.objectCount() != globalCells) fail(EM2_ERROR_RUNTIME, "The Cells file has a number of cells inconsistent with the expression counts.");
-        const CellRecord* records = static_cast<const CellRecord*>(cellsFile.data());
-        fromFile.resize(cellCount);
-        for (uint32_t i = 0; i < cellCount; i++) {
-            fromFile[i] = normalizationMethod == 1 ? records[cellIds[i]].norm1Inverse : records[cellIds[i]].norm2Inverse;
-        }
-    }
+    const std::vector<double> fromFile = normInversesFromFile(cellIds, cellCount, normalizationMethod);
     const int rc = em2_internal_gene_information(rowToc.data(), rowData, cellCount, static_cast<const uint32_t*>(genes.localIds.data()),
                                                  uint32_t(genes.localIds.objectCount()), geneCount, normalizationMethod,
                                                  fromFile.empty() ? nullptr : fromFile.data(),
                                                  informationContent ? informationContent->data() : nullptr,
                                                  expressingCellCount ? expressingCellCount->data() : nullptr);
+    if (rc != EM2_OK) fail(rc, em2_last_error());
+}
+
+std::vector<double> Matrix::normInversesFromFile(const uint32_t* cellIds, uint32_t count, int normalizationMethod) const
+{
+    std::vector<double> fromFile;
+    if (normalizationMethod == 0 || !fileExists(directoryName_ + "/Cells")) return fromFile;
+    MappedFile cellsFile;
+    cellsFile.openExisting(directoryName_ + "/Cells", false, sizeof(CellRecord));
+    if (cellsFile.objectCount() != toc_.objectCount() - 1) fail(EM2_ERROR_RUNTIME, "The Cells file has a number of cells inconsistent with the expression counts.");
+    const CellRecord* records = static_cast<const CellRecord*>(cellsFile.data());
+    fromFile.resize(count);
+    for (uint32_t i = 0; i < count; i++) {
+        fromFile[i] = normalizationMethod == 1 ? records[cellIds[i]].norm1Inverse : records[cellIds[i]].norm2Inverse;
+    }
+    return fromFile;
+}
+
+void Matrix::rankGenes(const std::string& geneSetName, const std::string& cellSetName, int normalizationMethod, const uint32_t* group,
+                       uint32_t groupCount, uint32_t* groupSize, uint32_t* nonZeroCount, uint64_t* rankSum2, uint64_t* tieSum,
+                       double* zScore, double* auc) const
+{
+    const char* who = "em2_matrix_rank_genes";
+    const GeneSet& genes = geneSet(geneSetName);
+    const MappedFile& cells = cellSet(cellSetName);
+    const uint32_t geneCount = genes.size(), setCount = uint32_t(cells.objectCount());
+    const uint32_t* setIds = static_cast<const uint32_t*>(cells.data());
+    if (normalizationMethod < 0 || normalizationMethod > 2) fail(EM2_ERROR_INVALID_ARGUMENT, "invalid normalization method (0 none, 1 L1, 2 L2)");
+    if (groupCount == 0) fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": groupCount must be positive");
+    if (setCount && !group) fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null argument");
+    // the universe: the cells of the set that are not excluded, in the set's order
+    std::vector<uint32_t> cellIds, groupOf;
+    for (uint32_t i = 0; i < setCount; i++) {
+        if (group[i] == EM2_GROUP_EXCLUDED) continue;
+        cellIds.push_back(setIds[i]);
+        groupOf.push_back(group[i]);
+    }
+    const uint32_t cellCount = uint32_t(cellIds.size());
+    const size_t cells2 = size_t(geneCount) * groupCount;
+    if ((!groupSize) || (geneCount && (!nonZeroCount || !rankSum2 || !tieSum))) fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": null argument");
+    if (geneCount == 0 || cellCount == 0) {
+        // nothing to rank: the integers of no cell, and the statistics em2_rank_genes_host.h gives for them
+        std::fill(groupSize, groupSize + groupCount, 0u);
+        for (const uint32_t g : groupOf) {                                    // (no gene: the groups still have their cells)
+            if (g < groupCount) groupSize[g]++;
+            else if (g != EM2_NO_GROUP) fail(EM2_ERROR_INVALID_ARGUMENT, std::string(who) + ": a group id is neither below groupCount nor the no-group value");
+        }
+        std::fill(nonZeroCount, nonZeroCount + cells2, 0u);
+        std::fill(rankSum2, rankSum2 + cells2, uint64_t(0));
+        std::fill(tieSum, tieSum + geneCount, uint64_t(0));
+        if (zScore) std::fill(zScore, zScore + cells2, 0.);
+        if (auc) std::fill(auc, auc + cells2, 0.5);
+        return;
+    }
+    std::vector<uint64_t> rowToc;
+    std::vector<em2_count> rowData;
+    gatherRows(who, cellIds.data(), cellCount, std::vector<uint32_t>(), rowToc, rowData);
+    const std::vector<double> fromFile = normInversesFromFile(cellIds.data(), cellCount, normalizationMethod);
+    const int rc = em2_internal_rank_genes(rowToc.data(), rowData.data(), cellCount, static_cast<const uint32_t*>(genes.localIds.data()),
+                                           uint32_t(genes.localIds.objectCount()), geneCount, normalizationMethod,
+                                           fromFile.empty() ? nullptr : fromFile.data(), groupOf.data(), groupCount, groupSize,
+                                           nonZeroCount, rankSum2, tieSum, zScore, auc);
     if (rc != EM2_OK) fail(rc, em2_last_error());
 }
 

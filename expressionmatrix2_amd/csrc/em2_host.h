@@ -172,6 +172,12 @@ public:
     // The cells' norm inverses come from the Cells file where the directory has one.
     void geneInformation(const std::string& geneSetName, const std::string& cellSetName, int normalizationMethod,
                          std::vector<float>* informationContent, std::vector<uint32_t>* expressingCellCount) const;
+    // em2_matrix_rank_genes: the rank-sum integers and statistics of the genes of a gene set for groups of the
+    // cells of a cell set; group[size of the cell set], a cell with EM2_GROUP_EXCLUDED is left out.  Outputs [genes][groupCount]
+    // (groupSize [groupCount], tieSum [genes]); zScore and auc may be NULL.
+    void rankGenes(const std::string& geneSetName, const std::string& cellSetName, int normalizationMethod, const uint32_t* group,
+                   uint32_t groupCount, uint32_t* groupSize, uint32_t* nonZeroCount, uint64_t* rankSum2, uint64_t* tieSum, double* zScore,
+                   double* auc) const;
     // createGeneSetUsingInformationContent (src/ExpressionMatrix.cpp:2022-2082), createWellExpressedGeneSet
     // (src/ExpressionMatrixGeneSets.cpp:314-362) and removeGeneSet (:12-32): the new set's files, and the set under its name.
     void createGeneSetUsingInformationContent(const std::string& existingGeneSetName, const std::string& cellSetName,
@@ -260,6 +266,8 @@ private:
     // The rows of `cellIds`, then the rows of `more`, as a CSR of their own with the global gene ids.
     void gatherRows(const char* who, const uint32_t* cellIds, uint32_t count, const std::vector<uint32_t>& more, std::vector<uint64_t>& toc,
                     std::vector<em2_count>& data) const;
+    // The norm1Inverse (method 1) or norm2Inverse (method 2) of these cells from the Cells file; empty where the directory has none.
+    std::vector<double> normInversesFromFile(const uint32_t* cellIds, uint32_t count, int normalizationMethod) const;
     // Writes GeneSet-<name>-* for the genes of `from` that `keep` names (ascending local id) and opens the new set.
     void addGeneSubset(const std::string& name, const GeneSet& from, const std::vector<bool>& keep);
     // The same for ascending global ids.

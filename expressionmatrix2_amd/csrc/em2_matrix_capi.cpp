@@ -280,6 +280,17 @@ int em2_matrix_gene_information_content(em2_matrix* matrix, const char* geneSetN
     });
 }
 
+int em2_matrix_rank_genes(em2_matrix* matrix, const char* geneSetName, const char* cellSetName, int normalizationMethod,
+                          const uint32_t* group, uint32_t groupCount, uint32_t* groupSize, uint32_t* nonZeroCount, uint64_t* rankSum2,
+                          uint64_t* tieSum, double* zScore, double* auc)
+{
+    if (!matrix || !geneSetName || !cellSetName) return nullArgument("em2_matrix_rank_genes");
+    return guarded([&] {
+        matrix->impl->rankGenes(geneSetName, cellSetName, normalizationMethod, group, groupCount, groupSize, nonZeroCount, rankSum2,
+                                tieSum, zScore, auc);
+    });
+}
+
 int em2_matrix_create_gene_set_using_information_content(em2_matrix* matrix, const char* existingGeneSetName, const char* cellSetName,
                                                          int normalizationMethod, double geneInformationContentThreshold,
                                                          const char* newGeneSetName)
@@ -654,6 +665,13 @@ int em2_meta_data_table_get(const em2_meta_data_table* table, char* values0, uin
     if (column) std::copy(t.column.begin(), t.column.end(), column);
     if (count) std::copy(t.count.begin(), t.count.end(), count);
     if (sums) std::copy(t.sums, t.sums + 4, sums);
+    return EM2_OK;
+}
+
+int em2_meta_data_table_cell_rows(const em2_meta_data_table* table, uint32_t* cellRow)
+{
+    if (!table || !cellRow) return nullArgument("em2_meta_data_table_cell_rows");
+    std::copy(table->table.cellRow.begin(), table->table.cellRow.end(), cellRow);
     return EM2_OK;
 }
 

@@ -530,6 +530,8 @@ void Matrix::metaDataTable(const std::string& cellSetName, const std::string& me
             out.counts[f].push_back(totals[f][order[rank]]);
         }
     }
+    out.cellRow.resize(n);
+    for (size_t i = 0; i < n; i++) out.cellRow[i] = position[0][compact[0][i]];
     if (fieldCount == 2) {
         std::vector<size_t> order(nonZeroCount);
         for (size_t t = 0; t < nonZeroCount; t++) order[t] = t;

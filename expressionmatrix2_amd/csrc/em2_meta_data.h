@@ -94,6 +94,7 @@ struct MetaDataTable {
     std::vector<std::string> values[2];                    // count descending, then value ascending as std::string compares
     std::vector<uint64_t> counts[2];
     std::vector<uint64_t> row, column, count;              // the cells that are not zero, ascending by (row, column)
+    std::vector<uint32_t> cellRow;                         // per cell of the set, in its order: the place of its value in values[0]
     uint64_t sums[4] = {0, 0, 0, 0};                       // sum v (v - 1) over the cells, t (t - 1) over rows, over columns; n
     int path = 0;                                          // of em2_contingency_sizes
 };

@@ -11,6 +11,7 @@ message text.  The work happens in libem2lsh.so (HIP, MI355X); when torch.distri
 than one rank the calls are collective and the scan is row-sharded over the ranks (sharded.py)."""
 import ctypes
 import enum
+import math
 
 import numpy as np
 
@@ -125,6 +126,17 @@ def _distributed():
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         return dist, dist.get_world_size()
     return None, 1
+
+
+def topGenes(result, n):
+    """Per group of a result of rankGenesByMetaData, rankGenesByClusterGraph or compareCellSets, the global ids of the n genes
+    of largest z, ties broken by ascending gene id -> {group name: [gene id]}."""
+    geneIds = np.asarray(result["geneIds"])
+    out = {}
+    for name, z in zip(result["groupNames"], np.asarray(result["zScore"])):
+        order = np.lexsort((geneIds, -z))
+        out[name] = geneIds[order[:int(n)]].tolist()
+    return out
 
 
 class ExpressionMatrix:
@@ -406,6 +418,83 @@ class ExpressionMatrix:
         out = np.zeros(count.value, dtype=np.float32)
         capi.check(lib.em2_matrix_gene_information_content(self._handle, _b(geneSetName), _b(cellSetName), int(method), capi._ptr(out)))
         return out
+
+    # ---- rank-sum marker genes (the reference has no such test) ----
+    def _rank_genes(self, geneSetName, cellSetName, normalizationMethod, group, groupNames):
+        """em2_matrix_rank_genes over the cells of a cell set: group is uint32 per cell of the set, in its order (a group,
+        capi.NO_GROUP, or capi.GROUP_EXCLUDED for a cell that is not part of the universe) -> the dict of the public methods."""
+        method = NormalizationMethod(normalizationMethod)
+        geneIds = np.asarray(self.getGeneSetGenes(geneSetName), dtype=np.uint32)
+        group = np.ascontiguousarray(group, dtype=np.uint32)
+        groupCount = len(groupNames)
+        if groupCount == 0:
+            raise ValueError("there is no group to rank genes for")
+        out = capi.rank_genes_arrays(len(geneIds), groupCount)
+        capi.check(capi.load().em2_matrix_rank_genes(self._handle, _b(geneSetName), _b(cellSetName), int(method), capi._ptr(group),
+                                                     groupCount, capi._ptr(out["groupSize"]), capi._ptr(out["nonZeroCount"]),
+                                                     capi._ptr(out["rankSum2"]), capi._ptr(out["tieSum"]), capi._ptr(out["zScore"]),
+                                                     capi._ptr(out["auc"])))
+        zScore = np.ascontiguousarray(out["zScore"].T)
+        pValue = np.array([math.erfc(abs(z) / math.sqrt(2.)) for z in zScore.reshape(-1).tolist()], dtype=np.float64).reshape(zScore.shape)
+        return {"groupNames": list(groupNames), "groupSizes": out["groupSize"], "geneIds": geneIds, "zScore": zScore,
+                "auc": np.ascontiguousarray(out["auc"].T), "pValue": pValue, "nonZeroCount": np.ascontiguousarray(out["nonZeroCount"].T),
+                "rankSum2": np.ascontiguousarray(out["rankSum2"].T), "tieSum": out["tieSum"]}
+
+    def rankGenesByMetaData(self, geneSetName="AllGenes", cellSetName="AllCells", metaDataName=_REQUIRED,
+                            normalizationMethod=NormalizationMethod.L2):
+        """The rank-sum (Mann-Whitney / Wilcoxon) test of every gene of the gene set, for every value of a meta data field over
+        the cell set against the cells of all other values, on the GPU (em2_matrix_rank_genes).  The groups are the values in
+        the order of histogramMetaData (count descending, then value ascending); a cell without the field has the value ""
+        like any other.  A cell's value for a gene is its count times the cell's norm inverse (over its whole row), 0 where
+        nothing is stored.  -> dict of numpy arrays: groupNames, groupSizes [K], geneIds (global) [G], zScore, auc, pValue
+        (two-sided, normal approximation without continuity correction, erfc(|z| / sqrt(2))), nonZeroCount, rankSum2, each
+        [K][G], and tieSum [G].  The integers (nonZeroCount, rankSum2 = twice the group's rank sum, tieSum) determine the rest."""
+        if metaDataName is _REQUIRED:
+            raise TypeError("rankGenesByMetaData(): metaDataName is required")
+        self.getGeneSetGenes(geneSetName)                                # "Gene set X does not exist."
+        cells = self._cell_set(cellSetName)                               # "Cell set X does not exist."
+        if len(cells) == 0:
+            raise RuntimeError("Cell set " + cellSetName + " is empty.")
+        handle = ctypes.c_void_p(None)
+        capi.check(capi.load().em2_matrix_meta_data_table(self._handle, _b(cellSetName), _b(metaDataName), None, ctypes.byref(handle)))
+        t = capi.meta_data_table_take(handle, cell_rows=True)
+        return self._rank_genes(geneSetName, cellSetName, normalizationMethod, t["cellRow"], t["values0"])
+
+    def rankGenesByClusterGraph(self, clusterGraphName, geneSetName=None, normalizationMethod=NormalizationMethod.L2):
+        """rankGenesByMetaData for the clusters of a cluster graph: the universe is the cells of the cluster graph's cell
+        graph, the groups are its clusters in the order of getClusterGraphVertices (groupNames holds their ids), and a cell of
+        the graph that is in no cluster belongs to no group but to every "rest".  geneSetName None: the graph's own gene set."""
+        c = self._cluster_graph(clusterGraphName)
+        clusterIds = self.getClusterGraphVertices(clusterGraphName)
+        r = c["result"]
+        cellSetName = c["cellSetName"]
+        cells = self._cell_set(cellSetName)
+        groupOfCell = {}
+        for group, clusterId in enumerate(clusterIds):
+            at = c["position"][clusterId]
+            for cellId in c["vertexCellIds"][r["cells"][int(r["cellOffsets"][at]):int(r["cellOffsets"][at + 1])]].tolist():
+                groupOfCell[cellId] = group
+        inGraph = set(c["vertexCellIds"].tolist())
+        group = np.array([groupOfCell.get(cellId, capi.NO_GROUP) if cellId in inGraph else capi.GROUP_EXCLUDED for cellId in cells.tolist()],
+                         dtype=np.uint32)
+        return self._rank_genes(c["geneSetName"] if geneSetName is None else geneSetName, cellSetName, normalizationMethod, group,
+                                clusterIds)
+
+    def compareCellSets(self, geneSetName=_REQUIRED, cellSetName0=_REQUIRED, cellSetName1=_REQUIRED,
+                        normalizationMethod=NormalizationMethod.L2):
+        """rankGenesByMetaData for two cell sets against each other: the universe is their union, the groups are the two sets
+        (groupNames holds their names), so z of group 0 is minus z of group 1.  Sets that share a cell raise ValueError."""
+        if _REQUIRED in (geneSetName, cellSetName0, cellSetName1):
+            raise TypeError("compareCellSets(): geneSetName, cellSetName0 and cellSetName1 are required")
+        self.getGeneSetGenes(geneSetName)
+        cells0, cells1 = self._cell_set(cellSetName0), self._cell_set(cellSetName1)
+        if len(np.intersect1d(cells0, cells1)):
+            raise ValueError("compareCellSets(): the cell sets " + cellSetName0 + " and " + cellSetName1 + " share a cell")
+        allCells = self._cell_set("AllCells")
+        group = np.full(len(allCells), capi.GROUP_EXCLUDED, dtype=np.uint32)
+        group[np.isin(allCells, cells0)] = 0
+        group[np.isin(allCells, cells1)] = 1
+        return self._rank_genes(geneSetName, "AllCells", normalizationMethod, group, [cellSetName0, cellSetName1])
 
     # ---- src/PythonModule.cpp:755-771 ----
     def computeCellSimilarity(self, geneSetName="AllGenes", cellId0=_REQUIRED, cellId1=_REQUIRED):
@@ -1350,7 +1439,7 @@ class ExpressionMatrix:
         result = capi.cluster_graph_create(toc, data, geneCount, vertexRows, v0, v1, labels, minClusterSize, k,
                                            similarityThreshold, similarityThresholdForMerge)
         self._clusterGraphs[clusterGraphName] = {
-            "geneSetName": geneSetName, "vertexCellIds": vertexCellIds, "result": result,
+            "geneSetName": geneSetName, "cellSetName": g["cellSetName"], "vertexCellIds": vertexCellIds, "result": result,
             "position": {int(clusterId): i for i, clusterId in enumerate(result["clusterIds"].tolist())},
         }
 

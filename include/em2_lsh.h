@@ -197,6 +197,55 @@ int em2_dev_gene_information_content(const uint64_t* d_toc, const em2_count* d_d
                                      double* d_informationContentDouble, uint32_t* d_expressingCellCount, void* d_workspace,
                                      size_t workspaceBytes, void* stream);
 
+/* Rank-sum (Mann-Whitney / Wilcoxon) marker genes: for every gene of a subset's CSR and every group of cells, the test of the
+ * group against the rest of the cells.  The reference has no such test (its compareClusters,
+ * src/ExpressionMatrixHttpServerClusterGraphs.cpp:595-900, is a scatter plot of two averages).
+ * Inputs: the CSR as em2_gene_information_content takes it (toc from 0, strictly ascending local gene ids below geneCount);
+ * normInverse NULL or [cellCount]; group[cellCount], each a group below groupCount or EM2_NO_GROUP -- such a cell belongs to no
+ * group but is part of every "rest"; groupCount >= 1.
+ * Values: the value of cell c for gene g is count * float(normInverse[c]), one float product (the count itself where
+ * normInverse is NULL), and +0 where the cell stores nothing for g, whatever the cell's factor.  -0 counts as +0.  +-inf are
+ * ordinary values.  A NaN value fails the call with EM2_ERROR_INVALID_ARGUMENT ("a value is not a number").
+ * Ranks of gene g, over all N = cellCount values: with m its stored entries sorted ascending at the positions 0 .. m-1,
+ * z = N - m, neg = the stored values < 0, nz = the stored values != 0 and t0 = N - nz (every zero, stored or not, is one tie
+ * group), TWICE the mid-rank of a value is
+ *     a + b + 1            for a run of equal values < 0 at the positions [a, b),
+ *     a + b + 1 + 2 z      for a run of equal values > 0 at the positions [a, b),
+ *     2 neg + t0 + 1       for every zero.
+ * Outputs, integers all, so that no sum has an order and every call gives the same bits:
+ *     groupSize[groupCount]                       the cells of the group;
+ *     nonZeroCount[geneCount][groupCount]         the cells of the group with a value != 0 for the gene;
+ *     rankSum2[geneCount][groupCount]  (64 bits)  the sum over the cells of the group of twice the mid-rank;
+ *     tieSum[geneCount]                (64 bits)  the sum of t^3 - t over all tie groups, the zeros' included.
+ * zScore and auc ([geneCount][groupCount], each may be NULL) are host arithmetic on those integers, in the order that
+ * csrc/em2_rank_genes_host.h states: with n the group's size and m = N - n, u2 = rankSum2 - n (n + 1) (twice U),
+ * var = n m (N^3 - N - tieSum) / (12 N (N - 1)), z = 0.5 (u2 - n m) / sqrt(var) (0 where var is not positive; no continuity
+ * correction), auc = u2 / (2 n m) (0.5 where n m = 0).  The two-sided p-value is erfc(|z| / sqrt(2)).
+ * EM2_ERROR_UNSUPPORTED, before any launch: cellCount > 2^21 (t^3 would leave 64 bits), 2^32 entries or more,
+ * geneCount * groupCount > 2^28. */
+#define EM2_NO_GROUP 0xffffffffu
+int em2_rank_genes(const uint64_t* toc, const em2_count* data, uint32_t cellCount, uint32_t geneCount, const double* normInverse,
+                   const uint32_t* group, uint32_t groupCount, uint32_t* groupSize, uint32_t* nonZeroCount, uint64_t* rankSum2,
+                   uint64_t* tieSum, double* zScore, double* auc);
+
+/* The integers of em2_rank_genes on device pointers and a stream (d_toc and d_data as em2_dev_gene_information_content takes
+ * them).  On an input error (EM2_ERROR_INVALID_ARGUMENT: the toc, a gene id, a NaN value, a group id that is neither below
+ * groupCount nor EM2_NO_GROUP) nothing is written outside the workspace.  d_workspace: at least
+ * em2_dev_rank_genes_workspace bytes (0: the shape is not supported).  Synchronises the stream. */
+size_t em2_dev_rank_genes_workspace(uint32_t cellCount, uint32_t geneCount, uint64_t entryCount, uint32_t groupCount);
+int em2_dev_rank_genes(const uint64_t* d_toc, const em2_count* d_data, uint32_t cellCount, uint32_t geneCount, uint64_t entryCount,
+                       const double* d_normInverse, const uint32_t* d_group, uint32_t groupCount, uint32_t* d_groupSize,
+                       uint32_t* d_nonZeroCount, uint64_t* d_rankSum2, uint64_t* d_tieSum, void* d_workspace, size_t workspaceBytes,
+                       void* stream);
+
+/* The most blocks any kernel of the call is launched with, the entries of a gene one workgroup of the accumulate pass takes
+ * (a chunk), and the largest groupCount whose counters that pass keeps in LDS (above it the adds go straight to global memory;
+ * at most 4096).  0 restores each default (16384 blocks, 2048 entries, 4096 groups).  The workspace size depends on the chunk:
+ * ask for it after the call.  Process-wide and meant for this project's tests alone (the result does not depend on any of
+ * them, which is what they show with it): unsupported elsewhere, and a call that runs while another thread changes them may
+ * size its launches by either value. */
+void em2_set_rank_genes_test_limits(uint32_t maxBlocks, uint32_t chunkEntries, uint32_t ldsGroupLimit);
+
 /* Cell::norm1Inverse and norm2Inverse as ExpressionMatrix::addCell defines them (src/ExpressionMatrix.cpp:241-263) for the
  * cells of a CSR: sum1 += value, sum2 += value * value (a float product), both sums double, in stored order;
  * 1. / sum1 and 1. / sqrt(sum2).  (The reference sums in the order of ingest, before it sorts the row by gene id.)  Host
@@ -1433,6 +1482,19 @@ int em2_matrix_remove_similar_gene_pairs(em2_matrix* matrix, const char* similar
 int em2_matrix_gene_information_content(em2_matrix* matrix, const char* geneSetName, const char* cellSetName, int normalizationMethod,
                                         float* out);
 
+/* em2_rank_genes for the genes of a gene set over the cells of a cell set, by name: the rows of the cells go to the device with
+ * their global gene ids, the norm inverses are those of the cells' WHOLE rows (from the Cells file where there is one, as
+ * em2_matrix_gene_information_content), the gene set is applied by the device subset, and the rest is em2_dev_rank_genes.
+ * group[size of the cell set], in the order of the cell set: a group below groupCount, EM2_NO_GROUP, or EM2_GROUP_EXCLUDED --
+ * such a cell is left out of the universe altogether (it is in no group and in no "rest"), which is how a caller ranks over a
+ * part of a cell set without storing a new one.  The outputs as em2_rank_genes's, the genes in the gene set's local order;
+ * zScore and auc may be NULL.  No cell left: every count is 0, zScore 0 and auc 0.5.
+ * Errors: "Gene set X does not exist.", "Cell set X does not exist.". */
+#define EM2_GROUP_EXCLUDED 0xfffffffeu
+int em2_matrix_rank_genes(em2_matrix* matrix, const char* geneSetName, const char* cellSetName, int normalizationMethod,
+                          const uint32_t* group, uint32_t groupCount, uint32_t* groupSize, uint32_t* nonZeroCount, uint64_t* rankSum2,
+                          uint64_t* tieSum, double* zScore, double* auc);
+
 /* ExpressionMatrix::createGeneSetUsingInformationContent (src/ExpressionMatrix.cpp:2022-2082; bound at
  * src/PythonModule.cpp:506-537): the genes of the existing set with double(information content) > threshold, in ascending
  * local id, as GeneSet-<newGeneSetName>-{GlobalIds,LocalIds}; usable by name at once.  Errors in the reference's order:
@@ -1523,7 +1585,10 @@ int em2_matrix_cell_set_names(em2_matrix* matrix, uint64_t* bytes, char* names);
  *                                          same checks.  em2_meta_data_table_sizes, then em2_meta_data_table_get (any may be
  *                                          NULL): values0[valueBytes0] (every value followed by a 0 byte), counts0[valueCount0],
  *                                          the same for field 1, row / column / count[nonZeroCount] ascending by (row, column),
- *                                          sums[4] = the three of em2_contingency_get and n. */
+ *                                          sums[4] = the three of em2_contingency_get and n.
+ *                                          em2_meta_data_table_cell_rows: cellRow[size of the cell set], for every cell of the
+ *                                          set in its order the place of its value of field 0 in values0 (the groups of
+ *                                          rankGenesByMetaData). */
 typedef struct em2_meta_data_table em2_meta_data_table;
 int em2_matrix_set_cell_meta_data(em2_matrix* matrix, uint32_t cellId, const char* name, const char* value);
 int em2_matrix_get_cell_meta_data_value(em2_matrix* matrix, uint32_t cellId, const char* metaDataName, uint64_t* bytes, char* value);
@@ -1539,6 +1604,7 @@ int em2_meta_data_table_sizes(const em2_meta_data_table* table, uint64_t* valueC
                               uint64_t* valueBytes1, uint64_t* nonZeroCount, int* path);
 int em2_meta_data_table_get(const em2_meta_data_table* table, char* values0, uint64_t* counts0, char* values1, uint64_t* counts1,
                             uint64_t* row, uint64_t* column, uint64_t* count, uint64_t* sums);
+int em2_meta_data_table_cell_rows(const em2_meta_data_table* table, uint32_t* cellRow);
 void em2_meta_data_table_free(em2_meta_data_table* table);
 /* Writes what the matrix holds in memory and has changed (the meta data store) to its files. */
 int em2_matrix_flush(em2_matrix* matrix);
